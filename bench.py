@@ -5,13 +5,19 @@ One "step" = one rk4 (3/8 rule) solver step = 4 evaluations of f(t,x) = alpha (A
 the synthetic ogbn-arxiv-shaped graph (169,343 nodes, ~2.48 M edges incl. self-loops, d = 128,
 attention_dim 16 / 4 heads, softmax over rows, add_source) -- BASELINE.json configs[2].  The K timed
 steps are ONE launch of the hipGraph-captured native solver (T = K, step_size = 1), state resident in HBM;
-the launch is repeated `--replays` times (each bracketed by a device synchronisation) and the MEDIAN is reported.
+the launch is repeated `--replays` times (each bracketed by a device synchronisation) and the MEDIAN is reported
+(one launch in a plain run, five with --full).
 
-  python bench.py --gpus 1 --steps 100 --warmup 10
+  python bench.py --gpus 1 --steps 100 --warmup 10         (plain run: set up, warm up, time K steps, ONE JSON line)
+  python bench.py --gpus 1 --steps 100 --warmup 10 --full  (+ roofline, cpu_baseline, parity and the other configurations)
   python bench.py --graph rmat --steps 8 --warmup 1        (BASELINE configs[4] shape on ONE GPU: 2 M nodes, d = 256)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (row-partitioned, RCCL halo)
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the CSR aggregation spmm_pair_kernel / spmm_wide_kernel
+`--dump-outputs DIR` writes what the last timed solve returned to DIR/*.npy (float32; a fixed, seeded sample of the rows when the
+whole state would exceed 32 MiB), so that two builds can be compared output for output on identical inputs.
+
+A plain run prints ONE JSON line: metric, value (steps/s), unit, ms_per_step, dtype and the workload.  The rest of this
+docstring is about --full, whose LAST line is the compact headline (rank 0).  `roofline` is for the dominant kernel (the CSR aggregation spmm_pair_kernel / spmm_wide_kernel
 + the hub-row fold): `achieved` = algorithmic bytes of DESIGN.md section 4 (SURVEY 8d's gather model) / its average launch
 duration, measured here with HIP events around a captured graph of the four rk4-stage variants the solver runs; `peak` = HBM's
 8 TB/s; `frac_algorithmic` = achieved / peak (exceeds 1 when the gathered table is resident in the Infinity Cache: the model
@@ -35,7 +41,8 @@ import time
 import torch
 
 T_PROCESS_START = time.perf_counter()
-DEFAULT_RUN_SECONDS = 290      # the default run (headline + every other configuration by child runs) is planned to end within this
+DEFAULT_RUN_SECONDS = 290      # the --full run (headline + every other configuration by child runs) is planned to end within this
+DUMP_SAMPLE_BYTES = 32 * 2 ** 20   # --dump-outputs: a state larger than this is written as a seeded sample of its rows
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -50,6 +57,12 @@ def parse():
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=100)
   ap.add_argument('--warmup', type=int, default=10)
+  ap.add_argument('--full', action='store_true',
+                  help='besides the headline: roofline probes, live PMC passes, the CPU baseline and parity against the oracle, and the '
+                       'other configurations by child runs (without it a run sets up, warms up, times the K steps and prints one line)')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='write the state the last timed solve returned to DIR/*.npy (float32; rows sampled with a fixed seed past %d MiB)'
+                       % (DUMP_SAMPLE_BYTES >> 20))
   ap.add_argument('--graph', default='arxiv', choices=['arxiv', 'arxiv_flat', 'cora', 'rmat'],
                   help='arxiv: ogbn-arxiv shape with 40 planted communities (the headline); arxiv_flat: same degree skew, NO community '
                        'structure (what the node relabelling gains without planted locality)')
@@ -80,10 +93,10 @@ def parse():
                        'Pubmed\'s ODE block (attention block, Laplacian, dopri5, adjoint=True with adjoint_method adaptive_heun -- the reference\'s default '
                        'adjoint method) on a Pubmed-shaped graph: ms per training iteration of the block, native stages vs the flat host loop')
   ap.add_argument('--no-configs', action='store_true',
-                  help='default line only: skip the `configs` block (the other BASELINE configurations, each measured by a child process of this script)')
+                  help='with --full: skip the `configs` block (the other BASELINE configurations, each measured by a child process of this script)')
   ap.add_argument('--configs-budget', type=float, default=None,
                   help='seconds the `configs` block may take in total (children that would not fit are skipped, and say so); default: what is '
-                       'left of %d s since the start of this process, so that the default run ends within about five minutes' % DEFAULT_RUN_SECONDS)
+                       'left of %d s since the start of this process, so that the --full run ends within about five minutes' % DEFAULT_RUN_SECONDS)
   ap.add_argument('--parity-only', action='store_true', help='one evaluation of the CPU oracle for the parity figure, no timed cpu_baseline leg')
   ap.add_argument('--keep-pmc', default=None, help='directory that receives the raw counter_collection.csv files of the live PMC passes')
   ap.add_argument('--train', action='store_true',
@@ -92,7 +105,8 @@ def parse():
   ap.add_argument('--no-adjoint', action='store_true',
                   help='with --train: opt[adjoint] off (run_GNN.py\'s default) -- recorded native solve + native reverse sweep, A/B against the host loop')
   ap.add_argument('--no-host-loop', action='store_true', help='with --train --no-adjoint: skip the host-loop A/B (the child the PMC passes profile)')
-  ap.add_argument('--replays', type=int, default=5, help='timed launches of the K-step solve (median reported)')
+  ap.add_argument('--replays', type=int, default=None,
+                  help='timed launches of the K-step solve (median reported); default 1 in a plain run of the solve, 5 otherwise')
   ap.add_argument('--seed', type=int, default=0)
   ap.add_argument('--norm-idx', type=int, default=0, choices=[0, 1], help='attention_norm_idx (1: softmax over columns, general 3-pass path)')
   ap.add_argument('--square-plus', action='store_true', help='squareplus normalisation (Cora best_params)')
@@ -1560,6 +1574,22 @@ def emit(out, configs=None):
   sys.stdout.flush()
 
 
+def dump_outputs(path, z):
+  """--dump-outputs: the [n, d] state the last timed solve returned (what a caller of the block receives), as float32 .npy.  Whole
+  (`z.npy`) when it fits DUMP_SAMPLE_BYTES, else the rows of a fixed seeded sample (`z_rows.npy`, the same rows for the same shape)
+  and their row ids (`z_row_ids.npy`, float64)."""
+  import numpy as np
+  os.makedirs(path, exist_ok=True)
+  z = z.detach()
+  n, d = z.shape
+  if n * d * 4 <= DUMP_SAMPLE_BYTES:
+    np.save(os.path.join(path, 'z.npy'), z.float().cpu().numpy())
+    return
+  rows = torch.randperm(n, generator=torch.Generator().manual_seed(12345))[:DUMP_SAMPLE_BYTES // (4 * d)].sort().values
+  np.save(os.path.join(path, 'z_rows.npy'), z[rows.to(z.device)].float().cpu().numpy())
+  np.save(os.path.join(path, 'z_row_ids.npy'), rows.double().numpy())
+
+
 def summarise_child(line):
   """What the parent keeps of a child's bench line."""
   r = line.get('roofline') or {}
@@ -1607,7 +1637,7 @@ def run_configs(args, budget_s):
       out[key] = {'skipped': 'the configs block had %.0f s of its %.0f s budget left, this child takes about %d s: run `python bench.py %s`'
                              % (max(left, 0.0), budget_s, expect, ' '.join(flags)), 'what': what}
       continue
-    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--no-configs', '--seed', str(args.seed)] + flags
+    cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--full', '--no-configs', '--seed', str(args.seed)] + flags
     env = dict(os.environ)
     if key == 'c3_arxiv_relabelling_off':
       env['GNPDE_REORDER'] = '0'
@@ -1661,6 +1691,12 @@ def main():
   world = int(os.environ.get('WORLD_SIZE', '1'))
   rank = int(os.environ.get('RANK', '0'))
   local_rank = int(os.environ.get('LOCAL_RANK', '0'))
+  sharded = args.gpus > 1 or world > 1 or os.environ.get('GNPDE_FORCE_SHARDED', '0') == '1'
+  other_mode = bool(args.train or args.config or args.pmc_child or sharded)
+  if args.dump_outputs and other_mode:
+    raise SystemExit('--dump-outputs writes the output of the one-GPU solve; it has no meaning with --train, --config or --gpus N > 1')
+  if args.replays is None:
+    args.replays = 5 if (args.full or other_mode) else 1
   if args.gpus > 1 and 'RANK' not in os.environ:
     return launch_ranks(args.gpus)        # `python bench.py --gpus N` as the driver runs `--gpus 1`: spawn the N ranks ourselves
   if args.gpus != world:
@@ -1747,6 +1783,8 @@ def main():
       torch.cuda.synchronize()
       times.append(time.perf_counter() - t0)
   assert torch.isfinite(z).all()
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, z)
   elapsed = sorted(times)[len(times) // 2]  # median replay
   steps_per_s = K / elapsed
   evals_per_step = 4 if args.method == 'rk4' else 1
@@ -1754,15 +1792,24 @@ def main():
   E = int(f.edge_index.shape[1])
   A, h = opt['attention_dim'], opt['heads']
 
-  # roofline of the dominant kernel (DESIGN.md section 4: B_spmm = E (4 + 4 + 4d) + N (4 + 8d) + 4dN with add_source)
-  if args.no_roofline_probe:
-    print(json.dumps({'metric': metric_name(args.graph, d, method=args.method), 'value': round(steps_per_s, 3), 'unit': 'steps/s', 'n_gpus': 1,
-                      'steps': K, 'warmup': W, 'ms_per_step': round(1e3 * elapsed / K, 4), 'higher_is_better': True,
-                      'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-                      'config': {'workload': workload_name(args.graph, args.function, K, args.method), 'graph': args.graph, 'nodes': n,
-                                 'edges_with_self_loops': E, 'd': d, 'hipgraph': use_graph},
-                      'roofline': None, 'cpu_baseline': None, 'note': 'profiling run: --no-roofline-probe'}))
+  # plain run (no --full): the headline figure and nothing else
+  if not args.full or args.no_roofline_probe:
+    line = {'metric': metric_name(args.graph, d, method=args.method), 'value': round(steps_per_s, 3), 'unit': 'steps/s', 'n_gpus': 1,
+            'steps': K, 'warmup': W, 'ms_per_step': round(1e3 * elapsed / K, 4), 'higher_is_better': True,
+            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'timing': {'replays': len(times), 'statistic': 'median'},
+            'config': {'workload': workload_name(args.graph, args.function, K, args.method), 'graph': args.graph, 'nodes': n,
+                       'edges_with_self_loops': E, 'd': d, 'attention_dim': A, 'heads': h, 'rhs_evals_per_step': evals_per_step,
+                       'hipgraph': use_graph, 'scale': args.scale},
+            'roofline': None, 'cpu_baseline': None,
+            'note': 'profiling run: --no-roofline-probe' if args.full else 'plain run: roofline, cpu_baseline and the other configurations with --full'}
+    if early is not None:
+      sol = early.solver
+      line['early_stop'] = {'best_val': sol.best_val, 'best_test': sol.best_test, 'best_time': sol.best_time, 'classes': 40, 'evaluations': K}
+    print(json.dumps(line))
     return
+
+  # roofline of the dominant kernel (DESIGN.md section 4: B_spmm = E (4 + 4 + 4d) + N (4 + 8d) + 4dN with add_source)
   t_spmm, graph, kname, fused = dominant_kernel_time(G, main_block, x)
   bytes_l = E * (8 + 4 * d) + n * (4 + 8 * d) + 4 * d * n                      # SURVEY.md 8d, B_l + source
   bytes_nl = E * (4 + 4 * A + 4 * d) + n * (4 + 12 * A + 12 * d) + 4 * d * n   # SURVEY.md 8d, B_nl + source

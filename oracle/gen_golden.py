@@ -334,6 +334,21 @@ def gen_beltrami():
                                                        'nfe': np.int64(block.odefunc.nfe)}, block)
 
 
+def gen_khop():
+  """RewireAttODEblock.add_khop_edges (k = 2) on a seeded edge list with duplicate entries and self loops: the two-hop edge list
+  and its weights, which pin oracle.restate.two_hop (what the native two-hop kernel is tested against)."""
+  import types
+  g = torch.Generator().manual_seed(3)
+  n = 60
+  ei = torch.randint(0, n, (2, 300), generator=g)
+  ei = torch.cat([ei, ei[:, :7], torch.tensor([[4, 9], [4, 9]])], dim=1)     # duplicates and self loops
+  w = torch.rand(ei.shape[1], generator=g)
+  fake = types.SimpleNamespace(num_nodes=n, odefunc=types.SimpleNamespace(edge_index=ei, edge_weight=w, attention_weights=None))
+  RewireAttODEblock.add_khop_edges(fake, k=2)
+  save('khop_add_edges', {'k': 2, 'num_nodes': n},
+       {'edge_index': ei, 'edge_weight': w, 'khop_edge_index': fake.data_edge_index, 'khop_weight': fake.odefunc.attention_weights})
+
+
 def gen_rewire():
   """RewireAttODEblock (src/block_transformer_rewiring.py): the eval forward, and training forwards whose rewiring
   (two-hop densification or random pairs, quantile threshold, renormalisation) is recorded edge by edge."""
@@ -607,6 +622,7 @@ if __name__ == '__main__':
   gen_gnn_options()
   gen_beltrami()
   gen_rewire()
+  gen_khop()
   gen_early()
   gen_adjoint()
   gen_regularised()

@@ -560,18 +560,13 @@ def test_meter_matches_the_reference_meter():
   assert (m.val, m.sum, m.cnt, m.get_average(), m.get_value()) == (0, 24, 3, 8.0, 0)
   m.reset()
   assert (m.val, m.sum, m.cnt) == (None, 0, 0)
-  path = '/root/reference/src/utils.py'
-  if os.path.exists(path):
-    src = open(path).read()
-    body = src[src.index('class Meter(object):'):src.index('class DummyDataset')]
-    ns = {}
-    exec(body, ns)
-    ref = ns['Meter']()
-    ours = G.Meter()
-    for v in (3, 5.5, 0):
-      ref.update(v)
-      ours.update(v)
-      assert vars(ref) == vars(ours) and ref.get_average() == ours.get_average() and ref.get_value() == ours.get_value()
+  # what the reference's own class holds and returns after each of these updates (recorded from src/utils.py)
+  ref = [({'val': 3, 'sum': 3, 'cnt': 1}, 3.0, 3), ({'val': 5.5, 'sum': 8.5, 'cnt': 2}, 4.25, 5.5),
+         ({'val': 0, 'sum': 8.5, 'cnt': 3}, 8.5 / 3, 0)]
+  ours = G.Meter()
+  for v, (state, average, value) in zip((3, 5.5, 0), ref):
+    ours.update(v)
+    assert vars(ours) == state and ours.get_average() == average and ours.get_value() == value
   import inspect
   assert 'self.fm = Meter()' in inspect.getsource(G.BaseGNN.__init__) and 'self.bm = Meter()' in inspect.getsource(G.BaseGNN.__init__)
 

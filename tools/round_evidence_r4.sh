@@ -15,7 +15,7 @@ prof() {  # name, command...
     "rocprofv3 --kernel-trace --stats -- $*   (commit $COMMIT)" > /dev/null 2>> "$OUT/$name.stats.log"
   find "$OUT/st_$name" -name '*kernel_trace.csv' -delete
 }
-B="python bench.py"
+B="python bench.py --full"
 prof arxiv_steps20 $B --graph arxiv --steps 20 --warmup 0 --no-cpu-baseline --no-roofline-probe --replays 1
 timeout 400 $B --steps 20 --warmup 5 > "$OUT/bench_default_steps20.json" 2> "$OUT/bench_default.err"
 timeout 400 $B --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/bench_steps100.json" 2>> "$OUT/bench_default.err"

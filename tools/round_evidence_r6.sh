@@ -15,7 +15,7 @@ prof() {  # name, command...
     "rocprofv3 --kernel-trace --stats -- $*   (commit $COMMIT)" > /dev/null 2>> "$OUT/$name.stats.log"
   rm -rf "$OUT/st_$name"
 }
-B="python bench.py"
+B="python bench.py --full"
 T0=$(date +%s)
 timeout 1700 $B --gpus 1 --steps 20 --warmup 5 --keep-pmc "$OUT/live_pmc" > "$OUT/bench_default_steps20.out" 2> "$OUT/bench_default.err"
 echo "default bench rc $? seconds $(( $(date +%s) - T0 ))" | tee "$OUT/bench_default.time"
