@@ -14,9 +14,12 @@ classes.  The FORWARD value is always the native kernels' (identical to inferenc
 * the other score functions (cosine / pearson / exp_kernel incl. the BLEND split kernel, GAT incl. mix_features): node-level
   transforms in PyTorch with autograd, everything per edge native (section "Native VJP of the attention for EVERY score
   function" below).
+* every head shape: gnpde_head_spmm takes any heads and d_k up to attention_dim = 256 (2A for the BLEND split kernel; GAT
+  up to 64 heads), the float4 kernel where d_k % 4 == 0 with attention_dim / 4 a power of two, a generic one otherwise.
 * what is left to the composite of PyTorch device ops (index_select / index_add, the reference's op sequence; it announces
-  itself once): head shapes the float4 head-SpMM does not cover, the second-order regularisers (a kernel-backed autograd
-  function is not twice differentiable), and opt['gnpde_composite_backward'] (the A/B reference of the gradient tests).
+  itself once): the second-order regularisers (twice_differentiable_rhs: a kernel-backed autograd function is not twice
+  differentiable), opt['gnpde_composite_backward'] (the A/B reference of the gradient tests), and attention widths beyond
+  256 (GAT: more than 64 heads).
 """
 import logging
 import math
@@ -118,11 +121,15 @@ class _LaplacianRhs(torch.autograd.Function):
 # --------------------------------------------------------------------------------------------------
 def _native_transformer_vjp_ok(func):
   lay, opt = func.multihead_att_layer, func.opt
-  a4 = lay.attention_dim // 4
-  # scaled-dot scores with ANY normaliser (softmax / squareplus over rows / columns); the head-SpMM of d q / d k needs
-  # float4 lanes over a power-of-two attention width
+  # scaled-dot scores with ANY normaliser (softmax / squareplus over rows / columns) and any head shape the head-SpMM of
+  # d q / d k takes (attention_dim <= 256)
   return (opt['attention_type'] == 'scaled_dot' and not opt['mix_features'] and not getattr(lay, 'split_kernel', False) and
-          lay.d_k % 4 == 0 and lay.attention_dim % 4 == 0 and a4 <= 64 and (a4 & (a4 - 1)) == 0)
+          _head_spmm_shape_ok(lay.attention_dim, lay.h))
+
+
+def _head_spmm_shape_ok(A, h):
+  """The head shapes gnpde_head_spmm takes: h >= 1 heads of A / h columns each, A <= 256."""
+  return h >= 1 and A >= h and A % h == 0 and A <= 256
 
 
 class _TransformerRhs(torch.autograd.Function):
@@ -300,9 +307,9 @@ class _GatAttention(torch.autograd.Function):
     with torch.no_grad():
       st, keep = ctx.struct_fn()
       c = ops.edge_attention_bwd_heads(graph, st, datt, post=2)
-      ones = torch.ones(graph.n, 4 * h, dtype=torch.float32, device=datt.device)     # head sums through the float4 head-SpMM
-      dts = ops.head_spmm(graph, c, ones, h, 4, 1.0, by_column=False)[:, ::4].contiguous()
-      dtd = ops.head_spmm(graph, c, ones, h, 4, 1.0, by_column=True)[:, ::4].contiguous()
+      ones = torch.ones(graph.n, h, dtype=torch.float32, device=datt.device)     # head sums: the head-SpMM with d_k = 1
+      dts = ops.head_spmm(graph, c, ones, h, 1, 1.0, by_column=False)
+      dtd = ops.head_spmm(graph, c, ones, h, 1, 1.0, by_column=True)
     return dts, dtd, None, None, None
 
 
@@ -365,9 +372,7 @@ def native_layer_attention(layer, x, edge):
 
 
 def _native_layer_vjp_ok(layer):
-  A, h = layer.kernel_att_dim, layer.h
-  dk, a4 = A // h, A // 4
-  return dk % 4 == 0 and A % 4 == 0 and a4 <= 64 and (a4 & (a4 - 1)) == 0
+  return _head_spmm_shape_ok(layer.kernel_att_dim, layer.h)      # (2A for the BLEND split kernel)
 
 
 def native_gat_attention(layer, x, edge):
@@ -389,8 +394,8 @@ def native_gat_attention(layer, x, edge):
 
 
 # --------------------------------------------------------------------------------------------------
-# composites of PyTorch device ops: twice-differentiable form for the second-order regularisers, and the fallback for
-# head shapes the float4 head-SpMM does not cover
+# composites of PyTorch device ops: twice-differentiable form for the second-order regularisers, the A/B reference of
+# opt['gnpde_composite_backward'], and the fallback for attention widths beyond what gnpde_head_spmm takes (> 256)
 # --------------------------------------------------------------------------------------------------
 def _segment_softmax(src, index, n):
   mx = torch.full((n,) + tuple(src.shape[1:]), float('-inf'), dtype=src.dtype, device=src.device)
@@ -556,8 +561,7 @@ def rhs_with_grad(func, x):
     composite = composite_transformer
   elif kind == 'ODEFuncAtt':
     lay = func.multihead_att_layer
-    pow2 = lay.h >= 1 and (lay.h & (lay.h - 1)) == 0 and lay.h <= 64
-    if pow2 and not func.opt.get('gnpde_composite_backward', False):
+    if 1 <= lay.h <= 64 and not func.opt.get('gnpde_composite_backward', False):
       att, wx = native_gat_attention(lay, x, func.edge_index)
       graph, sig = func._graph(x), not func.opt['no_alpha_sigmoid']
       if not func.opt['mix_features']:

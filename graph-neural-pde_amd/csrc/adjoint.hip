@@ -591,8 +591,13 @@ int check_adjoint(const gnpde_rhs_t* rhs, const gnpde_graph_t* gt, int method) {
                     "adjoint (exp kernel): scalars missing, attention_dim > 128 or more than 8 heads");
     GNPDE_CHECK_ARG(!unit || (at.heads >= 1 && normalise_heads_bwd_supported(at.att_dim, at.heads)), GNPDE_ESHAPE,
                     "adjoint: cosine_sim / pearson need d_k in {4, 8, 16}");
-    GNPDE_CHECK_ARG(at.att_dim % at.heads == 0 && (at.att_dim / at.heads) % 4 == 0 && a4 <= 64 && (a4 & (a4 - 1)) == 0, GNPDE_ESHAPE,
-                    "adjoint: attention_dim / 4 must be a power of two <= 64 and d_k a multiple of 4");
+    // scaled dot: any d_k (d q / d k by the generic head-SpMM); attention_dim % 4 == 0 keeps the q||k rows (stride 2A) 16-byte aligned
+    // for the other stage kernels
+    const bool any_dk = at.type == GNPDE_ATT_SCALED_DOT && at.heads >= 1 && at.att_dim % at.heads == 0 && at.att_dim % 4 == 0 &&
+                        at.att_dim <= kBlock;
+    GNPDE_CHECK_ARG(any_dk || (at.att_dim % at.heads == 0 && (at.att_dim / at.heads) % 4 == 0 && a4 <= 64 && (a4 & (a4 - 1)) == 0), GNPDE_ESHAPE,
+                    "adjoint: attention_dim / 4 must be a power of two <= 64 and d_k a multiple of 4 (scaled dot: attention_dim a "
+                    "multiple of 4 and <= 256)");
   }
   return 0;
 }

@@ -184,6 +184,127 @@ __global__ __launch_bounds__(kBlock) void head_spmm_kernel(const int* __restrict
         make_float4(scale * acc[0], scale * acc[1], scale * acc[2], scale * acc[3]);
 }
 
+// The same sum for the head shapes the float4 kernel does not take (any heads and d_k, A = heads * d_k <= 256, 4-byte-aligned
+// operands, any leading dimension).  A lane owns column vectors v = gl + j * LPE (j < CPL) of VW floats each: VW = 2 (float2) when
+// d_k is even and both operands allow 8-byte rows (a float2 then never straddles two heads), VW = 1 otherwise.  LPE = the power of
+// two >= A / VW, capped at 64, lanes per entry, so that 64 / LPE entries of one segment are gathered per wavefront iteration (16 at
+// A = 8: a lane per entry and column would leave 56 of 64 lanes idle), each entry's row coalesced across its LPE lanes; CPL > 1 only
+// when A / VW > 64.  One wavefront per segment, U = 4 independent position -> other end -> row chains in flight per lane, entry
+// slots folded by a butterfly, hub segments (> GNPDE_LONG_ROW) by whole blocks with a fixed-order LDS sum.  Every segment's row is
+// written, an empty one as zeros; no atomics.  (U = 16 / 8 for narrow rows was measured: no change at the ogbn-arxiv shape -- the
+// time follows the lanes per entry, DESIGN.md section 4 "Generic head-SpMM".)
+template <int VW, int CPL>
+__global__ __launch_bounds__(kBlock) void head_spmm_any_kernel(const int* __restrict__ segptr, const int* __restrict__ segpos,
+                                                              const int* __restrict__ other_of_pos, const float* __restrict__ ds,
+                                                              int h, int dk, int av, int lpe_shift, const float* __restrict__ feat,
+                                                              int ldf, float scale, int n, const int* __restrict__ long_segs,
+                                                              int n_long, float* __restrict__ out, int ldo) {
+  __shared__ float part[kWavesPerBlock][CPL * kWave * VW];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x >> 6;
+  const int lpe = 1 << lpe_shift;
+  const int es = lane >> lpe_shift, gl = lane & (lpe - 1);
+  const int n_es = kWave >> lpe_shift;      // entries per wavefront iteration
+  const bool hub = static_cast<int>(blockIdx.x) < n_long;    // block-uniform
+  int seg, b, e;
+  if (hub) {
+    seg = long_segs[blockIdx.x];
+    b = segptr[seg]; e = segptr[seg + 1];
+  } else {
+    seg = (static_cast<int>(blockIdx.x) - n_long) * kWavesPerBlock + wave;
+    if (seg >= n) return;                   // wavefront-uniform; no block barrier on this path
+    b = segptr[seg]; e = segptr[seg + 1];
+    if (e - b > GNPDE_LONG_ROW) return;     // a hub: its own block writes it
+  }
+  bool ok[CPL];
+  int hd[CPL];
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const int v = gl + j * lpe;
+    ok[j] = v < av;
+    hd[j] = ok[j] ? (v * VW) / dk : 0;
+  }
+  const int first = hub ? wave * n_es + es : es;
+  const int step = hub ? n_es * kWavesPerBlock : n_es;
+  float acc[CPL][VW];
+#pragma unroll
+  for (int j = 0; j < CPL; ++j)
+#pragma unroll
+    for (int c = 0; c < VW; ++c) acc[j][c] = 0.f;
+  constexpr int U = 4;
+  for (int t0 = b + first; t0 < e; t0 += U * step) {
+    float w[U][CPL], f[U][CPL][VW];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int t = t0 + u * step;
+#pragma unroll
+      for (int j = 0; j < CPL; ++j) {
+        w[u][j] = 0.f;
+#pragma unroll
+        for (int c = 0; c < VW; ++c) f[u][j][c] = 0.f;
+      }
+      if (t < e) {
+        const int p = segpos != nullptr ? segpos[t] : t;
+        const int o = other_of_pos[p];
+        const float* dsr = ds + static_cast<size_t>(p) * h;
+        const float* fr = feat + static_cast<size_t>(o) * ldf;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+          if (!ok[j]) continue;
+          const int col = (gl + j * lpe) * VW;
+          w[u][j] = dsr[hd[j]];
+          if constexpr (VW == 2) {
+            const float2 v = *reinterpret_cast<const float2*>(fr + col);
+            f[u][j][0] = v.x; f[u][j][1] = v.y;
+          } else {
+            f[u][j][0] = fr[col];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < CPL; ++j)
+#pragma unroll
+        for (int c = 0; c < VW; ++c) acc[j][c] = fmaf(w[u][j], f[u][j][c], acc[j][c]);
+  }
+  for (int off = lpe; off < kWave; off <<= 1)
+#pragma unroll
+    for (int j = 0; j < CPL; ++j)
+#pragma unroll
+      for (int c = 0; c < VW; ++c) acc[j][c] += __shfl_xor(acc[j][c], off, kWave);
+  if (hub) {
+    if (es == 0) {
+#pragma unroll
+      for (int j = 0; j < CPL; ++j)
+#pragma unroll
+        for (int c = 0; c < VW; ++c) part[wave][(j * lpe + gl) * VW + c] = acc[j][c];
+    }
+    __syncthreads();
+    if (wave != 0 || es != 0) return;
+#pragma unroll
+    for (int j = 0; j < CPL; ++j)
+#pragma unroll
+      for (int c = 0; c < VW; ++c) {
+        const int i = (j * lpe + gl) * VW + c;
+        acc[j][c] = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
+      }
+  }
+  if (es != 0) return;
+  float* orow = out + static_cast<size_t>(seg) * ldo;
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    if (!ok[j]) continue;
+    const int col = (gl + j * lpe) * VW;
+    if constexpr (VW == 2) {
+      *reinterpret_cast<float2*>(orow + col) = make_float2(scale * acc[j][0], scale * acc[j][1]);
+    } else {
+      orow[col] = scale * acc[j][0];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Row attention backward in one pass: recomputes the scaled-dot scores and their row softmax from q, k and writes
 //   ds[p, h] = scale (a[p,h] / H) (r[p] - sum_{p' in row} a[p',h] r[p'])   [* edge_w[p]]
@@ -1104,11 +1225,13 @@ extern "C" int gnpde_softmax_rows_bwd(const gnpde_graph_t* g, const float* att_e
 extern "C" int gnpde_head_spmm(const gnpde_graph_t* g, int32_t by_column, const float* ds_csr, int32_t heads, int32_t dk,
                                const float* feat, int32_t ldf, float scale, float* out, int32_t ldo, void* stream) {
   using namespace gnpde;
-  GNPDE_CHECK_ARG(g && ds_csr && feat && out && heads >= 1 && dk >= 4 && dk % 4 == 0, GNPDE_EINVAL, "head_spmm: bad arguments");
-  const int A = heads * dk, a4 = A / 4;
-  GNPDE_CHECK_ARG(a4 <= 64 && (a4 & (a4 - 1)) == 0, GNPDE_ESHAPE, "head_spmm: attention_dim/4 = %d must be a power of two <= 64", a4);
-  GNPDE_CHECK_ARG(ldf >= A && ldo >= A && ldf % 4 == 0 && ldo % 4 == 0 && reinterpret_cast<uintptr_t>(feat) % 16 == 0 &&
-                      reinterpret_cast<uintptr_t>(out) % 16 == 0, GNPDE_EINVAL, "head_spmm: operands must be 16-byte aligned");
+  GNPDE_CHECK_ARG(g && ds_csr && feat && out && heads >= 1 && dk >= 1, GNPDE_EINVAL, "head_spmm: bad arguments");
+  const long long a_wide = static_cast<long long>(heads) * dk;
+  GNPDE_CHECK_ARG(a_wide <= 256, GNPDE_ESHAPE, "head_spmm: heads * d_k = %lld must be <= 256", a_wide);
+  const int A = static_cast<int>(a_wide), a4 = A / 4;
+  const uintptr_t fa = reinterpret_cast<uintptr_t>(feat), oa = reinterpret_cast<uintptr_t>(out);
+  GNPDE_CHECK_ARG(ldf >= A && ldo >= A && fa % 4 == 0 && oa % 4 == 0, GNPDE_EINVAL,
+                  "head_spmm: leading dimensions must be >= heads * d_k and the operands 4-byte aligned");
   GNPDE_CHECK_ARG(!by_column || (g->cscptr && g->cscpos && g->rowidx), GNPDE_EINVAL, "head_spmm: column mode needs the CSC view");
   if (g->n == 0) return 0;
   const int* segptr = by_column ? g->cscptr : g->rowptr;
@@ -1122,6 +1245,30 @@ extern "C" int gnpde_head_spmm(const gnpde_graph_t* g, int32_t by_column, const 
   // <= 64 entries plus a wavefront class for the rest was measured slower: 60 + 110 us against 136 us at the
   // ogbn-arxiv shape -- both launches walk all segment pointers; the template keeps the option.)
   const unsigned grid64 = static_cast<unsigned>(nl + (g->n + kWavesPerBlock - 1) / kWavesPerBlock);
+  const bool vec4 = dk % 4 == 0 && a4 <= 64 && (a4 & (a4 - 1)) == 0 && ldf % 4 == 0 && ldo % 4 == 0 && fa % 16 == 0 && oa % 16 == 0;
+  if (!vec4) {          // every other head shape / alignment: the generic kernel
+    const int vw = (dk % 2 == 0 && ldf % 2 == 0 && ldo % 2 == 0 && fa % 8 == 0 && oa % 8 == 0) ? 2 : 1;
+    const int av = A / vw;
+    int shift = 0;
+    while ((1 << shift) < av && shift < 6) ++shift;
+    const int cpl = (av + (1 << shift) - 1) >> shift;
+#define GNPDE_HSA(VW, CPL)                                                                                                   \
+  hipLaunchKernelGGL((head_spmm_any_kernel<VW, CPL>), dim3(grid64), dim3(kBlock), 0, s, segptr, segpos, other, ds_csr, heads, dk, \
+                     av, shift, feat, ldf, scale, g->n, long_segs, nl, out, ldo)
+    if (vw == 2) {
+      if (cpl == 1) GNPDE_HSA(2, 1); else GNPDE_HSA(2, 2);
+    } else {
+      switch (cpl) {
+        case 1: GNPDE_HSA(1, 1); break;
+        case 2: GNPDE_HSA(1, 2); break;
+        case 3: GNPDE_HSA(1, 3); break;
+        default: GNPDE_HSA(1, 4); break;
+      }
+    }
+#undef GNPDE_HSA
+    GNPDE_LAUNCH_CHECK();
+    return 0;
+  }
 #define GNPDE_HS_ARGS(LO, HI, NL) segptr, segpos, other, ds_csr, heads, dk, feat, ldf, scale, g->n, LO, HI, long_segs, NL, out, ldo
 #define GNPDE_HS(N4) \
   hipLaunchKernelGGL((head_spmm_kernel<N4, 64, true>), dim3(grid64), dim3(kBlock), 0, s, GNPDE_HS_ARGS(0, GNPDE_LONG_ROW, nl));

@@ -680,15 +680,17 @@ def _solve_dopri5_recorded(func, y0, t, rtol, atol):
 # --------------------------------------------------------------------------------------------------
 def _transformer_stage_native(func):
   """GRAND-nl per-evaluation attention the native VJP stage of csrc/adjoint.hip covers: scaled-dot scores, and (round 6) cosine_sim /
-  pearson -- the scaled dot product of unit (mean-centred) head vectors, d_k in {4, 8, 16} -- and exp_kernel, with any normaliser."""
+  pearson -- the scaled dot product of unit (mean-centred) head vectors, d_k in {4, 8, 16} -- and exp_kernel, with any normaliser.
+  Scaled-dot scores take any d_k with attention_dim % 4 == 0 (16-byte q||k rows for the stage kernels) and <= 256 (d q / d k by the
+  generic head-SpMM); the other scores keep d_k % 4 == 0 with attention_dim / 4 a power of two."""
   lay, opt = func.multihead_att_layer, func.opt
   a4 = lay.attention_dim // 4
   if opt['mix_features'] or getattr(lay, 'split_kernel', False):
     return False
+  if opt['attention_type'] == 'scaled_dot':
+    return lay.attention_dim % lay.h == 0 and lay.attention_dim % 4 == 0 and lay.attention_dim <= 256
   if not (lay.d_k % 4 == 0 and lay.attention_dim % 4 == 0 and a4 <= 64 and (a4 & (a4 - 1)) == 0):
     return False
-  if opt['attention_type'] == 'scaled_dot':
-    return True
   if opt['attention_type'] == 'exp_kernel':       # (round 6; the BLEND split kernel -- two exp kernels multiplied -- keeps the stage loop)
     return lay.attention_dim <= 128 and lay.h <= 8
   return opt['attention_type'] in ('cosine_sim', 'pearson') and lay.d_k in (4, 8, 16)

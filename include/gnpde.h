@@ -263,7 +263,10 @@ int gnpde_softmax_rows_bwd(const gnpde_graph_t* g, const float* att_edge, int32_
 /* Head-wise weighted segment sum over the graph pattern (d q / d k of the attention scores):
  *   out[i, c] = scale * sum_{p in row i} ds[p, head(c)] * feat[col_p, c]           (by_column = 0)
  *   out[j, c] = scale * sum_{p in column j} ds[p, head(c)] * feat[row_p, c]        (by_column = 1, CSC view)
- * c < heads*dk, head(c) = c / dk; dk % 4 == 0 and heads*dk/4 a power of two <= 64. */
+ * c < A = heads*dk, head(c) = c / dk; heads >= 1, dk >= 1, A <= 256, ldf >= A, ldo >= A, feat and out 4-byte aligned, any
+ * leading dimension (feat may be the k half of a q||k row with A odd).  Every row of out is written (zeros for an empty
+ * segment); fixed summation order, no atomics, no allocation.  dk % 4 == 0 with A/4 a power of two, 16-byte-aligned
+ * operands and ld % 4 == 0 take the float4 kernel, every other shape a generic one (float2 or scalar lanes). */
 int gnpde_head_spmm(const gnpde_graph_t* g, int32_t by_column, const float* ds_csr, int32_t heads, int32_t dk,
                     const float* feat, int32_t ldf, float scale, float* out, int32_t ldo, void* stream);
 
