@@ -18,13 +18,14 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 7      # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 8      # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
 ADAPTIVE_HEUN, ADAPTIVE_DOPRI5 = range(2)
 TUNE_SPMM_VARIANT, TUNE_FUSED_BLOCKS_PER_CU, TUNE_ONE_PASS, TUNE_FORK, TUNE_ATT_GENERIC_ROWS, TUNE_RK4_CLASSIC = range(6)
 TUNE_ROW_FUSION, TUNE_ONE_PASS_VARIANT, TUNE_LINEAR_STREAMING, TUNE_SPMM_PART, TUNE_XCD_ROWS, TUNE_HUB_FOLD = 6, 7, 8, 9, 10, 11
+TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)
 
 ATT_TYPES = {'scaled_dot': ATT_SCALED_DOT, 'cosine_sim': ATT_COSINE, 'pearson': ATT_PEARSON,
              'exp_kernel': ATT_EXP_KERNEL}
@@ -156,6 +157,13 @@ PROTOTYPES = {
   'gnpde_adjoint_tape_swapped': (ctypes.c_int, [c_vp]),
   'gnpde_solver_tape_bytes': (ctypes.c_size_t, [ctypes.POINTER(RhsStruct), ctypes.c_int32, ctypes.c_int32]),
   'gnpde_solver_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t]),
+  'gnpde_to_bf16': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
+  'gnpde_spmm_lo': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, ctypes.c_int32,
+                                   c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_spmm_rhs_lo': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.POINTER(EpilogueStruct), c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_solver_gather_bytes': (ctypes.c_size_t, [ctypes.POINTER(RhsStruct), ctypes.c_int32]),
+  'gnpde_solver_set_gather': (ctypes.c_int, [c_vp, ctypes.c_int32, c_vp, ctypes.c_size_t]),
   'gnpde_adjoint_num_rhs_evals': (ctypes.c_int, [c_vp]),
   'gnpde_adjoint_destroy': (ctypes.c_int, [c_vp]),
   'gnpde_rhs_eval': (ctypes.c_int, [ctypes.POINTER(RhsStruct), c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
@@ -307,6 +315,8 @@ def f32c(t, name='tensor'):
 
 
 RHS_PADDED_ROWS = 1
+GATHER_FP32, GATHER_BF16 = 0, 1
+GATHER_DTYPES = {'fp32': GATHER_FP32, 'bf16': GATHER_BF16}
 
 
 def f32rows(t, name='tensor'):

@@ -109,7 +109,9 @@ enum {
   GNPDE_TUNE_LINEAR_DIAG = 13,         // A/B diagnostics of the staged projection kernel (1: no stores, 2: loads alone); never set in production
   GNPDE_TUNE_GMAX_SMALL = 16,          // 1: squareplus on a small grid keeps the slot atomics + memset + fold launch (A/B against the per-wave maxima folded by the second sweep)
   GNPDE_TUNE_ATT_ROWS16 = 17,          // 9: the row softmax of the scaled-dot row kernel (4 heads) keeps a whole wave per row of <= 16 entries (A/B against the quarter-wave packing)
-  GNPDE_TUNE_COUNT = 18
+  GNPDE_TUNE_LO_MAPPING = 18,          // bf16 gather operand, rows of 17..32 16-byte lanes in graphs of mostly short rows (A/B): 1 = two rows per wave, 32 lanes x 4
+                                       // elements (the fp32 mapping, 8-byte gathers), 2 = four rows per wave, 16 lanes x 8 elements (16-byte gathers; d % 8 == 0)
+  GNPDE_TUNE_COUNT = 19
 };
 extern int g_tune[GNPDE_TUNE_COUNT];
 
@@ -141,10 +143,21 @@ inline int fork_end(const Fork* f, hipStream_t s, hipStream_t branch) {
   return 0;
 }
 
+// bf16 shadow of a stage input (optional gather operand, gnpde_spmm_rhs_lo): [n, ld] bf16 bit patterns with the state's ld, rows
+// 8-byte aligned.  It travels through the launchers as one optional pair: the shadow the neighbour rows are gathered from and the
+// shadow of out_y that the same launch writes (so that the next stage finds its gather operand without an extra pass).
+struct LoPair {
+  const uint16_t* u_lo = nullptr;   // gathered instead of u (the row's own -u_i term still reads u)
+  uint16_t* out_y_lo = nullptr;     // nullable: bf16 rounding of out_y at the same element offsets
+};
+
 // internal launchers used by the solver (defined in the kernel translation units)
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes,
-                    hipStream_t stream, const Fork* fork = nullptr, bool padded_rows = false);
+                    hipStream_t stream, const Fork* fork = nullptr, bool padded_rows = false, const LoPair* lo = nullptr);
+
+// fp32 [n, d] (row stride ld) -> bf16 shadow [n, ld] (misc.hip)
+int launch_to_bf16(const float* src, long long n, int d, int ld, uint16_t* dst, hipStream_t s);
 
 // adjoint stage, row side (spmm.hip): F with its LINCOMB epilogue + r_e = g[row] . u[col] + per-wave dots of g . F and g . x0
 int adjoint_rows_dot_slots(const gnpde_graph_t* g, int d);

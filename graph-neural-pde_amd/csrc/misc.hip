@@ -2,6 +2,7 @@
 // stand-alone diffusion epilogue (GAT mix_features path, where the aggregate passes through Wout
 // before alpha (ax - x) + beta x0 is applied; reference src/function_GAT_attention.py:33-38,56-64).
 #include "common.h"
+#include "epilogue.h"
 
 namespace gnpde {
 namespace {
@@ -587,4 +588,47 @@ int launch_lincomb(const float* base, const float* const* v, const float* coef, 
 extern "C" int gnpde_lincomb(const float* base, const float* const* v, const float* coef, int32_t n_v, int64_t n, float* out,
                              void* stream) {
   return gnpde::launch_lincomb(base, v, coef, n_v, n, out, static_cast<hipStream_t>(stream), nullptr);
+}
+
+// fp32 [n, d] (row stride ld) -> the bf16 shadow layout [n, ld] of the optional gather operand (csrc/spmm.hip): fills the shadow of y0
+// at the start of a solve; every later shadow is written by the kernel that writes the stage input.  One lane per group of four
+// columns; groups that reach past d (padding columns, left alone) and unaligned operands go element by element.
+namespace gnpde {
+namespace {
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void to_bf16_kernel(const float* __restrict__ src, long long n, int d, int ld, int groups,
+                                                         uint16_t* __restrict__ dst) {
+  const long long total = n * groups;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<long long>(gridDim.x) * kBlock) {
+    const long long row = i / groups;
+    const int col = static_cast<int>(i - row * groups) * 4;
+    const size_t off = static_cast<size_t>(row) * ld + col;
+    if (VEC4 && col + 4 <= d) {
+      float v[4];
+      load_vec<4>(src + off, v);
+      *reinterpret_cast<uint2*>(dst + off) = make_uint2(bf16_pack2(v[0], v[1]), bf16_pack2(v[2], v[3]));
+    } else {
+      for (int c = 0; c < 4 && col + c < d; ++c) dst[off + c] = bf16_bits(src[off + c]);
+    }
+  }
+}
+}  // namespace
+
+int launch_to_bf16(const float* src, long long n, int d, int ld, uint16_t* dst, hipStream_t s) {
+  GNPDE_CHECK_ARG(src && dst && n >= 0 && d >= 1 && ld >= d, GNPDE_EINVAL, "to_bf16: bad arguments (n=%lld d=%d ld=%d)", n, d, ld);
+  GNPDE_CHECK_ARG(reinterpret_cast<uintptr_t>(dst) % 2 == 0, GNPDE_EINVAL, "to_bf16: dst is not 2-byte aligned");
+  if (n == 0) return 0;
+  const int groups = (d + 3) / 4;
+  long long blocks = (n * groups + kBlock - 1) / kBlock;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  const bool v4 = ld % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 8 == 0;
+  if (v4) hipLaunchKernelGGL((to_bf16_kernel<true>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, src, n, d, ld, groups, dst);
+  else hipLaunchKernelGGL((to_bf16_kernel<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, src, n, d, ld, groups, dst);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace gnpde
+
+extern "C" int gnpde_to_bf16(const float* src, int64_t n, int32_t d, int32_t ld, void* dst, void* stream) {
+  return gnpde::launch_to_bf16(src, n, d, ld, static_cast<uint16_t*>(dst), static_cast<hipStream_t>(stream));
 }

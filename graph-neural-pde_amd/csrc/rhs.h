@@ -48,7 +48,11 @@ RhsLayout rhs_layout(const gnpde_rhs_t& r);
 int check_rhs(const gnpde_rhs_t* r);
 // Enqueue f(u) with the given epilogue; `ws` follows rhs_layout(r).
 int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& epi, char* ws, const RhsLayout& L,
-                hipStream_t s, const Fork* fork = nullptr, const RhsRecord* record = nullptr);
+                hipStream_t s, const Fork* fork = nullptr, const RhsRecord* record = nullptr, const LoPair* lo = nullptr);
+// lo (optional bf16 gather operand): the aggregation gathers the neighbour rows from lo->u_lo and writes the shadow of epi.out_y to
+// lo->out_y_lo; projection, attention and the row's own term read the fp32 `u`, and the attention stays in launches of its own.
+// Offered for whole-graph descriptors on 16-byte lanes:
+bool rhs_gather_lo_supported(const gnpde_rhs_t& r);
 // epilogue with the descriptor's alpha / beta / x0 filled in
 gnpde_epilogue_t base_epilogue(const gnpde_rhs_t& r);
 

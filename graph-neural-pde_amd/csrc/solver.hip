@@ -74,11 +74,13 @@ int check_rhs(const gnpde_rhs_t* r) {
 
 // Enqueue f(u) with the given epilogue.  `ws` follows rhs_layout.
 int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& epi, char* ws, const RhsLayout& L,
-                hipStream_t s, const Fork* fork, const RhsRecord* record) {
+                hipStream_t s, const Fork* fork, const RhsRecord* record, const LoPair* lo) {
   const gnpde_graph_t* g = r.graph;
   const float* w = r.w_csr;
   if (record != nullptr && rhs_record_stride(r) == 0) record = nullptr;
-  if (record == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && fused_attn_supported(r.att, r.d, r.ld, u, &epi) &&
+  if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
+  // bf16 gather operand: the routes with the attention inside the aggregation kernel are not taken (separate launches run)
+  if (lo == nullptr && record == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && fused_attn_supported(r.att, r.d, r.ld, u, &epi) &&
       reinterpret_cast<uintptr_t>(r.proj_w) % 16 == 0) {
     // scaled-dot attention, softmax over rows: projection + attention + aggregation + epilogue in one pass
     return launch_attn_rhs_fused(g, &r.att, r.proj_w, r.proj_b, u, r.d, r.ld, &epi, ws + L.fused, L.fused_bytes, s);
@@ -115,7 +117,7 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
     }
     at.n_key_rows = r.n_state_rows > g->n ? r.n_state_rows : 0;     // halo rows: the GAT node terms cover them
     const bool padded = (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0;
-    if (record == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && fork == nullptr && r.proj_row_end == 0 && r.n_state_rows <= g->n &&
+    if (lo == nullptr && record == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && fork == nullptr && r.proj_row_end == 0 && r.n_state_rows <= g->n &&
         (r.d % 4 == 0 || padded) && attn_spmm_supported(g, at, r.d, r.ld, u, epi)) {
       // scaled-dot row softmax: the short rows are attended inside the aggregation kernel; only the hub rows' weights are
       // computed ahead (two small launches)
@@ -128,7 +130,13 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
     w = wmean;
   }
   return launch_spmm_rhs(g, w, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, fork,
-                         (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0);
+                         (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0, lo);
+}
+
+bool rhs_gather_lo_supported(const gnpde_rhs_t& r) {
+  const bool padded = (r.flags & GNPDE_RHS_PADDED_ROWS) != 0;
+  return r.ld % 4 == 0 && (r.d % 4 == 0 || padded) && r.d <= 1024 && r.n_state_rows <= r.graph->n && r.proj_row_end == 0 &&
+         r.graph->row_begin == 0;
 }
 
 gnpde_epilogue_t base_epilogue(const gnpde_rhs_t& r) {
@@ -167,9 +175,14 @@ struct gnpde_solver {
   int early_trace_capacity = 0;
   float* tape = nullptr;     // recorded solve (gnpde_solver_set_tape): n_evals + 1 state-sized slots, the stage inputs in evaluation order
   float* tape_rec = nullptr; // ... followed by one RhsRecord per evaluation (GRAND-nl with scaled-dot scores: q||k and the weights)
+  uint16_t* lo = nullptr;    // bf16 gather operand (gnpde_solver_set_gather): one shadow per stage-input buffer, caller's memory
 };
 
 namespace {
+
+// shadows of the stage-input buffers: y and ua (euler, midpoint), + ub and the fourth stage input of the compact rk4
+size_t lo_stride(const gnpde_rhs_t& r) { return align_up(static_cast<size_t>(r.graph->n) * r.ld * 2, 256); }
+int lo_count(int method) { return method == GNPDE_METHOD_RK4 ? 4 : 2; }
 
 size_t solver_layout(const gnpde_rhs_t& r, int method, gnpde_solver* s) {
   const size_t state = align_up(static_cast<size_t>(r.graph->n) * r.ld * 4, 256);
@@ -215,6 +228,21 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
                                    s->early_trace, s->early_trace_capacity, st);
   };
   if (s->early) GNPDE_HIP(hipMemsetAsync(s->early_state, 0, 8 * sizeof(int32_t), st));
+  // bf16 gather operand: shadow b belongs to one stage-input buffer; the kernel that writes a stage input writes its shadow, so
+  // only y0's is filled by a pass of its own.  pair(from, to): gather from shadow `from`, write the shadow of out_y to `to`.
+  const bool lo_on = s->lo != nullptr;
+  auto shadow = [&](int b) { return reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(s->lo) + b * lo_stride(r)); };
+  LoPair lo_store{};
+  auto pair = [&](int from, int to) -> const LoPair* {
+    if (!lo_on) return nullptr;
+    lo_store.u_lo = shadow(from);
+    lo_store.out_y_lo = shadow(to);
+    return &lo_store;
+  };
+  if (lo_on) {
+    const int crc = launch_to_bf16(y, r.graph->n, r.d, r.ld, shadow(0), st);
+    if (crc) return crc;
+  }
   if (s->tape != nullptr) {
     // Recorded solve: the same launches, every stage input written to a slot of its own instead of a recycled buffer -- the record
     // costs no extra pass over the state.  Slot 0 = y0, slot i = the input of evaluation i (rk4: u1..u4 of step n at 4n..4n+3),
@@ -271,12 +299,14 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
   if (s->method == GNPDE_METHOD_EULER) {
     float* cur = y;
     float* nxt = ua;
+    int cur_lo = 0, nxt_lo = 1;
     for (float dt : s->dts) {
       gnpde_epilogue_t e = base_epilogue(r);
       e.stage = GNPDE_STAGE_EULER; e.dt = dt; e.y = cur; e.out_y = nxt;
-      int rc = enqueue_rhs(r, cur, e, rws, s->L, st, fk);
+      int rc = enqueue_rhs(r, cur, e, rws, s->L, st, fk, nullptr, pair(cur_lo, nxt_lo));
       if (rc) return rc;
       float* t = cur; cur = nxt; nxt = t;
+      cur_lo ^= 1; nxt_lo ^= 1;
       rc = evaluate(cur);
       if (rc) return rc;
     }
@@ -290,10 +320,10 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       gnpde_epilogue_t e = base_epilogue(r);
       e.stage = GNPDE_STAGE_LINCOMB; e.y = y; e.n_prev = 0; e.out_k = nullptr;
       e.coef[0] = 0.5f * dt; e.out_y = ua;
-      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk);
+      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
       if (rc) return rc;
       e.coef[0] = dt; e.out_y = y;
-      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk);
+      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0));
       if (rc) return rc;
       rc = evaluate(y);
       if (rc) return rc;
@@ -311,16 +341,16 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       gnpde_epilogue_t e = base_epilogue(r);
       e.dt = dt;
       e.stage = GNPDE_STAGE_RK1C; e.out_y = ua;
-      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk);
+      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK2C; e.y = y; e.out_y = ub;
-      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk);
+      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2));
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK3C; e.k1 = ua; e.out_y = uc;
-      rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk);
+      rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 3));
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK4C; e.k1 = ub; e.out_y = y;
-      rc = enqueue_rhs(r, uc, e, rws, s->L, st, fk);
+      rc = enqueue_rhs(r, uc, e, rws, s->L, st, fk, nullptr, pair(3, 0));
       if (rc) return rc;
       rc = evaluate(y);
       if (rc) return rc;
@@ -331,16 +361,16 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
     gnpde_epilogue_t e = base_epilogue(r);
     e.dt = dt; e.y = y;
     e.stage = GNPDE_STAGE_RK1; e.out_k = k1; e.out_y = ua;
-    int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk);
+    int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
     if (rc) return rc;
     e.stage = GNPDE_STAGE_RK2; e.k1 = k1; e.out_k = k2; e.out_y = ub;
-    rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk);
+    rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2));
     if (rc) return rc;
     e.stage = GNPDE_STAGE_RK3; e.k2 = k2; e.out_k = k3; e.out_y = ua;
-    rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk);
+    rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 1));
     if (rc) return rc;
     e.stage = GNPDE_STAGE_RK4; e.k3 = k3; e.out_k = nullptr; e.out_y = y;
-    rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk);
+    rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0));
     if (rc) return rc;
     rc = evaluate(y);
     if (rc) return rc;
@@ -467,6 +497,8 @@ extern "C" size_t gnpde_solver_tape_bytes(const gnpde_rhs_t* rhs, int32_t method
 
 extern "C" int gnpde_solver_set_tape(gnpde_solver_t* s, void* tape, size_t tape_bytes) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "solver_set_tape: solver is null");
+  GNPDE_CHECK_ARG(tape == nullptr || s->lo == nullptr, GNPDE_EINVAL,
+                  "solver_set_tape: a recorded solve keeps the fp32 gather operand (detach the bf16 one first: gnpde_solver_set_gather(s, 0, NULL, 0))");
   drop_graph(s);
   s->tape = nullptr;
   s->tape_rec = nullptr;
@@ -477,6 +509,39 @@ extern "C" int gnpde_solver_set_tape(gnpde_solver_t* s, void* tape, size_t tape_
   s->tape = static_cast<float*>(tape);
   const size_t state = align_up(static_cast<size_t>(s->rhs.graph->n) * s->rhs.ld * 4, 256);
   s->tape_rec = rhs_record_stride(s->rhs) > 0 ? s->tape + (static_cast<size_t>(s->n_evals) + 1) * (state / 4) : nullptr;
+  return 0;
+}
+
+extern "C" size_t gnpde_solver_gather_bytes(const gnpde_rhs_t* rhs, int32_t method) {
+  if (check_rhs(rhs)) return 0;
+  if (method != GNPDE_METHOD_EULER && method != GNPDE_METHOD_RK4 && method != GNPDE_METHOD_MIDPOINT) {
+    set_error("solver_gather_bytes: bad method %d", method);
+    return 0;
+  }
+  if (!rhs_gather_lo_supported(*rhs)) {
+    set_error("solver_gather_bytes: the bf16 gather operand needs 16-byte lanes of a whole-graph state (d %% 4 == 0, or "
+              "GNPDE_RHS_PADDED_ROWS; ld %% 4 == 0): d=%d ld=%d", rhs->d, rhs->ld);
+    return 0;
+  }
+  return lo_count(method) * lo_stride(*rhs);
+}
+
+extern "C" int gnpde_solver_set_gather(gnpde_solver_t* s, int32_t dtype, void* mem, size_t bytes) {
+  GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "solver_set_gather: solver is null");
+  GNPDE_CHECK_ARG(dtype == GNPDE_GATHER_FP32 || dtype == GNPDE_GATHER_BF16, GNPDE_EINVAL, "solver_set_gather: bad dtype %d", dtype);
+  if (dtype == GNPDE_GATHER_FP32) {
+    drop_graph(s);
+    s->lo = nullptr;
+    return 0;
+  }
+  GNPDE_CHECK_ARG(s->tape == nullptr, GNPDE_EINVAL,
+                  "solver_set_gather: a recorded solve keeps the fp32 gather operand (detach the tape first: gnpde_solver_set_tape(s, NULL, 0))");
+  const size_t need = gnpde_solver_gather_bytes(&s->rhs, s->method);
+  if (need == 0) return GNPDE_ESHAPE;
+  GNPDE_CHECK_ARG(mem != nullptr && reinterpret_cast<uintptr_t>(mem) % 256 == 0 && bytes >= need, GNPDE_EWS,
+                  "solver_set_gather: %zu bytes (need %zu, 256-byte aligned)", bytes, need);
+  drop_graph(s);
+  s->lo = static_cast<uint16_t*>(mem);
   return 0;
 }
 

@@ -35,8 +35,14 @@ struct SpmmArgs {
   int short_rows;        // host-side hint: at least half of the rows have <= 16 entries (-> row pairs for d = 68..128)
   int row_shift;         // rows are dealt to the XCDs in blocks of 2^row_shift rows (xcd_row); < 0: contiguous eighths
   gnpde_epilogue_t ep;
+  // optional bf16 gather operand (kernels instantiated with LO): the neighbour rows come from u_lo [n, ld] instead of u (the row's
+  // own term still reads u), and the epilogue stores the bf16 rounding of out_y to out_y_lo (nullable) as well
+  const uint16_t* __restrict__ u_lo;
+  uint16_t* out_y_lo;
 };
 
+
+inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // Work item of wave `lw` (index local to the XCD) of a block that runs on XCD x = blockIdx % 8.  Every XCD gets every
 // 8th long-row chunk FIRST (512 entries each = the longest-running waves: they start at time 0 and overlap with
@@ -108,7 +114,7 @@ inline unsigned balanced_grid(const SpmmArgs& a, int wpb) {
   return static_cast<unsigned>(blocks * kXcds);
 }
 
-template <int VEC, int L, int K, int U, bool NTI, bool NT, int BLK = kBlock>
+template <int VEC, int L, int K, int U, bool NTI, bool NT, int BLK = kBlock, bool LO = false>
 __global__ __launch_bounds__(BLK) void spmm_rows_kernel(const SpmmArgs a) {
   constexpr int G = kWave / L;
   const int lane = threadIdx.x & (kWave - 1);
@@ -141,11 +147,20 @@ __global__ __launch_bounds__(BLK) void spmm_rows_kernel(const SpmmArgs a) {
       if (e < e1) {  // masked lanes issue no memory request
         const int c = NTI ? __builtin_nontemporal_load(a.colidx + e) : a.colidx[e];
         ww[t] = NTI ? __builtin_nontemporal_load(a.w + e) : a.w[e];
-        const float* src = a.u + static_cast<size_t>(c) * a.ld;
+        if constexpr (LO) {
+          const uint16_t* src = a.u_lo + static_cast<size_t>(c) * a.ld;
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const int col = (k * L + cl) * VEC;
-          if (col < a.d) load_vec<VEC>(src + col, vals[t][k]);
+          for (int k = 0; k < K; ++k) {
+            const int col = (k * L + cl) * VEC;
+            if (col < a.d) load_lo4(src + col, vals[t][k]);
+          }
+        } else {
+          const float* src = a.u + static_cast<size_t>(c) * a.ld;
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            const int col = (k * L + cl) * VEC;
+            if (col < a.d) load_vec<VEC>(src + col, vals[t][k]);
+          }
         }
       }
     }
@@ -192,7 +207,7 @@ __global__ __launch_bounds__(BLK) void spmm_rows_kernel(const SpmmArgs a) {
       const size_t off = static_cast<size_t>(row) * a.ld + col;
       float ui[VEC];
       load_vec<VEC>(a.u + off, ui);
-      epilogue<VEC, NT>(a.ep, alpha, beta, off, acc[k], ui);
+      epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc[k], ui, a.out_y_lo);
     }
   }
 }
@@ -248,9 +263,9 @@ __device__ __forceinline__ bool stage_prefetchable(int stage) {
 }
 
 // k = alpha (ax - u_i) + beta x0_i and the compact / euler / plain stages from operands already in registers
-template <int VEC, bool NT>
+template <int VEC, bool NT, bool LO = false>
 __device__ __forceinline__ void epilogue_pre(const gnpde_epilogue_t& ep, float alpha, float beta, size_t off,
-                                             const float (&ax)[VEC], const Pre<VEC, NT>& p) {
+                                             const float (&ax)[VEC], const Pre<VEC, NT>& p, uint16_t* lo = nullptr) {
   auto st = [](float* q, const float (&v)[VEC]) { if constexpr (NT) store_vec_nt<VEC>(q, v); else store_vec<VEC>(q, v); };
   constexpr float kThird = 1.0f / 3.0f;
   float k[VEC], o[VEC];
@@ -269,26 +284,31 @@ __device__ __forceinline__ void epilogue_pre(const gnpde_epilogue_t& ep, float a
 #pragma unroll
       for (int v = 0; v < VEC; ++v) o[v] = p.y[v] + dt * k[v];
       st(ep.out_y + off, o);
+      if constexpr (LO) store_lo<VEC>(lo, off, o);
       break;
     case GNPDE_STAGE_RK1C:
 #pragma unroll
       for (int v = 0; v < VEC; ++v) o[v] = p.ui[v] + (dt * k[v]) * kThird;
       st(ep.out_y + off, o);
+      if constexpr (LO) store_lo<VEC>(lo, off, o);
       break;
     case GNPDE_STAGE_RK2C:
 #pragma unroll
       for (int v = 0; v < VEC; ++v) o[v] = (2.0f * p.y[v] - p.ui[v]) + dt * k[v];
       st(ep.out_y + off, o);
+      if constexpr (LO) store_lo<VEC>(lo, off, o);
       break;
     case GNPDE_STAGE_RK3C:
 #pragma unroll
       for (int v = 0; v < VEC; ++v) o[v] = (2.0f * p.k1[v] - p.ui[v]) + dt * k[v];
       st(ep.out_y + off, o);
+      if constexpr (LO) store_lo<VEC>(lo, off, o);
       break;
     case GNPDE_STAGE_RK4C:
 #pragma unroll
       for (int v = 0; v < VEC; ++v) o[v] = (((6.0f * p.k1[v] + 3.0f * p.ui[v]) - p.y[v]) + dt * k[v]) * 0.125f;
       st(ep.out_y + off, o);
+      if constexpr (LO) store_lo<VEC>(lo, off, o);
       break;
     default:
       break;
@@ -299,6 +319,7 @@ __device__ __forceinline__ void epilogue_pre(const gnpde_epilogue_t& ep, float a
 // The long-row fold on 16-byte lanes: one wavefront per long row, the epilogue operands requested before the chunk loop and the
 // chunk partials fetched eight at a time (the scalar kernel above walks a chain of dependent-latency loads: 8.4 us for the 204
 // hub rows of the ogbn-arxiv shape, 99 us for the 27 896 of the R-MAT shape).  Same summation: the chunks of a row in chunk order.
+template <bool LO>
 __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs a, const int* __restrict__ long_rows,
                                                                  const int* __restrict__ long_chunk_ptr) {
   constexpr int VEC = 4;
@@ -340,18 +361,18 @@ __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs
     if (plain) {
       store_vec<VEC>(a.plain_out + off, acc);
     } else if (pre_ok) {
-      epilogue_pre<VEC, false>(a.ep, alpha, beta, off, acc, pre);
+      epilogue_pre<VEC, false, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
     } else {
       float ui[VEC];
       load_vec<VEC>(a.u + off, ui);
-      epilogue<VEC, false>(a.ep, alpha, beta, off, acc, ui);
+      epilogue<VEC, false, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
     }
   }
 }
 
 // U gathers of one wave (G neighbours each) from the 64 (column id, weight) pairs held one per lane in cv / wv.
 // G == 1: the entry is wave-uniform -> v_readlane, row base address in SGPRs.  TAIL: entries >= cnt are skipped.
-template <int VEC, int L, int U, bool TAIL, bool FULL>
+template <int VEC, int L, int U, bool TAIL, bool FULL, bool LO = false>
 __device__ __forceinline__ void gather_batch(const SpmmArgs& a, int cv, float wv, int t0, int cnt, int sub, int col,
                                              bool col_ok_rt, float (&acc)[VEC]) {
   const bool col_ok = FULL ? true : col_ok_rt;   // FULL: d == L * VEC, no column predicate
@@ -382,8 +403,13 @@ __device__ __forceinline__ void gather_batch(const SpmmArgs& a, int cv, float wv
   for (int t = 0; t < U; ++t) {
 #pragma unroll
     for (int v = 0; v < VEC; ++v) vals[t][v] = 0.0f;
-    const float* rowp = a.u + static_cast<size_t>(cs[t]) * a.ld;
-    if (oks[t]) load_vec<VEC>(rowp + col, vals[t]);
+    if constexpr (LO) {
+      const uint16_t* rowp = a.u_lo + static_cast<size_t>(cs[t]) * a.ld;
+      if (oks[t]) load_lo4(rowp + col, vals[t]);
+    } else {
+      const float* rowp = a.u + static_cast<size_t>(cs[t]) * a.ld;
+      if (oks[t]) load_vec<VEC>(rowp + col, vals[t]);
+    }
   }
 #pragma unroll
   for (int t = 0; t < U; ++t)
@@ -391,7 +417,7 @@ __device__ __forceinline__ void gather_batch(const SpmmArgs& a, int cv, float wv
     for (int v = 0; v < VEC; ++v) acc[v] = fmaf(ww[t], vals[t][v], acc[v]);
 }
 
-template <int VEC, int L, int U, int BLK, bool PERSIST, bool NT, bool FULL>
+template <int VEC, int L, int U, int BLK, bool PERSIST, bool NT, bool FULL, bool LO = false>
 __global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
   constexpr int G = kWave / L;
   constexpr int WPB = BLK / kWave;
@@ -440,8 +466,8 @@ __global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
       const int cnt = (e1 - base) < kWave ? (e1 - base) : kWave;   // wave-uniform
       // full batches of G*U entries without predicates (all U gathers issue back to back), then one predicated tail
       int t0 = 0;
-      for (; t0 + G * U <= cnt; t0 += G * U) gather_batch<VEC, L, U, false, FULL>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
-      if (t0 < cnt) gather_batch<VEC, L, U, true, FULL>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
+      for (; t0 + G * U <= cnt; t0 += G * U) gather_batch<VEC, L, U, false, FULL, LO>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
+      if (t0 < cnt) gather_batch<VEC, L, U, true, FULL, LO>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
     }
 
     // combine the G neighbour slots (lanes with equal column lane)
@@ -460,11 +486,11 @@ __global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
       continue;
     }
     if (pre_ok) {
-      epilogue_pre<VEC, NT>(a.ep, alpha, beta, off, acc, pre);
+      epilogue_pre<VEC, NT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
     } else {
       float ui[VEC];
       load_vec<VEC>(a.u + off, ui);
-      epilogue<VEC, NT>(a.ep, alpha, beta, off, acc, ui);
+      epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
     }
     if constexpr (!PERSIST) break;
   }
@@ -480,7 +506,7 @@ __global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
 // Each half keeps the wide kernel's summation order -- even entries into one accumulator, odd entries into a second, in
 // CSR order, then even + odd -- so the result is bit-identical to the shared-row mode whatever row a row is paired with.
 // A pair with a longer row falls back to the shared-row mode for its two rows in turn; hub chunks are shared-row items.
-template <int VEC, int U, bool NT, bool FULL>
+template <int VEC, int U, bool NT, bool FULL, bool LO = false>
 __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int e0, int e1, int chunk, int lane, int sub, int col,
                                                 bool col_ok, bool pre_ok, float alpha, float beta) {
   constexpr int L = 32, G = 2;
@@ -505,8 +531,8 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
     const float wv = in ? a.w[me] : 0.0f;
     const int cnt = (e1 - base) < kWave ? (e1 - base) : kWave;
     int t0 = 0;
-    for (; t0 + G * U <= cnt; t0 += G * U) gather_batch<VEC, L, U, false, FULL>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
-    if (t0 < cnt) gather_batch<VEC, L, U, true, FULL>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
+    for (; t0 + G * U <= cnt; t0 += G * U) gather_batch<VEC, L, U, false, FULL, LO>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
+    if (t0 < cnt) gather_batch<VEC, L, U, true, FULL, LO>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) acc[v] += __shfl_xor(acc[v], L, kWave);
@@ -520,15 +546,15 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
     return;
   }
   if (pre_ok) {
-    epilogue_pre<VEC, NT>(a.ep, alpha, beta, off, acc, pre);
+    epilogue_pre<VEC, NT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
   } else {
     float ui[VEC];
     load_vec<VEC>(a.u + off, ui);
-    epilogue<VEC, NT>(a.ep, alpha, beta, off, acc, ui);
+    epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
   }
 }
 
-template <int VEC, int U, int BLK, bool NT, bool FULL>
+template <int VEC, int U, int BLK, bool NT, bool FULL, bool LO = false>
 __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
   constexpr int L = 32;
   constexpr int WPB = BLK / kWave;
@@ -549,7 +575,7 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
     const int row = __builtin_amdgcn_readfirstlane(a.lc_row[chunk]);
     const int e0 = __builtin_amdgcn_readfirstlane(a.lc_begin[chunk]);
     const int e1 = __builtin_amdgcn_readfirstlane(a.lc_end[chunk]);
-    shared_row_item<VEC, U, NT, FULL>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
+    shared_row_item<VEC, U, NT, FULL, LO>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
     return;
   }
   const int per = rows_per_xcd(a);
@@ -573,7 +599,7 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
       if (!hv) continue;
       const int hr = __builtin_amdgcn_readlane(row, h * L);
       const int h0 = __builtin_amdgcn_readlane(e0, h * L), h1 = __builtin_amdgcn_readlane(e1, h * L);
-      shared_row_item<VEC, U, NT, FULL>(a, hr, h0, h1, -1, lane, half, col, col_ok, pre_ok, alpha, beta);
+      shared_row_item<VEC, U, NT, FULL, LO>(a, hr, h0, h1, -1, lane, half, col, col_ok, pre_ok, alpha, beta);
     }
     return;
   }
@@ -615,7 +641,11 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
       const bool ok = col_ok && t0 + t < len;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) vals[t][v] = 0.0f;
-      if (ok) load_vec<VEC>(a.u + static_cast<size_t>(cs[t]) * a.ld + col, vals[t]);
+      if constexpr (LO) {
+        if (ok) load_lo4(a.u_lo + static_cast<size_t>(cs[t]) * a.ld + col, vals[t]);
+      } else {
+        if (ok) load_vec<VEC>(a.u + static_cast<size_t>(cs[t]) * a.ld + col, vals[t]);
+      }
     }
 #pragma unroll
     for (int t = 0; t < U; ++t) {
@@ -637,11 +667,11 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
     return;
   }
   if (pre_ok) {
-    epilogue_pre<VEC, NT>(a.ep, alpha, beta, off, acc, pre);
+    epilogue_pre<VEC, NT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
   } else {
     float ui[VEC];
     load_vec<VEC>(a.u + off, ui);
-    epilogue<VEC, NT>(a.ep, alpha, beta, off, acc, ui);
+    epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
   }
 }
 
@@ -1173,6 +1203,198 @@ int dispatch_rows(const SpmmArgs& a, hipStream_t s) {
 }
 
 
+// bf16 gather operand (16-byte lanes of the state only): the default kernel of every width class with the gather element type
+// switched -- same work items, lane mapping and summation order as the fp32 kernels that dispatch_rows<4> picks by default, so a
+// plain aggregation from a shadow is bit-identical to gnpde_spmm on the widened table.  The A/B-only variants (pair_pipe,
+// pair_cached, the tune codes) have no bf16 form.
+template <int L, int K, int U>
+void launch_rows_lo(const SpmmArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((spmm_rows_kernel<4, L, K, U, false, true, kBlock, true>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
+}
+
+template <int L>
+void launch_wide_lo(const SpmmArgs& a, hipStream_t s) {
+  const unsigned grid = balanced_grid(a, 1);
+  if (a.d == L * 4) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, 64, false, true, true, true>), dim3(grid), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, 64, false, true, false, true>), dim3(grid), dim3(64), 0, s, a);
+}
+
+void launch_pair_lo(const SpmmArgs& a, hipStream_t s) {
+  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
+  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
+  long long blocks = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
+  if (blocks < 1) blocks = 1;
+  const unsigned grid = static_cast<unsigned>(blocks * kXcds);
+  if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, 16, 64, true, true, true>), dim3(grid), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((spmm_pair_kernel<4, 16, 64, true, false, true>), dim3(grid), dim3(64), 0, s, a);
+}
+
+// Row-QUAD form of the row-pair kernel for the bf16 gather operand: a bf16 row of d <= 128 columns is 256 bytes, so with the pair
+// kernel's mapping (32 lanes x 4 elements) a lane gathers 8 bytes per neighbour.  Here 16 lanes x 8 elements cover a row -- 16-byte
+// gathers again -- and the four quarters of a wave take four consecutive rows of <= 32 entries (ids and weights: two coalesced
+// 16-entry loads per quarter).  Per row the summation is the pair kernel's (even entries into one accumulator, odd entries into a
+// second, CSR order, then even + odd), so the results are bit-identical to it.  A quad with a longer row falls back to the
+// shared-row mode (32 x 4) for its rows in turn; hub chunks are shared-row items.  Needs d % 8 == 0, ld % 8 == 0, 16-byte aligned shadows.
+template <int U, bool NT>
+__global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
+  constexpr int VEC = 4, L = 16, E = 8;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int quarter = lane >> 4;
+  const int cl = lane & (L - 1);
+  const int col = cl * E;
+  const bool col_ok = col < a.d;
+  const int xcd = static_cast<int>(blockIdx.x % kXcds);
+  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds));
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, NT>(a.ep.stage);
+  const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
+  const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
+  // the shared-row mode keeps the 32 x 4 mapping
+  const int half = lane >> 5, col4 = (lane & 31) * VEC;
+  const bool col4_ok = col4 < a.d;
+
+  const int cx = chunks_of_xcd(a, xcd);
+  if (lw < cx) {   // hub chunk first (as item_of)
+    const int chunk = a.chunk_begin + lw * kXcds + xcd;
+    const int row = __builtin_amdgcn_readfirstlane(a.lc_row[chunk]);
+    const int e0 = __builtin_amdgcn_readfirstlane(a.lc_begin[chunk]);
+    const int e1 = __builtin_amdgcn_readfirstlane(a.lc_end[chunk]);
+    shared_row_item<VEC, 16, NT, false, true>(a, row, e0, e1, chunk, lane, half, col4, col4_ok, pre_ok, alpha, beta);
+    return;
+  }
+  const int per = rows_per_xcd(a);
+  const int r0 = 4 * (lw - cx);
+  if (r0 >= per) return;
+  int row = xcd_row(a, xcd, r0 + quarter);
+  bool have = row >= 0;
+  if (!have) row = 0;
+  int e0 = 0, e1 = 0;
+  if (have) {
+    e0 = a.rowptr[row];
+    e1 = a.rowptr[row + 1];
+  }
+  if (e1 - e0 > GNPDE_LONG_ROW) have = false;   // processed as chunks
+  const int len = have ? e1 - e0 : 0;
+  int cmax = 0;
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const int lh = __builtin_amdgcn_readlane(len, h * L);
+    cmax = lh > cmax ? lh : cmax;
+  }
+  if (cmax > 2 * L) {                           // a longer row in the quad: the whole wave shares each row in turn
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const int hv = __builtin_amdgcn_readlane(static_cast<int>(have), h * L);
+      if (!hv) continue;
+      const int hr = __builtin_amdgcn_readlane(row, h * L);
+      const int h0 = __builtin_amdgcn_readlane(e0, h * L), h1 = __builtin_amdgcn_readlane(e1, h * L);
+      shared_row_item<VEC, 16, NT, false, true>(a, hr, h0, h1, -1, lane, half, col4, col4_ok, pre_ok, alpha, beta);
+    }
+    return;
+  }
+
+  const size_t off = static_cast<size_t>(row) * a.ld + col;
+  Pre<VEC, NT> pre[2];
+  const bool mine = have && col_ok;
+  if (pre_ok && mine) {
+    auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
+    const int st = a.ep.stage;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const size_t o = off + h * VEC;
+      load_vec<VEC>(a.u + o, pre[h].ui);
+      if (a.ep.x0 != nullptr) ldp(a.ep.x0 + o, pre[h].x0);
+      if (st == GNPDE_STAGE_EULER || st == GNPDE_STAGE_RK2C || st == GNPDE_STAGE_RK4C) ldp(a.ep.y + o, pre[h].y);
+      if (st == GNPDE_STAGE_RK3C || st == GNPDE_STAGE_RK4C) ldp(a.ep.k1 + o, pre[h].k1);
+    }
+  }
+  // the whole row: two coalesced 16-entry loads per quarter
+  const bool in0 = cl < len, in1 = L + cl < len;
+  const int cv0 = in0 ? a.colidx[e0 + cl] : 0, cv1 = in1 ? a.colidx[e0 + L + cl] : 0;
+  const float wv0 = in0 ? a.w[e0 + cl] : 0.0f, wv1 = in1 ? a.w[e0 + L + cl] : 0.0f;
+  float acc0[E], acc1[E];
+#pragma unroll
+  for (int v = 0; v < E; ++v) acc0[v] = acc1[v] = 0.0f;
+  static_assert(U == L, "one batch per 16-entry id register");
+  for (int t0 = 0; t0 < cmax; t0 += U) {
+    const int cv = t0 == 0 ? cv0 : cv1;
+    const float wv = t0 == 0 ? wv0 : wv1;
+    uint4 raw[U];
+    float ww[U];
+    int cs[U];
+#pragma unroll
+    for (int t = 0; t < U; ++t) {
+      cs[t] = __shfl(cv, (quarter << 4) + t, kWave);
+      const float w = __shfl(wv, (quarter << 4) + t, kWave);
+      ww[t] = (col_ok && t0 + t < len) ? w : 0.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < U; ++t) {
+      raw[t] = make_uint4(0u, 0u, 0u, 0u);
+      if (col_ok && t0 + t < len) raw[t] = *reinterpret_cast<const uint4*>(a.u_lo + static_cast<size_t>(cs[t]) * a.ld + col);
+    }
+#pragma unroll
+    for (int t = 0; t < U; ++t) {
+      const float vals[E] = {__uint_as_float(raw[t].x << 16), __uint_as_float(raw[t].x & 0xffff0000u),
+                             __uint_as_float(raw[t].y << 16), __uint_as_float(raw[t].y & 0xffff0000u),
+                             __uint_as_float(raw[t].z << 16), __uint_as_float(raw[t].z & 0xffff0000u),
+                             __uint_as_float(raw[t].w << 16), __uint_as_float(raw[t].w & 0xffff0000u)};
+      if (t % 2 == 0) {
+#pragma unroll
+        for (int v = 0; v < E; ++v) acc0[v] = fmaf(ww[t], vals[v], acc0[v]);
+      } else {
+#pragma unroll
+        for (int v = 0; v < E; ++v) acc1[v] = fmaf(ww[t], vals[v], acc1[v]);
+      }
+    }
+  }
+  if (!mine) return;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const size_t o = off + h * VEC;
+    float acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = acc0[h * VEC + v] + acc1[h * VEC + v];
+    if (a.plain_out != nullptr) {
+      store_vec<VEC>(a.plain_out + o, acc);
+    } else if (pre_ok) {
+      epilogue_pre<VEC, NT, true>(a.ep, alpha, beta, o, acc, pre[h], a.out_y_lo);
+    } else {
+      float ui[VEC];
+      load_vec<VEC>(a.u + o, ui);
+      epilogue<VEC, NT, true>(a.ep, alpha, beta, o, acc, ui, a.out_y_lo);
+    }
+  }
+}
+
+void launch_quad_lo(const SpmmArgs& a, hipStream_t s) {
+  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
+  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
+  long long blocks = (cn + kXcds - 1) / kXcds + (per + 3) / 4;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL((spmm_quad_lo_kernel<16, true>), dim3(static_cast<unsigned>(blocks * kXcds)), dim3(kWave), 0, s, a);
+}
+
+int dispatch_rows_lo(const SpmmArgs& a, hipStream_t s) {
+  const int slots = (a.d + 3) / 4;
+  const bool quad_ok = a.d % 8 == 0 && a.ld % 8 == 0 && aligned(a.u_lo, 16) && aligned(a.out_y_lo, 16);
+  const bool quad = g_tune[GNPDE_TUNE_LO_MAPPING] == 2 && quad_ok;
+  if (slots <= 8) launch_rows_lo<8, 1, 4>(a, s);
+  else if (slots <= 16) launch_rows_lo<16, 1, 4>(a, s);
+  else if (slots <= 32 && a.short_rows && quad) launch_quad_lo(a, s);
+  else if (slots <= 32 && a.short_rows) launch_pair_lo(a, s);
+  else if (slots <= 32) launch_wide_lo<32>(a, s);
+  else if (slots <= 64) launch_wide_lo<64>(a, s);
+  else if (slots <= 128) launch_rows_lo<64, 2, 2>(a, s);
+  else if (slots <= 192) launch_rows_lo<64, 3, 1>(a, s);
+  else if (slots <= 256) launch_rows_lo<64, 4, 1>(a, s);
+  else {
+    set_error("spmm: feature width d=%d too large for 16-byte lanes (max %d)", a.d, 256 * 4);
+    return GNPDE_ESHAPE;
+  }
+  return 0;
+}
+
+
 // ------------------------------------------------------------------------------------------------
 // SDDMM: out[p] = scale * a[row_p] . b[col_p] for every stored entry -- the gradient of the aggregation
 // w.r.t. the edge weights (d w_e = alpha' g_row . x_col), needed when attention_weights carry gradients.
@@ -1290,7 +1512,6 @@ int dispatch_sddmm(const gnpde_graph_t* g, const float* a, const float* b, int d
   return 0;
 }
 
-inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // ------------------------------------------------------------------------------------------------
 // One stage of the native adjoint solve, row side (csrc/adjoint.hip): the aggregation F = alpha (A u - u) + beta x0 with its
@@ -1586,8 +1807,10 @@ namespace {
 
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes, hipStream_t stream,
-                    const Fork* fork, bool padded_rows) {
-  GNPDE_CHECK_ARG(g && u && (w_csr || g->e == 0), GNPDE_EINVAL, "spmm: null pointer");
+                    const Fork* fork, bool padded_rows, const LoPair* lo) {
+  if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
+  // (a plain aggregation from a shadow has no fp32 table at all)
+  GNPDE_CHECK_ARG(g && (u || (lo && plain_out)) && (w_csr || g->e == 0), GNPDE_EINVAL, "spmm: null pointer");
   GNPDE_CHECK_ARG(d >= 1 && ld >= d, GNPDE_EINVAL, "spmm: bad d=%d ld=%d", d, ld);
   GNPDE_CHECK_ARG((epi != nullptr) != (plain_out != nullptr), GNPDE_EINVAL, "spmm: need exactly one of epilogue / plain output");
   if (g->n == 0) return 0;
@@ -1653,8 +1876,17 @@ int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, 
   } else {
     GNPDE_CHECK_ARG(plain_out != u, GNPDE_EINVAL, "spmm: output aliases the gathered operand");
   }
+  if (lo != nullptr) {
+    a.u_lo = lo->u_lo;
+    a.out_y_lo = epi ? lo->out_y_lo : nullptr;
+    GNPDE_CHECK_ARG(a16 && aligned(a.u_lo, 8) && aligned(a.out_y_lo, 8), GNPDE_ESHAPE,
+                    "spmm: the bf16 gather operand needs 16-byte lanes (d %% 4 == 0, or padded rows with ld %% 4 == 0; 16-byte aligned "
+                    "operands, 8-byte aligned shadows): d=%d ld=%d", d, ld);
+    GNPDE_CHECK_ARG(a.out_y_lo == nullptr || a.out_y_lo != a.u_lo, GNPDE_EINVAL, "spmm: a stage must not write the shadow it gathers from");
+  }
   auto run = [&](const SpmmArgs& arg, hipStream_t st) -> int {
     if (arg.chunk_end <= arg.chunk_begin && arg.row_end <= arg.row_begin) return 0;
+    if (lo != nullptr) return dispatch_rows_lo(arg, st);
     if (a16) return dispatch_rows<4>(arg, st);
     if (a8) return dispatch_rows<2>(arg, st);
     return dispatch_rows<1>(arg, st);
@@ -1688,8 +1920,10 @@ int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, 
       if (rc != 0) return rc;
       GNPDE_LAUNCH_CHECK();
     }
-    if (a16)
-      hipLaunchKernelGGL(spmm_long_reduce4_kernel, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
+    if (lo != nullptr)
+      hipLaunchKernelGGL(spmm_long_reduce4_kernel<true>, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
+    else if (a16)
+      hipLaunchKernelGGL(spmm_long_reduce4_kernel<false>, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
     else
       hipLaunchKernelGGL(spmm_long_reduce_kernel, dim3(g->n_long_rows), dim3(kBlock), 0, br, a, g->long_rows,
                          g->long_chunk_ptr);
@@ -1813,4 +2047,23 @@ extern "C" int gnpde_sddmm(const gnpde_graph_t* g, const float* a, int32_t lda, 
   if (rc) return rc;
   GNPDE_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int gnpde_spmm_lo(const gnpde_graph_t* g, const float* w_csr, const void* u_lo, int32_t d, int32_t ld,
+                             float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(out != nullptr && u_lo != nullptr, GNPDE_EINVAL, "spmm_lo: out / u_lo is null");
+  gnpde::LoPair lo;
+  lo.u_lo = static_cast<const uint16_t*>(u_lo);
+  return gnpde::launch_spmm_rhs(g, w_csr, nullptr, d, ld, nullptr, out, workspace, workspace_bytes,
+                                static_cast<hipStream_t>(stream), nullptr, /*padded_rows=*/ld % 4 == 0, &lo);
+}
+
+extern "C" int gnpde_spmm_rhs_lo(const gnpde_graph_t* g, const float* w_csr, const float* u, const void* u_lo, int32_t d, int32_t ld,
+                                 const gnpde_epilogue_t* epi, void* out_y_lo, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(epi != nullptr && u != nullptr && u_lo != nullptr, GNPDE_EINVAL, "spmm_rhs_lo: epilogue / u / u_lo is null");
+  gnpde::LoPair lo;
+  lo.u_lo = static_cast<const uint16_t*>(u_lo);
+  lo.out_y_lo = static_cast<uint16_t*>(out_y_lo);
+  return gnpde::launch_spmm_rhs(g, w_csr, u, d, ld, epi, nullptr, workspace, workspace_bytes,
+                                static_cast<hipStream_t>(stream), nullptr, /*padded_rows=*/ld % 4 == 0, &lo);
 }

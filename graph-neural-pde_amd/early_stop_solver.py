@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .odeint import (time_grid, _native_ok, _solve_native, _solve_fixed_host, _solve_dopri5, _solve_dopri5_native,
-                     _solve_dopri5_device)
+                     _solve_dopri5_device, gather_dtype_requested, _note_gather)
 from . import ops
 
 
@@ -196,5 +196,7 @@ class EarlyStopInt(torch.nn.Module):
     self.solver.m2_weight = self.m2_weight
     self.solver.m2_bias = self.m2_bias
     self.solver.evaluator = self._get_evaluator(y0)
+    gather_dtype_requested(func)      # (a bad opt['gnpde_gather_dtype'] raises whatever path the solve takes)
+    _note_gather(func, 'fp32')        # only the native rk4 solve runs anything else, and says so
     _, solution = self.solver.integrate(times)
     return solution

@@ -6,6 +6,7 @@ Fixed-grid methods (`euler`, `rk4` == torchdiffeq 0.2.1's 3/8-rule rk4_alt_step_
 package's ODEFunc objects run as ONE native solver object whose whole time loop is a captured
 hipGraph (csrc/solver.hip).  Everything else (dopri5, foreign callables, several output times) runs
 the host loops below, which still evaluate f through the native kernels."""
+import contextlib
 import math
 import os
 
@@ -76,8 +77,44 @@ def _native_ok(func, y0, t):
           and len(t) == 2 and not func._needs_grad(y0))
 
 
+def gather_dtype_requested(func):
+  """opt['gnpde_gather_dtype'] (or GNPDE_GATHER_DTYPE): 'fp32' (default) or 'bf16' -- the element type of the neighbour rows the
+  aggregation gathers in no-grad fixed-step solves ("bf16 gather operand").  Anything else raises ValueError."""
+  opt = getattr(func, 'opt', None)
+  v = os.environ.get('GNPDE_GATHER_DTYPE', 'fp32')
+  if hasattr(opt, 'get'):
+    v = opt.get('gnpde_gather_dtype', v)
+  v = str(v).lower()
+  if v not in _lib.GATHER_DTYPES:
+    raise ValueError("gnpde_gather_dtype must be 'fp32' or 'bf16' (got %r)" % (v,))
+  return v
+
+
+_FP32_GATHER_DEPTH = [0]
+
+
+@contextlib.contextmanager
+def _fp32_gather():
+  """Solves inside run with the fp32 gather operand whatever the option says (forward solves of the adjoint method)."""
+  _FP32_GATHER_DEPTH[0] += 1
+  try:
+    yield
+  finally:
+    _FP32_GATHER_DEPTH[0] -= 1
+
+
+def _note_gather(func, used):
+  try:
+    func.gather_dtype_used = used       # what the last solve of this function ran with
+  except AttributeError:
+    pass
+
+
 def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None):
   from . import ops
+  gather = gather_dtype_requested(func)
+  if y0.shape[1] % 4 != 0 or _FP32_GATHER_DEPTH[0]:   # widths whose rows this layer pads, and the forward solve of the adjoint
+    gather = 'fp32'                                   # method, keep the fp32 operand (scope of the option: INTEGRATION.md)
   dts = list(step_sizes(t, step_size))
   n_evals = len(dts) * _EVALS_PER_STEP[method]
   # NFE guard with the reference's semantics (raise at the first evaluation that finds nfe > max_nfe)
@@ -92,7 +129,7 @@ def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None
   view = func._locality_view(y0) if hasattr(func, '_locality_view') else None
   if evaluator is not None and view is not None:
     evaluator = evaluator.relabelled(view)
-  key = (method, tuple(dts), tuple(y0.shape), str(y0.device), id(view))
+  key = (method, tuple(dts), tuple(y0.shape), str(y0.device), id(view), gather)
   ent = st.get(key)
   y0c = y0.detach()
   if ent is None:
@@ -142,7 +179,10 @@ def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None
     ent['sig'] = sig
   if getattr(ent['solver'], 'evaluator', None) is not evaluator:
     ent['solver'].set_early_stop(evaluator)     # per-step early-stopping evaluation inside the same hipGraph
+  if getattr(ent['solver'], 'gather_dtype', 'fp32') != gather:
+    ent['solver'].set_gather(gather)            # raises for a shape the bf16 kernels do not cover: never a silent fp32 run
   ent['solver'].run(ent['y'], use_graph=use_graph)
+  _note_gather(func, gather)
   func.nfe += n_evals
   out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
   out[0].copy_(y0c)
@@ -987,6 +1027,8 @@ def odeint(func, y0, t, *, rtol=1e-7, atol=1e-9, method=None, options=None, use_
     return _solve_tuple(odeint, func, y0, t, dict(rtol=rtol, atol=atol, method=method, options=options, use_graph=use_graph))
   options = dict(options or {})
   method = 'dopri5' if method is None else method
+  gather_dtype_requested(func)      # (a bad value raises whatever path the solve takes)
+  _note_gather(func, 'fp32')        # only the native fixed-step solve below runs anything else
   if method in ('euler', 'rk4', 'midpoint'):
     step_size = options.get('step_size', None)
     if step_size is None:
@@ -1436,7 +1478,8 @@ class _AdjointSolve(torch.autograd.Function):
   @staticmethod
   def forward(ctx, func, y0, t, fwd, adj, *params):
     ctx.func, ctx.adj = func, adj
-    ans = odeint(func, y0.detach(), t, **fwd)
+    with _fp32_gather():      # the forward of an adjoint solve is part of training: it keeps the fp32 gather operand
+      ans = odeint(func, y0.detach(), t, **fwd)
     ctx.save_for_backward(t, ans, *params)
     return ans
 

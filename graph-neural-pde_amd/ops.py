@@ -111,10 +111,54 @@ def make_epilogue(alpha, beta, x0, alpha_sigmoid, stage=_lib.STAGE_RHS, dt=0.0, 
   return e
 
 
-def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out=None, **stage_kw):
-  """f = alpha' (A u - u) + beta x0 with A given by (graph, w_csr); optional fused solver stage."""
+def _check_shadow(t, like, name):
+  """A bf16 shadow [n, d] of the fp32 state `like`: same shape, same row stride (elements), unit column stride."""
+  require_hip(t)
+  if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape != like.shape or t.stride(1) != 1 or t.stride(0) != like.stride(0):
+    raise _lib.GnpdeError('%s must be a bfloat16 [%d, %d] matrix with row stride %d (the state\'s)'
+                          % (name, like.shape[0], like.shape[1], like.stride(0)))
+  return t
+
+
+def to_bf16(x, out=None):
+  """The bf16 shadow of a float32 state [n, d] (round to nearest even, gnpde_to_bf16): same shape and row stride as x -- a padded
+  state (row stride > d) gets a padded shadow whose padding columns are left as allocated (zero)."""
+  require_hip(x)
+  x = _lib.f32rows(x, 'x')
+  n, d = x.shape
+  ld = x.stride(0)
+  if out is None:
+    out = torch.zeros(n, ld, dtype=torch.bfloat16, device=x.device)[:, :d]
+  else:
+    _check_shadow(out, x, 'out')
+  check(_lib.lib().gnpde_to_bf16(ptr(x), n, d, ld, ptr(out), stream_of(x)))
+  return out
+
+
+def spmm_lo(graph, w_csr, u_lo, out=None):
+  """Plain aggregation out = A widen(u_lo), gathered from the bf16 shadow u_lo [n, d] (gnpde_spmm_lo); fp32 accumulation and output.
+  d % 4 != 0 needs a padded shadow (row stride % 4 == 0, as ops.to_bf16 of a padded state gives) and returns a padded output."""
+  require_hip(u_lo, w_csr)
+  if u_lo.dtype != torch.bfloat16 or u_lo.dim() != 2 or u_lo.stride(1) != 1:
+    raise _lib.GnpdeError('u_lo must be a bfloat16 matrix with unit column stride')
+  n, d = u_lo.shape
+  ld = u_lo.stride(0)
+  if out is None:
+    out = torch.zeros(n, ld, dtype=torch.float32, device=u_lo.device)[:, :d]
+  elif out.dtype != torch.float32 or out.shape != u_lo.shape or out.stride(1) != 1 or out.stride(0) != ld:
+    raise _lib.GnpdeError('out must be float32 with the shape and row stride of u_lo')
+  L = _lib.lib()
+  ws = graph.workspace('spmm%d' % d, L.gnpde_spmm_workspace_bytes(graph.ref(), d))
+  check(L.gnpde_spmm_lo(graph.ref(), ptr(w_csr), ptr(u_lo), d, ld, ptr(out), ptr(ws), ws.numel(), stream_of(u_lo)))
+  return out
+
+
+def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out=None, gather_lo=None, **stage_kw):
+  """f = alpha' (A u - u) + beta x0 with A given by (graph, w_csr); optional fused solver stage.
+  gather_lo = (u_lo, out_y_lo): the neighbour rows are gathered from the bf16 shadow u_lo of u (ops.to_bf16) instead of u, and the
+  bf16 rounding of the stage's out_y is written to out_y_lo (None: not written) by the same launch (gnpde_spmm_rhs_lo)."""
   require_hip(u, w_csr, x0)
-  u = f32c(u, 'u')
+  u = _lib.f32rows(u, 'u') if gather_lo is not None else f32c(u, 'u')
   n, d = u.shape
   if n < graph.n:  # (a sharded state carries halo rows after the graph's own rows)
     raise _lib.GnpdeError('state has %d rows but the graph has %d nodes' % (n, graph.n))
@@ -130,6 +174,14 @@ def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out
   epi = make_epilogue(alpha_d, beta_d, x0c, alpha_sigmoid, **stage_kw)
   L = _lib.lib()
   ws = graph.workspace('spmm%d' % d, L.gnpde_spmm_workspace_bytes(graph.ref(), d))
+  if gather_lo is not None:
+    u_lo, out_y_lo = gather_lo
+    _check_shadow(u_lo, u, 'gather_lo[0]')
+    if out_y_lo is not None:
+      _check_shadow(out_y_lo, u, 'gather_lo[1]')
+    check(L.gnpde_spmm_rhs_lo(graph.ref(), ptr(w_csr), ptr(u), ptr(u_lo), d, u.stride(0), ctypes.byref(epi), ptr(out_y_lo), ptr(ws),
+                              ws.numel(), stream_of(u)))
+    return out
   check(L.gnpde_spmm_rhs(graph.ref(), ptr(w_csr), ptr(u), d, u.stride(0), ctypes.byref(epi), ptr(ws), ws.numel(),
                          stream_of(u)))
   return out
@@ -736,6 +788,24 @@ class FixedStepSolver(object):
                                           ptr(evaluator.trace) if evaluator.trace_capacity else None,
                                           evaluator.trace_capacity))
     self.evaluator = evaluator
+
+  def set_gather(self, dtype):
+    """Gather operand of the aggregation in the following runs (gnpde_solver_set_gather): 'bf16' attaches a bf16 shadow per
+    stage-input buffer (device memory owned here), 'fp32' detaches.  Raises for a shape out of scope and while a tape is attached."""
+    L = _lib.lib()
+    if dtype not in _lib.GATHER_DTYPES:
+      raise ValueError("gather dtype must be 'fp32' or 'bf16' (got %r)" % (dtype,))
+    if dtype == 'fp32':
+      check(L.gnpde_solver_set_gather(self.handle, _lib.GATHER_FP32, None, 0))
+      self.gather_mem = None
+    else:
+      nbytes = int(L.gnpde_solver_gather_bytes(self.desc.ref(), self.method))
+      if nbytes == 0:
+        raise _lib.GnpdeError('bf16 gather operand: %s' % L.gnpde_last_error().decode(errors='replace'))
+      mem = torch.zeros(nbytes, dtype=torch.uint8, device=self.ws.device)
+      check(L.gnpde_solver_set_gather(self.handle, _lib.GATHER_BF16, ptr(mem), mem.numel()))
+      self.gather_mem = mem
+    self.gather_dtype = dtype
 
   def set_tape(self, on=True):
     """Record the stage inputs of the following runs (gnpde_solver_set_tape): the tape is zero-filled device memory owned here."""

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 7   /* 7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 8   /* 8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -243,6 +243,23 @@ int gnpde_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, i
  * mix_features path, src/function_GAT_attention.py:33-36). */
 int gnpde_spmm(const gnpde_graph_t* g, const float* w_csr, const float* u, int32_t d, int32_t ld,
                float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Optional bf16 GATHER operand (mixed precision, opt-in).  The aggregation is bound by the bytes of the neighbour rows it gathers;
+ * these entry points gather them from a bf16 "shadow" of the stage input -- [n, ld] bf16 bit patterns (round to nearest even) with
+ * the state's ld, 8-byte aligned rows -- and keep everything else fp32: the accumulation, the row's own -u_i term (read from `u`),
+ * the source term, the stage algebra, the outputs.  One evaluation differs from the fp32 one by at most
+ * alpha' * 2^-8 * sum_e |w_e| |u[col_e]| per element.  Only 16-byte lanes: ld % 4 == 0 and 16-byte aligned fp32 operands, anything else
+ * returns GNPDE_ESHAPE.  A width d % 4 != 0 is taken with ld % 4 == 0 under the contract of GNPDE_RHS_PADDED_ROWS: the columns [d, ld) of
+ * EVERY operand, shadows and outputs included, are padding of whole [n, ld] allocations that may be read and overwritten.
+ *   gnpde_to_bf16      dst[i, j] = bf16(src[i, j]) for j < d; row stride ld on both sides, padding columns are left alone
+ *   gnpde_spmm_lo      out[i] = sum_e w[e] * u_lo[col_e]                       (plain aggregation from a given shadow)
+ *   gnpde_spmm_rhs_lo  gnpde_spmm_rhs with the neighbour rows gathered from u_lo; out_y_lo (NULL, or a shadow other than u_lo)
+ *                      receives the bf16 rounding of epi->out_y, written by the same kernel from the registers that hold out_y */
+int gnpde_to_bf16(const float* src, int64_t n, int32_t d, int32_t ld, void* dst, void* stream);
+int gnpde_spmm_lo(const gnpde_graph_t* g, const float* w_csr, const void* u_lo, int32_t d, int32_t ld,
+                  float* out, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_spmm_rhs_lo(const gnpde_graph_t* g, const float* w_csr, const float* u, const void* u_lo, int32_t d, int32_t ld,
+                      const gnpde_epilogue_t* epi, void* out_y_lo, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Sampled dense-dense product on the graph pattern: out_csr[p] = s * a[row_p] . b[col_p], with
  * s = 1 (scale NULL), *scale, or sigmoid(*scale).  This is the gradient of gnpde_spmm_rhs w.r.t. the
@@ -461,6 +478,19 @@ int gnpde_solver_run(gnpde_solver_t* s, float* y, int32_t use_graph, void* strea
  * tape == NULL detaches.  The reverse sweep is gnpde_adjoint_set_tape + gnpde_adjoint_run below. */
 size_t gnpde_solver_tape_bytes(const gnpde_rhs_t* rhs, int32_t method, int32_t n_steps);
 int    gnpde_solver_set_tape(gnpde_solver_t* s, void* tape, size_t tape_bytes);
+
+/* bf16 gather operand of a fixed-step solve (see gnpde_spmm_rhs_lo): with dtype = GNPDE_GATHER_BF16 every stage-input buffer of
+ * euler / midpoint / rk4 gets a shadow in `mem` (caller's device memory, 256-byte aligned, gnpde_solver_gather_bytes bytes); the kernel
+ * that writes a stage input writes its shadow, y0's is filled by gnpde_to_bf16 at the start of a run, and a stage never writes the
+ * shadow it gathers from.  The attention then always runs in launches of its own.  The state the caller gets back is fp32;
+ * results are deterministic but differ from the fp32 solve by the rounding of the gathered rows.  dtype = GNPDE_GATHER_FP32
+ * detaches.  Either call drops a captured hipGraph.  Excludes a tape: GNPDE_EINVAL while one is attached, and
+ * gnpde_solver_set_tape refuses while the mode is on.  gnpde_solver_gather_bytes returns 0 with gnpde_last_error set when the
+ * shape is out of scope (no 16-byte lanes, partitioned descriptors). */
+#define GNPDE_GATHER_FP32 0
+#define GNPDE_GATHER_BF16 1
+size_t gnpde_solver_gather_bytes(const gnpde_rhs_t* rhs, int32_t method);
+int    gnpde_solver_set_gather(gnpde_solver_t* s, int32_t dtype, void* mem, size_t bytes);
 
 /* The q||k projection of SpGraphTransAttentionLayer (nn.Linear Q and K, reference src/function_transformer_attention.py:174-175) as TWO
  * tables q [n, A], k [n, A] instead of interleaved rows [n, 2A]: when a key row is shorter than a 128-byte cache line (A <= 16) the
