@@ -21,10 +21,12 @@ from .block_transformer_rewiring import RewireAttODEblock
 from .early_stop_solver import EarlyStopInt, EarlyStopRK4, EarlyStopDopri5
 from .model_configurations import set_block, set_function, BlockNotDefined, FunctionNotDefined
 from .GNN import GNN, BaseGNN
+from .GNN_KNN import GNN_KNN
+from . import graph_rewiring
 from . import synthetic
 
 __all__ = ['GnpdeError', 'build', 'lib', 'CSRGraph', 'graph_of', 'partition_rows', 'ops', 'MaxNFEException',
            'get_rw_adj', 'gcn_norm_fill_val', 'add_remaining_self_loops', 'odeint', 'odeint_adjoint', 'time_grid',
            'ODEFunc', 'ODEblock', 'LaplacianODEFunc', 'ODEFuncTransformerAtt', 'SpGraphTransAttentionLayer',
            'ODEFuncAtt', 'SpGraphAttentionLayer', 'ConstantODEblock', 'AttODEblock', 'MixedODEblock', 'HardAttODEblock', 'RewireAttODEblock', 'EarlyStopInt', 'EarlyStopRK4', 'EarlyStopDopri5', 'set_block', 'set_function',
-           'synthetic']
+           'GNN_KNN', 'graph_rewiring', 'synthetic']

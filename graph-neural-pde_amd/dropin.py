@@ -6,7 +6,7 @@ ODEFuncTransformerAtt`, src/model_configurations.py:1-9; `from base_classes impo
 early_stop_solver import EarlyStopInt`, src/GNN_early.py:10).  `install()` answers those imports with the modules of this
 package, whatever the order of `sys.path`:
 
-    python -m gnpde_amd.dropin [--native-gnn] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
+    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
 
 or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before the first import of a reference module.
 
@@ -15,7 +15,10 @@ or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before th
   regulariser registry `REGULARIZATION_FNS`, ...) with `ODEFunc`, `ODEblock` and `RegularizedODEfunc` replaced by this
   package's -- the reference file is searched on `sys.path` at that moment, so the path may be set up after `install()`;
 * `GNN` (optional, `native_gnn=True` / `--native-gnn`): the model of `gnpde_amd/GNN.py`, whose encoder and `relu -> m2`
-  decoder are single native launches at test time; without it the reference's own `GNN.py` runs over the classes above.
+  decoder are single native launches at test time; without it the reference's own `GNN.py` runs over the classes above;
+* `graph_rewiring` (optional, `native_knn=True` / `--native-knn`): merged like `base_classes` -- the reference's own module with
+  `KNN` replaced by the native search of `gnpde_amd/graph_rewiring.py`.  `apply_KNN` looks `KNN` up when it is called, so
+  `run_GNN.py --rewire_KNN` then runs the native kernel; with no reference file on the path the module is this package's alone.
 """
 import importlib
 import importlib.abc
@@ -39,6 +42,11 @@ MODULES = {
 NATIVE_GNN = {'GNN': 'gnpde_amd.GNN'}                                            # GNN, BaseGNN (optional)
 MERGED = 'base_classes'
 OVERRIDES = ('ODEFunc', 'ODEblock', 'RegularizedODEfunc')                        # what base_classes takes from this package
+# merged modules: reference module name -> (module of this package, names taken from it, standalone).  The rest of the module
+# is the reference's own file where one is on sys.path; `standalone`: without such a file the module is this package's own, and
+# with one the reference's functions see the replaced names too (they look their siblings up when called: apply_KNN -> KNN).
+MERGES = {MERGED: ('gnpde_amd.base_classes', OVERRIDES, False)}
+NATIVE_KNN = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('KNN',), True)}    # optional: the native neighbour search
 
 
 def _reference_file(name):
@@ -51,11 +59,15 @@ def _reference_file(name):
   return None
 
 
-class _MergedBaseClasses(importlib.abc.MetaPathFinder, importlib.abc.Loader):
-  """`import base_classes`: the reference's module with the three hot-path types replaced (see the module docstring)."""
+class _MergedModules(importlib.abc.MetaPathFinder, importlib.abc.Loader):
+  """`import <name>` for the names of `table`: the reference's module with the listed names replaced by this package's (see
+  the module docstring); without a reference file on the path, this package's module alone."""
+
+  def __init__(self):
+    self.table = dict(MERGES)
 
   def find_spec(self, fullname, path=None, target=None):
-    if fullname != MERGED:
+    if fullname not in self.table:
       return None
     return importlib.util.spec_from_loader(fullname, self)
 
@@ -63,32 +75,44 @@ class _MergedBaseClasses(importlib.abc.MetaPathFinder, importlib.abc.Loader):
     return None
 
   def exec_module(self, module):
-    ref_path = _reference_file(MERGED)
+    name = module.__name__
+    target, overrides, standalone = self.table[name]
+    ours = importlib.import_module(target)
+    ref_path = _reference_file(name)
     if ref_path is not None:
-      spec = importlib.util.spec_from_file_location('_reference_' + MERGED, ref_path)
+      spec = importlib.util.spec_from_file_location('_reference_' + name, ref_path)
       ref = importlib.util.module_from_spec(spec)
       sys.modules[spec.name] = ref
       spec.loader.exec_module(ref)
-      for name in dir(ref):
-        if not name.startswith('__'):
-          setattr(module, name, getattr(ref, name))
+      for attr in dir(ref):
+        if not attr.startswith('__'):
+          setattr(module, attr, getattr(ref, attr))
       module.__file__ = ref_path
-    ours = importlib.import_module('gnpde_amd.base_classes')
-    for name in OVERRIDES:
-      setattr(module, name, getattr(ours, name))
+      if standalone:
+        for attr in overrides:
+          setattr(ref, attr, getattr(ours, attr))
+    elif standalone:
+      for attr in dir(ours):
+        if not attr.startswith('__'):
+          setattr(module, attr, getattr(ours, attr))
+    for attr in overrides:
+      setattr(module, attr, getattr(ours, attr))
     module.__gnpde_reference__ = ref_path
 
 
-_finder = _MergedBaseClasses()
+_finder = _MergedModules()
 
 
 def installed():
   return _finder in sys.meta_path
 
 
-def install(native_gnn=False):
+def install(native_gnn=False, native_knn=False):
   """Answer the reference's module names with this package (idempotent).  Returns the list of names now served."""
-  already = {name: sys.modules[name] for name in list(MODULES) + [MERGED] if name in sys.modules}
+  merges = dict(MERGES)
+  if native_knn:
+    merges.update(NATIVE_KNN)
+  already = {name: sys.modules[name] for name in list(MODULES) + list(merges) if name in sys.modules}
   table = dict(MODULES)
   if native_gnn:
     table.update(NATIVE_GNN)
@@ -99,16 +123,19 @@ def install(native_gnn=False):
                       'first import of a reference module' % ', '.join(sorted(foreign)))
   for name, target in table.items():
     sys.modules[name] = importlib.import_module(target)
+  _finder.table = merges
   if _finder not in sys.meta_path:
     sys.meta_path.insert(0, _finder)
-  return sorted(table) + [MERGED]
+  return sorted(table) + [MERGED] + sorted(n for n in merges if n != MERGED)
 
 
 def uninstall():
   """Undo install() (tests)."""
   if _finder in sys.meta_path:
     sys.meta_path.remove(_finder)
-  for name in list(MODULES) + list(NATIVE_GNN) + [MERGED, '_reference_' + MERGED]:
+  _finder.table = dict(MERGES)
+  merged = list(MERGES) + list(NATIVE_KNN)
+  for name in list(MODULES) + list(NATIVE_GNN) + merged + ['_reference_' + m for m in merged]:
     m = sys.modules.get(name)
     if isinstance(m, types.ModuleType) and (getattr(m, '__name__', '').startswith('gnpde_amd') or
                                             hasattr(m, '__gnpde_reference__') or name.startswith('_reference_')):
@@ -116,24 +143,27 @@ def uninstall():
 
 
 def main(argv=None):
-  """python -m gnpde_amd.dropin [--native-gnn] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
+  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
   to the front of sys.path, as `python SCRIPT` would put it)."""
   import runpy
   argv = list(sys.argv[1:] if argv is None else argv)
   native = False
+  native_knn = False
   while argv and argv[0].startswith('--'):
     flag = argv.pop(0)
     if flag == '--native-gnn':
       native = True
+    elif flag == '--native-knn':
+      native_knn = True
     else:
-      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] SCRIPT [ARGS...]' % flag)
+      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] SCRIPT [ARGS...]' % flag)
   if not argv:
-    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] SCRIPT [ARGS...]')
+    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] SCRIPT [ARGS...]')
   script = os.path.abspath(argv[0])
   if not os.path.isfile(script):
     raise SystemExit('gnpde_amd.dropin: no such script: %s' % argv[0])
   sys.path.insert(0, os.path.dirname(script))
-  install(native_gnn=native)
+  install(native_gnn=native, native_knn=native_knn)
   sys.argv = [script] + argv[1:]
   runpy.run_path(script, run_name='__main__')
 

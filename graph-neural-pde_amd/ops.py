@@ -284,6 +284,32 @@ def threshold_edges(edge_index, score, threshold, norm_idx, n_nodes):
   return out_ei[:, :k].contiguous(), out_w[:k].clone()
 
 
+KNN_MAX_K = 128
+
+
+def knn(x, k, return_dist=False):
+  """The k nearest rows of every row of x ([n, d] float32 on a HIP device; padded rows with unit column stride are read in
+  place) in squared Euclidean distance, the row itself included: indices int64 [n, k], ascending by (distance, index), and with
+  return_dist the distances [n, k] (gnpde_knn: distance tiles on the fp32 matrix cores, selection in LDS).  Replaces the pykeops
+  argKmin of the reference's graph_rewiring.KNN.  1 <= k <= min(n, 128)."""
+  if not isinstance(x, torch.Tensor) or x.dim() != 2:
+    raise _lib.GnpdeError('knn: x must be a [n, d] tensor')
+  require_hip(x)
+  x = _lib.f32rows(x.detach(), 'knn input')
+  n, d = x.shape
+  k = int(k)
+  if d < 1 or k < 1 or k > n or k > KNN_MAX_K:
+    raise _lib.GnpdeError('knn: k = %d outside 1 .. min(n = %d, %d) (d = %d)' % (k, n, KNN_MAX_K, d))
+  if n >= 2 ** 31 or x.stride(0) >= 2 ** 31:
+    raise _lib.GnpdeError('knn: n = %d exceeds int32 indices' % n)
+  L = _lib.lib()
+  idx = torch.empty(n, k, dtype=torch.int64, device=x.device)
+  dist = torch.empty(n, k, dtype=torch.float32, device=x.device) if return_dist else None
+  ws = torch.empty(max(int(L.gnpde_knn_workspace_bytes(n, d, k)), 1), dtype=torch.uint8, device=x.device)
+  check(L.gnpde_knn(ptr(x), n, d, x.stride(0), k, ptr(idx), ptr(dist), ptr(ws), ws.numel(), stream_of(x)))
+  return (idx, dist) if return_dist else idx
+
+
 def two_hop(graph, weight):
   """(edge_index [2, nnz] int64, value [nnz]) of coalesce(A ++ offdiag(A A)) / 2 for the operator A = (graph, weight in the
   caller's edge order): the densification step of the rewiring block (gnpde_two_hop_count / _fill); one host read for nnz."""

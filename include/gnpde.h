@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 8   /* 8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 9   /* 9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -757,6 +757,19 @@ size_t gnpde_threshold_edges_workspace_bytes(int64_t n_edges, int32_t n_nodes);
 int gnpde_threshold_edges(const int64_t* edge_index, const float* score, int64_t n_edges, const float* threshold,
                           int32_t norm_idx, int32_t n_nodes, int64_t* out_edge_index, float* out_weight, int64_t* out_count,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* k-nearest-neighbour rewiring in feature space (BLEND, `--rewire_KNN`; reference src/graph_rewiring.py:120-126, a pykeops
+ * LazyTensor.argKmin):  for every row i of x ([n, d] fp32, row stride ldx >= d) the k smallest D_ij = |x_i - x_j|^2 over ALL j, the
+ * diagonal included, as idx [n, k] int64 and (dist != NULL) dist [n, k] fp32.  One fused kernel forms the distance tiles on the fp32
+ * matrix cores (D = |x_i|^2 + |x_j|^2 - 2 x_i.x_j, clamped at 0, D_ii = 0 exactly) and selects in LDS; no [n, n] or [chunk, n] array
+ * is written.  A row's result is ascending by the computed distance, equal distances by ascending column (KeOps leaves tie order
+ * unspecified; this is this library's definition); no atomics: bit-identical from run to run.  For few rows the column range is
+ * split S ways over workgroups (partial lists in the workspace, then a merge launch); S follows from n and the CU count, or from
+ * gnpde_tune(19, S).  The workspace size depends on S: query it after any gnpde_tune call.
+ * Limits: 1 <= k <= min(n, 128), d >= 1, n <= INT32_MAX; otherwise GNPDE_ESHAPE / GNPDE_EINVAL (gnpde_knn_workspace_bytes: 0). */
+size_t gnpde_knn_workspace_bytes(int64_t n, int32_t d, int32_t k);
+int gnpde_knn(const float* x, int32_t n, int32_t d, int32_t ldx, int32_t k, int64_t* idx, float* dist, void* workspace,
+              size_t workspace_bytes, void* stream);
 
 /* Two-hop densification of the rewiring block (new_edges = 'k_hop_att', reference src/block_transformer_rewiring.py:68-86):
  *   S = coalesce(A ++ offdiag(A A)) / 2, i.e. torch_sparse.spspmm(A, A) -> remove_self_loops -> cat with A -> / 2 ->
