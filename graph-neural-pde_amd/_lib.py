@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 9      # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 10     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
@@ -148,6 +148,8 @@ PROTOTYPES = {
                                          c_float_p, ctypes.c_int32, c_vp, ctypes.c_size_t]),
   'gnpde_solver_run': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_adjoint_grad_floats': (ctypes.c_int, [ctypes.POINTER(RhsStruct)]),
+  'gnpde_split_kernel_grad_floats': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+  'gnpde_split_kernel_grads': (ctypes.c_int, [c_vp] * 7 + [ctypes.c_int32] * 5 + [c_vp, c_vp]),
   'gnpde_adjoint_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(RhsStruct), ctypes.POINTER(GraphStruct), ctypes.c_int32]),
   'gnpde_adjoint_create': (ctypes.c_int, [ctypes.POINTER(c_vp), ctypes.POINTER(RhsStruct), ctypes.POINTER(GraphStruct), c_vp, c_vp, c_vp,
                                           ctypes.c_int32, c_float_p, ctypes.c_int32, c_vp, ctypes.c_size_t]),

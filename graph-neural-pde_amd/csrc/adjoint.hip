@@ -439,21 +439,23 @@ __global__ __launch_bounds__(kBlock) void gat_dwx_kernel(const float* __restrict
 //     d q_ih = (T_ih - S1_ih q_ih) / l^2,   d k_jh = (U_jh - S2_jh k_jh) / l^2,
 //     d ov = 2 sum_ih S1_ih / ov,   d l = sum_e c_e |q_i - k_j|^2 / l^3 = sum_ih (S1_ih |q_ih|^2 - 2 q_ih . T_ih + S2_ih |k_ih|^2) / l^3.
 // In place on dqk = [T | U] (interleaved rows [n, 2A]); block b of the slab grid also leaves its share of (d ov, d l) in
-// partial[b][slot], partial[b][slot + 1].  One thread per column of the 2A-wide row, rows of the slab in order.
+// partial[b][slot], partial[b][slot + 1].  A thread walks the columns threadIdx.x, threadIdx.x + kBlock, ... of the 2A-wide row (2A <= 512:
+// the BLEND split kernel at the Cora width runs as one exp kernel of width 256) -- one column per thread up to 2A = kBlock, where the
+// sums are those of the one-column form term by term -- and the rows of the slab in order under each column; the scalar partials are
+// folded over the lanes, then the waves, in a fixed order.
 __global__ __launch_bounds__(kBlock) void exp_node_bwd_kernel(const float* __restrict__ s1, const float* __restrict__ s2, const float* __restrict__ q,
                                                              const float* __restrict__ k, int ldq, float* __restrict__ dqk, int n, int A, int h,
                                                              const float* __restrict__ lengthscale, const float* __restrict__ output_var,
                                                              int rows_per_block, float* __restrict__ partial, int stride, int slot) {
   __shared__ float red[2][kWavesPerBlock];
   const int dk = A / h;
-  const int col = threadIdx.x;                 // [0, 2A): q side then k side
   const int r0 = static_cast<int>(blockIdx.x) * rows_per_block;
   int r1 = r0 + rows_per_block;
   if (r1 > n) r1 = n;
   const float l = *lengthscale, ov = *output_var;
   const float inv_l2 = 1.0f / (l * l);
   float acc_l = 0.f, acc_ov = 0.f;
-  if (col < 2 * A) {
+  for (int col = threadIdx.x; col < 2 * A; col += kBlock) {      // [0, 2A): q side then k side
     const bool kside = col >= A;
     const int c = kside ? col - A : col;
     const int hh = c / dk;
@@ -474,6 +476,82 @@ __global__ __launch_bounds__(kBlock) void exp_node_bwd_kernel(const float* __res
     float* out = partial + static_cast<size_t>(blockIdx.x) * stride + slot;
     out[0] = 2.0f * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / ov;
     out[1] = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (l * l * l);
+  }
+}
+
+// ---- BLEND split kernel (reference src/function_transformer_attention.py:133-171): the layer runs as ONE exp kernel over the derived
+// projection Wcat [4A, d], bcat [4A] (per head the d_k rows of Qx / l_x on the feature and label columns, then the d_k rows of Qp / l_p
+// on the positional columns; the k half likewise), output_var = ov_x ov_p, lengthscale = 1.  The chain rule from the gradients of the
+// derived operands back to the twelve parameters of the layer, one launch:
+//   blocks 0, 1   d l_x / d l_p = -(1 / l) sum (d Wcat . Wcat + d bcat . bcat) over the feature / positional rows of both halves (Wcat is
+//                 zero wherever d Wcat has no source, so whole rows are summed), in double, strided over the threads, folded over the
+//                 lanes and the waves in a fixed order; block 0 also d ov_x = d ov ov_p, d ov_p = d ov ov_x
+//   blocks 2..    the weights and biases: out = d Wcat (or d bcat) at the source's place, divided by its length scale
+struct SplitGradArgs {
+  const float* __restrict__ g;        // d Wcat [4A, d], d bcat [4A], d ov, (d lengthscale: not a parameter)
+  const float* __restrict__ wcat;     // [4A, d]
+  const float* __restrict__ bcat;     // [4A]
+  const float* __restrict__ lx; const float* __restrict__ lp; const float* __restrict__ ovx; const float* __restrict__ ovp;
+  int h, dk, d, f0, p0;
+  float* __restrict__ out;            // d Qx.w [A, d - p0], d Qx.b [A], d Kx.w, d Kx.b, d Qp.w [A, p0], d Qp.b [A], d Kp.w, d Kp.b, d l_x, d l_p, d ov_x, d ov_p
+};
+
+__global__ __launch_bounds__(kBlock) void split_kernel_grads_kernel(const SplitGradArgs a) {
+  const int A = a.h * a.dk, d = a.d, fx = d - a.p0;
+  const long long nx = static_cast<long long>(A) * (fx + 1), np = static_cast<long long>(A) * (a.p0 + 1);    // floats of one (weight, bias) pair
+  const float* gb = a.g + static_cast<size_t>(4 * A) * d;
+  if (blockIdx.x < 2) {
+    __shared__ double red[kWavesPerBlock];
+    const bool pos = blockIdx.x == 1;
+    // item t of the sum: row (half, head, c) of this block's kind, entry e of the row's d weights and one bias
+    const long long items = static_cast<long long>(2 * A) * (d + 1);
+    double acc = 0.0;
+    for (long long t = threadIdx.x; t < items; t += kBlock) {
+      const int rr = static_cast<int>(t / (d + 1)), e = static_cast<int>(t - static_cast<long long>(rr) * (d + 1));
+      const int half = rr / A, hc = rr - half * A;
+      const int row = half * 2 * A + (hc / a.dk) * 2 * a.dk + (pos ? a.dk : 0) + hc % a.dk;
+      const float gv = e < d ? a.g[static_cast<size_t>(row) * d + e] : gb[row];
+      const float wv = e < d ? a.wcat[static_cast<size_t>(row) * d + e] : a.bcat[row];
+      acc += static_cast<double>(gv) * static_cast<double>(wv);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float* tail = a.out + 2 * nx + 2 * np;
+      const double l = static_cast<double>(pos ? *a.lp : *a.lx);
+      tail[pos ? 1 : 0] = static_cast<float>(-((red[0] + red[1]) + (red[2] + red[3])) / l);
+      if (!pos) {
+        const float dov = a.g[static_cast<size_t>(4 * A) * d + 4 * A];
+        tail[2] = dov * *a.ovp;
+        tail[3] = dov * *a.ovx;
+      }
+    }
+    return;
+  }
+  const float lx = *a.lx, lp = *a.lp;
+  const long long total = 2 * nx + 2 * np;
+  for (long long i = static_cast<long long>(blockIdx.x - 2) * kBlock + threadIdx.x; i < total; i += static_cast<long long>(gridDim.x - 2) * kBlock) {
+    const bool pos = i >= 2 * nx;
+    const long long j = pos ? i - 2 * nx : i;
+    const long long per = pos ? np : nx;
+    const int half = j >= per ? 1 : 0;
+    const long long o = j - half * per;
+    const int w = pos ? a.p0 : fx;                     // columns of the source weight
+    const long long nw = static_cast<long long>(A) * w;
+    const bool bias = o >= nw;
+    const int r = static_cast<int>(bias ? o - nw : o / w);              // row h d_k + c of the source
+    const int row = half * 2 * A + (r / a.dk) * 2 * a.dk + (pos ? a.dk : 0) + r % a.dk;
+    float v;
+    if (bias) {
+      v = gb[row];
+    } else {
+      const int jc = static_cast<int>(o - static_cast<long long>(r) * w);
+      const int col = pos ? a.f0 + jc : (jc < a.f0 ? jc : a.p0 + jc);   // label columns follow the positional block
+      v = a.g[static_cast<size_t>(row) * d + col];
+    }
+    a.out[i] = v / (pos ? lp : lx);
   }
 }
 
@@ -587,8 +665,8 @@ int check_adjoint(const gnpde_rhs_t* rhs, const gnpde_graph_t* gt, int method) {
     const bool unit = at.type == GNPDE_ATT_COSINE || at.type == GNPDE_ATT_PEARSON;
     const bool expk = at.type == GNPDE_ATT_EXP_KERNEL;
     GNPDE_CHECK_ARG(at.type == GNPDE_ATT_SCALED_DOT || unit || expk, GNPDE_ESHAPE, "adjoint: scaled-dot, cosine_sim, pearson and exp_kernel scores");
-    GNPDE_CHECK_ARG(!expk || (at.output_var && at.lengthscale && 2 * at.att_dim <= kBlock && at.heads <= kGatMaxHeads), GNPDE_ESHAPE,
-                    "adjoint (exp kernel): scalars missing, attention_dim > 128 or more than 8 heads");
+    GNPDE_CHECK_ARG(!expk || (at.output_var && at.lengthscale && at.att_dim <= kBlock && at.heads <= kGatMaxHeads), GNPDE_ESHAPE,
+                    "adjoint (exp kernel): scalars missing, attention_dim > 256 or more than 8 heads");
     GNPDE_CHECK_ARG(!unit || (at.heads >= 1 && normalise_heads_bwd_supported(at.att_dim, at.heads)), GNPDE_ESHAPE,
                     "adjoint: cosine_sim / pearson need d_k in {4, 8, 16}");
     // scaled dot: any d_k (d q / d k by the generic head-SpMM); attention_dim % 4 == 0 keeps the q||k rows (stride 2A) 16-byte aligned
@@ -1062,6 +1140,32 @@ extern "C" int gnpde_adjoint_grad_floats(const gnpde_rhs_t* rhs) {
   const int M = rhs->kind != GNPDE_RHS_LAPLACIAN ? rhs->proj_m : 0;
   const int extra = (rhs->kind == GNPDE_RHS_TRANSFORMER && rhs->att.type == GNPDE_ATT_EXP_KERNEL) ? 2 : 0;
   return M * rhs->d + M + extra + 2;
+}
+
+extern "C" int gnpde_split_kernel_grad_floats(int32_t heads, int32_t d_k, int32_t d) {
+  if (heads < 1 || d_k < 1 || d < 1) return 0;
+  return 2 * heads * d_k * (d + 2) + 4;
+}
+
+extern "C" int gnpde_split_kernel_grads(const float* grads_cat, const float* wcat, const float* bcat, const float* lengthscale_x,
+                                        const float* lengthscale_p, const float* output_var_x, const float* output_var_p, int32_t heads,
+                                        int32_t d_k, int32_t d, int32_t f0, int32_t p0, float* out, void* stream) {
+  GNPDE_CHECK_ARG(grads_cat && wcat && bcat && lengthscale_x && lengthscale_p && output_var_x && output_var_p && out, GNPDE_EINVAL,
+                  "split_kernel_grads: null pointer");
+  GNPDE_CHECK_ARG(heads >= 1 && d_k >= 1 && d >= 1 && static_cast<long long>(heads) * d_k <= 256 && d <= 4096, GNPDE_EINVAL,
+                  "split_kernel_grads: heads=%d d_k=%d d=%d (attention_dim = heads * d_k must divide into its heads and be <= 256)", heads, d_k, d);
+  GNPDE_CHECK_ARG(f0 >= 0 && p0 >= 1 && f0 + p0 <= d && d - p0 >= 1, GNPDE_EINVAL,
+                  "split_kernel_grads: feature columns %d + positional columns %d exceed the state width %d", f0, p0, d);
+  SplitGradArgs a{};
+  a.g = grads_cat; a.wcat = wcat; a.bcat = bcat;
+  a.lx = lengthscale_x; a.lp = lengthscale_p; a.ovx = output_var_x; a.ovp = output_var_p;
+  a.h = heads; a.dk = d_k; a.d = d; a.f0 = f0; a.p0 = p0; a.out = out;
+  const long long total = 2LL * heads * d_k * (d + 2);
+  long long blocks = (total + kBlock - 1) / kBlock;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(split_kernel_grads_kernel, dim3(static_cast<unsigned>(2 + blocks)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" size_t gnpde_adjoint_workspace_bytes(const gnpde_rhs_t* rhs, const gnpde_graph_t* graph_t, int32_t method) {

@@ -107,7 +107,8 @@ class SpGraphTransAttentionLayer(nn.Module):
     if ent is None or ent[1].device != dev:
       ent = [None, torch.zeros(4 * A, self.in_features, dtype=torch.float32, device=dev),
              torch.zeros(4 * A, dtype=torch.float32, device=dev),
-             torch.ones(1, dtype=torch.float32, device=dev), torch.ones(1, dtype=torch.float32, device=dev)]
+             torch.ones(1, dtype=torch.float32, device=dev), torch.ones(1, dtype=torch.float32, device=dev),
+             torch.ones(4, dtype=torch.float32, device=dev)]     # [5]: (l_x, l_p, ov_x, ov_p) the derived operands were formed from
       self._bufs['qk'] = ent
     if ent[0] != sig:
       f0, p0 = opt['feat_hidden_dim'], opt['pos_enc_hidden_dim']
@@ -125,8 +126,16 @@ class SpGraphTransAttentionLayer(nn.Module):
           b[:, :dk] = (lx.bias / self.lengthscale_x).view(h, dk)
           b[:, dk:] = (lp.bias / self.lengthscale_p).view(h, dk)
         ent[3].copy_(self.output_var_x * self.output_var_p)
+        ent[5].copy_(torch.cat((self.lengthscale_x, self.lengthscale_p, self.output_var_x, self.output_var_p)))
       ent[0] = sig
     return ent[1], ent[2]
+
+  def split_operands(self):
+    """(signature, Wcat, bcat, [l_x, l_p, ov_x, ov_p]) of the split kernel AS LAST REFRESHED (no refresh here): what a recorded forward
+    solve ran with -- its reverse sweep differentiates these values, whatever an optimiser did to the parameters since (the chain rule
+    back to the twelve parameters, gnpde_split_kernel_grads, needs the length scales the derived rows were divided by)."""
+    ent = self._bufs['qk']
+    return ent[0], ent[1], ent[2], ent[5]
 
   def _reweight_csr(self, graph):
     if not (self.opt['reweight_attention'] and self.edge_weights is not None):

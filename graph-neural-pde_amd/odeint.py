@@ -722,17 +722,24 @@ def _transformer_stage_native(func):
   """GRAND-nl per-evaluation attention the native VJP stage of csrc/adjoint.hip covers: scaled-dot scores, and (round 6) cosine_sim /
   pearson -- the scaled dot product of unit (mean-centred) head vectors, d_k in {4, 8, 16} -- and exp_kernel, with any normaliser.
   Scaled-dot scores take any d_k with attention_dim % 4 == 0 (16-byte q||k rows for the stage kernels) and <= 256 (d q / d k by the
-  generic head-SpMM); the other scores keep d_k % 4 == 0 with attention_dim / 4 a power of two."""
+  generic head-SpMM); the other scores keep d_k % 4 == 0 with attention_dim / 4 a power of two.  The BLEND split kernel (beltrami +
+  exp_kernel) is ONE exp kernel over the derived projection of SpGraphTransAttentionLayer._split_qk_weights: the exp-kernel rule
+  applies to its width kernel_att_dim = 2 attention_dim and its heads of 2 d_k (gnpde_split_kernel_grads maps the gradients of the
+  derived operands back to the layer's parameters, _grad_vector_by_param)."""
   lay, opt = func.multihead_att_layer, func.opt
-  a4 = lay.attention_dim // 4
-  if opt['mix_features'] or getattr(lay, 'split_kernel', False):
+  if opt['mix_features']:
     return False
+  if getattr(lay, 'split_kernel', False):
+    A, dk = lay.kernel_att_dim, 2 * lay.d_k
+  else:
+    A, dk = lay.attention_dim, lay.d_k
+  a4 = A // 4
   if opt['attention_type'] == 'scaled_dot':
-    return lay.attention_dim % lay.h == 0 and lay.attention_dim % 4 == 0 and lay.attention_dim <= 256
-  if not (lay.d_k % 4 == 0 and lay.attention_dim % 4 == 0 and a4 <= 64 and (a4 & (a4 - 1)) == 0):
+    return A % lay.h == 0 and A % 4 == 0 and A <= 256
+  if not (dk % 4 == 0 and A % 4 == 0 and a4 <= 64 and (a4 & (a4 - 1)) == 0):
     return False
-  if opt['attention_type'] == 'exp_kernel':       # (round 6; the BLEND split kernel -- two exp kernels multiplied -- keeps the stage loop)
-    return lay.attention_dim <= 128 and lay.h <= 8
+  if opt['attention_type'] == 'exp_kernel':       # (exp_node_bwd_kernel walks the 2A <= 512 columns of a q||k row)
+    return A <= 256 and lay.h <= 8
   return opt['attention_type'] in ('cosine_sim', 'pearson') and lay.d_k in (4, 8, 16)
 
 
@@ -742,12 +749,17 @@ def _gat_stage_native(func):
   return (not opt['mix_features']) and 2 <= lay.h <= 8 and lay.attention_dim % 4 == 0 and lay.attention_dim <= 256
 
 
-def _stage_projection_t(func, ex, dev):
-  """[d, m] projection weights of the per-evaluation attention, transposed for P = d(q||k) W, in a buffer with a persistent address."""
+def _stage_projection_t(func, ex, dev, forward_values=False):
+  """[d, m] projection weights of the per-evaluation attention, transposed for P = d(q||k) W, in a buffer with a persistent address.
+  forward_values (the reverse sweep of a recorded solve): the BLEND split kernel's derived projection is taken as the forward pass left
+  it, not re-derived from parameters an optimiser may have stepped since."""
+  lay = func.multihead_att_layer
   if func.__class__.__name__ == 'ODEFuncAtt':
-    src = func.multihead_att_layer.W.detach()                    # [d, A] as the reference stores it
+    src = lay.W.detach()                    # [d, A] as the reference stores it
+  elif forward_values and getattr(lay, 'split_kernel', False):
+    src = lay.split_operands()[1].t()
   else:
-    wqk, _ = func.multihead_att_layer.qk_weights()
+    wqk, _ = lay.qk_weights()
     src = wqk.t()
   if ex.get('proj_wt') is None or ex['proj_wt'].shape != tuple(src.shape):
     ex['proj_wt'] = torch.empty(tuple(src.shape), dtype=torch.float32, device=dev)
@@ -782,21 +794,53 @@ def _recorded_fixed_ok(func, y0, t, method):
   return False
 
 
-def _grad_vector_by_param(func, g, d):
-  """{id(parameter): its slice of the native gradient vector} (gnpde_adjoint_run: d[Wq;Wk], d[bq;bk], d alpha_train, d beta_train)."""
+def _split_kernel_grads(func, g, d, ex):
+  """{id(parameter): gradient} of the BLEND split kernel's twelve parameters from the gradients of the derived operands
+  (gnpde_split_kernel_grads: one launch into a persistent buffer, no host synchronisation)."""
+  from . import ops
+  lay, opt = func.multihead_att_layer, func.opt
+  A, h, dk = lay.attention_dim, lay.h, lay.d_k
+  f0, p0 = int(opt['feat_hidden_dim']), int(opt['pos_enc_hidden_dim'])
+  _, wcat, bcat, scal = lay.split_operands()
+  L = _lib.lib()
+  nf = int(L.gnpde_split_kernel_grad_floats(h, dk, d))
+  out = ex.get('split_grads')
+  if out is None or out.numel() != nf or out.device != g.device:
+    out = ex['split_grads'] = torch.zeros(nf, dtype=torch.float32, device=g.device)
+  _lib.require_hip(g, wcat, bcat, scal, out)
+  _lib.check(L.gnpde_split_kernel_grads(_lib.ptr(g), _lib.ptr(wcat), _lib.ptr(bcat), _lib.ptr(scal[0:1]), _lib.ptr(scal[1:2]), _lib.ptr(scal[2:3]),
+                                        _lib.ptr(scal[3:4]), h, dk, d, f0, p0, _lib.ptr(out), _lib.stream_of(g)))
+  by_param, pos = {}, 0
+  for lin, w in ((lay.Qx, d - p0), (lay.Kx, d - p0), (lay.Qp, p0), (lay.Kp, p0)):
+    by_param[id(lin.weight)] = out[pos:pos + A * w].view(A, w)
+    by_param[id(lin.bias)] = out[pos + A * w:pos + A * w + A]
+    pos += A * (w + 1)
+  for i, p in enumerate((lay.lengthscale_x, lay.lengthscale_p, lay.output_var_x, lay.output_var_p)):
+    by_param[id(p)] = out[pos + i].reshape(p.shape)
+  return by_param
+
+
+def _grad_vector_by_param(func, g, d, ex=None):
+  """{id(parameter): its slice of the native gradient vector} (gnpde_adjoint_run: d[Wq;Wk], d[bq;bk], d alpha_train, d beta_train).
+  BLEND split kernel: the vector holds the gradients of the DERIVED operands (Wcat [4A, d], bcat [4A], output_var, lengthscale = 1);
+  the twelve parameters get theirs through gnpde_split_kernel_grads into a buffer kept in `ex`."""
   by_param = {}
   tail = 0
   if func.__class__.__name__ == 'ODEFuncTransformerAtt':
     lay = func.multihead_att_layer
-    A = lay.attention_dim
-    gram = g[:2 * A * d].view(2 * A, d)
-    gb = g[2 * A * d:2 * A * d + 2 * A]
-    by_param = {id(lay.Q.weight): gram[:A], id(lay.K.weight): gram[A:], id(lay.Q.bias): gb[:A], id(lay.K.bias): gb[A:]}
+    A = lay.kernel_att_dim
     tail = 2 * A * d + 2 * A
-    if func.opt['attention_type'] == 'exp_kernel':      # two more slots: d output_var, d lengthscale
-      by_param[id(lay.output_var)] = g[tail].reshape(lay.output_var.shape)
-      by_param[id(lay.lengthscale)] = g[tail + 1].reshape(lay.lengthscale.shape)
+    if getattr(lay, 'split_kernel', False):
+      by_param = _split_kernel_grads(func, g, d, ex if ex is not None else func.__dict__.setdefault('_split_grad_state', {}))
       tail += 2
+    else:
+      gram = g[:2 * A * d].view(2 * A, d)
+      gb = g[2 * A * d:2 * A * d + 2 * A]
+      by_param = {id(lay.Q.weight): gram[:A], id(lay.K.weight): gram[A:], id(lay.Q.bias): gb[:A], id(lay.K.bias): gb[A:]}
+      if func.opt['attention_type'] == 'exp_kernel':      # two more slots: d output_var, d lengthscale
+        by_param[id(lay.output_var)] = g[tail].reshape(lay.output_var.shape)
+        by_param[id(lay.lengthscale)] = g[tail + 1].reshape(lay.lengthscale.shape)
+        tail += 2
   elif func.__class__.__name__ == 'ODEFuncAtt':      # d W^T [A, d], then d a in the first 2 d_k of the A slots behind it
     lay = func.multihead_att_layer
     A = lay.attention_dim
@@ -871,6 +915,8 @@ class _RecordedFixedGrid(torch.autograd.Function):
     else:
       view.leave(ent['y'], out=out[1])
     ctx.func, ctx.ent, ctx.gen, ctx.desc, ctx.graph, ctx.view = func, ent, sol.tape_generation, desc, graph, view
+    lay = getattr(func, 'multihead_att_layer', None)
+    ctx.split_sig = lay.split_operands()[0] if getattr(lay, 'split_kernel', False) else None      # (the derived operands this solve ran with)
     ctx.method, ctx.dts, ctx.params = method, dts, params
     ctx.heads = 0 if edge_values is None else (edge_values.shape[1] if edge_values.dim() == 2 else 0)
     ctx.has_edge_values = edge_values is not None
@@ -896,7 +942,10 @@ class _RecordedFixedGrid(torch.autograd.Function):
       ex = ent['extra']
       proj_wt = w_t = None
       if nl:
-        proj_wt = _stage_projection_t(func, ex, dev)
+        if ctx.split_sig is not None and func.multihead_att_layer.split_operands()[0] != ctx.split_sig:
+          raise _lib.GnpdeError('recorded fixed-grid solve: the derived split-kernel projection of this forward pass was re-derived from '
+                                'updated parameters by a later evaluation (backward must run before the next use of the function)')
+        proj_wt = _stage_projection_t(func, ex, dev, forward_values=True)
       else:
         w_csr = func._weights_csr(graph)
         if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
@@ -946,7 +995,7 @@ class _RecordedFixedGrid(torch.autograd.Function):
         order = gt.perm_long if ent['sweep'].swapped else graph.perm_long      # (the products lie in the order of the graph the row kernel ran on)
         dw_e[order] = a * ex['r_acc'][:E]
         dw = (dw_e / ctx.heads).unsqueeze(1).expand(E, ctx.heads).contiguous() if ctx.heads else dw_e
-      by_param = _grad_vector_by_param(func, ent['grads'], d)
+      by_param = _grad_vector_by_param(func, ent['grads'], d, ex)
       gparams = []
       for i, p in enumerate(ctx.params):
         g = by_param.get(id(p)) if need[5 + i] else None
@@ -965,7 +1014,7 @@ def _fixed_tape_estimate(func, y0, n_evals):
   total = (n_evals + 1) * n * ld * 4
   lay = getattr(func, 'multihead_att_layer', None)
   if func.__class__.__name__ == 'ODEFuncTransformerAtt' and lay is not None and func.edge_index is not None:
-    total += n_evals * (n * 2 * lay.attention_dim * 4 + int(func.edge_index.shape[1]) * 4)
+    total += n_evals * (n * 2 * lay.kernel_att_dim * 4 + int(func.edge_index.shape[1]) * 4)
   return total
 
 
@@ -1143,9 +1192,10 @@ def _adjoint_fixed_grid(func, params, y, a, gparams, span, method, step_size):
 
 
 def _adjoint_native_ok(func, y, method):
-  """The fixed-grid adjoint solve runs as ONE native object (csrc/adjoint.hip) for GRAND-l and for GRAND-nl with scaled-dot, cosine_sim
-  or pearson scores (any normaliser), alpha' = sigmoid(alpha_train) or the raw alpha_train; everything else (GAT, exp_kernel, the BLEND
-  split kernel) keeps the stage-by-stage loop above."""
+  """The fixed-grid adjoint solve runs as ONE native object (csrc/adjoint.hip) for GRAND-l, for GRAND-nl with scaled-dot, cosine_sim,
+  pearson or exp_kernel scores -- the BLEND split kernel included -- (any normaliser), alpha' = sigmoid(alpha_train) or the raw
+  alpha_train, and for the GAT function, within the shapes of _transformer_stage_native / _gat_stage_native; everything else keeps the
+  stage-by-stage loop above."""
   if method not in ('euler', 'rk4') or not hasattr(func, '_descriptor'):
     return False
   if not (y.is_cuda and y.dim() == 2 and y.dtype == torch.float32 and y.shape[1] <= 256):
@@ -1231,7 +1281,7 @@ def _adjoint_native(func, params, y, a, span, method, step_size):
     a_out.copy_(ab)
   else:
     view.leave(ab, out=a_out)
-  by_param = _grad_vector_by_param(func, ent['grads'], y.shape[1])
+  by_param = _grad_vector_by_param(func, ent['grads'], y.shape[1], ex)
   return a_out, [by_param.get(id(p)) for p in params]
 
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 9   /* 9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 10  /* 10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -515,7 +515,8 @@ size_t gnpde_rhs_workspace_bytes(const gnpde_rhs_t* rhs);
  * of this library's kernels (projection, attention, aggregation with the NEXT stage input formed in its epilogue, SDDMM,
  * normaliser backward, head-SpMMs, aggregation on the transposed CSR, one pass for the parameter gradients) and the whole
  * backward solve is one captured hipGraph.  rhs: GNPDE_RHS_LAPLACIAN (constant weights) or GNPDE_RHS_TRANSFORMER with
- * scaled-dot scores (any normaliser), alpha_sigmoid = 1, d <= 256 in 16-byte lanes.
+ * scaled-dot scores (any normaliser), alpha_sigmoid = 1, d <= 256 in 16-byte lanes; exp_kernel scores up to attention_dim = 256, 8 heads
+ * (grads then carries two more slots behind d[bq;bk]: d output_var, d lengthscale).
  *   graph_t      CSR of the transposed operator over the SAME edge list;
  *   t_from_csr   [e] device (GRAND-nl): CSR position in rhs->graph of the entry stored at position p of graph_t;
  *   proj_wt      [d, 2A] device (GRAND-nl): rhs->proj_w transposed;   w_t_csr  [e] device (GRAND-l): the weights in graph_t's order.
@@ -545,6 +546,30 @@ int    gnpde_adjoint_set_tape(gnpde_adjoint_t* s, const void* tape, size_t tape_
 int    gnpde_adjoint_tape_swapped(const gnpde_adjoint_t* s);
 int    gnpde_adjoint_num_rhs_evals(const gnpde_adjoint_t* s);
 int    gnpde_adjoint_destroy(gnpde_adjoint_t* s);
+
+/* The BLEND split kernel (reference src/function_transformer_attention.py:133-171: beltrami + exp_kernel -- an exp kernel on the feature
+ * and label columns with Qx, Kx, lengthscale_x, output_var_x times one on the positional columns with Qp, Kp, lengthscale_p,
+ * output_var_p) runs here as ONE exp kernel of heads of width 2 d_k over a derived projection
+ *   Wcat [4A, d], bcat [4A]: per head the d_k rows of Qx / l_x on the feature columns [0, f0) and the label columns [f0 + p0, d), then the
+ *                            d_k rows of Qp / l_p on the positional columns [f0, f0 + p0); rows [0, 2A) from Qx / Qp, rows [2A, 4A) from Kx / Kp;
+ *   output_var = ov_x ov_p, lengthscale = 1
+ * (att_dim = 2A, proj_m = 4A; the adjoint solve and the recorded sweep take it up to att_dim = 256 like the plain exp kernel).
+ * gnpde_split_kernel_grads is the chain rule from what gnpde_adjoint_run leaves in `grads` for that descriptor back to the layer's
+ * twelve parameters, one launch, capturable (no allocation, no synchronisation, the scalars read from device memory):
+ *   grads_cat  [4A d + 4A + 2] device: d Wcat, d bcat, d output_var, (d lengthscale: the derived 1 is no parameter);
+ *   wcat, bcat the derived operands the solve used;   lengthscale_x / _p, output_var_x / _p: device scalars;
+ *   out        [gnpde_split_kernel_grad_floats = 2A (d + 2) + 4] device:
+ *              d Qx.weight [A, d - p0], d Qx.bias [A], d Kx.weight, d Kx.bias, d Qp.weight [A, p0], d Qp.bias [A], d Kp.weight, d Kp.bias,
+ *              d lengthscale_x, d lengthscale_p, d output_var_x, d output_var_p, with
+ *                d Qx.weight[h d_k + c, j] = d Wcat[h 2 d_k + c, j < f0 ? j : p0 + j] / l_x,   d Qp.weight[h d_k + c, j] = d Wcat[h 2 d_k + d_k + c, f0 + j] / l_p
+ *                (entries of d Wcat where Wcat is structurally zero are dropped), the k half and the biases likewise,
+ *                d l_x = -(1 / l_x) sum (d Wcat . Wcat + d bcat . bcat) over the feature rows of both halves (double, fixed order), d l_p over the
+ *                positional rows,   d ov_x = d output_var ov_p,   d ov_p = d output_var ov_x.
+ * Returns GNPDE_EINVAL before any launch for null pointers, heads * d_k > 256 or f0 + p0 > d. */
+int gnpde_split_kernel_grad_floats(int32_t heads, int32_t d_k, int32_t d);
+int gnpde_split_kernel_grads(const float* grads_cat, const float* wcat, const float* bcat, const float* lengthscale_x,
+                             const float* lengthscale_p, const float* output_var_x, const float* output_var_p, int32_t heads, int32_t d_k,
+                             int32_t d, int32_t f0, int32_t p0, float* out, void* stream);
 
 /* f(u) of a descriptor with an arbitrary epilogue / stage (building block of host-controlled adaptive
  * solvers); the epilogue's alpha / beta / x0 / alpha_sigmoid fields are taken from the descriptor. */
