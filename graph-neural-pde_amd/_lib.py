@@ -23,8 +23,9 @@ ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
 ADAPTIVE_HEUN, ADAPTIVE_DOPRI5 = range(2)
-TUNE_SPMM_VARIANT, TUNE_FUSED_BLOCKS_PER_CU, TUNE_ONE_PASS, TUNE_FORK, TUNE_ATT_GENERIC_ROWS, TUNE_RK4_CLASSIC = range(6)
-TUNE_ROW_FUSION, TUNE_ONE_PASS_VARIANT, TUNE_LINEAR_STREAMING, TUNE_SPMM_PART, TUNE_XCD_ROWS, TUNE_HUB_FOLD = 6, 7, 8, 9, 10, 11
+# gnpde_tune keys (csrc/common.h); 0, 8 and 13 are retired slots: the library refuses any value but 0 for them
+TUNE_FUSED_BLOCKS_PER_CU, TUNE_ONE_PASS, TUNE_FORK, TUNE_ATT_GENERIC_ROWS, TUNE_RK4_CLASSIC = range(1, 6)
+TUNE_ROW_FUSION, TUNE_ONE_PASS_VARIANT, TUNE_SPMM_PART, TUNE_XCD_ROWS, TUNE_HUB_FOLD = 6, 7, 9, 10, 11
 TUNE_KNN_SPLITS = 19     # column splits of the k-nearest-neighbour search: 0 = chosen from n and the CU count, S > 0 forces S
 TUNE_KNN_VARIANT = 20    # tile-kernel variants of the search (A/B): 1 = 32-float K chunks for k > 32, 2 = the k > 32 kernel for every k
 TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)

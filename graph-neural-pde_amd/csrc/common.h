@@ -88,9 +88,10 @@ __host__ __device__ __forceinline__ int xcd_row_of(int row_begin, int row_end, i
   return row < row_end ? static_cast<int>(row) : -1;
 }
 
-// kernel-variant knobs for A/B measurements (gnpde_tune); 0 = the default variant
+// kernel-variant knobs for A/B measurements (gnpde_tune); 0 = the default variant.  RETIRED slots keep their numbers and accept only 0:
+// their experiments are decided and recorded in profiles/ and DESIGN.md sections 3, 4 and 8; the code that ran them was last in c657da7.
 enum {
-  GNPDE_TUNE_SPMM_VARIANT = 0,         // aggregation kernel <L,K,U,nontemporal> variant (tools/spmm_ab.py)
+  GNPDE_TUNE_RETIRED_0 = 0,            // retired: aggregation kernel variants (<L,K,U,nontemporal>, wide / pair / pipelined forms)
   GNPDE_TUNE_FUSED_BLOCKS_PER_CU = 1,  // persistent grid of the one-pass kernel
   GNPDE_TUNE_ONE_PASS = 2,             // 1: GRAND-nl evaluations use the one-pass kernel
   GNPDE_TUNE_FORK = 3,                 // 1: hub-row work on a second stream (fork / join)
@@ -99,14 +100,14 @@ enum {
   GNPDE_TUNE_ROW_FUSION = 6,           // row attention + aggregation in one kernel (attn_spmm_kernel): 0 = only for graphs whose state fits an XCD's L2
                                        // (launch-bound evaluations), 1 = always (slower at scale, A/B), 2 = never
   GNPDE_TUNE_ONE_PASS_VARIANT = 7,     // register / unroll variants of the one-pass kernel (tools/onepass_ab.py)
-  GNPDE_TUNE_LINEAR_STREAMING = 8,     // 1: one-tile-per-wave projection kernel instead of the persistent one
+  GNPDE_TUNE_RETIRED_8 = 8,            // retired: projection kernel variants (streaming, fragment loads, staged forms and their grids)
   GNPDE_TUNE_SPMM_PART = 9,            // measurement only: 1 = hub chunks only, 2 = rows only (results are then incomplete)
   GNPDE_TUNE_XCD_ROWS = 10,            // 0: as gnpde_graph_t.xcd_deal says; 1: contiguous eighths for every graph; 2: hashed blocks for every graph
   GNPDE_TUNE_HUB_FOLD = 11,            // 2: phase 1 of the hub-row attention folds the row's chunk partials straight from memory instead of staging them through LDS (default: staged)
   GNPDE_TUNE_ADJOINT_GRAM = 12,        // 1: weight-gradient Gram blocks of the adjoint stage on the VALU (scalar-operand kernel) instead of the matrix cores
   GNPDE_TUNE_SWEEP_UNSWAPPED = 15,     // 1: the reverse sweep over a recorded solve gathers the STATE rows again (round-6 first form) instead of the cotangent rows only (A/B)
   GNPDE_TUNE_KEY_TABLE = 14,           // 1: keep q||k interleaved [n, 2A] where the solver would write two tables (A/B)
-  GNPDE_TUNE_LINEAR_DIAG = 13,         // A/B diagnostics of the staged projection kernel (1: no stores, 2: loads alone); never set in production
+  GNPDE_TUNE_RETIRED_13 = 13,          // retired: diagnostics of the staged projection kernel (no stores / loads alone)
   GNPDE_TUNE_GMAX_SMALL = 16,          // 1: squareplus on a small grid keeps the slot atomics + memset + fold launch (A/B against the per-wave maxima folded by the second sweep)
   GNPDE_TUNE_ATT_ROWS16 = 17,          // 9: the row softmax of the scaled-dot row kernel (4 heads) keeps a whole wave per row of <= 16 entries (A/B against the quarter-wave packing)
   GNPDE_TUNE_LO_MAPPING = 18,          // bf16 gather operand, rows of 17..32 16-byte lanes in graphs of mostly short rows (A/B): 1 = two rows per wave, 32 lanes x 4

@@ -16,6 +16,9 @@ namespace gnpde { int g_tune[GNPDE_TUNE_COUNT] = {0}; }
 
 extern "C" int gnpde_tune(int32_t key, int32_t value) {
   GNPDE_CHECK_ARG(key >= 0 && key < gnpde::GNPDE_TUNE_COUNT, GNPDE_EINVAL, "tune: bad key %d", key);
+  const bool retired = key == gnpde::GNPDE_TUNE_RETIRED_0 || key == gnpde::GNPDE_TUNE_RETIRED_8 || key == gnpde::GNPDE_TUNE_RETIRED_13;
+  GNPDE_CHECK_ARG(!retired || value == 0, GNPDE_EINVAL, "tune: key %d is retired: the variant %d it selected was removed (it was last in c657da7; "
+                  "its measurements are in profiles/ and DESIGN.md)", key, value);
   gnpde::g_tune[key] = value;
   return 0;
 }

@@ -285,9 +285,7 @@ template <int MT, int KB>
 __global__ __launch_bounds__(kBlock) void linear_staged_kernel(const float* __restrict__ x, int n, int ldx,
                                                                const float* __restrict__ W, int ldw,
                                                                const float* __restrict__ b, float* __restrict__ out,
-                                                               int ldo, int col_base, int relu, int variant) {
-  // variant (A/B knob gnpde_tune(8, 3 | 4 | 5), bit 0: nontemporal loads of x, bit 1: every wave walks a CONTIGUOUS range of tiles
-  // instead of striding over the table by the grid; results are bit-identical in every variant)
+                                                               int ldo, int col_base, int relu) {
   constexpr int CPR = KB * 4;                 // 16-byte chunks per row (d = 16 KB floats)
   constexpr int CHUNKS = 16 * CPR;            // per tile
   constexpr int PER_LANE = CHUNKS / kWave;    // = KB
@@ -296,15 +294,9 @@ __global__ __launch_bounds__(kBlock) void linear_staged_kernel(const float* __re
   const int wave = threadIdx.x >> 6;
   const int r = lane & 15, kq = lane >> 4;
   const long long n_tiles = (static_cast<long long>(n) + 15) / 16;
-  const long long n_waves = static_cast<long long>(gridDim.x) * kWavesPerBlock;
-  const bool contiguous = (variant & 2) != 0;
-  const bool nt = (variant & 1) != 0;
-  const long long per_wave = (n_tiles + n_waves - 1) / n_waves;
-  const long long wid = static_cast<long long>(blockIdx.x) * kWavesPerBlock + wave;
-  const long long stride = contiguous ? 1 : n_waves;
-  long long tile = contiguous ? wid * per_wave : wid;
-  const long long tile_end = contiguous ? ((wid + 1) * per_wave < n_tiles ? (wid + 1) * per_wave : n_tiles) : n_tiles;
-  if (tile >= tile_end) return;
+  const long long stride = static_cast<long long>(gridDim.x) * kWavesPerBlock;   // every wave strides over the table by the grid
+  long long tile = static_cast<long long>(blockIdx.x) * kWavesPerBlock + wave;
+  if (tile >= n_tiles) return;
 
   f32x4 bv[KB][MT];
 #pragma unroll
@@ -325,8 +317,7 @@ __global__ __launch_bounds__(kBlock) void linear_staged_kernel(const float* __re
       const int c = it * kWave + lane;
       long long row = tl * 16 + c / CPR;
       if (row >= n) row = n - 1;               // ragged last tile: clamp reads, mask writes
-      const f32x4* src = reinterpret_cast<const f32x4*>(x + static_cast<size_t>(row) * ldx + 4 * (c % CPR));
-      g[it] = nt ? __builtin_nontemporal_load(src) : *src;
+      g[it] = *reinterpret_cast<const f32x4*>(x + static_cast<size_t>(row) * ldx + 4 * (c % CPR));
     }
   };
   f32x4* my = slab[wave];
@@ -340,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void linear_staged_kernel(const float* __re
       my[rr * CPR + (j ^ (rr & 7))] = g[it];
     }
     const long long next = tile + stride;
-    const bool more = next < tile_end;
+    const bool more = next < n_tiles;
     if (more) load_tile(next, g);              // in flight during the MFMAs of this tile
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -374,14 +365,12 @@ __global__ __launch_bounds__(kBlock) void linear_staged_kernel(const float* __re
   }
 }
 
-// Round 6 variants of the staged kernel for the q||k projection shape (MT = 2: m = 32 output columns), selected by
-// gnpde_tune(8, 6 | 7 | 8) for A/B runs and by default where they measured faster:
-//   PAIRC  column tile t of lane r is output column 2 r + t, so a lane's two accumulators of an output row are ADJACENT columns and leave
-//          as one 8-byte store: a store instruction writes four complete 128-byte output rows (the kernel above writes every output
-//          line as two 64-byte halves by two different instructions);
-//   DEPTH2 two row tiles of x in flight per wave (registers) instead of one.
-// Same MFMA sequence and k order per output element: bit-identical results.
-template <int KB, bool PAIRC, bool DEPTH2, int DIAG = 0>
+// The staged kernel for the q||k projection shape (MT = 2: m = 32 output columns) with PAIRED columns: column tile t of lane r is output
+// column 2 r + t, so a lane's two accumulators of an output row are ADJACENT columns and leave as one 8-byte store: a store instruction
+// writes four complete 128-byte output rows (the kernel above writes every output line as two 64-byte halves by two different
+// instructions).  Same MFMA sequence and k order per output element: bit-identical results.  (Two row tiles of x in flight per wave
+// measured slower, 28.0 vs 25.8 us: profiles/r06_linear_*.txt.)
+template <int KB>
 __global__ __launch_bounds__(kBlock) void linear_staged2_kernel(const float* __restrict__ x, int n, int ldx,
                                                                 const float* __restrict__ W, int ldw,
                                                                 const float* __restrict__ b, float* __restrict__ out,
@@ -389,8 +378,6 @@ __global__ __launch_bounds__(kBlock) void linear_staged2_kernel(const float* __r
                                                                 int split = 0) {
   // out2 / split (round 6): output columns >= split go to out2[row * ldo + col - split] -- the q||k projection as TWO tables [n, A] when a
   // key row is shorter than a cache line (A <= 16: the attention's gathers of 64-byte k rows then fetch no q halves of 128-byte lines)
-  // DIAG (A/B diagnostics, gnpde_tune(13, v)): 1 = no output stores (unless a result is NaN), 2 = no LDS / MFMA work (the loads alone)
-  constexpr int diag = DIAG;
   constexpr int MT = 2;
   constexpr int CPR = KB * 4;
   constexpr int CHUNKS = 16 * CPR;
@@ -406,7 +393,7 @@ __global__ __launch_bounds__(kBlock) void linear_staged2_kernel(const float* __r
 
   int wcol[MT];
 #pragma unroll
-  for (int t = 0; t < MT; ++t) wcol[t] = col_base + (PAIRC ? 2 * r + t : t * 16 + r);
+  for (int t = 0; t < MT; ++t) wcol[t] = col_base + (2 * r + t);
   f32x4 bv[KB][MT];
 #pragma unroll
   for (int u = 0; u < KB; ++u)
@@ -434,16 +421,14 @@ __global__ __launch_bounds__(kBlock) void linear_staged2_kernel(const float* __r
     }
   };
   f32x4* my = slab[wave];
-  auto consume = [&](long long tl, const f32x4 (&g)[PER_LANE]) {
+  auto consume = [&](const f32x4 (&g)[PER_LANE]) {
 #pragma unroll
     for (int it = 0; it < PER_LANE; ++it) {
       const int rr = it * RPI + lr;
-      if (diag == 2) { if (g[it][0] != g[it][0]) out[lane] = g[it][1]; continue; }
       my[rr * CPR + (j ^ (rr & 7))] = g[it];
     }
   };
   auto compute = [&](long long tl) {
-    if (diag == 2) return;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     f32x4 acc[MT];
@@ -465,51 +450,24 @@ __global__ __launch_bounds__(kBlock) void linear_staged2_kernel(const float* __r
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const long long orow = row0 + 4 * kq + i;
-      if (orow < n && (diag != 1 || acc[0][i] != acc[0][i])) {
-        if constexpr (PAIRC) {
-          const int c0 = col_base + 2 * r;
-          float* dst = (split > 0 && c0 >= split) ? out2 + static_cast<size_t>(orow) * ldo + (c0 - split) : out + static_cast<size_t>(orow) * ldo + c0;
-          *reinterpret_cast<float2*>(dst) = make_float2(acc[0][i] + bias[0], acc[1][i] + bias[1]);
-        } else {
-#pragma unroll
-          for (int t = 0; t < MT; ++t) {
-            float* dst = (split > 0 && wcol[t] >= split) ? out2 + static_cast<size_t>(orow) * ldo + (wcol[t] - split)
-                                                         : out + static_cast<size_t>(orow) * ldo + wcol[t];
-            *dst = acc[t][i] + bias[t];
-          }
-        }
+      if (orow < n) {
+        const int c0 = col_base + 2 * r;
+        float* dst = (split > 0 && c0 >= split) ? out2 + static_cast<size_t>(orow) * ldo + (c0 - split) : out + static_cast<size_t>(orow) * ldo + c0;
+        *reinterpret_cast<float2*>(dst) = make_float2(acc[0][i] + bias[0], acc[1][i] + bias[1]);
       }
     }
     __builtin_amdgcn_wave_barrier();           // the fragment reads above precede the next tile's slab writes
   };
-  if constexpr (!DEPTH2) {
-    f32x4 g[PER_LANE];
-    load_tile(tile, g);
-    while (true) {
-      consume(tile, g);
-      const long long next = tile + stride;
-      const bool more = next < n_tiles;
-      if (more) load_tile(next, g);
-      compute(tile);
-      if (!more) break;
-      tile = next;
-    }
-  } else {
-    f32x4 ga[PER_LANE], gb[PER_LANE];
-    load_tile(tile, ga);
-    if (tile + stride < n_tiles) load_tile(tile + stride, gb);
-    while (true) {
-      consume(tile, ga);
-      if (tile + 2 * stride < n_tiles) load_tile(tile + 2 * stride, ga);
-      compute(tile);
-      tile += stride;
-      if (tile >= n_tiles) break;
-      consume(tile, gb);
-      if (tile + 2 * stride < n_tiles) load_tile(tile + 2 * stride, gb);
-      compute(tile);
-      tile += stride;
-      if (tile >= n_tiles) break;
-    }
+  f32x4 g[PER_LANE];
+  load_tile(tile, g);
+  while (true) {
+    consume(g);
+    const long long next = tile + stride;
+    const bool more = next < n_tiles;
+    if (more) load_tile(next, g);                // in flight during the MFMAs of this tile
+    compute(tile);
+    if (!more) break;
+    tile = next;
   }
 }
 
@@ -520,41 +478,33 @@ void launch_tile(const float* x, int n, int d, int ldx, const float* W, int m, i
   const bool full_cols = ALIGNED && (d % 16 == 0) && (col + 16 * MT <= m);
   const long long tiles = (static_cast<long long>(n) + 15) / 16;
   if constexpr (MT <= 2) {
-    if (full_cols && d <= 128 && g_tune[GNPDE_TUNE_LINEAR_STREAMING] != 1) {     // (values >= 3: variants of the staged kernel)
+    if (full_cols && d <= 128) {
       // persistent grid: enough wavefronts to fill the chip (8 per SIMD at these register counts would be
       // ideal; W fragments + double-buffered A cost ~150 VGPRs -> 3 per SIMD), each striding over tiles
       long long blocks = 256LL * 3;
       const long long need = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
       if (blocks > need) blocks = need;
       const unsigned pg = static_cast<unsigned>(blocks);
-      // d = 64 / 128 (4 or 8 chunks per lane and tile): full-line loads transposed through LDS (linear_staged_kernel);
-      // gnpde_tune(8, 2) keeps the fragment-shaped loads for A/B runs
-      if ((d == 128 || d == 64) && g_tune[GNPDE_TUNE_LINEAR_STREAMING] != 2) {
-        const int knob = g_tune[GNPDE_TUNE_LINEAR_STREAMING];
+      // d = 64 / 128 (4 or 8 chunks per lane and tile): full-line loads transposed through LDS (linear_staged_kernel)
+      if (d == 128 || d == 64) {
         if constexpr (MT == 2) {
-          if ((knob == 0 || (knob >= 6 && knob <= 11)) && ldo % 2 == 0 && col % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) {
-            // 0 (default since round 6) = 9: paired columns on a grid of 4 workgroups per CU (3 resident: the fourth starts as one ends) --
-            // 24.4 -> 24.0 us in the headline solve, 26.9 -> 25.8 us stand-alone (profiles/r06_linear_ab.txt); 6: paired columns;
-            // 7: two tiles in flight; 8: both; 10 / 11: 7 / 8 on grids of 4 / 2 workgroups per CU; 12: the round-3 kernel
-            long long pg2 = (knob == 0 || knob >= 9) ? 256LL * (knob == 11 ? 2 : 4) : blocks;
+          if (ldo % 2 == 0 && col % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) {
+            // paired columns on a grid of 4 workgroups per CU (3 resident: the fourth starts as one ends) -- 24.4 -> 24.0 us in the
+            // headline solve, 26.9 -> 25.8 us stand-alone (profiles/r06_linear_*.txt)
+            long long pg2 = 256LL * 4;
             if (pg2 > need) pg2 = need;
             const unsigned g2 = static_cast<unsigned>(pg2);
-            const int kv = knob == 0 ? 6 : (knob >= 9 ? knob - 3 : knob);
-#define GNPDE_LS2(KBV, PC, D2) hipLaunchKernelGGL((linear_staged2_kernel<KBV, PC, D2>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu)
-            const int diag = g_tune[GNPDE_TUNE_LINEAR_DIAG];
-            if (d == 128 && diag == 1) hipLaunchKernelGGL((linear_staged2_kernel<8, true, false, 1>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
-            else if (d == 128 && diag == 2) hipLaunchKernelGGL((linear_staged2_kernel<8, true, false, 2>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
-            else if (d == 128) { if (kv == 6) GNPDE_LS2(8, true, false); else if (kv == 7) GNPDE_LS2(8, false, true); else GNPDE_LS2(8, true, true); }
-            else { if (kv == 6) GNPDE_LS2(4, true, false); else if (kv == 7) GNPDE_LS2(4, false, true); else GNPDE_LS2(4, true, true); }
-#undef GNPDE_LS2
+            if (d == 128)
+              hipLaunchKernelGGL((linear_staged2_kernel<8>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
+            else
+              hipLaunchKernelGGL((linear_staged2_kernel<4>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
             return;
           }
         }
-        const int variant = knob >= 3 && knob <= 5 ? knob - 2 : 0;     // 3 / 4 / 5 -> 1 / 2 / 3
         if (d == 128)
-          hipLaunchKernelGGL((linear_staged_kernel<MT, 8>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu, variant);
+          hipLaunchKernelGGL((linear_staged_kernel<MT, 8>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
         else
-          hipLaunchKernelGGL((linear_staged_kernel<MT, 4>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu, variant);
+          hipLaunchKernelGGL((linear_staged_kernel<MT, 4>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
         return;
       }
 #define GNPDE_LP(KBV) \
@@ -574,7 +524,7 @@ void launch_tile(const float* x, int n, int d, int ldx, const float* W, int m, i
     }
   }
   if constexpr (MT >= 4 && ALIGNED) {
-    if (full_cols && d <= 256 && g_tune[GNPDE_TUNE_LINEAR_STREAMING] == 0) {   // W staged in LDS, persistent workgroups
+    if (full_cols && d <= 256) {   // W staged in LDS, persistent workgroups
       const long long need = (tiles + 7) / 8;
       if (d <= 128) {
         long long blocks = 256LL * (MT == 4 ? 4 : 2);
@@ -613,7 +563,7 @@ void launch_linear(const float* x, int n, int d, int ldx, const float* W, int m,
                    int ldo, hipStream_t s, int relu) {
   if constexpr (ALIGNED) {
     const long long tiles = (static_cast<long long>(n) + 15) / 16;
-    if (tiles <= kSmallLinearTiles && d % 16 == 0 && m % 16 == 0 && g_tune[GNPDE_TUNE_LINEAR_STREAMING] == 0) {
+    if (tiles <= kSmallLinearTiles && d % 16 == 0 && m % 16 == 0) {
       const unsigned gx = static_cast<unsigned>((tiles + kWavesPerBlock - 1) / kWavesPerBlock);
       if (m % 32 == 0)
         hipLaunchKernelGGL((linear_kernel<2, true, true, 8>), dim3(gx, m / 32), dim3(kBlock), 0, s, x, n, d, ldx, W, m, ldw, b, out, ldo, 0, 0, relu);
@@ -648,8 +598,7 @@ void launch_linear(const float* x, int n, int d, int ldx, const float* W, int m,
 bool linear_split_supported(const float* x, long long n, int d, int ldx, const float* W, int m, int ldw, int split) {
   const long long tiles = (n + 15) / 16;
   return m == 32 && split == 16 && (d == 64 || d == 128) && tiles > kSmallLinearTiles && ldx % 4 == 0 && ldw % 4 == 0 &&
-         reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0 && g_tune[GNPDE_TUNE_LINEAR_STREAMING] == 0 &&
-         g_tune[GNPDE_TUNE_KEY_TABLE] != 1;
+         reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0 && g_tune[GNPDE_TUNE_KEY_TABLE] != 1;
 }
 
 int launch_linear_split(const float* x, int n, int d, int ldx, const float* W, int m, int ldw, const float* b, float* out_q, float* out_k,
@@ -662,8 +611,8 @@ int launch_linear_split(const float* x, int n, int d, int ldx, const float* W, i
   const long long need = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
   if (blocks > need) blocks = need;
   const unsigned g2 = static_cast<unsigned>(blocks);
-  if (d == 128) hipLaunchKernelGGL((linear_staged2_kernel<8, true, false>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out_q, split, 0, 0, out_k, split);
-  else hipLaunchKernelGGL((linear_staged2_kernel<4, true, false>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out_q, split, 0, 0, out_k, split);
+  if (d == 128) hipLaunchKernelGGL((linear_staged2_kernel<8>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out_q, split, 0, 0, out_k, split);
+  else hipLaunchKernelGGL((linear_staged2_kernel<4>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out_q, split, 0, 0, out_k, split);
   GNPDE_LAUNCH_CHECK();
   return 0;
 }

@@ -42,6 +42,10 @@ struct SpmmArgs {
 };
 
 
+// The per-row streaming operands of every aggregation kernel's epilogue (x0, y, k1 in; k, y out) are read and written once per
+// launch: nontemporal, so that they do not evict the gathered table from L2 (cached form measured slower, profiles/r02_ab_*.log).
+constexpr bool kNT = true;
+
 inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // Work item of wave `lw` (index local to the XCD) of a block that runs on XCD x = blockIdx % 8.  Every XCD gets every
@@ -114,13 +118,13 @@ inline unsigned balanced_grid(const SpmmArgs& a, int wpb) {
   return static_cast<unsigned>(blocks * kXcds);
 }
 
-template <int VEC, int L, int K, int U, bool NTI, bool NT, int BLK = kBlock, bool LO = false>
-__global__ __launch_bounds__(BLK) void spmm_rows_kernel(const SpmmArgs a) {
+template <int VEC, int L, int K, int U, bool LO = false>
+__global__ __launch_bounds__(kBlock) void spmm_rows_kernel(const SpmmArgs a) {
   constexpr int G = kWave / L;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;
   const int xcd = static_cast<int>(blockIdx.x % kXcds);
-  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) * (BLK / kWave) + wave);
+  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) * kWavesPerBlock + wave);
   const Item it = item_of(a, xcd, lw);
   if (!it.valid) return;
   const int sub = lane / L;   // neighbour slot
@@ -145,8 +149,8 @@ __global__ __launch_bounds__(BLK) void spmm_rows_kernel(const SpmmArgs a) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) vals[t][k][v] = 0.0f;
       if (e < e1) {  // masked lanes issue no memory request
-        const int c = NTI ? __builtin_nontemporal_load(a.colidx + e) : a.colidx[e];
-        ww[t] = NTI ? __builtin_nontemporal_load(a.w + e) : a.w[e];
+        const int c = a.colidx[e];
+        ww[t] = a.w[e];
         if constexpr (LO) {
           const uint16_t* src = a.u_lo + static_cast<size_t>(c) * a.ld;
 #pragma unroll
@@ -207,7 +211,7 @@ __global__ __launch_bounds__(BLK) void spmm_rows_kernel(const SpmmArgs a) {
       const size_t off = static_cast<size_t>(row) * a.ld + col;
       float ui[VEC];
       load_vec<VEC>(a.u + off, ui);
-      epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc[k], ui, a.out_y_lo);
+      epilogue<VEC, kNT, LO>(a.ep, alpha, beta, off, acc[k], ui, a.out_y_lo);
     }
   }
 }
@@ -246,9 +250,8 @@ __global__ __launch_bounds__(kBlock) void spmm_long_reduce_kernel(const SpmmArgs
 //    index load -> U gathers, not (index load -> gather) x 64/(G U);
 //  * the per-row streaming operands of the epilogue (u_i, x0_i, y_i, k1_i) are requested BEFORE the gather
 //    loop, so their latency overlaps the gathers instead of extending the wave's life;
-//  * BLK = 64: one wavefront per workgroup, so a finished wave frees its slot at once (rows of a power-law
-//    graph differ by 100x in length; with 4 waves per workgroup the slots of the short ones idle until the
-//    longest is done);  PERSIST: a resident grid strides over the work items instead of one launch slot per row.
+//  * one wavefront per workgroup, so a finished wave frees its slot at once (rows of a power-law graph differ
+//    by 100x in length; with 4 waves per workgroup the slots of the short ones idle until the longest is done).
 // Same work items, same summation order inside a row (entries in CSR order, G slots combined by the xor
 // butterfly), same epilogue arithmetic.
 // ------------------------------------------------------------------------------------------------
@@ -417,36 +420,37 @@ __device__ __forceinline__ void gather_batch(const SpmmArgs& a, int cv, float wv
     for (int v = 0; v < VEC; ++v) acc[v] = fmaf(ww[t], vals[t][v], acc[v]);
 }
 
-template <int VEC, int L, int U, int BLK, bool PERSIST, bool NT, bool FULL, bool LO = false>
-__global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
+template <int VEC, int L, int U, bool FULL, bool LO = false>
+__global__ __launch_bounds__(kWave) void spmm_wide_kernel(const SpmmArgs a) {
   constexpr int G = kWave / L;
-  constexpr int WPB = BLK / kWave;
   const int lane = threadIdx.x & (kWave - 1);
   const int sub = lane / L;   // neighbour slot
   const int cl = lane % L;    // column lane
   const int col = cl * VEC;
   const bool col_ok = FULL ? true : col < a.d;
   const int xcd = static_cast<int>(blockIdx.x % kXcds);
-  int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) * WPB + static_cast<int>(threadIdx.x >> 6));
-  const int stride = static_cast<int>(gridDim.x / kXcds) * WPB;   // waves per XCD of this launch
+  int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) + static_cast<int>(threadIdx.x >> 6));
+  const int stride = static_cast<int>(gridDim.x / kXcds);   // waves per XCD of this launch
   const int lw_end = chunks_of_xcd(a, xcd) + rows_per_xcd(a);
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, NT>(a.ep.stage);
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, kNT>(a.ep.stage);
   const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
   const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
 
+  // One item per wave: the grid has a wave for every item (balanced_grid), so stride >= lw_end and the loop body runs once.  It stays
+  // written as the loop it was when a resident grid strode over the items: as straight-line code (and as a call of shared_row_item
+  // with L as a parameter) the compiler emits a different instruction stream for all eight instantiations, and this kernel is only
+  // changed together with a measurement.
   for (; lw < lw_end; lw += stride) {
     const Item it = item_of(a, xcd, lw);
-    if (!it.valid) {
-      if constexpr (PERSIST) continue; else break;
-    }
+    if (!it.valid) break;
     const int row = it.row, e0 = it.e0, e1 = it.e1, chunk = it.chunk;
     const size_t off = static_cast<size_t>(row) * a.ld + col;
 
     // epilogue operands: in flight while the neighbours are gathered
-    Pre<VEC, NT> pre;
+    Pre<VEC, kNT> pre;
     const bool do_pre = pre_ok && chunk < 0 && sub == 0 && col_ok;
     if (do_pre) {
-      auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
+      auto ldp = [](const float* q, float (&v)[VEC]) { load_vec_nt<VEC>(q, v); };
       load_vec<VEC>(a.u + off, pre.ui);
       if (a.ep.x0 != nullptr) ldp(a.ep.x0 + off, pre.x0);
       const int st = a.ep.stage;
@@ -486,13 +490,13 @@ __global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
       continue;
     }
     if (pre_ok) {
-      epilogue_pre<VEC, NT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
+      epilogue_pre<VEC, kNT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
     } else {
       float ui[VEC];
       load_vec<VEC>(a.u + off, ui);
-      epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
+      epilogue<VEC, kNT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
     }
-    if constexpr (!PERSIST) break;
+    break;
   }
 }
 
@@ -506,15 +510,15 @@ __global__ __launch_bounds__(BLK) void spmm_wide_kernel(const SpmmArgs a) {
 // Each half keeps the wide kernel's summation order -- even entries into one accumulator, odd entries into a second, in
 // CSR order, then even + odd -- so the result is bit-identical to the shared-row mode whatever row a row is paired with.
 // A pair with a longer row falls back to the shared-row mode for its two rows in turn; hub chunks are shared-row items.
-template <int VEC, int U, bool NT, bool FULL, bool LO = false>
+template <int VEC, int U, bool FULL, bool LO = false>
 __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int e0, int e1, int chunk, int lane, int sub, int col,
                                                 bool col_ok, bool pre_ok, float alpha, float beta) {
   constexpr int L = 32, G = 2;
   const size_t off = static_cast<size_t>(row) * a.ld + col;
-  Pre<VEC, NT> pre;
+  Pre<VEC, kNT> pre;   // epilogue operands: in flight while the neighbours are gathered
   const bool do_pre = pre_ok && chunk < 0 && sub == 0 && col_ok;
   if (do_pre) {
-    auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
+    auto ldp = [](const float* q, float (&v)[VEC]) { load_vec_nt<VEC>(q, v); };
     load_vec<VEC>(a.u + off, pre.ui);
     if (a.ep.x0 != nullptr) ldp(a.ep.x0 + off, pre.x0);
     const int st = a.ep.stage;
@@ -527,9 +531,10 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
   for (int base = e0; base < e1; base += kWave) {
     const int me = base + lane;
     const bool in = me < e1;
-    const int cv = in ? a.colidx[me] : 0;
-    const float wv = in ? a.w[me] : 0.0f;
-    const int cnt = (e1 - base) < kWave ? (e1 - base) : kWave;
+    const int cv = in ? a.colidx[me] : 0;     // ONE coalesced load of 64 column ids ...
+    const float wv = in ? a.w[me] : 0.0f;     // ... and weights per wave
+    const int cnt = (e1 - base) < kWave ? (e1 - base) : kWave;   // wave-uniform
+    // full batches of G*U entries without predicates (all U gathers issue back to back), then one predicated tail
     int t0 = 0;
     for (; t0 + G * U <= cnt; t0 += G * U) gather_batch<VEC, L, U, false, FULL, LO>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
     if (t0 < cnt) gather_batch<VEC, L, U, true, FULL, LO>(a, cv, wv, t0, cnt, sub, col, col_ok, acc);
@@ -539,33 +544,32 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
   if (sub != 0 || !col_ok) return;
   if (chunk >= 0) {
     store_vec<VEC>(a.partial + static_cast<size_t>(chunk) * a.ldp + col, acc);
-    return;
+    return;  // spmm_long_reduce_kernel folds the chunks of a row in chunk order
   }
   if (a.plain_out != nullptr) {
     store_vec<VEC>(a.plain_out + off, acc);
     return;
   }
   if (pre_ok) {
-    epilogue_pre<VEC, NT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
+    epilogue_pre<VEC, kNT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
   } else {
     float ui[VEC];
     load_vec<VEC>(a.u + off, ui);
-    epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
+    epilogue<VEC, kNT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
   }
 }
 
-template <int VEC, int U, int BLK, bool NT, bool FULL, bool LO = false>
-__global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
-  constexpr int L = 32;
-  constexpr int WPB = BLK / kWave;
+template <int VEC, bool FULL, bool LO = false>
+__global__ __launch_bounds__(kWave) void spmm_pair_kernel(const SpmmArgs a) {
+  constexpr int L = 32, U = 16;   // 16 gathers in flight per half
   const int lane = threadIdx.x & (kWave - 1);
   const int half = lane >> 5;
   const int cl = lane & (L - 1);
   const int col = cl * VEC;
   const bool col_ok = FULL ? true : col < a.d;
   const int xcd = static_cast<int>(blockIdx.x % kXcds);
-  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) * WPB + static_cast<int>(threadIdx.x >> 6));
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, NT>(a.ep.stage);
+  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) + static_cast<int>(threadIdx.x >> 6));
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, kNT>(a.ep.stage);
   const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
   const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
 
@@ -575,7 +579,7 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
     const int row = __builtin_amdgcn_readfirstlane(a.lc_row[chunk]);
     const int e0 = __builtin_amdgcn_readfirstlane(a.lc_begin[chunk]);
     const int e1 = __builtin_amdgcn_readfirstlane(a.lc_end[chunk]);
-    shared_row_item<VEC, U, NT, FULL, LO>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
+    shared_row_item<VEC, U, FULL, LO>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
     return;
   }
   const int per = rows_per_xcd(a);
@@ -599,16 +603,16 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
       if (!hv) continue;
       const int hr = __builtin_amdgcn_readlane(row, h * L);
       const int h0 = __builtin_amdgcn_readlane(e0, h * L), h1 = __builtin_amdgcn_readlane(e1, h * L);
-      shared_row_item<VEC, U, NT, FULL, LO>(a, hr, h0, h1, -1, lane, half, col, col_ok, pre_ok, alpha, beta);
+      shared_row_item<VEC, U, FULL, LO>(a, hr, h0, h1, -1, lane, half, col, col_ok, pre_ok, alpha, beta);
     }
     return;
   }
 
   const size_t off = static_cast<size_t>(row) * a.ld + col;
-  Pre<VEC, NT> pre;
+  Pre<VEC, kNT> pre;
   const bool mine = have && col_ok;
   if (pre_ok && mine) {
-    auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
+    auto ldp = [](const float* q, float (&v)[VEC]) { load_vec_nt<VEC>(q, v); };
     load_vec<VEC>(a.u + off, pre.ui);
     if (a.ep.x0 != nullptr) ldp(a.ep.x0 + off, pre.x0);
     const int st = a.ep.stage;
@@ -667,11 +671,11 @@ __global__ __launch_bounds__(BLK) void spmm_pair_kernel(const SpmmArgs a) {
     return;
   }
   if (pre_ok) {
-    epilogue_pre<VEC, NT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
+    epilogue_pre<VEC, kNT, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
   } else {
     float ui[VEC];
     load_vec<VEC>(a.u + off, ui);
-    epilogue<VEC, NT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
+    epilogue<VEC, kNT, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
   }
 }
 
@@ -757,7 +761,7 @@ __device__ __forceinline__ float chunk_weights(const float (&sc)[H], float m, fl
   return wv;
 }
 
-template <int VEC, int L, int U, int H, int DK4, bool NT, bool FULL>
+template <int VEC, int L, int U, int H, int DK4, bool FULL>
 __global__ __launch_bounds__(kWave) void attn_spmm_kernel(const AttnSpmmArgs fa) {
   const SpmmArgs& a = fa.s;
   constexpr int G = kWave / L;
@@ -772,12 +776,12 @@ __global__ __launch_bounds__(kWave) void attn_spmm_kernel(const AttnSpmmArgs fa)
   if (!it.valid) return;
   const int row = it.row, e0 = it.e0, e1 = it.e1, chunk = it.chunk;
   const size_t off = static_cast<size_t>(row) * a.ld + col;
-  const bool pre_ok = stage_prefetchable<VEC, NT>(a.ep.stage);
+  const bool pre_ok = stage_prefetchable<VEC, kNT>(a.ep.stage);
 
-  Pre<VEC, NT> pre;
+  Pre<VEC, kNT> pre;
   const bool do_pre = pre_ok && chunk < 0 && sub == 0 && col_ok;
   if (do_pre) {
-    auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
+    auto ldp = [](const float* q, float (&v)[VEC]) { load_vec_nt<VEC>(q, v); };
     load_vec<VEC>(a.u + off, pre.ui);
     if (a.ep.x0 != nullptr) ldp(a.ep.x0 + off, pre.x0);
     const int st = a.ep.stage;
@@ -868,11 +872,11 @@ __global__ __launch_bounds__(kWave) void attn_spmm_kernel(const AttnSpmmArgs fa)
   const float alpha = alpha_of(a.ep);
   const float beta = a.ep.x0 != nullptr ? *a.ep.beta : 0.0f;
   if (pre_ok) {
-    epilogue_pre<VEC, NT>(a.ep, alpha, beta, off, acc, pre);
+    epilogue_pre<VEC, kNT>(a.ep, alpha, beta, off, acc, pre);
   } else {
     float ui[VEC];
     load_vec<VEC>(a.u + off, ui);
-    epilogue<VEC, NT>(a.ep, alpha, beta, off, acc, ui);
+    epilogue<VEC, kNT>(a.ep, alpha, beta, off, acc, ui);
   }
 }
 
@@ -882,8 +886,8 @@ bool launch_attn_spmm_hd(const AttnSpmmArgs& fa, hipStream_t st) {
   const int slots = (a.d + 3) / 4;
   const unsigned grid = balanced_grid(a, 1);
 #define GNPDE_AS(LL)                                                                                                     \
-  if (a.d == LL * 4) hipLaunchKernelGGL((attn_spmm_kernel<4, LL, 8, H, DK4, true, true>), dim3(grid), dim3(kWave), 0, st, fa); \
-  else hipLaunchKernelGGL((attn_spmm_kernel<4, LL, 8, H, DK4, true, false>), dim3(grid), dim3(kWave), 0, st, fa);
+  if (a.d == LL * 4) hipLaunchKernelGGL((attn_spmm_kernel<4, LL, 8, H, DK4, true>), dim3(grid), dim3(kWave), 0, st, fa); \
+  else hipLaunchKernelGGL((attn_spmm_kernel<4, LL, 8, H, DK4, false>), dim3(grid), dim3(kWave), 0, st, fa);
   if (slots <= 16) return false;
   if (slots <= 32) { GNPDE_AS(32) return true; }
   if (slots <= 64) { GNPDE_AS(64) return true; }
@@ -891,310 +895,58 @@ bool launch_attn_spmm_hd(const AttnSpmmArgs& fa, hipStream_t st) {
   return false;
 }
 
-// resident grid for the persistent variants: every CU filled with the waves its registers admit
-inline unsigned persistent_grid(int wpb) { return xcd_grid(256LL * 32 / wpb); }
-
-template <int VEC, int L, int U, int BLK, bool PERSIST>
-void launch_wide(const SpmmArgs& a, hipStream_t s) {
-  constexpr int WPB = BLK / kWave;
-  unsigned grid = balanced_grid(a, WPB);
-  if (PERSIST && grid > persistent_grid(WPB)) grid = persistent_grid(WPB);
-  if (a.d == L * VEC) hipLaunchKernelGGL((spmm_wide_kernel<VEC, L, U, BLK, PERSIST, true, true>), dim3(grid), dim3(BLK), 0, s, a);
-  else hipLaunchKernelGGL((spmm_wide_kernel<VEC, L, U, BLK, PERSIST, true, false>), dim3(grid), dim3(BLK), 0, s, a);
-}
-
-// Software-pipelined, resident form of the row-pair kernel.  A wave of the one-item-per-wave kernels pays three dependent memory
-// round trips per row (row pointer -> column ids / weights -> neighbour rows) and has data in flight during one of them only.
-// Here a resident wave strides over the pairs of its XCD and keeps three pairs in different stages: while the neighbour rows of
-// pair A are gathered, the column ids / weights of pair B and the row pointers of pair C are already on their way, so an
-// iteration waits for ONE round trip.  Same per-row arithmetic and summation order as spmm_pair_kernel (bit-identical).
-template <int VEC, int U, int BLK, bool NT, bool FULL>
-__global__ __launch_bounds__(BLK) void spmm_pair_pipe_kernel(const SpmmArgs a) {
-  constexpr int L = 32;
-  constexpr int WPB = BLK / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int half = lane >> 5;
-  const int cl = lane & (L - 1);
-  const int col = cl * VEC;
-  const bool col_ok = FULL ? true : col < a.d;
-  const int xcd = static_cast<int>(blockIdx.x % kXcds);
-  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) * WPB + static_cast<int>(threadIdx.x >> 6));
-  const int wpx = static_cast<int>(gridDim.x / kXcds) * WPB;       // waves of this XCD
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, NT>(a.ep.stage);
-  const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
-  const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
-
-  const int cx = chunks_of_xcd(a, xcd);
-  int j = lw;
-  for (; j < cx; j += wpx) {   // hub chunks first
-    const int chunk = a.chunk_begin + j * kXcds + xcd;
-    const int row = __builtin_amdgcn_readfirstlane(a.lc_row[chunk]);
-    const int e0 = __builtin_amdgcn_readfirstlane(a.lc_begin[chunk]);
-    const int e1 = __builtin_amdgcn_readfirstlane(a.lc_end[chunk]);
-    shared_row_item<VEC, U, NT, FULL>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
-  }
-  const int per = rows_per_xcd(a);
-  const int first = a.row_begin + xcd * per;
-  int last = first + per;
-  if (last > a.row_end) last = a.row_end;
-  const int n_pairs = last > first ? (last - first + 1) / 2 : 0;
-  int p = j - cx;
-  if (p >= n_pairs) return;
-
-  // stage 1: row pointers of a pair (half h: row first + 2 p + h); rows longer than GNPDE_LONG_ROW are chunk items
-  auto header = [&](int pp, int& row, int& e0, int& len) {
-    row = first + 2 * pp + half;
-    const bool have = pp < n_pairs && row < last;
-    int b = 0, e = 0;
-    if (have) {
-      b = a.rowptr[row];
-      e = a.rowptr[row + 1];
-    }
-    e0 = b;
-    len = (have && e - b <= GNPDE_LONG_ROW) ? e - b : -1;      // -1: nothing to do for this half
-  };
-  // stage 2: the row's first 32 column ids / weights, one coalesced load per half
-  auto columns = [&](int e0, int len, int& cv, float& wv) {
-    const bool in = cl < len;
-    cv = in ? a.colidx[e0 + cl] : 0;
-    wv = in ? a.w[e0 + cl] : 0.0f;
-  };
-  int row_a, e0_a, len_a, row_b, e0_b, len_b, row_c, e0_c, len_c;
-  int cv_a, cv_b;
-  float wv_a, wv_b;
-  header(p, row_a, e0_a, len_a);
-  columns(e0_a, len_a, cv_a, wv_a);
-  header(p + wpx, row_b, e0_b, len_b);
-
-  for (;;) {
-    columns(e0_b, len_b, cv_b, wv_b);              // pair B: ids / weights on their way ...
-    header(p + 2 * wpx, row_c, e0_c, len_c);       // pair C: row pointers on their way ...
-    const int la = __builtin_amdgcn_readlane(len_a, 0), lb = __builtin_amdgcn_readlane(len_a, L);
-    if (la > L || lb > L) {                        // a longer row in the pair: both halves share each row in turn
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int hl = h == 0 ? la : lb;
-        if (hl < 0) continue;
-        const int hr = __builtin_amdgcn_readlane(row_a, h * L), h0 = __builtin_amdgcn_readlane(e0_a, h * L);
-        shared_row_item<VEC, U, NT, FULL>(a, hr, h0, h0 + hl, -1, lane, half, col, col_ok, pre_ok, alpha, beta);
-      }
-    } else {                                       // ... while pair A gathers its neighbour rows
-      const size_t off = static_cast<size_t>(row_a) * a.ld + col;
-      Pre<VEC, NT> pre;
-      const bool mine = len_a >= 0 && col_ok;
-      if (pre_ok && mine) {
-        auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
-        load_vec<VEC>(a.u + off, pre.ui);
-        if (a.ep.x0 != nullptr) ldp(a.ep.x0 + off, pre.x0);
-        const int st = a.ep.stage;
-        if (st == GNPDE_STAGE_EULER || st == GNPDE_STAGE_RK2C || st == GNPDE_STAGE_RK4C) ldp(a.ep.y + off, pre.y);
-        if (st == GNPDE_STAGE_RK3C || st == GNPDE_STAGE_RK4C) ldp(a.ep.k1 + off, pre.k1);
-      }
-      const int cmax = la > lb ? la : lb;
-      float acc0[VEC], acc1[VEC];
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) acc0[v] = acc1[v] = 0.0f;
-      for (int t0 = 0; t0 < cmax; t0 += U) {
-        float vals[U][VEC];
-        float ww[U];
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-          const int idx = t0 + t;
-          const int c = __shfl(cv_a, (half << 5) + idx, kWave);
-          const float w = __shfl(wv_a, (half << 5) + idx, kWave);
-          const bool ok = col_ok && idx < len_a;
-          ww[t] = ok ? w : 0.0f;
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) vals[t][v] = 0.0f;
-          if (ok) load_vec<VEC>(a.u + static_cast<size_t>(c) * a.ld + col, vals[t]);
-        }
-#pragma unroll
-        for (int t = 0; t < U; ++t) {
-          if (t % 2 == 0) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc0[v] = fmaf(ww[t], vals[t][v], acc0[v]);
-          } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc1[v] = fmaf(ww[t], vals[t][v], acc1[v]);
-          }
-        }
-      }
-      if (mine) {
-        float acc[VEC];
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v] = acc0[v] + acc1[v];
-        if (a.plain_out != nullptr) {
-          store_vec<VEC>(a.plain_out + off, acc);
-        } else if (pre_ok) {
-          epilogue_pre<VEC, NT>(a.ep, alpha, beta, off, acc, pre);
-        } else {
-          float ui[VEC];
-          load_vec<VEC>(a.u + off, ui);
-          epilogue<VEC, NT>(a.ep, alpha, beta, off, acc, ui);
-        }
-      }
-    }
-    p += wpx;
-    if (p >= n_pairs) break;
-    row_a = row_b; e0_a = e0_b; len_a = len_b; cv_a = cv_b; wv_a = wv_b;
-    row_b = row_c; e0_b = e0_c; len_b = len_c;
-  }
+template <int L>
+void launch_wide(const SpmmArgs& a, hipStream_t s) {   // 8 gathers in flight, one wavefront per workgroup
+  const unsigned grid = balanced_grid(a, 1);
+  if (a.d == L * 4) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, true>), dim3(grid), dim3(kWave), 0, s, a);
+  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, false>), dim3(grid), dim3(kWave), 0, s, a);
 }
 
 // row pairs: one wave per two consecutive rows (hub chunks first, as balanced_grid)
-template <int VEC, int U, int BLK>
+inline unsigned pair_grid(const SpmmArgs& a) {
+  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
+  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
+  long long blocks = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
+  if (blocks < 1) blocks = 1;
+  return static_cast<unsigned>(blocks * kXcds);
+}
+
 void launch_pair(const SpmmArgs& a, hipStream_t s) {
-  constexpr int WPB = BLK / kWave;
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
-  const long long per_xcd = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
-  long long blocks = (per_xcd + WPB - 1) / WPB;
-  if (blocks < 1) blocks = 1;
-  const unsigned grid = static_cast<unsigned>(blocks * kXcds);
-  if (a.d == 32 * VEC) hipLaunchKernelGGL((spmm_pair_kernel<VEC, U, BLK, true, true>), dim3(grid), dim3(BLK), 0, s, a);
-  else hipLaunchKernelGGL((spmm_pair_kernel<VEC, U, BLK, true, false>), dim3(grid), dim3(BLK), 0, s, a);
-}
-
-// A/B (gnpde_tune(0, 135)): the same kernel with ordinary (cached) loads and stores of the per-row streaming operands
-template <int VEC, int U, int BLK>
-void launch_pair_cached(const SpmmArgs& a, hipStream_t s) {
-  constexpr int WPB = BLK / kWave;
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
-  const long long per_xcd = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
-  long long blocks = (per_xcd + WPB - 1) / WPB;
-  if (blocks < 1) blocks = 1;
-  const unsigned grid = static_cast<unsigned>(blocks * kXcds);
-  if (a.d == 32 * VEC) hipLaunchKernelGGL((spmm_pair_kernel<VEC, U, BLK, false, true>), dim3(grid), dim3(BLK), 0, s, a);
-  else hipLaunchKernelGGL((spmm_pair_kernel<VEC, U, BLK, false, false>), dim3(grid), dim3(BLK), 0, s, a);
-}
-
-// resident grid of the pipelined row-pair kernel: `waves_per_cu` waves on every CU, shrunk when there is less work than that
-template <int VEC, int U, int BLK>
-void launch_pair_pipe(const SpmmArgs& a, hipStream_t s, int waves_per_cu) {
-  constexpr int WPB = BLK / kWave;
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per = (rn + kXcds - 1) / kXcds;
-  const long long per_xcd = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
-  long long blocks = (per_xcd + WPB - 1) / WPB;             // per XCD, one item per wave
-  const long long resident = 256LL * waves_per_cu / WPB / kXcds;
-  if (blocks > resident) blocks = resident;
-  if (blocks < 1) blocks = 1;
-  const unsigned grid = static_cast<unsigned>(blocks * kXcds);
-  SpmmArgs c = a;
-  c.row_shift = -1;   // this (A/B only) kernel walks a contiguous range of row pairs per XCD
-  if (a.d == 32 * VEC) hipLaunchKernelGGL((spmm_pair_pipe_kernel<VEC, U, BLK, true, true>), dim3(grid), dim3(BLK), 0, s, c);
-  else hipLaunchKernelGGL((spmm_pair_pipe_kernel<VEC, U, BLK, true, false>), dim3(grid), dim3(BLK), 0, s, c);
-}
-
-// tune codes >= 100 (tools/spmm_ab.py): 100 + 10 * {0: U4, 1: U8, 2: U16} + {0: 256 thr, 1: 64 thr, 2: 256 thr persistent,
-// 3: 64 thr persistent}
-template <int VEC, int L>
-bool dispatch_wide(const SpmmArgs& a, hipStream_t s, int code) {
-  switch (code) {
-    case 100: launch_wide<VEC, L, 4, 256, false>(a, s); return true;
-    case 101: launch_wide<VEC, L, 4, 64, false>(a, s); return true;
-    case 102: launch_wide<VEC, L, 4, 256, true>(a, s); return true;
-    case 103: launch_wide<VEC, L, 4, 64, true>(a, s); return true;
-    case 110: launch_wide<VEC, L, 8, 256, false>(a, s); return true;
-    case 111: launch_wide<VEC, L, 8, 64, false>(a, s); return true;
-    case 112: launch_wide<VEC, L, 8, 256, true>(a, s); return true;
-    case 113: launch_wide<VEC, L, 8, 64, true>(a, s); return true;
-    case 120: launch_wide<VEC, L, 16, 256, false>(a, s); return true;
-    case 121: launch_wide<VEC, L, 16, 64, false>(a, s); return true;
-    case 122: launch_wide<VEC, L, 16, 256, true>(a, s); return true;
-    case 123: launch_wide<VEC, L, 16, 64, true>(a, s); return true;
-    default: return false;
-  }
-}
-
-template <int VEC, int L, int K, int U, bool NTI, bool NT = NTI>
-void launch_rows(const SpmmArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((spmm_rows_kernel<VEC, L, K, U, NTI, NT>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
+  if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
+  else hipLaunchKernelGGL((spmm_pair_kernel<4, false>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
 }
 
 template <int VEC, int L, int K, int U>
-void launch_rows_b64(const SpmmArgs& a, hipStream_t s) {   // one wavefront per workgroup (A/B: intra-block imbalance)
-  hipLaunchKernelGGL((spmm_rows_kernel<VEC, L, K, U, false, true, 64>), dim3(balanced_grid(a, 1)), dim3(64), 0, s, a);
+void launch_rows(const SpmmArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((spmm_rows_kernel<VEC, L, K, U>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
 }
 
+// One line per width class (slots = lanes of VEC floats that cover a row); what every class takes was measured, the alternatives that
+// lost are recorded in DESIGN.md section 3 and profiles/.
 template <int VEC>
 int dispatch_rows(const SpmmArgs& a, hipStream_t s) {
   const int slots = (a.d + VEC - 1) / VEC;
-  int code = g_tune[GNPDE_TUNE_SPMM_VARIANT];
-  // default for 16-byte lanes and rows of 17..64 lanes (d = 68..256): the wide-row kernel, 8 gathers in flight, one
-  // wavefront per workgroup -- measured best at the ogbn-arxiv shape (178 vs 221 us) and within 1 % of the best at the
-  // R-MAT d = 256 shape (16.6 vs 16.8 ms), tools/spmm_ab.py, profiles/r02_ab_*.log
-  // rows of 17..32 lanes (d = 68..128) in graphs whose rows are mostly short (the ogbn-arxiv shape: median 8 entries): two rows
-  // per wave, 16 gathers in flight per half (spmm_pair_kernel; bit-identical results): 171 vs 184 us at the ogbn-arxiv shape,
-  // 193 vs 230 us on a uniform degree-8 graph, but 2 % slower at degree 24 -- hence the hint (profiles/r02_ab_row_pairs.txt)
-  if (code == 0 && VEC == 4 && slots > 16 && slots <= 32 && a.short_rows) code = 133;
-  if (code == 0 && VEC == 4 && slots > 16 && slots <= 64) code = 111;
-  if (code == 99) code = 0;   // A/B: force the round-1 kernel
-  if (code >= 130 && code <= 149 && VEC == 4 && slots > 16 && slots <= 32) {   // row pairs (A/B)
+  if (slots <= 8) launch_rows<VEC, 8, 1, 4>(a, s);
+  else if (slots <= 16) launch_rows<VEC, 16, 1, 4>(a, s);
+  else if (slots <= 64) {
     if constexpr (VEC == 4) {
-      switch (code) {
-        case 140: launch_pair_pipe<4, 8, 64>(a, s, 16); return 0;
-        case 141: launch_pair_pipe<4, 16, 64>(a, s, 12); return 0;
-        case 142: launch_pair_pipe<4, 8, 256>(a, s, 16); return 0;
-        case 143: launch_pair_pipe<4, 16, 256>(a, s, 12); return 0;
-        case 144: launch_pair_pipe<4, 8, 64>(a, s, 20); return 0;
-        case 145: launch_pair_pipe<4, 16, 64>(a, s, 8); return 0;
-        case 146: launch_pair_pipe<4, 8, 64>(a, s, 32); return 0;
-        case 147: launch_pair_pipe<4, 16, 64>(a, s, 16); return 0;
-        case 130: launch_pair<4, 8, 64>(a, s); return 0;
-        case 131: launch_pair<4, 8, 256>(a, s); return 0;
-        case 132: launch_pair<4, 4, 64>(a, s); return 0;
-        case 133: launch_pair<4, 16, 64>(a, s); return 0;
-        case 134: launch_pair<4, 4, 256>(a, s); return 0;
-        case 135: launch_pair_cached<4, 16, 64>(a, s); return 0;
-        default: launch_pair<4, 16, 256>(a, s); return 0;
-      }
-    }
-  }
-  if (code >= 100) {
-    bool done = false;
-    if (slots <= 16) done = dispatch_wide<VEC, 16>(a, s, code);
-    else if (slots <= 32) done = dispatch_wide<VEC, 32>(a, s, code);
-    else if (slots <= 64) done = dispatch_wide<VEC, 64>(a, s, code);
-    if (done) return 0;
-  }
-  if (code == 50) {
-    if (slots <= 32 && slots > 16) { launch_rows_b64<VEC, 16, 2, 4>(a, s); return 0; }
-    if (slots <= 64 && slots > 32) { launch_rows_b64<VEC, 32, 2, 4>(a, s); return 0; }
-  }
-  if (slots <= 8) launch_rows<VEC, 8, 1, 4, false, true>(a, s);
-  else if (slots <= 16) launch_rows<VEC, 16, 1, 4, false, true>(a, s);
-  else if (slots <= 32) {
-    if constexpr (VEC == 4) {  // the headline shape (d = 128): tunable for A/B runs
-      const int v = g_tune[GNPDE_TUNE_SPMM_VARIANT];
-      switch (v) {
-        case 1: launch_rows<4, 32, 1, 8, false>(a, s); break;
-        case 2: launch_rows<4, 16, 2, 2, false>(a, s); break;
-        case 3: launch_rows<4, 32, 1, 4, true>(a, s); break;
-        case 4: launch_rows<4, 32, 1, 8, true>(a, s); break;
-        case 5: launch_rows<4, 16, 2, 4, false>(a, s); break;
-        case 6: launch_rows<4, 32, 1, 2, false>(a, s); break;
-        case 7: launch_rows<4, 16, 2, 4, true>(a, s); break;
-        case 8: launch_rows<4, 16, 2, 8, true>(a, s); break;
-        case 9: launch_rows<4, 8, 4, 2, true>(a, s); break;
-        case 10: launch_rows<4, 8, 4, 4, true>(a, s); break;
-        case 11: launch_rows<4, 16, 2, 4, true, false>(a, s); break;
-        case 12: launch_rows<4, 16, 2, 4, false, true>(a, s); break;
-        case 13: launch_rows<4, 16, 2, 2, true>(a, s); break;
-        case 14: launch_rows<4, 32, 1, 4, false, true>(a, s); break;
-        case 15: launch_rows<4, 32, 1, 4, true, false>(a, s); break;
-        case 16: launch_rows<4, 32, 1, 4, false>(a, s); break;
-        default: launch_rows<4, 16, 2, 4, false, true>(a, s); break;  // measured best on MI355X (tools/spmm_ab.py)
-      }
+      // 16-byte lanes, rows of 17..64 lanes (d = 68..256): the wide-row kernel, 8 gathers in flight, one wavefront per workgroup --
+      // measured best at the ogbn-arxiv shape (178 vs 221 us) and within 1 % of the best at the R-MAT d = 256 shape (16.6 vs
+      // 16.8 ms), profiles/r02_ab_*.log.
+      // Rows of 17..32 lanes (d = 68..128) in graphs whose rows are mostly short (the ogbn-arxiv shape: median 8 entries): two rows
+      // per wave, 16 gathers in flight per half (spmm_pair_kernel; bit-identical results): 171 vs 184 us at the ogbn-arxiv shape,
+      // 193 vs 230 us on a uniform degree-8 graph, but 2 % slower at degree 24 -- hence the hint (profiles/r02_ab_row_pairs.txt)
+      if (slots <= 32 && a.short_rows) launch_pair(a, s);
+      else if (slots <= 32) launch_wide<32>(a, s);
+      else launch_wide<64>(a, s);
     } else {
-      launch_rows<VEC, 16, 2, 4, false, true>(a, s);
+      if (slots <= 32) launch_rows<VEC, 16, 2, 4>(a, s);
+      else launch_rows<VEC, 32, 2, 4>(a, s);
     }
   }
-  else if (slots <= 64) launch_rows<VEC, 32, 2, 4, false, true>(a, s);
-  else if (slots <= 128) launch_rows<VEC, 64, 2, 2, false, true>(a, s);
-  else if (slots <= 192) launch_rows<VEC, 64, 3, 1, false, true>(a, s);
-  else if (slots <= 256) launch_rows<VEC, 64, 4, 1, false, true>(a, s);
+  else if (slots <= 128) launch_rows<VEC, 64, 2, 2>(a, s);
+  else if (slots <= 192) launch_rows<VEC, 64, 3, 1>(a, s);
+  else if (slots <= 256) launch_rows<VEC, 64, 4, 1>(a, s);
   else {
     set_error("spmm: feature width d=%d too large for VEC=%d (max %d)", a.d, VEC, 256 * VEC);
     return GNPDE_ESHAPE;
@@ -1204,29 +956,23 @@ int dispatch_rows(const SpmmArgs& a, hipStream_t s) {
 
 
 // bf16 gather operand (16-byte lanes of the state only): the default kernel of every width class with the gather element type
-// switched -- same work items, lane mapping and summation order as the fp32 kernels that dispatch_rows<4> picks by default, so a
-// plain aggregation from a shadow is bit-identical to gnpde_spmm on the widened table.  The A/B-only variants (pair_pipe,
-// pair_cached, the tune codes) have no bf16 form.
+// switched -- same work items, lane mapping and summation order as the fp32 kernels that dispatch_rows<4> picks, so a plain
+// aggregation from a shadow is bit-identical to gnpde_spmm on the widened table.
 template <int L, int K, int U>
 void launch_rows_lo(const SpmmArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((spmm_rows_kernel<4, L, K, U, false, true, kBlock, true>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL((spmm_rows_kernel<4, L, K, U, true>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
 }
 
 template <int L>
 void launch_wide_lo(const SpmmArgs& a, hipStream_t s) {
   const unsigned grid = balanced_grid(a, 1);
-  if (a.d == L * 4) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, 64, false, true, true, true>), dim3(grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, 64, false, true, false, true>), dim3(grid), dim3(64), 0, s, a);
+  if (a.d == L * 4) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, true, true>), dim3(grid), dim3(kWave), 0, s, a);
+  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, false, true>), dim3(grid), dim3(kWave), 0, s, a);
 }
 
 void launch_pair_lo(const SpmmArgs& a, hipStream_t s) {
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
-  long long blocks = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
-  if (blocks < 1) blocks = 1;
-  const unsigned grid = static_cast<unsigned>(blocks * kXcds);
-  if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, 16, 64, true, true, true>), dim3(grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((spmm_pair_kernel<4, 16, 64, true, false, true>), dim3(grid), dim3(64), 0, s, a);
+  if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
+  else hipLaunchKernelGGL((spmm_pair_kernel<4, false, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
 }
 
 // Row-QUAD form of the row-pair kernel for the bf16 gather operand: a bf16 row of d <= 128 columns is 256 bytes, so with the pair
@@ -1235,7 +981,7 @@ void launch_pair_lo(const SpmmArgs& a, hipStream_t s) {
 // 16-entry loads per quarter).  Per row the summation is the pair kernel's (even entries into one accumulator, odd entries into a
 // second, CSR order, then even + odd), so the results are bit-identical to it.  A quad with a longer row falls back to the
 // shared-row mode (32 x 4) for its rows in turn; hub chunks are shared-row items.  Needs d % 8 == 0, ld % 8 == 0, 16-byte aligned shadows.
-template <int U, bool NT>
+template <int U>
 __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
   constexpr int VEC = 4, L = 16, E = 8;
   const int lane = threadIdx.x & (kWave - 1);
@@ -1245,7 +991,7 @@ __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
   const bool col_ok = col < a.d;
   const int xcd = static_cast<int>(blockIdx.x % kXcds);
   const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds));
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, NT>(a.ep.stage);
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, kNT>(a.ep.stage);
   const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
   const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
   // the shared-row mode keeps the 32 x 4 mapping
@@ -1258,7 +1004,7 @@ __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
     const int row = __builtin_amdgcn_readfirstlane(a.lc_row[chunk]);
     const int e0 = __builtin_amdgcn_readfirstlane(a.lc_begin[chunk]);
     const int e1 = __builtin_amdgcn_readfirstlane(a.lc_end[chunk]);
-    shared_row_item<VEC, 16, NT, false, true>(a, row, e0, e1, chunk, lane, half, col4, col4_ok, pre_ok, alpha, beta);
+    shared_row_item<VEC, 16, false, true>(a, row, e0, e1, chunk, lane, half, col4, col4_ok, pre_ok, alpha, beta);
     return;
   }
   const int per = rows_per_xcd(a);
@@ -1287,16 +1033,16 @@ __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
       if (!hv) continue;
       const int hr = __builtin_amdgcn_readlane(row, h * L);
       const int h0 = __builtin_amdgcn_readlane(e0, h * L), h1 = __builtin_amdgcn_readlane(e1, h * L);
-      shared_row_item<VEC, 16, NT, false, true>(a, hr, h0, h1, -1, lane, half, col4, col4_ok, pre_ok, alpha, beta);
+      shared_row_item<VEC, 16, false, true>(a, hr, h0, h1, -1, lane, half, col4, col4_ok, pre_ok, alpha, beta);
     }
     return;
   }
 
   const size_t off = static_cast<size_t>(row) * a.ld + col;
-  Pre<VEC, NT> pre[2];
+  Pre<VEC, kNT> pre[2];
   const bool mine = have && col_ok;
   if (pre_ok && mine) {
-    auto ldp = [](const float* q, float (&v)[VEC]) { if constexpr (NT) load_vec_nt<VEC>(q, v); else load_vec<VEC>(q, v); };
+    auto ldp = [](const float* q, float (&v)[VEC]) { load_vec_nt<VEC>(q, v); };
     const int st = a.ep.stage;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1357,11 +1103,11 @@ __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
     if (a.plain_out != nullptr) {
       store_vec<VEC>(a.plain_out + o, acc);
     } else if (pre_ok) {
-      epilogue_pre<VEC, NT, true>(a.ep, alpha, beta, o, acc, pre[h], a.out_y_lo);
+      epilogue_pre<VEC, kNT, true>(a.ep, alpha, beta, o, acc, pre[h], a.out_y_lo);
     } else {
       float ui[VEC];
       load_vec<VEC>(a.u + o, ui);
-      epilogue<VEC, NT, true>(a.ep, alpha, beta, o, acc, ui, a.out_y_lo);
+      epilogue<VEC, kNT, true>(a.ep, alpha, beta, o, acc, ui, a.out_y_lo);
     }
   }
 }
@@ -1371,7 +1117,7 @@ void launch_quad_lo(const SpmmArgs& a, hipStream_t s) {
   const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
   long long blocks = (cn + kXcds - 1) / kXcds + (per + 3) / 4;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((spmm_quad_lo_kernel<16, true>), dim3(static_cast<unsigned>(blocks * kXcds)), dim3(kWave), 0, s, a);
+  hipLaunchKernelGGL((spmm_quad_lo_kernel<16>), dim3(static_cast<unsigned>(blocks * kXcds)), dim3(kWave), 0, s, a);
 }
 
 int dispatch_rows_lo(const SpmmArgs& a, hipStream_t s) {
@@ -1801,9 +1547,6 @@ int launch_adjoint_rows(const gnpde_graph_t* g, const float* w_csr, const float*
   }
   return 0;
 }
-
-namespace {
-}  // namespace
 
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes, hipStream_t stream,

@@ -44,7 +44,7 @@ extern "C" {
 
 int         gnpde_abi_version(void);
 const char* gnpde_last_error(void);
-/* Select a kernel variant for A/B measurements (key 0: aggregation kernel variant); 0 = default. */
+/* Select a kernel variant for A/B measurements; 0 = default.  Keys 0, 8 and 13 are retired: any value but 0 is GNPDE_EINVAL. */
 int         gnpde_tune(int32_t key, int32_t value);
 
 /* ------------------------------------------------------------------------------------------------

@@ -482,6 +482,26 @@ def test_xcd_row_map_takes_every_row_exactly_once(contiguous):
     _xcd_map(0, 10, 7)
 
 
+def test_retired_tune_keys_fail_loudly():
+  """Keys 0, 8 and 13 selected aggregation / projection variants that are gone: a value other than 0 is refused (an old A/B command line
+  must not silently measure the default), 0 is accepted; the live keys keep taking their values."""
+  L = _lib.lib()
+  for key, value in ((0, 135), (8, 6), (13, 1)):
+    assert L.gnpde_tune(key, value) == -1     # GNPDE_EINVAL
+    assert 'retired' in L.gnpde_last_error().decode()
+    with pytest.raises(G.GnpdeError, match='retired'):
+      G.ops.tune(key, value)
+  for key in (0, 8, 13):
+    assert L.gnpde_tune(key, 0) == 0
+  live = ((9, 1), (9, 2), (10, 1), (10, 2), (14, 1), (15, 1), (16, 1), (17, 9), (18, 1), (18, 2), (19, 4), (20, 1), (20, 2))
+  try:
+    for key, value in live:
+      assert L.gnpde_tune(key, value) == 0
+  finally:
+    for key, _ in live:
+      _lib.check(L.gnpde_tune(key, 0))
+
+
 def test_xcd_deal_is_chosen_per_graph():
   """Row length that depends on the bits of the row id, as in an R-MAT graph (expected degree x 0.32 per set bit): contiguous
   eighths -- and any fixed round robin of blocks -- leave the XCDs 1.5 - 2x out of balance, the hashed deal within a few per cent (0.2 % at the R-MAT size); the graph
