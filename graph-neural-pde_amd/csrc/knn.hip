@@ -18,12 +18,12 @@
 // Every result is a function of the sorted set of (distance, column) keys and the distance of a pair does not depend on the
 // tiling: bit-identical from run to run and for every S.
 #include "common.h"
+#include "wave_sort.h"
 
 namespace gnpde {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
 
 constexpr int kTM = 64;              // query rows per workgroup (16 per wave)
 constexpr int kTN = 64;              // columns per step
@@ -33,32 +33,6 @@ constexpr int kMaxK = 128;
 constexpr int kMaxMergeKeys = 4096;  // S * k of the merge kernel (32 KiB of LDS per row)
 constexpr int kMaxSplits = 32;
 constexpr u64 kPadKey = ~0ull;
-
-// LDS traffic of ONE wave on rows no other wave touches: program order is enough for the hardware, the fence keeps the
-// compiler (and the LDS counter) in line
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// ascending bitonic sort of b[0 .. P) (P a power of two >= 2) by one wave
-__device__ __forceinline__ void wave_sort(u64* b, int P, int lane) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int p = lane; p < (P >> 1); p += kWave) {
-        const int i = ((p & ~(stride - 1)) << 1) | (p & (stride - 1));
-        const int j = i | stride;
-        const bool up = (i & size) == 0;
-        const u64 a = b[i], c = b[j];
-        if ((a > c) == up) {
-          b[i] = c;
-          b[j] = a;
-        }
-      }
-      wave_lds_sync();
-    }
-  }
-}
 
 __global__ __launch_bounds__(kBlock) void knn_norms_kernel(const float* __restrict__ x, int n, int d, long long ldx,
                                                           float* __restrict__ norms) {

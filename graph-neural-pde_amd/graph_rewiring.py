@@ -1,9 +1,17 @@
-"""k-nearest-neighbour rewiring in feature space (BLEND's `--rewire_KNN`; reference src/graph_rewiring.py:116-147): `KNN` and
+"""Graph rewiring under the reference's names and signatures (src/graph_rewiring.py).
+
+k-nearest-neighbour rewiring in feature space (BLEND's `--rewire_KNN`; reference src/graph_rewiring.py:116-147): `KNN` and
 `apply_KNN` under the reference's names and signatures.  The search is the native kernel behind `ops.knn` (the reference uses a
 pykeops LazyTensor.argKmin); making the edge set undirected is torch device ops (once per rewiring).
 
 Tie order is a definition of this package (KeOps leaves it unspecified): a node's neighbours are ascending by the computed
-distance, equal distances by ascending node index; a node is its own first neighbour (distance exactly 0)."""
+distance, equal distances by ascending node index; a node is its own first neighbour (distance exactly 0).
+
+Graph diffusion rewiring (`--rewiring gdc`, and `--beltrami --pos_enc_type GDC`; reference graph_rewiring.py:51-90, 345-401):
+`apply_gdc` and `GDCWrapper`.  The reference's class subclasses torch_geometric.transforms.GDC and inverts a dense [n, n] matrix;
+here the diffusion matrix is formed column block by column block with the aggregation kernel and sparsified on the device
+(`ops.gdc`; the definition is in include/gnpde.h).  torch_geometric is not imported.  One deliberate difference: zero entries are
+never emitted (PyG's dense top-k also emits zero-weight edges, in arbitrary order)."""
 import torch
 
 from . import ops
@@ -43,3 +51,104 @@ def apply_KNN(data, pos_encoding, model, opt):
   else:
     raise Exception("Need to set rewire_KNN_T")
   return ei
+
+
+class GDCWrapper(object):
+  """The reference's GDCWrapper (graph_rewiring.py:345-401) without torch_geometric: same constructor, `__call__(data)` and
+  `position_encoding(data)`.  diffusion_kwargs: method 'ppr' (alpha), 'heat' (t) or 'coeff' (coeffs); sparsification_kwargs: method
+  'topk' (k; dim = 0, per column, is the only orientation the reference uses) or 'threshold' (eps).  `exact` and the approximate
+  push's `eps` in diffusion_kwargs are accepted and ignored: this path computes the exact object up to `tol` (the truncated tail
+  of the series, 1e-6 by default), for every size.  Sparsification by avg_degree is not built."""
+
+  def __init__(self, self_loop_weight=1, normalization_in='sym', normalization_out='col',
+               diffusion_kwargs=dict(method='ppr', alpha=0.15), sparsification_kwargs=dict(method='threshold', avg_degree=64),
+               exact=True, tol=1e-6, block=256):
+    self.self_loop_weight = self_loop_weight
+    self.normalization_in = normalization_in
+    self.normalization_out = normalization_out
+    self.diffusion_kwargs = diffusion_kwargs
+    self.sparsification_kwargs = sparsification_kwargs
+    self.exact = exact
+    self.tol = tol
+    self.block = block
+
+  def _diffusion(self):
+    kw = self.diffusion_kwargs
+    method = kw.get('method')
+    if method == 'ppr':
+      return dict(method='ppr', alpha=kw['alpha'])
+    if method == 'heat':
+      return dict(method='heat', t=kw['t'])
+    if method == 'coeff':
+      return dict(method='coeff', coeffs=kw['coeffs'])
+    raise ValueError('GDCWrapper: unknown diffusion method %r' % (method,))
+
+  def _sparsification(self):
+    kw = self.sparsification_kwargs
+    method = kw.get('method')
+    if method == 'topk':
+      if kw.get('dim', 0) != 0:
+        raise NotImplementedError('GDCWrapper: top-k along dim = %r is not built (the reference uses dim = 0, per column)' % kw.get('dim'))
+      return dict(k=kw['k'])
+    if method == 'threshold':
+      if 'eps' not in kw:
+        raise NotImplementedError('GDCWrapper: threshold sparsification by avg_degree is not built; give eps')
+      return dict(eps=kw['eps'])
+    raise ValueError('GDCWrapper: unknown sparsification method %r' % (method,))
+
+  def _common(self, data):
+    n = data.num_nodes[0] if isinstance(data.num_nodes, list) else data.num_nodes
+    kw = dict(self_loop_weight=float(self.self_loop_weight) if self.self_loop_weight else 0.0, normalization_in=self.normalization_in,
+              normalization_out=self.normalization_out, tol=self.tol, block=self.block)
+    kw.update(self._diffusion())
+    return int(n), kw
+
+  @torch.no_grad()
+  def __call__(self, data):
+    """data.edge_index / data.edge_attr replaced by the diffused, sparsified, normalised graph, sorted by (row, col) as
+    torch_sparse.coalesce returns it."""
+    n, kw = self._common(data)
+    kw.update(self._sparsification())
+    ei, ew = ops.gdc(data.edge_index, data.edge_attr, n, **kw)
+    order = torch.sort(ei[0] * n + ei[1]).indices       # (row, col) pairs are unique
+    data.edge_index, data.edge_attr = ei[:, order].contiguous(), ew[order].contiguous()
+    return data
+
+  @torch.no_grad()
+  def position_encoding(self, data):
+    """The dense [n, n] diffusion matrix, normalised, entry [i, j] = S[i, j] (no sparsification, reference :363-401)."""
+    n, kw = self._common(data)
+    return ops.gdc(data.edge_index, data.edge_attr, n, dense_out=True, **kw)
+
+
+def apply_gdc(data, opt, type="combined"):
+  """The reference's apply_gdc (graph_rewiring.py:51-90) with the same option mapping: gdc_method with ppr_alpha / heat_time,
+  gdc_sparsification with gdc_k (per-column top-k) or gdc_threshold, self_loop_weight, 'sym' in and 'col' out, pos_enc_orientation.
+  opt['exact'] and the push tolerance are accepted and ignored (see GDCWrapper); opt['gnpde_gdc_tol'] (1e-6) truncates the series."""
+  num_edges = lambda d: int(d.edge_index.shape[1])
+  print('raw data contains {} edges and {} nodes'.format(num_edges(data), data.num_nodes))
+  print('performing gdc transformation with method {}, sparsification {}'.format(opt['gdc_method'], opt['gdc_sparsification']))
+  if opt['gdc_method'] == 'ppr':
+    diff_args = dict(method='ppr', alpha=opt['ppr_alpha'])
+  else:
+    diff_args = dict(method='heat', t=opt['heat_time'])
+  if opt['gdc_sparsification'] == 'topk':
+    sparse_args = dict(method='topk', k=opt['gdc_k'], dim=0)
+  else:
+    sparse_args = dict(method='threshold', eps=opt['gdc_threshold'])
+  diff_args['eps'] = opt.get('gdc_threshold')
+  print('gdc sparse args: {}'.format(sparse_args))
+  gdc = GDCWrapper(float(opt['self_loop_weight']) if opt['self_loop_weight'] != 0 else None, normalization_in='sym',
+                   normalization_out='col', diffusion_kwargs=diff_args, sparsification_kwargs=sparse_args,
+                   exact=opt.get('exact', True), tol=opt.get('gnpde_gdc_tol', 1e-6))
+  if isinstance(data.num_nodes, list):
+    data.num_nodes = data.num_nodes[0]
+  if type == 'combined':
+    data = gdc(data)
+  elif type == 'pos_encoding':
+    if opt['pos_enc_orientation'] == "row":  # encode row of S_hat
+      return gdc.position_encoding(data)
+    elif opt['pos_enc_orientation'] == "col":  # encode col of S_hat
+      return gdc.position_encoding(data).T
+  print('following rewiring data contains {} edges and {} nodes'.format(num_edges(data), data.num_nodes))
+  return data

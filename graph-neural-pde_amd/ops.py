@@ -333,6 +333,209 @@ def two_hop(graph, weight):
   return out_ei, out_w
 
 
+GDC_MAX_K = 128
+GDC_MAX_TERMS = 4096        # M of the truncated series
+GDC_DENSE_CAP = 2 << 30     # bytes of the [n, n] matrix the dense mode agrees to write
+
+
+def gdc_terms(method, param, tol=1e-6):
+  """The coefficients theta_0 .. theta_M of S = sum_m theta_m T^m that `gdc` uses (pure Python, float64):
+  'ppr' (param = alpha): theta_m = alpha (1 - alpha)^m;  'heat' (param = t): theta_m = e^-t t^m / m!;  'coeff' (param = a list): the
+  list as given.  M is the smallest with 1 - sum_{m <= M} theta_m <= tol."""
+  import math
+  if method == 'coeff':
+    theta = [float(c) for c in param]
+    if not theta or len(theta) > GDC_MAX_TERMS + 1 or any(not math.isfinite(c) or c < 0 for c in theta):
+      raise ValueError('gdc: coeffs must be 1 .. %d finite non-negative numbers' % (GDC_MAX_TERMS + 1))
+    return theta
+  tol = float(tol)
+  if not 0.0 < tol < 1.0:
+    raise ValueError('gdc: tol = %r outside (0, 1)' % tol)
+  if method == 'ppr':
+    alpha = float(param)
+    if not 0.0 < alpha <= 1.0:
+      raise ValueError('gdc: ppr alpha = %r outside (0, 1]' % alpha)
+    term = lambda m: alpha * (1.0 - alpha) ** m
+  elif method == 'heat':
+    t = float(param)
+    if not (t >= 0.0 and math.isfinite(t)):
+      raise ValueError('gdc: heat t = %r is not a finite non-negative number' % t)
+    term = lambda m: math.exp(m * math.log(t) - t - math.lgamma(m + 1.0)) if t > 0.0 else (1.0 if m == 0 else 0.0)
+  else:
+    raise ValueError("gdc: method %r is not 'ppr', 'heat' or 'coeff'" % (method,))
+  theta = []
+  while True:
+    theta.append(term(len(theta)))
+    if 1.0 - math.fsum(theta) <= tol:
+      return theta
+    if len(theta) > GDC_MAX_TERMS:
+      raise ValueError('gdc: the series needs more than %d terms for tol = %g (%s, %r)' % (GDC_MAX_TERMS, tol, method, param))
+
+
+def _segment_sums(w_sorted, counts, divide=False):
+  """Sums of the consecutive segments of w_sorted with the given lengths (int64 device tensor), formed in a fixed order
+  (gnpde_gdc_segment_sums: no atomics); divide: w_sorted is divided by its segment's sum in place (0 for a zero sum)."""
+  offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=w_sorted.device)
+  torch.cumsum(counts, 0, out=offsets[1:])
+  sums = torch.zeros(counts.numel(), dtype=torch.float32, device=w_sorted.device)
+  if counts.numel() and w_sorted.numel():
+    check(_lib.lib().gnpde_gdc_segment_sums(ptr(w_sorted), ptr(offsets), counts.numel(), ptr(sums), int(bool(divide)),
+                                            stream_of(w_sorted)))
+  return sums
+
+
+def _sums_by(index, w, n):
+  """sums[i] = sum of w over index == i, deterministic (stable sort + fixed-order segment sums)."""
+  order = torch.sort(index, stable=True).indices
+  return _segment_sums(w[order].contiguous(), torch.bincount(index, minlength=n))
+
+
+def _gdc_normalise(row, col, w, n, kind):
+  """Step 2 / 5 of the definition on a coalesced list; the reciprocal of zero is 0."""
+  if kind is None:
+    return w
+  inv = lambda s, p: torch.where(s > 0, s.double().pow(p).float(), torch.zeros_like(s))
+  if kind == 'sym':
+    r = inv(_sums_by(row, w, n), -0.5)
+    return w * r[row] * r[col]
+  if kind in ('col', 'row'):
+    idx = col if kind == 'col' else row
+    s = _sums_by(idx, w, n)[idx]
+    return torch.where(s > 0, w / s, torch.zeros_like(w))
+  raise ValueError("gdc: normalisation %r is not 'sym', 'col', 'row' or None" % (kind,))
+
+
+def gdc_transition(edge_index, edge_weight, n, self_loop_weight=1.0, normalization_in='sym'):
+  """Steps 1-2 of the definition in include/gnpde.h (device tensors): (row, col, w) of T, coalesced and sorted by (row, col)."""
+  dev = edge_index.device
+  row, col = edge_index[0].long(), edge_index[1].long()
+  w = torch.ones(row.numel(), dtype=torch.float32, device=dev) if edge_weight is None else f32c(edge_weight.detach().reshape(-1), 'edge_weight')
+  if w.numel() != row.numel():
+    raise ValueError('gdc: %d weights for %d edges' % (w.numel(), row.numel()))
+  # every term of the series must be non-negative: the error bound is relative and the selection keys order positive floats
+  if edge_weight is not None and w.numel() and not bool((torch.isfinite(w) & (w >= 0)).all()):
+    raise ValueError('gdc: edge weights must be finite and non-negative')
+  self_loop_weight = float(self_loop_weight or 0.0)
+  if not 0.0 <= self_loop_weight < float('inf'):
+    raise ValueError('gdc: self_loop_weight = %r is not a finite non-negative number' % (self_loop_weight,))
+  if row.numel() and (int(torch.minimum(row.min(), col.min())) < 0 or int(torch.maximum(row.max(), col.max())) >= n):
+    raise ValueError('gdc: edge index outside [0, %d)' % n)
+  if self_loop_weight:
+    loop = torch.arange(n, dtype=torch.int64, device=dev)
+    row, col = torch.cat([row, loop]), torch.cat([col, loop])
+    w = torch.cat([w, torch.full((n,), self_loop_weight, dtype=torch.float32, device=dev)])
+  key, order = torch.sort(row * n + col, stable=True)
+  uniq, counts = torch.unique_consecutive(key, return_counts=True)
+  w = _segment_sums(w[order].contiguous(), counts)
+  row, col = torch.div(uniq, n, rounding_mode='floor'), uniq % n
+  return row, col, _gdc_normalise(row, col, w, n, normalization_in)
+
+
+def gdc(edge_index, edge_weight, n, *, method, alpha=None, t=None, coeffs=None, k=None, eps=None, self_loop_weight=1.0,
+        normalization_in='sym', normalization_out='col', tol=1e-6, block=256, dense_out=False, dense_cap_bytes=GDC_DENSE_CAP):
+  """Graph diffusion rewiring (the definition is in include/gnpde.h): S = sum_m theta_m T^m for 'ppr' (alpha), 'heat' (t) or
+  'coeff' (coeffs), truncated by gdc_terms(.., tol); per column the k largest strictly positive entries (k) or the entries >= eps
+  (eps); output normalisation over the kept entries.  Returns (edge_index [2, E'] int64 with row = i, col = j for a kept S[i, j],
+  edge_weight [E']) grouped by ascending column, within a column by value descending and equal values by ascending row;
+  bit-identical from run to run.  dense_out: no sparsification, the normalised [n, n] matrix (refused above dense_cap_bytes).
+  Columns are processed in blocks of `block` (a multiple of 4, <= 256) on an [n, block] slab; no [n, n] array exists otherwise.
+  Zero entries are never emitted (torch_geometric's dense top-k emits them, in arbitrary order)."""
+  n = int(n)
+  if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+    raise ValueError('gdc: edge_index must be [2, E]')
+  if n < 1 or n >= 2 ** 31:
+    raise ValueError('gdc: n = %d outside 1 .. 2^31 - 1' % n)
+  block = int(block)
+  if block < 4 or block > 256 or block % 4:
+    raise ValueError('gdc: block = %d is not a multiple of 4 in 4 .. 256' % block)
+  if normalization_in not in ('sym', 'col', 'row') or normalization_out not in ('sym', 'col', 'row', None):
+    raise ValueError('gdc: unknown normalisation (%r in, %r out)' % (normalization_in, normalization_out))
+  param = {'ppr': alpha, 'heat': t, 'coeff': coeffs}.get(method)
+  if method not in ('ppr', 'heat', 'coeff') or param is None:
+    raise ValueError("gdc: method %r needs its parameter (ppr: alpha, heat: t, coeff: coeffs)" % (method,))
+  theta = gdc_terms(method, param, tol)
+  if not dense_out:
+    if (k is None) == (eps is None):
+      raise ValueError('gdc: give exactly one of k (top-k per column) and eps (threshold)')
+    if k is not None and not 1 <= int(k) <= GDC_MAX_K:
+      raise ValueError('gdc: k = %r outside 1 .. %d' % (k, GDC_MAX_K))
+    if eps is not None and not float(eps) > 0.0:
+      raise ValueError('gdc: eps = %r is not positive (zeros are never kept)' % (eps,))
+  elif 4 * n * n > int(dense_cap_bytes):
+    raise _lib.GnpdeError('gdc: the dense %d x %d matrix exceeds the cap of %d bytes' % (n, n, int(dense_cap_bytes)))
+  for t in (edge_index, edge_weight):
+    if t is not None and not t.is_cuda:
+      raise _lib.GnpdeError('gdc runs only on a HIP device (got a %s tensor); there is no CPU fallback' % t.device.type)
+  from .graph import CSRGraph
+  dev = edge_index.device
+  L = _lib.lib()
+  row, col, w = gdc_transition(edge_index.detach(), edge_weight, n, self_loop_weight, normalization_in)
+  graph = CSRGraph(torch.stack([row, col]), n, dev)            # sorted by (row, col): CSR order is the list's own
+  w_csr = w[graph.perm_long].contiguous() if graph.e else w
+  theta_dev = torch.tensor(theta, dtype=torch.float32, device=dev)
+  kk = 0 if (dense_out or k is None) else int(k)
+  ws = torch.empty(max(int(L.gnpde_gdc_workspace_bytes(graph.ref(), block, kk)), 256), dtype=torch.uint8, device=dev)
+  slab = torch.empty(n, block, dtype=torch.float32, device=dev)
+  stream = stream_of(slab)
+  run_block = lambda j0: check(L.gnpde_gdc_block(graph.ref(), ptr(w_csr), ptr(theta_dev), len(theta), j0, block, ptr(slab), ptr(ws),
+                                                 ws.numel(), stream))
+  i64 = dict(dtype=torch.int64, device=dev)
+  if dense_out:
+    dense = torch.empty(n, n, dtype=torch.float32, device=dev)
+    for j0 in range(0, n, block):
+      run_block(j0)
+      check(L.gnpde_gdc_dense(graph.ref(), ptr(slab), j0, block, int(normalization_out == 'col'), ptr(dense), int(dense_cap_bytes),
+                              ptr(ws), ws.numel(), stream))
+    if normalization_out == 'row':
+      s = dense.sum(dim=1, keepdim=True)
+      dense = torch.where(s > 0, dense / s, torch.zeros_like(dense))
+    elif normalization_out == 'sym':
+      r = dense.sum(dim=1)
+      r = torch.where(r > 0, r.double().pow(-0.5).float(), torch.zeros_like(r))
+      dense = dense * r[:, None] * r[None, :]
+    return dense
+  native_col = normalization_out == 'col'
+  if kk:
+    keys = torch.empty(n, kk, **i64)               # uint64 bit patterns
+    offsets = torch.zeros(n + 1, **i64)
+    for j0 in range(0, n, block):
+      run_block(j0)
+      check(L.gnpde_gdc_topk(graph.ref(), ptr(slab), j0, block, kk, ptr(keys), ptr(offsets[1:]), ptr(ws), ws.numel(), stream))
+    torch.cumsum(offsets[1:].clone(), 0, out=offsets[1:])
+    total = int(offsets[-1].item())                # the one host read
+    out_ei = torch.empty(2, total, **i64)
+    out_w = torch.empty(total, dtype=torch.float32, device=dev)
+    if total:
+      check(L.gnpde_gdc_emit(ptr(keys), ptr(offsets), n, kk, int(native_col), ptr(out_ei), total, ptr(out_w), stream))
+  else:
+    eps = float(eps)
+    parts = []
+    counts = torch.zeros(block, **i64)
+    offsets = torch.zeros(block + 1, **i64)
+    for j0 in range(0, n, block):
+      run_block(j0)
+      counts.zero_()
+      check(L.gnpde_gdc_threshold_count(graph.ref(), ptr(slab), j0, block, eps, ptr(counts), ptr(ws), ws.numel(), stream))
+      torch.cumsum(counts, 0, out=offsets[1:])
+      total = int(offsets[-1].item())              # one host read per block: the output size is data dependent
+      if total == 0:
+        continue
+      ei = torch.empty(2, total, **i64)
+      ew = torch.empty(total, dtype=torch.float32, device=dev)
+      check(L.gnpde_gdc_threshold_fill(graph.ref(), j0, block, eps, ptr(offsets), ptr(ei), total, ptr(ew), ptr(ws), ws.numel(), stream))
+      # within a column: value descending, equal values by ascending row (the fill wrote ascending rows; both sorts are stable)
+      order = torch.sort(ew, descending=True, stable=True).indices
+      order = order[torch.sort(ei[1][order], stable=True).indices]
+      parts.append((ei[:, order], ew[order]))
+    out_ei = torch.cat([p[0] for p in parts], dim=1) if parts else torch.zeros(2, 0, **i64)
+    out_w = torch.cat([p[1] for p in parts]) if parts else torch.zeros(0, dtype=torch.float32, device=dev)
+    if native_col and out_w.numel():
+      _segment_sums(out_w, torch.bincount(out_ei[1], minlength=n), divide=True)
+  if normalization_out in ('row', 'sym') and out_w.numel():
+    out_w = _gdc_normalise(out_ei[0], out_ei[1], out_w, n, normalization_out)
+  return out_ei, out_w
+
+
 def edge_attention_bwd_heads(graph, att, datt_edge, post=0):
   """ds [E,h] (CSR order) from a per-head gradient in edge order (gnpde_edge_attention_bwd_heads); post: 0 raw-score gradient,
   1 times the score (exp kernels), 2 times LeakyReLU' (GAT)."""

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 10  /* 10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 11  /* 11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -809,6 +809,55 @@ int gnpde_two_hop_count(const int32_t* rowptr, const int32_t* col, int32_t n_nod
 int gnpde_two_hop_fill(const int32_t* rowptr, const int32_t* col, const float* w, int32_t n_nodes, const int64_t* out_rowptr,
                        int64_t* out_edge_index, int64_t out_ld, float* out_weight, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* Graph diffusion rewiring (GDC; `--rewiring gdc` and BLEND's `--pos_enc_type GDC`, reference src/graph_rewiring.py:51-90, 345-401,
+ * a subclass of torch_geometric.transforms.GDC).  Definition (this header is the authority; PyG is no dependency):
+ *   1. A = the caller's weighted edges, a loop of self_loop_weight appended to EVERY node when that weight is non-zero, duplicate
+ *      (row, col) entries summed.
+ *   2. T = normalise(A): 'sym' w_e deg[row]^-1/2 deg[col]^-1/2 with deg_i = sum over row_e = i of w_e; 'col' w_e / (sum of the
+ *      column's weights); 'row' likewise over rows; the reciprocal of zero is 0.  (Steps 1-2 are the caller's: torch device ops.)
+ *   3. S = sum_{m = 0 .. M} theta_m T^m: ppr theta_m = alpha (1 - alpha)^m, heat theta_m = e^-t t^m / m!, or a caller's list;
+ *      M is the smallest with 1 - sum_{m <= M} theta_m <= tol (the caller's, Python gdc_terms).
+ *   4. per column j of S: top-k keeps the k largest STRICTLY POSITIVE entries, ordered by value descending, equal values by
+ *      ascending row; a column with fewer positive entries yields fewer.  threshold keeps the entries >= eps (eps > 0).  Zeros are
+ *      never emitted (PyG's dense top-k also emits zero-weight edges, in arbitrary order: the one deliberate difference).
+ *   5. output normalisation over the kept entries ('col': every non-empty column sums to 1), the same zero rule; no NaN / Inf.
+ *   6. edge_index [2, E'] int64 with row = i, col = j for a kept S[i, j], grouped by ascending column; within a column as in 4
+ *      (top-k) or by ascending row (threshold fill).  No atomics anywhere: bit-identical from run to run.
+ * A column block S[:, j0 .. j0 + block) is a Horner recurrence on an [n, block] slab:  X = theta_M E, then M times X <- T X
+ * (gnpde_spmm, as it is) and X[j0 + b, b] += theta_m.  theta is a DEVICE array of n_terms = M + 1 floats.  No [n, n] array
+ * exists outside gnpde_gdc_dense.  g: the graph of T (row_begin = 0), w_csr its weights in CSR order.
+ *   gnpde_gdc_block            slab [n, block] (row stride block) <- S[:, j0 .. j0 + block), columns past n are zero
+ *   gnpde_gdc_topk             slab -> keys [n, k] uint64 (rows j0 .. of it: ~value bits << 32 | row, ascending = the order of 4,
+ *                              padded with ~0) and counts[j0 + b] = kept entries of column j0 + b (int64)
+ *   gnpde_gdc_emit             after the last block: offsets [n + 1] = exclusive scan of counts (the caller's) -> out_edge_index
+ *                              ([2, out_ld] int64, row-major), out_weight = value (normalise = 0) or value / column sum (1);
+ *                              the sum of a column is formed in a fixed order
+ *   gnpde_gdc_threshold_count  slab -> counts [block] int64 (column j0 + b at b; columns past n are not written)
+ *   gnpde_gdc_threshold_fill   must follow the count of the SAME block on the same stream and workspace: offsets [block + 1] =
+ *                              exclusive scan of counts -> (row, col, value) at offsets[b] .., rows ascending
+ *   gnpde_gdc_segment_sums     sums[s] = sum of w[offsets[s] .. offsets[s + 1]) in a fixed order (sums may be NULL); divide != 0:
+ *                              the segment is divided by its sum in place (an empty sum gives 0): 'col' / 'row' / 'sym' sums
+ *   gnpde_gdc_dense            dense [n, n] fp32: dense[i, j0 + b] = S[i, j0 + b] (normalise = 0) or / the column's sum (1);
+ *                              GNPDE_ESHAPE when 4 n^2 > cap_bytes
+ * Limits: block a multiple of 4 in 4 .. 256, 1 <= k <= 128, n <= INT32_MAX, 1 <= n_terms <= 4097 (M <= 4096), eps > 0; outside
+ * them GNPDE_ESHAPE / GNPDE_EINVAL with gnpde_last_error set and nothing launched (gnpde_gdc_workspace_bytes: 0).  One workspace
+ * (k = 0 when no top-k follows) serves every call of a block; it includes the aggregation's scratch. */
+size_t gnpde_gdc_workspace_bytes(const gnpde_graph_t* g, int32_t block, int32_t k);
+int gnpde_gdc_block(const gnpde_graph_t* g, const float* w_csr, const float* theta, int32_t n_terms, int64_t j0, int32_t block,
+                    float* slab, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_gdc_topk(const gnpde_graph_t* g, const float* slab, int64_t j0, int32_t block, int32_t k, uint64_t* keys,
+                   int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_gdc_emit(const uint64_t* keys, const int64_t* offsets, int32_t n, int32_t k, int32_t normalise,
+                   int64_t* out_edge_index, int64_t out_ld, float* out_weight, void* stream);
+int gnpde_gdc_threshold_count(const gnpde_graph_t* g, const float* slab, int64_t j0, int32_t block, float eps, int64_t* counts,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_gdc_threshold_fill(const gnpde_graph_t* g, int64_t j0, int32_t block, float eps, const int64_t* offsets,
+                             int64_t* out_edge_index, int64_t out_ld, float* out_weight, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int gnpde_gdc_segment_sums(float* w, const int64_t* offsets, int64_t n_segments, float* sums, int32_t divide, void* stream);
+int gnpde_gdc_dense(const gnpde_graph_t* g, const float* slab, int64_t j0, int32_t block, int32_t normalise, float* dense,
+                    size_t cap_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-partitioned solve over the GPUs of one node: one process per GPU, RCCL point-to-point halo exchange once per
