@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 11     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 12     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
@@ -27,6 +27,8 @@ ADAPTIVE_HEUN, ADAPTIVE_DOPRI5 = range(2)
 TUNE_FUSED_BLOCKS_PER_CU, TUNE_ONE_PASS, TUNE_FORK, TUNE_ATT_GENERIC_ROWS, TUNE_RK4_CLASSIC = range(1, 6)
 TUNE_ROW_FUSION, TUNE_ONE_PASS_VARIANT, TUNE_SPMM_PART, TUNE_XCD_ROWS, TUNE_HUB_FOLD = 6, 7, 9, 10, 11
 TUNE_KNN_SPLITS = 19     # column splits of the k-nearest-neighbour search: 0 = chosen from n and the CU count, S > 0 forces S
+METRIC_SQEUCLIDEAN = 0   # GNPDE_METRIC_* of include/gnpde.h (the key of a pair in gnpde_knn_metric / gnpde_radius_*)
+METRIC_POINCARE = 1
 TUNE_KNN_VARIANT = 20    # tile-kernel variants of the search (A/B): 1 = 32-float K chunks for k > 32, 2 = the k > 32 kernel for every k
 TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)
 
@@ -231,6 +233,15 @@ PROTOTYPES = {
                                            c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_knn_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
   'gnpde_knn': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_knn_metric': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp,
+                                      ctypes.c_size_t, c_vp]),
+  'gnpde_radius_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32]),
+  'gnpde_radius_quantile': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, c_vp, c_vp,
+                                           ctypes.c_size_t, c_vp]),
+  'gnpde_radius_count': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_float, c_vp, c_vp,
+                                        ctypes.c_size_t, c_vp]),
+  'gnpde_radius_fill': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_float, c_vp,
+                                       ctypes.c_int64, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_gdc_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(GraphStruct), ctypes.c_int32, ctypes.c_int32]),
   'gnpde_gdc_block': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_vp, c_vp,
                                      ctypes.c_size_t, c_vp]),

@@ -6,7 +6,7 @@ ODEFuncTransformerAtt`, src/model_configurations.py:1-9; `from base_classes impo
 early_stop_solver import EarlyStopInt`, src/GNN_early.py:10).  `install()` answers those imports with the modules of this
 package, whatever the order of `sys.path`:
 
-    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
+    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
 
 or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before the first import of a reference module.
 
@@ -21,7 +21,9 @@ or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before th
   `run_GNN.py --rewire_KNN` then runs the native kernel; with no reference file on the path the module is this package's alone.
   `native_gdc=True` / `--native-gdc` merges the same module with `apply_gdc` and `GDCWrapper` replaced (graph diffusion rewiring,
   `--rewiring gdc` and `--pos_enc_type GDC`): `data.py`'s `from graph_rewiring import apply_gdc` then gets the native one.  Both
-  flags together replace all three names.
+  flags together replace all three names.  `native_posdist=True` / `--native-posdist` likewise replaces `apply_pos_dist_rewire`
+  (positional-distance rewiring, `--rewiring pos_enc_knn`) and the helpers it calls (`apply_beltrami`, `hyperbolize`,
+  `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold`); the flags combine.
 """
 import importlib
 import importlib.abc
@@ -51,6 +53,9 @@ OVERRIDES = ('ODEFunc', 'ODEblock', 'RegularizedODEfunc')                       
 MERGES = {MERGED: ('gnpde_amd.base_classes', OVERRIDES, False)}
 NATIVE_KNN = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('KNN',), True)}    # optional: the native neighbour search
 NATIVE_GDC = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('apply_gdc', 'GDCWrapper'), True)}   # optional: native graph diffusion rewiring
+# optional: native positional-distance rewiring (--rewiring pos_enc_knn) with the helpers it calls
+NATIVE_POSDIST = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('apply_pos_dist_rewire', 'apply_beltrami', 'hyperbolize', 'apply_feat_KNN',
+                                                                   'apply_dist_KNN', 'apply_dist_threshold'), True)}
 
 
 def _reference_file(name):
@@ -111,10 +116,10 @@ def installed():
   return _finder in sys.meta_path
 
 
-def install(native_gnn=False, native_knn=False, native_gdc=False):
+def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist=False):
   """Answer the reference's module names with this package (idempotent).  Returns the list of names now served."""
   merges = dict(MERGES)
-  for on, extra in ((native_knn, NATIVE_KNN), (native_gdc, NATIVE_GDC)):
+  for on, extra in ((native_knn, NATIVE_KNN), (native_gdc, NATIVE_GDC), (native_posdist, NATIVE_POSDIST)):
     if on:
       for name, (target, names, standalone) in extra.items():
         before = merges.get(name, (target, (), standalone))[1]
@@ -141,7 +146,7 @@ def uninstall():
   if _finder in sys.meta_path:
     sys.meta_path.remove(_finder)
   _finder.table = dict(MERGES)
-  merged = sorted(set(MERGES) | set(NATIVE_KNN) | set(NATIVE_GDC))
+  merged = sorted(set(MERGES) | set(NATIVE_KNN) | set(NATIVE_GDC) | set(NATIVE_POSDIST))
   for name in list(MODULES) + list(NATIVE_GNN) + merged + ['_reference_' + m for m in merged]:
     m = sys.modules.get(name)
     if isinstance(m, types.ModuleType) and (getattr(m, '__name__', '').startswith('gnpde_amd') or
@@ -150,13 +155,14 @@ def uninstall():
 
 
 def main(argv=None):
-  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
+  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
   to the front of sys.path, as `python SCRIPT` would put it)."""
   import runpy
   argv = list(sys.argv[1:] if argv is None else argv)
   native = False
   native_knn = False
   native_gdc = False
+  native_posdist = False
   while argv and argv[0].startswith('--'):
     flag = argv.pop(0)
     if flag == '--native-gnn':
@@ -165,15 +171,17 @@ def main(argv=None):
       native_knn = True
     elif flag == '--native-gdc':
       native_gdc = True
+    elif flag == '--native-posdist':
+      native_posdist = True
     else:
-      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] SCRIPT [ARGS...]' % flag)
+      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] SCRIPT [ARGS...]' % flag)
   if not argv:
-    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] SCRIPT [ARGS...]')
+    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] SCRIPT [ARGS...]')
   script = os.path.abspath(argv[0])
   if not os.path.isfile(script):
     raise SystemExit('gnpde_amd.dropin: no such script: %s' % argv[0])
   sys.path.insert(0, os.path.dirname(script))
-  install(native_gnn=native, native_knn=native_knn, native_gdc=native_gdc)
+  install(native_gnn=native, native_knn=native_knn, native_gdc=native_gdc, native_posdist=native_posdist)
   sys.argv = [script] + argv[1:]
   runpy.run_path(script, run_name='__main__')
 

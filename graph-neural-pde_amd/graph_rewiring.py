@@ -11,7 +11,19 @@ Graph diffusion rewiring (`--rewiring gdc`, and `--beltrami --pos_enc_type GDC`;
 `apply_gdc` and `GDCWrapper`.  The reference's class subclasses torch_geometric.transforms.GDC and inverts a dense [n, n] matrix;
 here the diffusion matrix is formed column block by column block with the aggregation kernel and sparsified on the device
 (`ops.gdc`; the definition is in include/gnpde.h).  torch_geometric is not imported.  One deliberate difference: zero entries are
-never emitted (PyG's dense top-k also emits zero-weight edges, in arbitrary order)."""
+never emitted (PyG's dense top-k also emits zero-weight edges, in arbitrary order).
+
+Positional-distance rewiring (`--rewiring pos_enc_knn`; reference graph_rewiring.py:285-342, hyperbolic_distances.py:7-14,
+distances_kNN.py): `apply_pos_dist_rewire` with `hyperbolize`, `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold` and
+`apply_beltrami`.  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
+it or hands it to sklearn's NearestNeighbors(metric='precomputed'); here the edge set comes straight from the encodings
+(`ops.knn(metric=...)`, `ops.radius_graph`), so the helpers take ENCODINGS where the reference's take a distance matrix.
+Deliberate differences: no [n, n] distance pickle is written; the edge set is computed whether or not a cache file existed (the
+reference's HYP branch leaves `ei` unbound on a cache hit); a stale `data.edge_attr` is dropped; scipy, sklearn and
+torch_geometric are not imported."""
+import os
+import pickle
+
 import torch
 
 from . import ops
@@ -151,4 +163,118 @@ def apply_gdc(data, opt, type="combined"):
     elif opt['pos_enc_orientation'] == "col":  # encode col of S_hat
       return gdc.position_encoding(data).T
   print('following rewiring data contains {} edges and {} nodes'.format(num_edges(data), data.num_nodes))
+  return data
+
+
+HYPERBOLIZE_CAP = 2 << 30     # bytes of the dense [n, n] float32 matrix `hyperbolize` agrees to write
+POS_DIST_QUANTILE = 1 / 1000  # the reference's default of apply_dist_threshold / threshold_mat (distances_kNN.py:21, 31)
+
+
+def _encodings(x):
+  """Positional encodings as a float32 matrix on the device the native ops run on (the reference's pickles hold CPU tensors or
+  ndarrays)."""
+  x = torch.as_tensor(x)
+  if x.dtype != torch.float32:
+    x = x.to(torch.float32)
+  if not x.is_cuda and torch.cuda.is_available():
+    x = x.cuda()
+  return x
+
+
+def hyperbolize(x):
+  """Dense [n, n] float32 matrix of Poincare-ball distances arccosh(1 + 2 |x_i - x_j|^2 / ((1 - |x_i|^2)(1 - |x_j|^2))) between the
+  rows of x (reference hyperbolic_distances.py:7-14): every row of the native search with k = n, scattered into place.  For small
+  n and for tests only: it refuses above HYPERBOLIZE_CAP bytes, as `ops.gdc(dense_out=True)` does, and above the largest k of
+  the search (n <= 128).  Nothing else in this module needs this matrix."""
+  x = _encodings(x)
+  n = x.shape[0]
+  if 4 * n * n > HYPERBOLIZE_CAP or n > ops.KNN_MAX_K:
+    raise ops._lib.GnpdeError('hyperbolize: a dense [%d, %d] matrix is refused (n <= %d, %d bytes); use ops.knn(metric='
+                              "'poincare') or ops.radius_graph" % (n, n, ops.KNN_MAX_K, HYPERBOLIZE_CAP))
+  idx, dist = ops.knn(x, n, return_dist=True, metric='poincare')
+  out = torch.empty(n, n, dtype=torch.float32, device=dist.device)
+  out.scatter_(1, idx, dist)
+  return out
+
+
+def _knn_edges(x, k, metric):
+  ind = ops.knn(_encodings(x), int(k), metric=metric)
+  n = ind.shape[0]
+  src = torch.arange(n, dtype=torch.int64, device=ind.device).repeat_interleave(int(k))
+  return torch.stack([src, ind.reshape(-1)], dim=0)
+
+
+def apply_feat_KNN(x, k):
+  """edge_index [2, n k] int64 (row 0: every node k times, row 1: its k nearest rows of x in Euclidean distance, itself first):
+  the reference's distances_kNN.apply_feat_KNN (:5-11, sklearn NearestNeighbors) on the native search.  x: ENCODINGS [n, d]."""
+  return _knn_edges(x, k, 'sqeuclidean')
+
+
+def apply_dist_KNN(x, k):
+  """The reference's distances_kNN.apply_dist_KNN (:13-19) for hyperbolic distances -- but x is the ENCODINGS [n, d] (points of the
+  Poincare ball), not the precomputed [n, n] distance matrix: the distances are formed tile by tile inside the search."""
+  return _knn_edges(x, k, 'poincare')
+
+
+def apply_dist_threshold(x, quant=POS_DIST_QUANTILE, metric='sqeuclidean'):
+  """edge_index [2, E] int64 of every pair, self loops included, whose distance is <= the quant-quantile of all n^2 distances,
+  sorted by (row, col): the reference's distances_kNN.apply_dist_threshold (:21-32, np.quantile + np.where) -- but x is the
+  ENCODINGS [n, d], not a distance matrix; metric 'sqeuclidean' (Euclidean distances) or 'poincare' (hyperbolic)."""
+  return ops.radius_graph(_encodings(x), quantile=quant, metric=metric)
+
+
+def apply_beltrami(data, opt, data_dir='../data'):
+  """Positional encodings (reference graph_rewiring.py:244-282): the cached pickle `<data_dir>/pos_encodings/<dataset>_<type>.pkl`
+  the reference loads (the 'data' entry for DW* types); otherwise, for pos_enc_type 'GDC', the native
+  `apply_gdc(type='pos_encoding')`, cached as the reference caches it.  Generating DeepWalk or hyperbolic embeddings is not
+  built: a missing pickle of such a type is an error."""
+  pos_enc_dir = os.path.join(data_dir, 'pos_encodings')
+  fname = os.path.join(pos_enc_dir, '%s_%s.pkl' % (opt['dataset'], opt['pos_enc_type']))
+  print('[i] Looking for positional encodings in %s...' % fname)
+  if os.path.exists(fname):
+    print('    Found them! Loading cached version')
+    with open(fname, 'rb') as f:
+      pos_encoding = pickle.load(f)
+    if opt['pos_enc_type'].startswith('DW'):
+      pos_encoding = pos_encoding['data']
+    return pos_encoding
+  if opt['pos_enc_type'] != 'GDC':
+    raise FileNotFoundError('apply_beltrami: no cached positional encodings %s, and type %r cannot be generated here'
+                            % (fname, opt['pos_enc_type']))
+  print('    Encodings not found! Calculating and caching them')
+  pos_encoding = apply_gdc(data, opt, type='pos_encoding')
+  os.makedirs(pos_enc_dir, exist_ok=True)
+  with open(fname, 'wb') as f:
+    pickle.dump(pos_encoding, f)
+  return pos_encoding
+
+
+def apply_pos_dist_rewire(data, opt, data_dir='../data', pos_encoding=None):
+  """data.edge_index replaced by the graph of positional-encoding distances (reference graph_rewiring.py:285-342), same branch table:
+    pos_enc_type HYP* + gdc_sparsification 'topk'       Poincare k-NN with k = opt['gdc_k']
+    pos_enc_type HYP* + 'threshold'                     Poincare radius graph at the quantile opt['pos_dist_quantile']
+    pos_enc_type DW*  + 'topk'                          Euclidean k-NN with k = opt['gdc_k']
+    pos_enc_type DW*  + 'threshold'                     Euclidean radius graph at the reference's default quantile 1/1000
+  pos_encoding: the encodings [n, d], when the caller has them; otherwise apply_beltrami(data, opt, data_dir) loads them.
+  Differences from the reference (module docstring): no [n, n] distance pickle, the edge set is always computed, edge_attr is
+  dropped.  edge_index is int64 [2, E] on the device of the search."""
+  kind, sparse = opt['pos_enc_type'], opt['gdc_sparsification']
+  if kind.startswith('HYP'):
+    metric = 'poincare'
+  elif kind.startswith('DW'):
+    metric = 'sqeuclidean'
+  else:
+    raise ValueError('apply_pos_dist_rewire: positional encoding type %r is neither HYP* nor DW*' % (kind,))
+  if sparse not in ('topk', 'threshold'):
+    raise ValueError('apply_pos_dist_rewire: gdc_sparsification %r is neither topk nor threshold' % (sparse,))
+  if pos_encoding is None:
+    pos_encoding = apply_beltrami(data, opt, data_dir)
+  if sparse == 'topk':
+    ei = apply_dist_KNN(pos_encoding, opt['gdc_k']) if metric == 'poincare' else apply_feat_KNN(pos_encoding, opt['gdc_k'])
+  else:
+    quant = opt['pos_dist_quantile'] if metric == 'poincare' else POS_DIST_QUANTILE
+    ei = apply_dist_threshold(pos_encoding, quant, metric=metric)
+  data.edge_index = ei.to(torch.int64)
+  if getattr(data, 'edge_attr', None) is not None:
+    data.edge_attr = None
   return data

@@ -285,29 +285,130 @@ def threshold_edges(edge_index, score, threshold, norm_idx, n_nodes):
 
 
 KNN_MAX_K = 128
+METRICS = {'sqeuclidean': _lib.METRIC_SQEUCLIDEAN, 'poincare': _lib.METRIC_POINCARE}
 
 
-def knn(x, k, return_dist=False):
-  """The k nearest rows of every row of x ([n, d] float32 on a HIP device; padded rows with unit column stride are read in
-  place) in squared Euclidean distance, the row itself included: indices int64 [n, k], ascending by (distance, index), and with
-  return_dist the distances [n, k] (gnpde_knn: distance tiles on the fp32 matrix cores, selection in LDS).  Replaces the pykeops
-  argKmin of the reference's graph_rewiring.KNN.  1 <= k <= min(n, 128)."""
+def _metric(metric, who):
+  if metric not in METRICS:
+    raise _lib.GnpdeError('%s: unknown metric %r (one of %s)' % (who, metric, ', '.join(sorted(METRICS))))
+  return METRICS[metric]
+
+
+def _rows_for_tiles(x, who):
+  """The [n, d] float32 device matrix the tile kernels read (padded rows with unit column stride in place)."""
   if not isinstance(x, torch.Tensor) or x.dim() != 2:
-    raise _lib.GnpdeError('knn: x must be a [n, d] tensor')
+    raise _lib.GnpdeError('%s: x must be a [n, d] tensor' % who)
   require_hip(x)
-  x = _lib.f32rows(x.detach(), 'knn input')
+  x = _lib.f32rows(x.detach(), who + ' input')
+  n, d = x.shape
+  if n < 1 or d < 1:
+    raise _lib.GnpdeError('%s: empty input [%d, %d]' % (who, n, d))
+  if n >= 2 ** 31 or x.stride(0) >= 2 ** 31:
+    raise _lib.GnpdeError('%s: n = %d exceeds int32 indices' % (who, n))
+  return x
+
+
+def knn(x, k, return_dist=False, metric='sqeuclidean'):
+  """The k nearest rows of every row of x ([n, d] float32 on a HIP device; padded rows with unit column stride are read in
+  place), the row itself included: indices int64 [n, k], ascending by (key, index), and with return_dist the distances [n, k]
+  (gnpde_knn_metric: key tiles on the fp32 matrix cores, selection in LDS).  metric 'sqeuclidean': the key and the returned
+  distance are the squared Euclidean distance (replaces the pykeops argKmin of the reference's graph_rewiring.KNN).  metric
+  'poincare': rows are points of the Poincare ball, the key is r = |x_i - x_j|^2 / ((1 - |x_i|^2)(1 - |x_j|^2)) and the returned
+  distance the hyperbolic arccosh(1 + 2 r) (include/gnpde.h has the definition; replaces hyperbolize + NearestNeighbors(metric=
+  'precomputed') of the reference's apply_dist_KNN).  A row is its own first neighbour at distance exactly 0.
+  1 <= k <= min(n, 128)."""
+  m = _metric(metric, 'knn')
+  x = _rows_for_tiles(x, 'knn')
   n, d = x.shape
   k = int(k)
-  if d < 1 or k < 1 or k > n or k > KNN_MAX_K:
+  if k < 1 or k > n or k > KNN_MAX_K:
     raise _lib.GnpdeError('knn: k = %d outside 1 .. min(n = %d, %d) (d = %d)' % (k, n, KNN_MAX_K, d))
-  if n >= 2 ** 31 or x.stride(0) >= 2 ** 31:
-    raise _lib.GnpdeError('knn: n = %d exceeds int32 indices' % n)
   L = _lib.lib()
   idx = torch.empty(n, k, dtype=torch.int64, device=x.device)
   dist = torch.empty(n, k, dtype=torch.float32, device=x.device) if return_dist else None
   ws = torch.empty(max(int(L.gnpde_knn_workspace_bytes(n, d, k)), 1), dtype=torch.uint8, device=x.device)
-  check(L.gnpde_knn(ptr(x), n, d, x.stride(0), k, ptr(idx), ptr(dist), ptr(ws), ws.numel(), stream_of(x)))
+  check(L.gnpde_knn_metric(ptr(x), n, d, x.stride(0), k, m, ptr(idx), ptr(dist), ptr(ws), ws.numel(), stream_of(x)))
   return (idx, dist) if return_dist else idx
+
+
+def key_to_distance(key, metric='sqeuclidean'):
+  """The distance a key stands for, in float64: sqrt(key) ('sqeuclidean') or arccosh(1 + 2 key) ('poincare', as
+  log1p(2 r + 2 sqrt(r (r + 1))))."""
+  import math
+  key = float(key)
+  if METRICS[metric] == _lib.METRIC_POINCARE:
+    return math.log1p(2.0 * key + 2.0 * math.sqrt(key * (key + 1.0))) if math.isfinite(key) else key
+  return math.sqrt(key)
+
+
+def distance_to_key(dist, metric='sqeuclidean'):
+  """The largest float32 key whose float64 distance (key_to_distance) is <= dist: the radius graph {distance <= dist} is the set
+  {key <= that key}.  dist >= 0.  Exact inverse of key_to_distance on float32 keys."""
+  import math
+  import numpy as np
+  dist = float(dist)
+  if not dist >= 0.0:
+    raise _lib.GnpdeError('radius_graph: threshold = %r is no distance (>= 0)' % (dist,))
+  if math.isinf(dist):
+    return float('inf')
+  if METRICS[metric] == _lib.METRIC_POINCARE:
+    guess = math.sinh(0.5 * dist) ** 2 if dist < 700.0 else float('inf')     # (cosh t - 1) / 2
+  else:
+    guess = dist * dist
+  top = np.float32(np.finfo(np.float32).max)
+  key = np.float32(min(guess, float(top)))
+  with np.errstate(over='ignore'):
+    while key > 0 and key_to_distance(key, metric) > dist:
+      key = np.nextafter(key, np.float32(0))
+    while key < top and key_to_distance(np.nextafter(key, top), metric) <= dist:
+      key = np.nextafter(key, top)
+  return float(key)
+
+
+def radius_graph(x, *, quantile=None, threshold=None, metric='sqeuclidean', max_edges=2 ** 28, return_threshold=False):
+  """edge_index [2, E] int64, sorted by (row, column), of every pair (i, j) -- self loops included -- of the rows of x ([n, d]
+  float32 on a HIP device, padded rows read in place) whose distance is within a radius: what np.where(dist <= thresh) gives on
+  the dense distance matrix (the reference's distances_kNN.apply_dist_threshold), without that matrix.
+  Exactly one of:  quantile = q in [0, 1]: the radius is the key of rank floor((n^2 - 1) q) among all n^2 keys, which selects the
+  set np.quantile's interpolated threshold selects (include/gnpde.h has the argument);  threshold = a distance (Euclidean for
+  'sqeuclidean', hyperbolic for 'poincare'), turned into a key on the host (distance_to_key).
+  Raises GnpdeError when E > max_edges, after the count and before anything of size E is allocated.
+  return_threshold: (edge_index, tau_key, tau_distance) -- the key that was used (float32 value) and key_to_distance of it in
+  float64, so that threshold=tau_distance selects the same set; for a quantile it is the LOWER order statistic, not numpy's
+  interpolated number."""
+  m = _metric(metric, 'radius_graph')
+  if (quantile is None) == (threshold is None):
+    raise _lib.GnpdeError('radius_graph: give exactly one of quantile= and threshold=')
+  if quantile is not None:
+    q = float(quantile)
+    if not (0.0 <= q <= 1.0):
+      raise _lib.GnpdeError('radius_graph: quantile = %r outside [0, 1]' % (quantile,))
+    tau_key = None
+  else:
+    tau_key = distance_to_key(threshold, metric)
+  x = _rows_for_tiles(x, 'radius_graph')
+  n, d = x.shape
+  dev = x.device
+  L = _lib.lib()
+  ws = torch.empty(max(int(L.gnpde_radius_workspace_bytes(n, d)), 1), dtype=torch.uint8, device=dev)
+  tau_dev = None
+  if tau_key is None:
+    tau_dev = torch.empty(2, dtype=torch.float32, device=dev)
+    check(L.gnpde_radius_quantile(ptr(x), n, d, x.stride(0), m, q, ptr(tau_dev), ptr(ws), ws.numel(), stream_of(x)))
+  rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+  given = 0.0 if tau_key is None else tau_key
+  check(L.gnpde_radius_count(ptr(x), n, d, x.stride(0), m, ptr(tau_dev), given, ptr(rowptr), ptr(ws), ws.numel(), stream_of(x)))
+  E = int(rowptr[-1].item())
+  if E > int(max_edges):
+    raise _lib.GnpdeError('radius_graph: %d edges exceed max_edges = %d' % (E, int(max_edges)))
+  ei = torch.empty(2, E, dtype=torch.int64, device=dev)
+  if E > 0:
+    check(L.gnpde_radius_fill(ptr(x), n, d, x.stride(0), m, ptr(tau_dev), given, ptr(ei), E, ptr(ws), ws.numel(), stream_of(x)))
+  if not return_threshold:
+    return ei
+  if tau_key is None:
+    tau_key = float(tau_dev[0].item())
+  return ei, tau_key, key_to_distance(tau_key, metric)
 
 
 def two_hop(graph, weight):

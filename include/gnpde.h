@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 11  /* 11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 12  /* 12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -790,11 +790,57 @@ int gnpde_threshold_edges(const int64_t* edge_index, const float* score, int64_t
  * is written.  A row's result is ascending by the computed distance, equal distances by ascending column (KeOps leaves tie order
  * unspecified; this is this library's definition); no atomics: bit-identical from run to run.  For few rows the column range is
  * split S ways over workgroups (partial lists in the workspace, then a merge launch); S follows from n and the CU count, or from
- * gnpde_tune(19, S).  The workspace size depends on S: query it after any gnpde_tune call.
+ * gnpde_tune(19, S).  The workspace size depends on S: query it after any gnpde_tune call (it serves either metric of gnpde_knn_metric).
  * Limits: 1 <= k <= min(n, 128), d >= 1, n <= INT32_MAX; otherwise GNPDE_ESHAPE / GNPDE_EINVAL (gnpde_knn_workspace_bytes: 0). */
 size_t gnpde_knn_workspace_bytes(int64_t n, int32_t d, int32_t k);
 int gnpde_knn(const float* x, int32_t n, int32_t d, int32_t ldx, int32_t k, int64_t* idx, float* dist, void* workspace,
               size_t workspace_bytes, void* stream);
+
+/* Positional-distance rewiring (BLEND, `--rewiring pos_enc_knn`; reference src/graph_rewiring.py:285-342 with
+ * src/hyperbolic_distances.py:7-14 and src/distances_kNN.py: scipy pdist + squareform, a dense float64 [n, n] matrix, np.quantile and
+ * sklearn's NearestNeighbors(metric='precomputed')).  Every selection here works on the KEY of a pair, formed tile by tile on the fp32
+ * matrix cores and never stored:
+ *   GNPDE_METRIC_SQEUCLIDEAN  key_ij = D_ij = (s_i + s_j) - 2 x_i.x_j clamped at 0, D_ii = 0 exactly; s_i the fp32 squared norm of the
+ *                             pre-pass (gnpde_knn's key).  Distance: sqrt(D) (gnpde_knn itself returns D, as it always has).
+ *   GNPDE_METRIC_POINCARE     key_ij = r_ij = fl(D_ij / fl(a_i a_j)), ONE IEEE fp32 division, with a_i = max(1 - s_i, 2^-24) (2^-24 is
+ *                             the smallest positive value 1 - s takes in fp32; the reference clamps at the float64 epsilon), r_ii = +0.
+ *                             The hyperbolic distance arccosh(1 + 2 r) is monotone in r, so selections order and compare keys and
+ *                             never distances; where a distance is returned it is log1pf(2 r + 2 sqrtf(r (r + 1))).
+ * Inputs must be finite.  Rows on or outside the unit ball get the clamp, as in the reference, not an error.  Keys are non-negative
+ * floats: their bit patterns order as unsigned integers.  key_ij is bit-identical to key_ji: the products are the same, the k order
+ * is the same and the additions commute.
+ *
+ * gnpde_knn_metric: gnpde_knn (below) on the keys of `metric`; dist holds the distance of the key as defined above (metric 0: D).
+ * gnpde_knn forwards metric 0 and is bit for bit what it was.
+ *
+ * Radius graph: the edge set {(i, j) : key_ij <= tau}, self loops included, as edge_index [2, E] int64 sorted by (row, column) -- what
+ * np.where(dist <= thresh) gives.  tau is the caller's key, or the quantile key: the key of rank lo = floor((n^2 - 1) q) (rank 0 is the
+ * smallest; the arithmetic is in host double, as numpy does it) among all n^2 keys, the diagonal included.  That selects the set
+ * np.quantile's linearly interpolated threshold t selects: t lies in [v_lo, v_lo+1) (it is v_lo + g (v_lo+1 - v_lo) with 0 <= g < 1) and
+ * no key lies strictly between two consecutive order statistics, so {key <= t} = {key <= v_lo}.  The tau that is returned is that lower
+ * order statistic v_lo, not numpy's interpolated number.
+ *   gnpde_radius_quantile  three sweeps of the tile pipeline (radix select over 11 / 11 / 10 key bits; LDS histograms flushed with
+ *                          64-bit integer atomics, whose sums do not depend on the order of arrival; a one-wave kernel between the
+ *                          sweeps; no host read) -> tau_out (DEVICE, two floats: the key tau and its distance)
+ *   gnpde_radius_count     rowptr [n + 1] (device int64; rowptr[n] = E) for tau = tau_dev[0] (device, e.g. tau_out) or, tau_dev NULL,
+ *                          tau_key; the caller reads E and allocates
+ *   gnpde_radius_fill      must follow the count of the SAME x, tau, workspace and gnpde_tune state on the same stream:
+ *                          out_edge_index ([2, out_ld] int64, row-major, out_ld >= E), a row's columns ascending.  No atomics.
+ * For few row tiles the column range is split S ways (gnpde_tune(19, S) forces S); per-split per-row counts place the entries, so the
+ * result is a pure function of the input: bit-identical from run to run and for every S.  The workspace size depends on S.
+ * Limits: n <= INT32_MAX, q in [0, 1], a known metric (GNPDE_ESHAPE otherwise; gnpde_radius_workspace_bytes: 0); the row scan of the
+ * count is one workgroup (sized for graphs of up to a few million nodes). */
+#define GNPDE_METRIC_SQEUCLIDEAN 0
+#define GNPDE_METRIC_POINCARE    1
+int gnpde_knn_metric(const float* x, int32_t n, int32_t d, int32_t ldx, int32_t k, int32_t metric, int64_t* idx, float* dist,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t gnpde_radius_workspace_bytes(int64_t n, int32_t d);
+int gnpde_radius_quantile(const float* x, int64_t n, int32_t d, int32_t ldx, int32_t metric, double q, float* tau_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_radius_count(const float* x, int64_t n, int32_t d, int32_t ldx, int32_t metric, const float* tau_dev, float tau_key,
+                       int64_t* rowptr, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_radius_fill(const float* x, int64_t n, int32_t d, int32_t ldx, int32_t metric, const float* tau_dev, float tau_key,
+                      int64_t* out_edge_index, int64_t out_ld, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Two-hop densification of the rewiring block (new_edges = 'k_hop_att', reference src/block_transformer_rewiring.py:68-86):
  *   S = coalesce(A ++ offdiag(A A)) / 2, i.e. torch_sparse.spspmm(A, A) -> remove_self_loops -> cat with A -> / 2 ->
