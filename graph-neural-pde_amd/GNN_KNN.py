@@ -2,25 +2,29 @@
 `graph_rewiring.apply_KNN` searches in -- `forward_encoder` (the encoder output, `rewire_KNN_T = 'T0'`) and `forward_ODE` (the
 diffused state, 'TN').  `forward(x, pos_encoding)` is the parent's.
 
-Not built here: `opt['fa_layer']` (the extra diffusion over `add_edges` / `edge_sampling` edge sets, reference GNN_KNN.py:65-83)
-raises NotImplementedError, and there is no `GNNKNNEarly`.  Those two -- `fa_layer` with `add_edges` / `edge_sampling`, and the
-early-stopping variant -- are the natural follow-up."""
+`opt['fa_layer']` (the extra diffusion over `add_edges` / `edge_sampling` edge sets, reference GNN_KNN.py:65-83) raises
+NotImplementedError HERE: the layer lives in the subclass `GNN_FA` (GNN_FA.py), which the drop-in serves under the name `GNN_KNN`
+with `--native-edge-sampling`.  There is no `GNNKNNEarly`; the early-stopping variant is the natural follow-up."""
 import torch
 import torch.nn.functional as F
 
 from .GNN import GNN
 
 
+FA_LAYER_REFUSAL = ("opt['fa_layer'] (add_edges / edge_sampling diffusion of GNN_KNN) is not implemented in this class: "
+                    "use gnpde_amd.GNN_FA")
+
+
 class GNN_KNN(GNN):
   def __init__(self, opt, dataset, device=torch.device('cpu')):
     if opt.get('fa_layer', False):
-      raise NotImplementedError("opt['fa_layer'] (add_edges / edge_sampling diffusion of GNN_KNN) is not implemented")
+      raise NotImplementedError(FA_LAYER_REFUSAL)
     super(GNN_KNN, self).__init__(opt, dataset, device)
     self.data_edge_index = dataset.data.edge_index.to(device)
 
   def forward(self, x, pos_encoding=None):
     if self.opt.get('fa_layer', False):
-      raise NotImplementedError("opt['fa_layer'] (add_edges / edge_sampling diffusion of GNN_KNN) is not implemented")
+      raise NotImplementedError(FA_LAYER_REFUSAL)
     return super(GNN_KNN, self).forward(x, pos_encoding)
 
   def forward_encoder(self, x, pos_encoding=None):
@@ -52,7 +56,7 @@ class GNN_KNN(GNN):
   def forward_ODE(self, x, pos_encoding=None):
     """Encoder -> ODE block -> the `augment` split (reference GNN_KNN.py:148-182)."""
     if self.opt.get('fa_layer', False):
-      raise NotImplementedError("opt['fa_layer'] (add_edges / edge_sampling diffusion of GNN_KNN) is not implemented")
+      raise NotImplementedError(FA_LAYER_REFUSAL)
     x = self.forward_encoder(x, pos_encoding)
     self.odeblock.set_x0(x)
     if self.training and self.odeblock.nreg > 0:

@@ -8,6 +8,8 @@
 //                         floats (histograms by integer atomics: order-independent, hence exact and deterministic), then
 //                         torch's linear interpolation IN FLOAT32 as torch.quantile computes it (rank = fl32(q) * fl32(n-1)),
 //                         so that the kept edge set equals the reference's bit for bit;
+//   gnpde_select_edges    the same stable compaction with score >= threshold and nothing else (edge_sampling of the fully-adjacent
+//                         layer, reference src/graph_rewiring.py:157-169): no weights, no renormalisation;
 //   gnpde_threshold_edges one stable stream compaction of (row, col, score) -- block counts, one-block scan, scatter -- and
 //                         the per-endpoint renormalisation (sums by float atomics, as the reference's scatter-add on a GPU).
 // 10 passes over [E] floats instead of a sort: ~40 us at the ogbn-arxiv shape.
@@ -90,6 +92,11 @@ __global__ void select_finish_kernel(const SelectState* st, float w, float* out)
 constexpr int kItems = 16;                   // elements per thread of the compaction
 constexpr int kTile = kBlock * kItems;       // per block
 
+// kInclusive: keep score >= threshold (gnpde_select_edges) instead of score > threshold (gnpde_threshold_edges)
+template <bool kInclusive>
+__device__ __forceinline__ bool kept(float score, float t) { return kInclusive ? score >= t : score > t; }
+
+template <bool kInclusive>
 __global__ __launch_bounds__(kBlock) void keep_count_kernel(const float* __restrict__ score, long long n,
                                                            const float* __restrict__ thr, unsigned* __restrict__ counts) {
   __shared__ unsigned red[kWavesPerBlock];
@@ -98,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void keep_count_kernel(const float* __restr
   unsigned c = 0;
   for (int j = 0; j < kItems; ++j) {
     const long long i = base + static_cast<long long>(j) * kBlock + threadIdx.x;
-    if (i < n && score[i] > t) ++c;
+    if (i < n && kept<kInclusive>(score[i], t)) ++c;
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, kWave);
@@ -133,7 +140,8 @@ __global__ __launch_bounds__(kBlock) void keep_scan_kernel(unsigned* __restrict_
   if (threadIdx.x == 0) *out_count = static_cast<long long>(carry);
 }
 
-// stable scatter of the kept entries: order inside a block = (item j, thread) = ascending original index
+// stable scatter of the kept entries: order inside a block = (item j, thread) = ascending original index; out_w may be NULL
+template <bool kInclusive>
 __global__ __launch_bounds__(kBlock) void keep_scatter_kernel(const long long* __restrict__ ei, const float* __restrict__ score,
                                                              long long n, const float* __restrict__ thr,
                                                              const unsigned* __restrict__ offsets, long long* __restrict__ out_ei,
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void keep_scatter_kernel(const long long* _
   __syncthreads();
   for (int j = 0; j < kItems; ++j) {
     const long long i = base + static_cast<long long>(j) * kBlock + threadIdx.x;
-    const bool keep = i < n && score[i] > t;
+    const bool keep = i < n && kept<kInclusive>(score[i], t);
     const unsigned long long ballot = __ballot(keep);
     const unsigned before = __popcll(ballot & ((1ull << lane) - 1ull));
     if (lane == 0) wave_cnt[wave] = __popcll(ballot);
@@ -158,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void keep_scatter_kernel(const long long* _
     if (keep) {
       out_ei[pos] = ei[i];
       out_ei[out_stride + pos] = ei[n + i];
-      out_w[pos] = score[i];
+      if (out_w) out_w[pos] = score[i];
     }
     __syncthreads();
     if (threadIdx.x == 0) running += (wave_cnt[0] + wave_cnt[1]) + (wave_cnt[2] + wave_cnt[3]);
@@ -244,12 +252,12 @@ extern "C" int gnpde_threshold_edges(const int64_t* edge_index, const float* sco
   }
   const long long* ei = reinterpret_cast<const long long*>(edge_index);
   long long* oe = reinterpret_cast<long long*>(out_edge_index);
-  hipLaunchKernelGGL(keep_count_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, score, static_cast<long long>(n_edges),
+  hipLaunchKernelGGL(keep_count_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, score, static_cast<long long>(n_edges),
                      threshold, counts);
   GNPDE_LAUNCH_CHECK();
   hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(kBlock), 0, s, counts, static_cast<int>(blocks), reinterpret_cast<long long*>(out_count));
   GNPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(keep_scatter_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, ei, score,
+  hipLaunchKernelGGL(keep_scatter_kernel<false>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, ei, score,
                      static_cast<long long>(n_edges), threshold, counts, oe, static_cast<long long>(n_edges), out_weight);
   GNPDE_LAUNCH_CHECK();
   GNPDE_HIP(hipMemsetAsync(sums, 0, static_cast<size_t>(n_nodes) * 4, s));
@@ -259,6 +267,36 @@ extern "C" int gnpde_threshold_edges(const int64_t* edge_index, const float* sco
   GNPDE_LAUNCH_CHECK();
   hipLaunchKernelGGL(endpoint_div_kernel, dim3(grid_for(n_edges)), dim3(kBlock), 0, s, endpoint, out_weight,
                      reinterpret_cast<const long long*>(out_count), sums);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t gnpde_select_edges_workspace_bytes(int64_t n_edges) {
+  const long long blocks = (n_edges + kTile - 1) / kTile;
+  return align_up(static_cast<size_t>(blocks > 0 ? blocks : 1) * 4, 256);
+}
+
+extern "C" int gnpde_select_edges(const int64_t* edge_index, const float* score, int64_t n_edges, const float* threshold,
+                                  int64_t* out_edge_index, int64_t* out_count, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(out_count && n_edges >= 0 && (n_edges == 0 || (edge_index && score && threshold && out_edge_index)), GNPDE_EINVAL,
+                  "select_edges: bad arguments");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_edges == 0) {
+    GNPDE_HIP(hipMemsetAsync(out_count, 0, sizeof(int64_t), s));
+    return 0;
+  }
+  GNPDE_CHECK_ARG(workspace && workspace_bytes >= gnpde_select_edges_workspace_bytes(n_edges), GNPDE_EWS, "select_edges: workspace too small");
+  const long long blocks = (n_edges + kTile - 1) / kTile;
+  GNPDE_CHECK_ARG(blocks <= 0x7fffffffLL, GNPDE_ESHAPE, "select_edges: too many edges");
+  unsigned* counts = static_cast<unsigned*>(workspace);
+  hipLaunchKernelGGL(keep_count_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, score, static_cast<long long>(n_edges),
+                     threshold, counts);
+  GNPDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(kBlock), 0, s, counts, static_cast<int>(blocks), reinterpret_cast<long long*>(out_count));
+  GNPDE_LAUNCH_CHECK();
+  hipLaunchKernelGGL(keep_scatter_kernel<true>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s,
+                     reinterpret_cast<const long long*>(edge_index), score, static_cast<long long>(n_edges), threshold, counts,
+                     reinterpret_cast<long long*>(out_edge_index), static_cast<long long>(n_edges), static_cast<float*>(nullptr));
   GNPDE_LAUNCH_CHECK();
   return 0;
 }

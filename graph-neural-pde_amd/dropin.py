@@ -6,7 +6,7 @@ ODEFuncTransformerAtt`, src/model_configurations.py:1-9; `from base_classes impo
 early_stop_solver import EarlyStopInt`, src/GNN_early.py:10).  `install()` answers those imports with the modules of this
 package, whatever the order of `sys.path`:
 
-    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
+    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
 
 or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before the first import of a reference module.
 
@@ -24,6 +24,9 @@ or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before th
   flags together replace all three names.  `native_posdist=True` / `--native-posdist` likewise replaces `apply_pos_dist_rewire`
   (positional-distance rewiring, `--rewiring pos_enc_knn`) and the helpers it calls (`apply_beltrami`, `hyperbolize`,
   `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold`); the flags combine.
+  `native_edge_sampling=True` / `--native-edge-sampling` replaces `add_edges`, `add_outgoing_attention_edges`, `edge_sampling` and
+  `apply_edge_sampling` in the same merged module and serves a module `GNN_KNN` whose class `GNN_KNN` is this package's `GNN_FA`
+  (GNN_KNN with the fully-adjacent layer), so `run_GNN.py --fa_layer` runs the native layer.
 """
 import importlib
 import importlib.abc
@@ -56,6 +59,19 @@ NATIVE_GDC = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('apply_gdc', 'GDCW
 # optional: native positional-distance rewiring (--rewiring pos_enc_knn) with the helpers it calls
 NATIVE_POSDIST = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('apply_pos_dist_rewire', 'apply_beltrami', 'hyperbolize', 'apply_feat_KNN',
                                                                    'apply_dist_KNN', 'apply_dist_threshold'), True)}
+# optional: native edge-sampling rewiring (the fully-adjacent layer) and the model class that runs it, served as GNN_KNN.GNN_KNN
+NATIVE_EDGE_SAMPLING = {'graph_rewiring': ('gnpde_amd.graph_rewiring', ('add_edges', 'add_outgoing_attention_edges', 'edge_sampling',
+                                                                         'apply_edge_sampling'), True)}
+FA_MODULE = 'GNN_KNN'
+
+
+def _fa_module():
+  """Module `GNN_KNN` of the drop-in: the name GNN_KNN bound to GNN_FA."""
+  from gnpde_amd.GNN_FA import GNN_FA
+  m = types.ModuleType(FA_MODULE)
+  m.GNN_KNN = m.GNN_FA = GNN_FA
+  m.__gnpde_reference__ = None
+  return m
 
 
 def _reference_file(name):
@@ -116,15 +132,17 @@ def installed():
   return _finder in sys.meta_path
 
 
-def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist=False):
+def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist=False, native_edge_sampling=False):
   """Answer the reference's module names with this package (idempotent).  Returns the list of names now served."""
   merges = dict(MERGES)
-  for on, extra in ((native_knn, NATIVE_KNN), (native_gdc, NATIVE_GDC), (native_posdist, NATIVE_POSDIST)):
+  for on, extra in ((native_knn, NATIVE_KNN), (native_gdc, NATIVE_GDC), (native_posdist, NATIVE_POSDIST),
+                    (native_edge_sampling, NATIVE_EDGE_SAMPLING)):
     if on:
       for name, (target, names, standalone) in extra.items():
         before = merges.get(name, (target, (), standalone))[1]
         merges[name] = (target, before + names, standalone)
-  already = {name: sys.modules[name] for name in list(MODULES) + list(merges) if name in sys.modules}
+  extra_names = [FA_MODULE] if native_edge_sampling else []
+  already = {name: sys.modules[name] for name in list(MODULES) + list(merges) + extra_names if name in sys.modules}
   table = dict(MODULES)
   if native_gnn:
     table.update(NATIVE_GNN)
@@ -135,10 +153,12 @@ def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist
                       'first import of a reference module' % ', '.join(sorted(foreign)))
   for name, target in table.items():
     sys.modules[name] = importlib.import_module(target)
+  if native_edge_sampling:
+    sys.modules[FA_MODULE] = _fa_module()
   _finder.table = merges
   if _finder not in sys.meta_path:
     sys.meta_path.insert(0, _finder)
-  return sorted(table) + [MERGED] + sorted(n for n in merges if n != MERGED)
+  return sorted(list(table) + extra_names) + [MERGED] + sorted(n for n in merges if n != MERGED)
 
 
 def uninstall():
@@ -147,7 +167,7 @@ def uninstall():
     sys.meta_path.remove(_finder)
   _finder.table = dict(MERGES)
   merged = sorted(set(MERGES) | set(NATIVE_KNN) | set(NATIVE_GDC) | set(NATIVE_POSDIST))
-  for name in list(MODULES) + list(NATIVE_GNN) + merged + ['_reference_' + m for m in merged]:
+  for name in list(MODULES) + list(NATIVE_GNN) + [FA_MODULE] + merged + ['_reference_' + m for m in merged]:
     m = sys.modules.get(name)
     if isinstance(m, types.ModuleType) and (getattr(m, '__name__', '').startswith('gnpde_amd') or
                                             hasattr(m, '__gnpde_reference__') or name.startswith('_reference_')):
@@ -155,7 +175,7 @@ def uninstall():
 
 
 def main(argv=None):
-  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
+  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
   to the front of sys.path, as `python SCRIPT` would put it)."""
   import runpy
   argv = list(sys.argv[1:] if argv is None else argv)
@@ -163,6 +183,7 @@ def main(argv=None):
   native_knn = False
   native_gdc = False
   native_posdist = False
+  native_edge_sampling = False
   while argv and argv[0].startswith('--'):
     flag = argv.pop(0)
     if flag == '--native-gnn':
@@ -173,15 +194,18 @@ def main(argv=None):
       native_gdc = True
     elif flag == '--native-posdist':
       native_posdist = True
+    elif flag == '--native-edge-sampling':
+      native_edge_sampling = True
     else:
-      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] SCRIPT [ARGS...]' % flag)
+      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]' % flag)
   if not argv:
-    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] SCRIPT [ARGS...]')
+    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]')
   script = os.path.abspath(argv[0])
   if not os.path.isfile(script):
     raise SystemExit('gnpde_amd.dropin: no such script: %s' % argv[0])
   sys.path.insert(0, os.path.dirname(script))
-  install(native_gnn=native, native_knn=native_knn, native_gdc=native_gdc, native_posdist=native_posdist)
+  install(native_gnn=native, native_knn=native_knn, native_gdc=native_gdc, native_posdist=native_posdist,
+          native_edge_sampling=native_edge_sampling)
   sys.argv = [script] + argv[1:]
   runpy.run_path(script, run_name='__main__')
 

@@ -20,7 +20,17 @@ it or hands it to sklearn's NearestNeighbors(metric='precomputed'); here the edg
 (`ops.knn(metric=...)`, `ops.radius_graph`), so the helpers take ENCODINGS where the reference's take a distance matrix.
 Deliberate differences: no [n, n] distance pickle is written; the edge set is computed whether or not a cache file existed (the
 reference's HYP branch leaves `ei` unbound on a cache hit); a stale `data.edge_attr` is dropped; scipy, sklearn and
-torch_geometric are not imported."""
+torch_geometric are not imported.
+
+Edge-sampling rewiring (`--fa_layer` of GNN_KNN, and `apply_edge_sampling`; reference graph_rewiring.py:150-241): `add_edges`,
+`add_outgoing_attention_edges`, `edge_sampling` and `apply_edge_sampling` under the reference's names and signatures, on the native
+generator, multinomial, union and `>=` selection of `ops` (csrc/edge_sampling.hip; include/gnpde.h defines them).  The random
+stream is this package's own Philox4x32-10 stream, keyed by opt['edge_sampling_seed'] (default torch.initial_seed(), read once
+per model) and a per-model call counter: equal seeds give equal edge sets call by call.  Refused, because they cannot work in
+the reference either: the add types 'anchored' and 'degree' (its `cat` is unbound), the four `*_distance*` sampling spaces (they
+name an attention type the attention layer does not have), removal on a block whose `get_attention_weights` does not read
+`odefunc.edge_index`, and three configurations whose per-edge arrays keep the OLD length (reweight_attention, the Laplacian
+function on the constant block, the mixed block).  `GNN_FA` (GNN_FA.py) is the model that runs the layer."""
 import os
 import pickle
 
@@ -278,3 +288,140 @@ def apply_pos_dist_rewire(data, opt, data_dir='../data', pos_encoding=None):
   if getattr(data, 'edge_attr', None) is not None:
     data.edge_attr = None
   return data
+
+
+ADD_TYPES = ('random', 'importance', 'n2_radius')
+ADD_TYPES_BROKEN = ('anchored', 'degree')
+SAMPLING_SPACES_BROKEN = ('pos_distance', 'z_distance', 'pos_distance_QK', 'z_distance_QK')
+SAMPLING_BLOCKS = ('attention',)      # blocks whose get_attention_weights reads odefunc.edge_index and nothing of the old length
+
+
+def _sampling_stream(model):
+  """(seed, call) of the next drawing call of this model; the call counter advances."""
+  st = getattr(model, '_edge_sampling_state', None)
+  if st is None:
+    seed = model.opt.get('edge_sampling_seed')
+    st = model._edge_sampling_state = {'seed': int(torch.initial_seed() if seed is None else seed), 'call': 0}
+  call = st['call']
+  st['call'] = call + 1
+  return st['seed'], call
+
+
+def check_edge_sampling_supported(model, opt, removal=None):
+  """Raise for the option combinations that cannot run on a changed edge set (module docstring).  removal: whether edges are
+  removed as well (default: opt['edge_sampling_rmv'] != 0)."""
+  mopt = model.opt
+  add_type = opt.get('edge_sampling_add_type')
+  if add_type in ADD_TYPES_BROKEN:
+    raise NotImplementedError("edge_sampling_add_type %r is not implemented: the reference's add_edges crashes on it (its `cat` is "
+                              "never assigned, graph_rewiring.py:211-220)" % (add_type,))
+  if add_type is not None and add_type not in ADD_TYPES:
+    raise ValueError('edge_sampling_add_type %r is none of %s' % (add_type, ', '.join(ADD_TYPES)))
+  if mopt.get('reweight_attention'):
+    raise NotImplementedError("opt['reweight_attention'] cannot be combined with edge sampling: the attention layer's stored "
+                              "edge_weights keep the length of the original edge set")
+  if mopt.get('block') == 'constant' and mopt.get('function') == 'laplacian':
+    raise NotImplementedError("edge sampling with function 'laplacian' on block 'constant' is not possible: odefunc.edge_weight "
+                              "keeps the length of the original edge set")
+  if mopt.get('block') == 'mixed':
+    raise NotImplementedError("edge sampling on block 'mixed' is not possible: its mixing term odefunc.edge_weight keeps the "
+                              "length of the original edge set")
+  if removal is None:
+    removal = opt.get('edge_sampling_rmv', 0) != 0
+  if removal:
+    space = opt.get('edge_sampling_space', 'attention')
+    if space in SAMPLING_SPACES_BROKEN:
+      raise NotImplementedError("edge_sampling_space %r is not implemented: the reference sets it as an attention_type that "
+                                "SpGraphTransAttentionLayer does not have" % (space,))
+    if space != 'attention':
+      raise ValueError("edge_sampling_space %r is not 'attention'" % (space,))
+    if mopt.get('block') not in SAMPLING_BLOCKS:
+      raise NotImplementedError("edge removal (edge_sampling_rmv != 0) needs a block whose get_attention_weights reads "
+                                "odefunc.edge_index: block %r has none that fits the changed edge set (supported: %s)"
+                                % (mopt.get('block'), ', '.join(SAMPLING_BLOCKS)))
+
+
+def set_edge_index(model, edge_index):
+  """odefunc.edge_index <- edge_index, the regularised twin kept in step (as ODEblock._share_graph does)."""
+  if edge_index.shape[1] > ops.INT32_MAX:
+    raise ops._lib.GnpdeError('an edge set of %d columns is refused: positions of an edge set are int32' % edge_index.shape[1])
+  block = model.odeblock
+  block.odefunc.edge_index = edge_index
+  block.reg_odefunc.odefunc.edge_index = edge_index
+  return edge_index
+
+
+def _both_directions(a, b):
+  return torch.cat([torch.stack([a, b], dim=0), torch.stack([b, a], dim=0)], dim=1)
+
+
+@torch.no_grad()
+def add_outgoing_attention_edges(model, M):
+  """[2, 2 M] new edges (M pairs, both directions) whose first endpoint is drawn from softmax(importance), importance_j = the
+  mean over node j's incoming edges of the head-mean attention, and whose second endpoint is uniform (reference :177-197)."""
+  f = model.odeblock.odefunc
+  if f.attention_weights is None:
+    raise ops._lib.GnpdeError("add_outgoing_attention_edges: odefunc.attention_weights has not been set (edge_sampling_add_type "
+                              "'importance' needs a block that stores its attention)")
+  atts = f.attention_weights.detach()
+  if atts.dim() == 2:
+    atts = atts.mean(dim=1)
+  M = int(M)
+  seed, call = _sampling_stream(model)
+  importance = ops.node_importance(f.edge_index, atts, model.num_nodes)
+  anchors = ops.sample_nodes(importance, M, seed, 0, call)
+  partners = ops.random_nodes(model.num_nodes, M, seed, 1, call, device=importance.device)
+  return _both_directions(anchors, partners)
+
+
+@torch.no_grad()
+def add_edges(model, opt):
+  """The edge set of the extra diffusion (reference :200-224): odefunc.edge_index joined with M = int(E * edge_sampling_add) new
+  pairs in both directions, unique columns ascending by (row, col); 'n2_radius': all n^2 pairs.  'importance' with M == 0 returns
+  edge_index as it is, not uniqued, as the reference does."""
+  check_edge_sampling_supported(model, opt, removal=False)
+  n = model.num_nodes
+  ei = model.odeblock.odefunc.edge_index
+  M = int(ei.shape[1] * opt['edge_sampling_add'])
+  kind = opt['edge_sampling_add_type']
+  if kind == 'n2_radius':
+    ops.require_hip(ei)
+    return ops.full_adjacency(n, device=ei.device)
+  if kind == 'random':
+    ops.require_hip(ei)
+    seed, call = _sampling_stream(model)
+    new_edges = _both_directions(ops.random_nodes(n, M, seed, 0, call, device=ei.device), ops.random_nodes(n, M, seed, 1, call, device=ei.device))
+  elif M > 0:
+    new_edges = add_outgoing_attention_edges(model, M)
+  else:
+    return ei
+  return ops.edge_union(ei, new_edges, n)
+
+
+@torch.no_grad()
+def edge_sampling(model, z, opt):
+  """Keep the columns of odefunc.edge_index whose head-mean attention at state z is >= its edge_sampling_rmv quantile, in their
+  order; with edge_sampling_sym the undirected set.  Written to odefunc.edge_index and returned (reference :150-174)."""
+  check_edge_sampling_supported(model, opt, removal=True)
+  mean_att = model.odeblock.get_attention_weights(z).detach()
+  if mean_att.dim() == 2:
+    mean_att = mean_att.mean(dim=1)
+  threshold = ops.quantile(mean_att, opt['edge_sampling_rmv'])
+  ei = ops.select_edges(model.odeblock.odefunc.edge_index, mean_att, threshold)
+  if opt['edge_sampling_sym']:
+    ei = to_undirected(ei, model.num_nodes)
+  return set_edge_index(model, ei)
+
+
+@torch.no_grad()
+def apply_edge_sampling(x, pos_encoding, model, opt):
+  """add_edges, then edge_sampling at the encoder output ('T0') or the diffused state ('TN') (reference :227-241)."""
+  print("Rewiring with edge sampling")
+  set_edge_index(model, add_edges(model, opt))
+  if opt['edge_sampling_T'] == "T0":
+    z = model.forward_encoder(x, pos_encoding)
+  elif opt['edge_sampling_T'] == 'TN':
+    z = model.forward_ODE(x, pos_encoding)
+  else:
+    raise Exception("Need to set edge_sampling_T")
+  edge_sampling(model, z, opt)

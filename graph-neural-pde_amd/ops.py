@@ -284,6 +284,192 @@ def threshold_edges(edge_index, score, threshold, norm_idx, n_nodes):
   return out_ei[:, :k].contiguous(), out_w[:k].clone()
 
 
+# ---- edge-sampling rewiring of the fully-adjacent layer (csrc/edge_sampling.hip; definitions in include/gnpde.h) ----------------
+SAMPLING_FLAGS = ((_lib.SAMPLING_EMPTY_COLUMN, 'a node has no incoming edge (its importance is 0 / 0)'),
+                  (_lib.SAMPLING_NONFINITE, 'a logit is not finite'),
+                  (_lib.SAMPLING_ZERO_MASS, 'the weights sum to zero'),
+                  (_lib.SAMPLING_INDEX_RANGE, 'an edge index lies outside [0, n)'))
+INT32_MAX = 2 ** 31 - 1
+
+
+def _sampling_device(device, who):
+  device = torch.device('cuda' if device is None else device)
+  if device.type != 'cuda':
+    raise _lib.GnpdeError('%s runs only on a HIP device (got %s); there is no CPU fallback' % (who, device.type))
+  if not torch.cuda.is_available():
+    raise _lib.GnpdeError('%s runs only on a HIP device and none is available; there is no CPU fallback' % who)
+  if device.index is None:
+    device = torch.device('cuda', torch.cuda.current_device())
+  return device
+
+
+def _stream_on(device):
+  return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _draw_args(count, seed, stream, call, who):
+  count, seed, stream, call = int(count), int(seed), int(stream), int(call)
+  if count < 0:
+    raise _lib.GnpdeError('%s: count = %d is negative' % (who, count))
+  if not (0 <= stream < 2 ** 32 and 0 <= call < 2 ** 32):
+    raise _lib.GnpdeError('%s: stream = %d / call = %d outside [0, 2^32)' % (who, stream, call))
+  return count, seed & (2 ** 64 - 1), stream, call
+
+
+def _raise_flags(flag, who):
+  bits = int(flag.item())
+  if bits:
+    raise _lib.GnpdeError('%s: %s' % (who, '; '.join(text for bit, text in SAMPLING_FLAGS if bits & bit)))
+
+
+def _edge_list(edge_index, name):
+  if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+    raise _lib.GnpdeError('%s must be a [2, E] tensor' % name)
+  require_hip(edge_index)
+  if edge_index.dtype != torch.int64:
+    raise _lib.GnpdeError('%s must be int64 (got %s)' % (name, edge_index.dtype))
+  ei = edge_index.detach()
+  return ei if ei.is_contiguous() else ei.contiguous()
+
+
+def philox_words(seed, stream, call, first_block, n_words, device=None):
+  """n_words 32-bit words of the Philox4x32-10 stream (seed, stream, call), starting at counter block first_block, as an int64
+  device vector (values in [0, 2^32)): word w is word (w & 3) of block first_block + (w >> 2) (gnpde_philox_words)."""
+  n_words, seed, stream, call = _draw_args(n_words, seed, stream, call, 'philox_words')
+  first_block = int(first_block)
+  if not 0 <= first_block < 2 ** 64:
+    raise _lib.GnpdeError('philox_words: first_block = %d outside [0, 2^64)' % first_block)
+  device = _sampling_device(device, 'philox_words')
+  out = torch.empty(n_words, dtype=torch.int32, device=device)
+  if n_words:
+    check(_lib.lib().gnpde_philox_words(seed, stream, call, first_block, n_words, ptr(out), _stream_on(device)))
+  return out.to(torch.int64) & 0xffffffff
+
+
+def random_nodes(n, count, seed, stream, call, device=None):
+  """count node indices uniform over [0, n) as an int64 device vector: draw i = (word i of the stream * n) >> 32
+  (gnpde_random_nodes).  1 <= n <= INT32_MAX."""
+  count, seed, stream, call = _draw_args(count, seed, stream, call, 'random_nodes')
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('random_nodes: n = %d outside 1 .. INT32_MAX' % n)
+  device = _sampling_device(device, 'random_nodes')
+  out = torch.empty(count, dtype=torch.int64, device=device)
+  if count:
+    check(_lib.lib().gnpde_random_nodes(n, count, seed, stream, call, ptr(out), _stream_on(device)))
+  return out
+
+
+def node_importance(edge_index, att_mean, n):
+  """[n] float32: per node, the mean of att_mean ([E] float32, in the order of edge_index's columns) over its INCOMING edges
+  (column index = the node), summed in a fixed order (gnpde_node_importance).  Raises GnpdeError when a node has no incoming
+  edge."""
+  from .graph import graph_of
+  ei = _edge_list(edge_index, 'node_importance: edge_index')
+  require_hip(att_mean)
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('node_importance: n = %d outside 1 .. INT32_MAX' % n)
+  att = f32c(att_mean.detach().reshape(-1), 'att_mean')
+  if att.numel() != ei.shape[1]:
+    raise _lib.GnpdeError('node_importance: %d values for %d edges' % (att.numel(), ei.shape[1]))
+  if att.device != ei.device:
+    raise _lib.GnpdeError('node_importance: att_mean is on %s but edge_index is on %s' % (att.device, ei.device))
+  if ei.shape[1] > INT32_MAX:
+    raise _lib.GnpdeError('node_importance: %d edges exceed int32 positions' % ei.shape[1])
+  if ei.shape[1] == 0:
+    raise _lib.GnpdeError('node_importance: ' + SAMPLING_FLAGS[0][1])
+  graph = graph_of(edge_index if edge_index.is_contiguous() else ei, n, ei.device)
+  out = torch.empty(n, dtype=torch.float32, device=ei.device)
+  flag = torch.zeros(1, dtype=torch.int32, device=ei.device)
+  check(_lib.lib().gnpde_node_importance(graph.ref(), ptr(att), ptr(out), ptr(flag), stream_of(att)))
+  _raise_flags(flag, 'node_importance')
+  return out
+
+
+def sample_nodes(logits, count, seed, stream, call):
+  """count draws with replacement from softmax(logits) ([n] float32 on a HIP device) as an int64 vector: the fixed-point
+  multinomial of gnpde_sample_nodes (include/gnpde.h has the definition).  Raises GnpdeError for a non-finite logit."""
+  if not isinstance(logits, torch.Tensor) or logits.dim() != 1:
+    raise _lib.GnpdeError('sample_nodes: logits must be a vector')
+  require_hip(logits)
+  count, seed, stream, call = _draw_args(count, seed, stream, call, 'sample_nodes')
+  s = f32c(logits.detach(), 'logits')
+  n = s.numel()
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('sample_nodes: n = %d outside 1 .. INT32_MAX' % n)
+  out = torch.empty(count, dtype=torch.int64, device=s.device)
+  if count == 0:
+    return out
+  L = _lib.lib()
+  flag = torch.zeros(1, dtype=torch.int32, device=s.device)
+  ws = torch.empty(int(L.gnpde_sample_nodes_workspace_bytes(n)), dtype=torch.uint8, device=s.device)
+  check(L.gnpde_sample_nodes(ptr(s), n, count, seed, stream, call, ptr(out), ptr(flag), ptr(ws), ws.numel(), stream_of(s)))
+  _raise_flags(flag, 'sample_nodes')
+  return out
+
+
+def edge_union(a, b, n):
+  """The unique columns of cat(a, b) ([2, *] int64 device edge lists over n nodes), ascending by (row, col): what
+  torch.unique(torch.cat([a, b], dim=1), dim=1) returns (gnpde_edge_union); one host read for the count."""
+  a = _edge_list(a, 'edge_union: a')
+  b = _edge_list(b, 'edge_union: b')
+  if a.device != b.device:
+    raise _lib.GnpdeError('edge_union: a is on %s but b is on %s' % (a.device, b.device))
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('edge_union: n = %d outside 1 .. INT32_MAX' % n)
+  ea, eb = a.shape[1], b.shape[1]
+  if ea + eb == 0:
+    return torch.empty(2, 0, dtype=torch.int64, device=a.device)
+  L = _lib.lib()
+  out = torch.empty(2, ea + eb, dtype=torch.int64, device=a.device)
+  cnt = torch.zeros(1, dtype=torch.int64, device=a.device)
+  flag = torch.zeros(1, dtype=torch.int32, device=a.device)
+  ws = torch.empty(int(L.gnpde_edge_union_workspace_bytes(ea, eb)), dtype=torch.uint8, device=a.device)
+  check(L.gnpde_edge_union(ptr(a), ea, ptr(b), eb, n, ptr(out), ptr(cnt), ptr(flag), ptr(ws), ws.numel(), stream_of(a)))
+  _raise_flags(flag, 'edge_union')
+  return out[:, :int(cnt.item())].contiguous()
+
+
+def select_edges(edge_index, score, threshold):
+  """edge_index[:, score >= threshold], the kept columns in their order (gnpde_select_edges): stable compaction, no weights, no
+  renormalisation (threshold_edges keeps `>` and renormalises).  threshold: a device scalar (e.g. ops.quantile's) or a number."""
+  ei = _edge_list(edge_index, 'select_edges: edge_index')
+  require_hip(score)
+  sc = f32c(score.detach().reshape(-1), 'score')
+  E = ei.shape[1]
+  if sc.numel() != E:
+    raise _lib.GnpdeError('select_edges: %d scores for %d edges' % (sc.numel(), E))
+  if sc.device != ei.device:
+    raise _lib.GnpdeError('select_edges: score is on %s but edge_index is on %s' % (sc.device, ei.device))
+  if E == 0:
+    return ei.clone()
+  if isinstance(threshold, torch.Tensor):
+    require_hip(threshold)
+    thr = threshold.detach().to(torch.float32).reshape(1)
+  else:
+    thr = torch.full((1,), float(threshold), dtype=torch.float32, device=ei.device)
+  L = _lib.lib()
+  out = torch.empty_like(ei)
+  cnt = torch.zeros(1, dtype=torch.int64, device=ei.device)
+  ws = torch.empty(int(L.gnpde_select_edges_workspace_bytes(E)), dtype=torch.uint8, device=ei.device)
+  check(L.gnpde_select_edges(ptr(ei), ptr(sc), E, ptr(thr), ptr(out), ptr(cnt), ptr(ws), ws.numel(), stream_of(sc)))
+  return out[:, :int(cnt.item())].contiguous()
+
+
+def full_adjacency(n, device=None):
+  """All n^2 pairs [2, n^2] int64, row-major, the diagonal included (the reference's utils.get_full_adjacency).  n^2 <= INT32_MAX:
+  positions of an edge set are int32."""
+  n = int(n)
+  if n < 1 or n * n > INT32_MAX:
+    raise _lib.GnpdeError('full_adjacency: n = %d (n^2 must lie in 1 .. INT32_MAX: edge positions are int32)' % n)
+  device = _sampling_device(device, 'full_adjacency')
+  out = torch.empty(2, n * n, dtype=torch.int64, device=device)
+  check(_lib.lib().gnpde_full_adjacency(n, ptr(out), _stream_on(device)))
+  return out
+
+
 KNN_MAX_K = 128
 METRICS = {'sqeuclidean': _lib.METRIC_SQEUCLIDEAN, 'poincare': _lib.METRIC_POINCARE}
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 12  /* 12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 13  /* 13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -841,6 +841,58 @@ int gnpde_radius_count(const float* x, int64_t n, int32_t d, int32_t ldx, int32_
                        int64_t* rowptr, void* workspace, size_t workspace_bytes, void* stream);
 int gnpde_radius_fill(const float* x, int64_t n, int32_t d, int32_t ldx, int32_t metric, const float* tau_dev, float tau_key,
                       int64_t* out_edge_index, int64_t out_ld, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Edge-sampling rewiring of BLEND's fully-adjacent layer (`--fa_layer`; reference src/graph_rewiring.py:150-241 add_edges /
+ * add_outgoing_attention_edges / edge_sampling, called by src/GNN_KNN.py:65-83 inside every forward).  The reference composes
+ * np.random.choice, torch.multinomial, torch.unique(dim=1), torch.quantile (16 M element limit) and a boolean mask.
+ *
+ * Random numbers: Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; the Random123 generator), written out in the kernel.
+ *   key = (seed low word, seed high word);  counter = (block low word, block high word, stream, call);
+ *   word i of a stream = word (i & 3) of block (i >> 2).  `stream` separates the two endpoints of a pair (0 = anchors / first
+ *   endpoints, 1 = partners), `call` separates successive add_edges calls of one model.  A word is a pure function of
+ *   (seed, stream, call, i): results do not depend on the launch shape and are the same on every device.
+ *   gnpde_philox_words   out[w] = word (w & 3) of block first_block + (w >> 2), w in [0, n_words)   (for tests of the generator)
+ *   gnpde_random_nodes   out[i] = (word_i * n) >> 32 in exact integer arithmetic: uniform over [0, n), 1 <= n <= INT32_MAX
+ * gnpde_node_importance  out[j] = (sum of att_mean over the edges whose column is j) / (their number); att_mean [E] is in the
+ *   caller's edge order, g the graph of that edge list with its CSC view.  One wave per column: lane l adds the column's entries
+ *   l, l + 64, ... in CSC order, then a fixed butterfly adds the 64 partial sums, so a hub column is 64 fixed chunks combined in a
+ *   fixed order.  No atomics on floats: bit-identical from run to run.  A column without entries (0 / 0 in the reference, which
+ *   then fails inside multinomial) sets GNPDE_SAMPLING_EMPTY_COLUMN in *flag and gives 0.
+ * gnpde_sample_nodes     `count` draws with replacement from softmax(logits) over n nodes, in fixed point:
+ *     t_j = expf(s_j - max s) in fp32;  w_j = (uint64)(t_j 2^32)  (the scaling is exact; the maximum contributes exactly 2^32);
+ *     C = inclusive prefix sums of w in uint64 -- integer addition is associative, so any scan order gives the same bits;
+ *     draw i: r = (word 2i << 32) | word (2i + 1),  target = high 64 bits of r * C_n,  answer = the first j with C_j > target
+ *     (binary search).  A node of weight 0 is never drawn.  A non-finite logit sets GNPDE_SAMPLING_NONFINITE, C_n == 0 sets
+ *     GNPDE_SAMPLING_ZERO_MASS (the draws are then 0 and meaningless).
+ * gnpde_edge_union       the ascending unique columns of cat(a, b) -- what torch.unique(cat, dim=1) returns: columns ordered by
+ *   (row, col).  a [2, n_a], b [2, n_b] int64 row-major; keys row * n_nodes + col in 64 bits, radix sort, unique, decode.
+ *   out_edge_index is [2, n_a + n_b] (row stride n_a + n_b), its first *out_count (device int64) columns are written.  An index
+ *   outside [0, n_nodes) sets GNPDE_SAMPLING_INDEX_RANGE.
+ * gnpde_select_edges     stable compaction of the columns of edge_index ([2, n_edges], row-major) whose score is >= *threshold
+ *   (device scalar) into out_edge_index ([2, n_edges] capacity, same row stride); *out_count (device int64) = number kept.
+ *   No weights and no renormalisation (gnpde_threshold_edges keeps its `>` and its renormalisation).  NaN scores are dropped.
+ * gnpde_full_adjacency   out [2, n^2]: column i n + j = (i, j), the diagonal included (reference src/utils.py:161-167).
+ * `flag` is ONE device int32 that the kernels OR bits into; the caller zeroes it and reads it.  Everything runs on the caller's
+ * stream; argument errors return a code before any launch.  A workspace query returns 0 (and the entry point GNPDE_ESTATE) when
+ * the sort's / scan's own temporary-storage query fails. */
+#define GNPDE_SAMPLING_EMPTY_COLUMN 1
+#define GNPDE_SAMPLING_NONFINITE    2
+#define GNPDE_SAMPLING_ZERO_MASS    4
+#define GNPDE_SAMPLING_INDEX_RANGE  8
+int gnpde_philox_words(uint64_t seed, uint32_t stream_id, uint32_t call, uint64_t first_block, int64_t n_words, uint32_t* out,
+                       void* stream);
+int gnpde_random_nodes(int32_t n, int64_t count, uint64_t seed, uint32_t stream_id, uint32_t call, int64_t* out, void* stream);
+int gnpde_node_importance(const gnpde_graph_t* g, const float* att_mean, float* out, int32_t* flag, void* stream);
+size_t gnpde_sample_nodes_workspace_bytes(int32_t n);
+int gnpde_sample_nodes(const float* logits, int32_t n, int64_t count, uint64_t seed, uint32_t stream_id, uint32_t call, int64_t* out,
+                       int32_t* flag, void* workspace, size_t workspace_bytes, void* stream);
+size_t gnpde_edge_union_workspace_bytes(int64_t n_a, int64_t n_b);
+int gnpde_edge_union(const int64_t* a, int64_t n_a, const int64_t* b, int64_t n_b, int32_t n_nodes, int64_t* out_edge_index,
+                     int64_t* out_count, int32_t* flag, void* workspace, size_t workspace_bytes, void* stream);
+size_t gnpde_select_edges_workspace_bytes(int64_t n_edges);
+int gnpde_select_edges(const int64_t* edge_index, const float* score, int64_t n_edges, const float* threshold,
+                       int64_t* out_edge_index, int64_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_full_adjacency(int32_t n, int64_t* out_edge_index, void* stream);
 
 /* Two-hop densification of the rewiring block (new_edges = 'k_hop_att', reference src/block_transformer_rewiring.py:68-86):
  *   S = coalesce(A ++ offdiag(A A)) / 2, i.e. torch_sparse.spspmm(A, A) -> remove_self_loops -> cat with A -> / 2 ->

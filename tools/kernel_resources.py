@@ -5,7 +5,8 @@
 Recompiles each .hip file for gfx950 with -Rpass-analysis=kernel-resource-usage (objects go to a temporary directory, the
 library is untouched) and prints one line per kernel instantiation: VGPRs, AGPRs, SGPRs, scratch bytes per lane, spills, LDS
 bytes per workgroup and the occupancy the compiler derives from them (waves per SIMD; 8 is the gfx950 maximum at <= 64 VGPRs).
-Kernels that spill or use scratch are listed again at the end -- a hot kernel there is the first thing to fix.
+Kernels that spill or use scratch are listed again at the end -- a hot kernel there is the first thing to fix.  rocprim's
+dispatch stubs that use no resource at all are counted, not listed.
 """
 import os
 import re
@@ -72,8 +73,14 @@ def main():
     for f in files:
       rows += analyse(os.path.join(CSRC, f), tmp)
   rows = [r for r in rows if 'vgpr' in r]
+  # rocprim's dispatch stubs (trampoline_kernel / compile_time_verifier instantiations that use no register, LDS or scratch) identify
+  # nothing: library kernels are listed only when they use a resource
+  stub = lambda r: r['name'].startswith('rocprim::') and not (r['vgpr'] or r.get('lds', 0) or r.get('scratch', 0))   # noqa: E731
+  n_stubs = sum(1 for r in rows if stub(r))
+  rows = [r for r in rows if not stub(r)]
   lines = ['# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage over graph-neural-pde_amd/csrc/*.hip',
            '# (tools/kernel_resources.py; occupancy = waves per SIMD as the compiler derives it from VGPRs + AGPRs and LDS)',
+           '# (%d rocprim dispatch stubs without registers, LDS or scratch are not listed)' % n_stubs,
            '%-12s %-86s %5s %5s %5s %7s %6s %7s %4s' % ('file', 'kernel', 'VGPR', 'AGPR', 'SGPR', 'scratch', 'spills', 'LDS', 'occ')]
   for r in sorted(rows, key=lambda r: (r['file'], r['name'])):
     lines.append('%-12s %-86s %5d %5d %5d %7d %6d %7d %4d' % (
