@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 13     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 14     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
@@ -195,6 +195,10 @@ PROTOTYPES = {
   'gnpde_stream_read': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_quantile_workspace_bytes': (ctypes.c_size_t, []),
   'gnpde_quantile': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_double, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_rank_select_begin': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_rank_select_hist': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_rank_select_pick': (ctypes.c_int, [ctypes.c_int32, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_rank_select_values': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_graph_build_device_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int32]),
   'gnpde_graph_build_device': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32] + [c_vp] * 8 + [c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_graph_build_device_long': (ctypes.c_int, [c_vp, c_vp] + [ctypes.c_int32] * 4 + [c_vp] * 8 + [c_vp, ctypes.c_size_t, c_vp]),
@@ -256,6 +260,13 @@ PROTOTYPES = {
   'gnpde_gdc_segment_sums': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_gdc_dense': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_size_t,
                                      c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_gdc_push_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]),
+  'gnpde_gdc_push_count': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_gdc_push_fill': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_gdc_push_residuals': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_philox_words': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64, c_vp, c_vp]),
   'gnpde_random_nodes': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp]),
   'gnpde_node_importance': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, c_vp, c_vp]),

@@ -31,7 +31,7 @@ __device__ __forceinline__ float value_of(unsigned k) {
 struct SelectState {
   unsigned prefix[2];        // bits found so far (high to low)
   unsigned long long k[2];   // rank among the elements that share the prefix
-  unsigned hist[2][256];
+  unsigned long long hist[2][256];   // 64-bit: the values fed piece by piece (gnpde_rank_select_hist) can pass 2^32 in all
 };
 
 __global__ __launch_bounds__(kBlock) void select_init_kernel(SelectState* st, unsigned long long k0, unsigned long long k1) {
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void select_hist_kernel(const float* __rest
   __syncthreads();
   for (int i = threadIdx.x; i < 512; i += blockDim.x) {
     const unsigned c = (&h[0][0])[i];
-    if (c) atomicAdd(&(&st->hist[0][0])[i], c);
+    if (c) atomicAdd(&(&st->hist[0][0])[i], static_cast<unsigned long long>(c));
   }
 }
 
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(64) void select_pick_kernel(SelectState* st, int sh
     unsigned long long k = st->k[r];
     unsigned digit = 255;
     for (unsigned dgt = 0; dgt < 256; ++dgt) {
-      const unsigned c = st->hist[r][dgt];
+      const unsigned long long c = st->hist[r][dgt];
       if (k < c) { digit = dgt; break; }
       k -= c;
     }
@@ -226,6 +226,50 @@ extern "C" int gnpde_quantile(const float* v, int64_t n, double q, float* out, v
     GNPDE_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(select_finish_kernel, dim3(1), dim3(1), 0, s, st, rank - lo, out);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+
+// the select of gnpde_quantile with the caller's two ascending ranks, fed piece by piece (the histogram kernel ADDS to the state):
+// begin, then for pass 0 .. 3: hist over every piece, pick; then values.  Graph diffusion rewiring's threshold by avg_degree.
+__global__ void select_values_kernel(const SelectState* st, float* out) {
+  out[0] = value_of(st->prefix[0]);
+  out[1] = value_of(st->prefix[1]);
+}
+
+extern "C" int gnpde_rank_select_begin(int64_t k0, int64_t k1, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(k0 >= 0 && k1 >= 0, GNPDE_EINVAL, "rank_select_begin: negative rank");
+  GNPDE_CHECK_ARG(workspace && workspace_bytes >= sizeof(SelectState), GNPDE_EWS, "rank_select_begin: workspace too small");
+  hipLaunchKernelGGL(select_init_kernel, dim3(1), dim3(kBlock), 0, static_cast<hipStream_t>(stream), static_cast<SelectState*>(workspace),
+                     static_cast<unsigned long long>(k0), static_cast<unsigned long long>(k1));
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gnpde_rank_select_hist(const float* v, int64_t n, int32_t pass, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(v && n >= 1 && pass >= 0 && pass <= 3, GNPDE_EINVAL, "rank_select_hist: bad arguments");
+  // a workgroup counts its share of ONE piece in 32 bits (LDS); the state's totals over all pieces are 64-bit
+  GNPDE_CHECK_ARG(n <= (1ll << 32), GNPDE_ESHAPE, "rank_select_hist: a piece of %lld values exceeds 2^32 (feed smaller pieces)", static_cast<long long>(n));
+  GNPDE_CHECK_ARG(workspace && workspace_bytes >= sizeof(SelectState), GNPDE_EWS, "rank_select_hist: workspace too small");
+  hipLaunchKernelGGL(select_hist_kernel, dim3(grid_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), v, static_cast<long long>(n),
+                     static_cast<SelectState*>(workspace), 24 - 8 * pass);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gnpde_rank_select_pick(int32_t pass, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(pass >= 0 && pass <= 3, GNPDE_EINVAL, "rank_select_pick: pass = %d outside 0 .. 3", pass);
+  GNPDE_CHECK_ARG(workspace && workspace_bytes >= sizeof(SelectState), GNPDE_EWS, "rank_select_pick: workspace too small");
+  hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<SelectState*>(workspace),
+                     24 - 8 * pass);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int gnpde_rank_select_values(float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  GNPDE_CHECK_ARG(out != nullptr, GNPDE_EINVAL, "rank_select_values: null output");
+  GNPDE_CHECK_ARG(workspace && workspace_bytes >= sizeof(SelectState), GNPDE_EWS, "rank_select_values: workspace too small");
+  hipLaunchKernelGGL(select_values_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), static_cast<const SelectState*>(workspace), out);
   GNPDE_LAUNCH_CHECK();
   return 0;
 }

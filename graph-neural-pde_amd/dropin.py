@@ -6,7 +6,7 @@ ODEFuncTransformerAtt`, src/model_configurations.py:1-9; `from base_classes impo
 early_stop_solver import EarlyStopInt`, src/GNN_early.py:10).  `install()` answers those imports with the modules of this
 package, whatever the order of `sys.path`:
 
-    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
+    python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-gdc-push] [--native-posdist] [--native-edge-sampling] /path/to/graph-neural-pde/src/run_GNN.py --dataset Cora --function transformer ...
 
 or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before the first import of a reference module.
 
@@ -21,7 +21,9 @@ or, from Python, `import gnpde_amd.dropin; gnpde_amd.dropin.install()` before th
   `run_GNN.py --rewire_KNN` then runs the native kernel; with no reference file on the path the module is this package's alone.
   `native_gdc=True` / `--native-gdc` merges the same module with `apply_gdc` and `GDCWrapper` replaced (graph diffusion rewiring,
   `--rewiring gdc` and `--pos_enc_type GDC`): `data.py`'s `from graph_rewiring import apply_gdc` then gets the native one.  Both
-  flags together replace all three names.  `native_posdist=True` / `--native-posdist` likewise replaces `apply_pos_dist_rewire`
+  flags together replace all three names.  `native_gdc_push=True` / `--native-gdc-push` is `--native-gdc` plus the option
+  `gnpde_gdc_approx = 'push'` for every `apply_gdc` call whose opt does not set it: `run_GNN.py --rewiring gdc --gdc_sparsification
+  threshold` without `--exact` then runs the approximate forward push, as the reference does.  `native_posdist=True` / `--native-posdist` likewise replaces `apply_pos_dist_rewire`
   (positional-distance rewiring, `--rewiring pos_enc_knn`) and the helpers it calls (`apply_beltrami`, `hyperbolize`,
   `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold`); the flags combine.
   `native_edge_sampling=True` / `--native-edge-sampling` replaces `add_edges`, `add_outgoing_attention_edges`, `edge_sampling` and
@@ -132,9 +134,10 @@ def installed():
   return _finder in sys.meta_path
 
 
-def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist=False, native_edge_sampling=False):
+def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist=False, native_edge_sampling=False, native_gdc_push=False):
   """Answer the reference's module names with this package (idempotent).  Returns the list of names now served."""
   merges = dict(MERGES)
+  native_gdc = native_gdc or native_gdc_push
   for on, extra in ((native_knn, NATIVE_KNN), (native_gdc, NATIVE_GDC), (native_posdist, NATIVE_POSDIST),
                     (native_edge_sampling, NATIVE_EDGE_SAMPLING)):
     if on:
@@ -156,6 +159,8 @@ def install(native_gnn=False, native_knn=False, native_gdc=False, native_posdist
   if native_edge_sampling:
     sys.modules[FA_MODULE] = _fa_module()
   _finder.table = merges
+  if native_gdc_push:
+    importlib.import_module('gnpde_amd.graph_rewiring').GDC_APPROX_DEFAULT = 'push'
   if _finder not in sys.meta_path:
     sys.meta_path.insert(0, _finder)
   return sorted(list(table) + extra_names) + [MERGED] + sorted(n for n in merges if n != MERGED)
@@ -166,6 +171,8 @@ def uninstall():
   if _finder in sys.meta_path:
     sys.meta_path.remove(_finder)
   _finder.table = dict(MERGES)
+  if 'gnpde_amd.graph_rewiring' in sys.modules:
+    sys.modules['gnpde_amd.graph_rewiring'].GDC_APPROX_DEFAULT = None
   merged = sorted(set(MERGES) | set(NATIVE_KNN) | set(NATIVE_GDC) | set(NATIVE_POSDIST))
   for name in list(MODULES) + list(NATIVE_GNN) + [FA_MODULE] + merged + ['_reference_' + m for m in merged]:
     m = sys.modules.get(name)
@@ -175,13 +182,14 @@ def uninstall():
 
 
 def main(argv=None):
-  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
+  """python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-gdc-push] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]: install(), then run SCRIPT as __main__ (its directory goes
   to the front of sys.path, as `python SCRIPT` would put it)."""
   import runpy
   argv = list(sys.argv[1:] if argv is None else argv)
   native = False
   native_knn = False
   native_gdc = False
+  native_gdc_push = False
   native_posdist = False
   native_edge_sampling = False
   while argv and argv[0].startswith('--'):
@@ -192,20 +200,22 @@ def main(argv=None):
       native_knn = True
     elif flag == '--native-gdc':
       native_gdc = True
+    elif flag == '--native-gdc-push':
+      native_gdc_push = True
     elif flag == '--native-posdist':
       native_posdist = True
     elif flag == '--native-edge-sampling':
       native_edge_sampling = True
     else:
-      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]' % flag)
+      raise SystemExit('gnpde_amd.dropin: unknown option %s\nusage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-gdc-push] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]' % flag)
   if not argv:
-    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]')
+    raise SystemExit('usage: python -m gnpde_amd.dropin [--native-gnn] [--native-knn] [--native-gdc] [--native-gdc-push] [--native-posdist] [--native-edge-sampling] SCRIPT [ARGS...]')
   script = os.path.abspath(argv[0])
   if not os.path.isfile(script):
     raise SystemExit('gnpde_amd.dropin: no such script: %s' % argv[0])
   sys.path.insert(0, os.path.dirname(script))
   install(native_gnn=native, native_knn=native_knn, native_gdc=native_gdc, native_posdist=native_posdist,
-          native_edge_sampling=native_edge_sampling)
+          native_edge_sampling=native_edge_sampling, native_gdc_push=native_gdc_push)
   sys.argv = [script] + argv[1:]
   runpy.run_path(script, run_name='__main__')
 

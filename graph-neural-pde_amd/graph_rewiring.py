@@ -11,7 +11,8 @@ Graph diffusion rewiring (`--rewiring gdc`, and `--beltrami --pos_enc_type GDC`;
 `apply_gdc` and `GDCWrapper`.  The reference's class subclasses torch_geometric.transforms.GDC and inverts a dense [n, n] matrix;
 here the diffusion matrix is formed column block by column block with the aggregation kernel and sparsified on the device
 (`ops.gdc`; the definition is in include/gnpde.h).  torch_geometric is not imported.  One deliberate difference: zero entries are
-never emitted (PyG's dense top-k also emits zero-weight edges, in arbitrary order).
+never emitted (PyG's dense top-k also emits zero-weight edges, in arbitrary order).  With opt['gnpde_gdc_approx'] = 'push' and a false
+opt['exact'] the reference's approximate branch runs instead: a forward push per source (`ops.gdc_push`), nothing dense.
 
 Positional-distance rewiring (`--rewiring pos_enc_knn`; reference graph_rewiring.py:285-342, hyperbolic_distances.py:7-14,
 distances_kNN.py): `apply_pos_dist_rewire` with `hyperbolize`, `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold` and
@@ -75,16 +76,27 @@ def apply_KNN(data, pos_encoding, model, opt):
   return ei
 
 
+GDC_APPROX_DEFAULT = None     # apply_gdc's opt['gnpde_gdc_approx'] when the opt does not set it (the drop-in's --native-gdc-push: 'push')
+
+
 class GDCWrapper(object):
   """The reference's GDCWrapper (graph_rewiring.py:345-401) without torch_geometric: same constructor, `__call__(data)` and
   `position_encoding(data)`.  diffusion_kwargs: method 'ppr' (alpha), 'heat' (t) or 'coeff' (coeffs); sparsification_kwargs: method
-  'topk' (k; dim = 0, per column, is the only orientation the reference uses) or 'threshold' (eps).  `exact` and the approximate
-  push's `eps` in diffusion_kwargs are accepted and ignored: this path computes the exact object up to `tol` (the truncated tail
-  of the series, 1e-6 by default), for every size.  Sparsification by avg_degree is not built."""
+  'topk' (k; dim = 0, per column, is the only orientation the reference uses) or 'threshold' (eps, or avg_degree: the threshold
+  that keeps avg_degree n entries, torch_geometric's __calculate_eps__; on the exact path 1 <= avg_degree < n).
+  approx=None (the default): `exact` and the approximate push's `eps` in diffusion_kwargs are accepted and ignored; the exact object
+  up to `tol` (the truncated tail of the series, 1e-6 by default) is computed for every size.
+  approx='push' AND exact false: torch_geometric's approximate branch -- the forward push of `ops.gdc_push` with tolerance
+  diffusion_kwargs['eps'], then the sparse threshold and the output normalisation; nothing dense, cost ~ n / (alpha eps).  As in
+  torch_geometric that branch has ppr only (heat / coeff: NotImplementedError), no top-k, the unweighted graph and
+  self_loop_weight None or 1."""
 
   def __init__(self, self_loop_weight=1, normalization_in='sym', normalization_out='col',
                diffusion_kwargs=dict(method='ppr', alpha=0.15), sparsification_kwargs=dict(method='threshold', avg_degree=64),
-               exact=True, tol=1e-6, block=256):
+               exact=True, tol=1e-6, block=256, approx=None):
+    if approx not in (None, 'push'):
+      raise ValueError("GDCWrapper: approx = %r is neither None nor 'push'" % (approx,))
+    self.approx = approx
     self.self_loop_weight = self_loop_weight
     self.normalization_in = normalization_in
     self.normalization_out = normalization_out
@@ -105,7 +117,7 @@ class GDCWrapper(object):
       return dict(method='coeff', coeffs=kw['coeffs'])
     raise ValueError('GDCWrapper: unknown diffusion method %r' % (method,))
 
-  def _sparsification(self):
+  def _sparsification(self, n):
     kw = self.sparsification_kwargs
     method = kw.get('method')
     if method == 'topk':
@@ -114,8 +126,36 @@ class GDCWrapper(object):
       return dict(k=kw['k'])
     if method == 'threshold':
       if 'eps' not in kw:
-        raise NotImplementedError('GDCWrapper: threshold sparsification by avg_degree is not built; give eps')
+        if int(kw['avg_degree']) >= n:
+          raise NotImplementedError('GDCWrapper: threshold sparsification by avg_degree = %d >= n = %d on the exact path is not built: '
+                                    'it keeps every entry of the dense [n, n] matrix; give eps or a smaller avg_degree'
+                                    % (int(kw['avg_degree']), n))
+        return dict(avg_degree=int(kw['avg_degree']))
       return dict(eps=kw['eps'])
+    raise ValueError('GDCWrapper: unknown sparsification method %r' % (method,))
+
+  def _takes_push(self):
+    return self.approx == 'push' and not self.exact
+
+  def _push(self, data, n):
+    """(edge_index, values) of the approximate diffusion matrix, sorted by (row, col), before sparsification."""
+    kw = self.diffusion_kwargs
+    if kw.get('method') != 'ppr':
+      raise NotImplementedError("GDCWrapper: approx = 'push' has no %r diffusion: the forward push approximates ppr only "
+                                "(torch_geometric's approximate branch raises for heat as well)" % (kw.get('method'),))
+    if kw.get('eps') is None:
+      raise ValueError("GDCWrapper: approx = 'push' needs the push tolerance diffusion_kwargs['eps']")
+    return ops.gdc_push(data.edge_index, n, kw['alpha'], kw['eps'], self_loop_weight=self.self_loop_weight,
+                        normalization_in=self.normalization_in, edge_weight=data.edge_attr)
+
+  def _push_sparsification(self):
+    kw = self.sparsification_kwargs
+    method = kw.get('method')
+    if method == 'topk':
+      raise NotImplementedError("GDCWrapper: approx = 'push' has no top-k sparsification: torch_geometric's sparse path "
+                                "(sparsify_sparse) has no top-k either; use method 'threshold'")
+    if method == 'threshold':
+      return dict(eps=kw['eps']) if 'eps' in kw else dict(avg_degree=int(kw['avg_degree']))
     raise ValueError('GDCWrapper: unknown sparsification method %r' % (method,))
 
   def _common(self, data):
@@ -130,7 +170,12 @@ class GDCWrapper(object):
     """data.edge_index / data.edge_attr replaced by the diffused, sparsified, normalised graph, sorted by (row, col) as
     torch_sparse.coalesce returns it."""
     n, kw = self._common(data)
-    kw.update(self._sparsification())
+    if self._takes_push():
+      sparse = self._push_sparsification()
+      ei, ew = self._push(data, n)
+      data.edge_index, data.edge_attr = ops.gdc_sparse_threshold(ei, ew, n, normalization_out=self.normalization_out, **sparse)
+      return data
+    kw.update(self._sparsification(n))
     ei, ew = ops.gdc(data.edge_index, data.edge_attr, n, **kw)
     order = torch.sort(ei[0] * n + ei[1]).indices       # (row, col) pairs are unique
     data.edge_index, data.edge_attr = ei[:, order].contiguous(), ew[order].contiguous()
@@ -140,13 +185,24 @@ class GDCWrapper(object):
   def position_encoding(self, data):
     """The dense [n, n] diffusion matrix, normalised, entry [i, j] = S[i, j] (no sparsification, reference :363-401)."""
     n, kw = self._common(data)
+    if self._takes_push():
+      if 4 * n * n > ops.GDC_DENSE_CAP:
+        raise ops._lib.GnpdeError('GDCWrapper.position_encoding: the dense %d x %d matrix exceeds the cap of %d bytes' % (n, n, ops.GDC_DENSE_CAP))
+      ei, ew = self._push(data, n)
+      if self.normalization_out is not None and ew.numel():
+        ew = ops._gdc_normalise(ei[0], ei[1], ew, n, self.normalization_out)
+      dense = torch.zeros(n, n, dtype=torch.float32, device=ew.device)
+      dense[ei[0], ei[1]] = ew                            # (row, col) pairs are unique
+      return dense
     return ops.gdc(data.edge_index, data.edge_attr, n, dense_out=True, **kw)
 
 
 def apply_gdc(data, opt, type="combined"):
   """The reference's apply_gdc (graph_rewiring.py:51-90) with the same option mapping: gdc_method with ppr_alpha / heat_time,
   gdc_sparsification with gdc_k (per-column top-k) or gdc_threshold, self_loop_weight, 'sym' in and 'col' out, pos_enc_orientation.
-  opt['exact'] and the push tolerance are accepted and ignored (see GDCWrapper); opt['gnpde_gdc_tol'] (1e-6) truncates the series."""
+  opt['gnpde_gdc_tol'] (1e-6) truncates the series.  opt['gnpde_gdc_approx'] = 'push' together with a false opt['exact'] takes the
+  approximate forward push with tolerance opt['gdc_threshold'], as the reference does for exact = False; without that option
+  opt['exact'] and the push tolerance are accepted and ignored (see GDCWrapper)."""
   num_edges = lambda d: int(d.edge_index.shape[1])
   print('raw data contains {} edges and {} nodes'.format(num_edges(data), data.num_nodes))
   print('performing gdc transformation with method {}, sparsification {}'.format(opt['gdc_method'], opt['gdc_sparsification']))
@@ -162,7 +218,7 @@ def apply_gdc(data, opt, type="combined"):
   print('gdc sparse args: {}'.format(sparse_args))
   gdc = GDCWrapper(float(opt['self_loop_weight']) if opt['self_loop_weight'] != 0 else None, normalization_in='sym',
                    normalization_out='col', diffusion_kwargs=diff_args, sparsification_kwargs=sparse_args,
-                   exact=opt.get('exact', True), tol=opt.get('gnpde_gdc_tol', 1e-6))
+                   exact=opt.get('exact', True), tol=opt.get('gnpde_gdc_tol', 1e-6), approx=opt.get('gnpde_gdc_approx', GDC_APPROX_DEFAULT))
   if isinstance(data.num_nodes, list):
     data.num_nodes = data.num_nodes[0]
   if type == 'combined':

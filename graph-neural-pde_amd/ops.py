@@ -718,15 +718,44 @@ def gdc_transition(edge_index, edge_weight, n, self_loop_weight=1.0, normalizati
   return row, col, _gdc_normalise(row, col, w, n, normalization_in)
 
 
-def gdc(edge_index, edge_weight, n, *, method, alpha=None, t=None, coeffs=None, k=None, eps=None, self_loop_weight=1.0,
-        normalization_in='sym', normalization_out='col', tol=1e-6, block=256, dense_out=False, dense_cap_bytes=GDC_DENSE_CAP):
+def _rank_select(pieces, k0, k1, device):
+  """[2] float32 device tensor: the order statistics of ascending ranks k0, k1 (0 = the smallest) among all values of the float32
+  device tensors that pieces() yields -- the same pieces on each of its four calls (gnpde_rank_select_*: the streaming radix select
+  of gnpde_quantile with integer ranks; nothing is sorted or kept)."""
+  L = _lib.lib()
+  ws = torch.empty(int(L.gnpde_quantile_workspace_bytes()), dtype=torch.uint8, device=device)
+  out = torch.empty(2, dtype=torch.float32, device=device)
+  stream = _stream_on(device)
+  check(L.gnpde_rank_select_begin(int(k0), int(k1), ptr(ws), ws.numel(), stream))
+  for p in range(4):
+    for v in pieces():
+      check(L.gnpde_rank_select_hist(ptr(v), v.numel(), p, ptr(ws), ws.numel(), stream))
+    check(L.gnpde_rank_select_pick(p, ptr(ws), ws.numel(), stream))
+  check(L.gnpde_rank_select_values(ptr(out), ptr(ws), ws.numel(), stream))
+  return out
+
+
+def _avg_degree_eps(pieces, n_fed, keep, device):
+  """torch_geometric's GDC.__calculate_eps__ without the sort: the mean (float32) of the keep-th and (keep + 1)-th largest of the
+  n_fed >= keep + 1 values fed, as a 0-d device tensor."""
+  two = _rank_select(pieces, n_fed - keep - 1, n_fed - keep, device)
+  return (two[0] + two[1]) * 0.5
+
+
+def gdc(edge_index, edge_weight, n, *, method, alpha=None, t=None, coeffs=None, k=None, eps=None, avg_degree=None, self_loop_weight=1.0,
+        normalization_in='sym', normalization_out='col', tol=1e-6, block=256, dense_out=False, dense_cap_bytes=GDC_DENSE_CAP,
+        return_eps=False):
   """Graph diffusion rewiring (the definition is in include/gnpde.h): S = sum_m theta_m T^m for 'ppr' (alpha), 'heat' (t) or
   'coeff' (coeffs), truncated by gdc_terms(.., tol); per column the k largest strictly positive entries (k) or the entries >= eps
   (eps); output normalisation over the kept entries.  Returns (edge_index [2, E'] int64 with row = i, col = j for a kept S[i, j],
   edge_weight [E']) grouped by ascending column, within a column by value descending and equal values by ascending row;
   bit-identical from run to run.  dense_out: no sparsification, the normalised [n, n] matrix (refused above dense_cap_bytes).
   Columns are processed in blocks of `block` (a multiple of 4, <= 256) on an [n, block] slab; no [n, n] array exists otherwise.
-  Zero entries are never emitted (torch_geometric's dense top-k emits them, in arbitrary order)."""
+  Zero entries are never emitted (torch_geometric's dense top-k emits them, in arbitrary order).
+  avg_degree (instead of eps): the threshold is the mean of the (avg_degree n)-th and (avg_degree n + 1)-th largest of all n^2
+  entries (torch_geometric's __calculate_eps__), found by a streaming radix select that forms every column block once per digit
+  pass (four extra sweeps of the diffusion, no sort, no [n, n] array); 1 <= avg_degree < n.  A cut that falls among the zeros keeps
+  every positive entry.  return_eps: the threshold used is returned as a third value (a float)."""
   n = int(n)
   if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
     raise ValueError('gdc: edge_index must be [2, E]')
@@ -742,8 +771,10 @@ def gdc(edge_index, edge_weight, n, *, method, alpha=None, t=None, coeffs=None, 
     raise ValueError("gdc: method %r needs its parameter (ppr: alpha, heat: t, coeff: coeffs)" % (method,))
   theta = gdc_terms(method, param, tol)
   if not dense_out:
-    if (k is None) == (eps is None):
-      raise ValueError('gdc: give exactly one of k (top-k per column) and eps (threshold)')
+    if (k is not None) + (eps is not None) + (avg_degree is not None) != 1:
+      raise ValueError('gdc: give exactly one of k (top-k per column), eps (threshold) and avg_degree (threshold by edge count)')
+    if avg_degree is not None and not 1 <= int(avg_degree) < n:
+      raise ValueError('gdc: avg_degree = %r outside 1 .. n - 1 (avg_degree >= n keeps the whole dense matrix)' % (avg_degree,))
     if k is not None and not 1 <= int(k) <= GDC_MAX_K:
       raise ValueError('gdc: k = %r outside 1 .. %d' % (k, GDC_MAX_K))
     if eps is not None and not float(eps) > 0.0:
@@ -795,6 +826,15 @@ def gdc(edge_index, edge_weight, n, *, method, alpha=None, t=None, coeffs=None, 
     if total:
       check(L.gnpde_gdc_emit(ptr(keys), ptr(offsets), n, kk, int(native_col), ptr(out_ei), total, ptr(out_w), stream))
   else:
+    if avg_degree is not None:
+      def slabs():
+        for j0 in range(0, n, block):
+          run_block(j0)
+          yield slab.reshape(-1)
+      # columns past n of the last slab are zeros: they sit below every rank read here (all values are >= 0)
+      n_fed = n * block * ((n + block - 1) // block)
+      eps = float(_avg_degree_eps(slabs, n_fed, int(avg_degree) * n, dev).item())
+      eps = max(eps, float(torch.finfo(torch.float32).tiny))       # a cut among the zeros: every positive entry
     eps = float(eps)
     parts = []
     counts = torch.zeros(block, **i64)
@@ -820,7 +860,155 @@ def gdc(edge_index, edge_weight, n, *, method, alpha=None, t=None, coeffs=None, 
       _segment_sums(out_w, torch.bincount(out_ei[1], minlength=n), divide=True)
   if normalization_out in ('row', 'sym') and out_w.numel():
     out_w = _gdc_normalise(out_ei[0], out_ei[1], out_w, n, normalization_out)
+  if return_eps:
+    return out_ei, out_w, (eps if not kk else None)
   return out_ei, out_w
+
+
+GDC_PUSH_SLOW_BYTES = 1 << 30    # budget of the slow path's per-workgroup scratch areas (36 n bytes each) when slow_groups is not given
+GDC_PUSH_SLOW_GROUPS = 256       # and their largest number then (one per compute unit)
+GDC_PUSH_RESIDUALS_MAX_N = 4096
+
+
+def _push_status(status):
+  if status:
+    raise _lib.GnpdeError('gdc_push: the push kernel reported status %d (1: round guard reached, 2: a column index out of range, '
+                          '4: offsets that are not those of the count pass, the source was not written)' % status)
+
+
+def gdc_push(edge_index, n, alpha, eps, self_loop_weight=1, normalization_in='sym', *, edge_weight=None, batch=None, capacity=-1,
+             slow_groups=None, return_info=False, return_residuals=False):
+  """Approximate personalised PageRank of EVERY node by forward push (gnpde_gdc_push_*; the definition is in include/gnpde.h): the
+  `exact = False` branch of torch_geometric's GDC (diffusion_matrix_approx) without anything dense.  edge_index: the unweighted
+  graph; unit self loops are added for self_loop_weight = 1 (None / 0: none), duplicates removed.  p_s(u) is the estimate of
+  source s at node u, 0 <= PPR - p < eps deg(u) on an undirected graph.  Returns (edge_index [2, E] int64, values [E]
+  float32) sorted by (row, col), one entry per p_s(u) > 0:
+    normalization_in 'row': entry [s, u] = p_s(u);  'sym': [s, u] = deg(s)^1/2 p_s(u) deg(u)^-1/2 (0 for degree 0);
+    'col': the transpose of the row form, entry [u, s] = p_s(u).
+  Bit-identical from run to run and for every batch (sources per launch), capacity (distinct nodes of the LDS hash: -1 the
+  built-in 1536, 0 forces every source through the slow path) and slow_groups (scratch areas of the slow path, 36 n bytes each;
+  default: as many as fit GDC_PUSH_SLOW_BYTES, at most GDC_PUSH_SLOW_GROUPS; only the areas a call uses are cleared).  Host
+  synchronisations: the graph preparation (index check, torch.unique), one read of the output size between the count and the
+  fill pass, one read of the fill pass's status word.  return_info: a third value, dict(slow_sources=, residuals=) -- residuals
+  [n, n] float32 dense (row s = r_s) with return_residuals, n <= 4096.  Refused, as the reference refuses them: edge weights and
+  self_loop_weight other than None / 1 (NotImplementedError)."""
+  n = int(n)
+  if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+    raise ValueError('gdc_push: edge_index must be [2, E]')
+  if n < 1 or n > INT32_MAX:
+    raise ValueError('gdc_push: n = %d outside 1 .. 2^31 - 1' % n)
+  if edge_weight is not None:
+    raise NotImplementedError('gdc_push: a weighted graph needs the exact path (the reference asserts exact for edge weights); '
+                              'the push is defined on the unweighted graph')
+  if self_loop_weight not in (None, 0, 1):
+    raise NotImplementedError('gdc_push: self_loop_weight = %r is not None or 1 (the reference asserts exact or self_loop_weight == 1)'
+                              % (self_loop_weight,))
+  alpha, eps = float(alpha), float(eps)
+  if not 0.0 < alpha < 1.0:
+    raise ValueError('gdc_push: alpha = %r outside (0, 1)' % alpha)
+  if not (0.0 < eps < float('inf')):
+    raise ValueError('gdc_push: eps = %r is not a positive finite number' % eps)
+  if normalization_in not in ('sym', 'col', 'row'):
+    raise ValueError('gdc_push: normalization_in %r is not sym, col or row' % (normalization_in,))
+  if batch is not None and int(batch) < 1:
+    raise ValueError('gdc_push: batch = %r is not positive' % (batch,))
+  if return_residuals and n > GDC_PUSH_RESIDUALS_MAX_N:
+    raise _lib.GnpdeError('gdc_push: the dense residual read-out is for n <= %d (n = %d)' % (GDC_PUSH_RESIDUALS_MAX_N, n))
+  if not edge_index.is_cuda:
+    raise _lib.GnpdeError('gdc_push runs only on a HIP device (got a %s tensor); there is no CPU fallback' % edge_index.device.type)
+  from .graph import CSRGraph
+  dev = edge_index.device
+  L = _lib.lib()
+  row, col = edge_index[0].detach().long(), edge_index[1].detach().long()
+  if row.numel() and (int(torch.minimum(row.min(), col.min())) < 0 or int(torch.maximum(row.max(), col.max())) >= n):
+    raise ValueError('gdc_push: edge index outside [0, %d)' % n)
+  if self_loop_weight:
+    loop = torch.arange(n, dtype=torch.int64, device=dev)
+    row, col = torch.cat([row, loop]), torch.cat([col, loop])
+  key = torch.unique(row * n + col)                              # sorted: CSR order is the list's own
+  row, col = torch.div(key, n, rounding_mode='floor'), key % n
+  graph = CSRGraph(torch.stack([row, col]), n, dev)
+  deg = torch.bincount(row, minlength=n)
+  batches = [(0, n)] if batch is None else [(s0, min(int(batch), n - s0)) for s0 in range(0, n, int(batch))]
+  widest = max(ns for _, ns in batches)
+  if slow_groups is None:
+    per_group = int(L.gnpde_gdc_push_workspace_bytes(n, 1, 2)) - int(L.gnpde_gdc_push_workspace_bytes(n, 1, 1))
+    slow_groups = max(1, min(GDC_PUSH_SLOW_GROUPS, GDC_PUSH_SLOW_BYTES // max(per_group, 1)))
+  slow_groups = int(slow_groups)
+  ws_bytes = int(L.gnpde_gdc_push_workspace_bytes(n, widest, slow_groups))
+  if ws_bytes == 0:
+    raise _lib.GnpdeError('gdc_push: slow_groups = %d outside 1 .. 1024' % slow_groups)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+  stream = stream_of(ws)
+  i64 = dict(dtype=torch.int64, device=dev)
+  common = (alpha, eps, int(capacity), slow_groups)
+  info = torch.zeros(2, **i64)
+  offsets = torch.zeros(n + 1, **i64)
+  for s0, ns in batches:
+    check(L.gnpde_gdc_push_count(graph.ref(), s0, ns, *common, ptr(offsets[1 + s0:]), ptr(info), ptr(ws), ws.numel(), stream))
+  torch.cumsum(offsets[1:].clone(), 0, out=offsets[1:])
+  total, n_slow, status = torch.cat([offsets[-1:], info]).tolist()          # the host read of the output size
+  _push_status(status)
+  out_ei = torch.empty(2, total, **i64)
+  out_p = torch.empty(total, dtype=torch.float32, device=dev)
+  info_fill = torch.zeros(2, **i64)
+  if total:
+    for s0, ns in batches:
+      check(L.gnpde_gdc_push_fill(graph.ref(), s0, ns, *common, ptr(offsets[s0:]), ptr(out_ei), total, ptr(out_p), ptr(info_fill),
+                                  ptr(ws), ws.numel(), stream))
+  resid = None
+  if return_residuals:
+    resid = torch.empty(n, n, dtype=torch.float32, device=dev)
+    for s0, ns in batches:
+      check(L.gnpde_gdc_push_residuals(graph.ref(), s0, ns, *common, ptr(resid[s0:]), ptr(info_fill), ptr(ws), ws.numel(), stream))
+  if total or return_residuals:
+    _push_status(int(info_fill[1].item()))       # a source the fill pass refused would leave its output unwritten
+  src, dst, w = out_ei[0], out_ei[1], out_p
+  if normalization_in == 'sym':
+    root = deg.double().sqrt()
+    inv = torch.where(deg > 0, 1.0 / root.clamp(min=1.0), torch.zeros_like(root))
+    w = (root[src] * w.double() * inv[dst]).float()
+  elif normalization_in == 'col':
+    order = torch.sort(dst * n + src).indices                   # (row, col) pairs are unique
+    out_ei, w = torch.stack([dst[order], src[order]]), w[order].contiguous()
+  if return_info:
+    return out_ei, w, dict(slow_sources=int(n_slow), residuals=resid)
+  return out_ei, w
+
+
+def gdc_sparse_threshold(edge_index, w, n, *, eps=None, avg_degree=None, normalization_out='col', return_eps=False):
+  """torch_geometric's sparsify_sparse + output transition_matrix on a sparse list sorted by (row, col) (gdc_push's): keep the
+  entries >= eps, or with avg_degree the entries >= the mean of the (avg_degree n)-th and (avg_degree n + 1)-th largest values
+  (every entry when there are no more than avg_degree n; a streaming radix select, nothing is sorted); then the output
+  normalisation over the kept entries with fixed-order sums.  The order is kept.  return_eps: the threshold used (a float, None
+  when every entry is kept) is returned as a third value."""
+  if (eps is None) == (avg_degree is None):
+    raise ValueError('gdc_sparse_threshold: give exactly one of eps and avg_degree')
+  if normalization_out not in ('sym', 'col', 'row', None):
+    raise ValueError('gdc_sparse_threshold: normalization_out %r is not sym, col, row or None' % (normalization_out,))
+  if eps is not None and not float(eps) > 0.0:
+    raise ValueError('gdc_sparse_threshold: eps = %r is not positive' % (eps,))
+  require_hip(edge_index, w)
+  n = int(n)
+  w = f32c(w, 'values')
+  thr = None
+  if eps is not None:
+    thr = torch.full((1,), float(eps), dtype=torch.float32, device=w.device)
+  else:
+    keep = int(avg_degree) * n
+    if keep < 1:
+      raise ValueError('gdc_sparse_threshold: avg_degree = %r is not positive' % (avg_degree,))
+    if w.numel() > keep:
+      thr = _avg_degree_eps(lambda: (w,), w.numel(), keep, w.device).reshape(1)
+  if thr is not None and w.numel():
+    pos = torch.arange(w.numel(), dtype=torch.int64, device=w.device)
+    kept = select_edges(torch.stack([pos, pos]), w, thr)[0]
+    edge_index, w = edge_index[:, kept].contiguous(), w[kept].contiguous()
+  if normalization_out is not None and w.numel():
+    w = _gdc_normalise(edge_index[0], edge_index[1], w, n, normalization_out)
+  if return_eps:
+    return edge_index, w, (None if thr is None else float(thr.item()))
+  return edge_index, w
 
 
 def edge_attention_bwd_heads(graph, att, datt_edge, post=0):

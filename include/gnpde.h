@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 13  /* 13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 14  /* 14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -778,6 +778,16 @@ int gnpde_stream_read(const float* table, int64_t n_floats, int32_t passes, floa
  * ---------------------------------------------------------------------------------------------- */
 size_t gnpde_quantile_workspace_bytes(void);
 int gnpde_quantile(const float* v, int64_t n, double q, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The same radix select with the CALLER's two ranks (ascending, 0 = the smallest) over values fed piece by piece: begin; then for
+ * pass = 0 .. 3: gnpde_rank_select_hist over every piece (it adds to the state), gnpde_rank_select_pick; then
+ * gnpde_rank_select_values: out[0], out[1] (device) = the order statistics of rank k0, k1 among everything fed.  The pieces must be
+ * the same in every pass; ranks at or past the number of values fed give an unspecified value.  The totals are counted in 64
+ * bits (any number of pieces); one piece holds at most 2^32 values (GNPDE_ESHAPE).  Workspace: gnpde_quantile's.
+ * (torch_geometric's GDC.__calculate_eps__ sorts all values; graph diffusion rewiring's threshold by avg_degree uses this.) */
+int gnpde_rank_select_begin(int64_t k0, int64_t k1, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_rank_select_hist(const float* v, int64_t n, int32_t pass, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_rank_select_pick(int32_t pass, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_rank_select_values(float* out, void* workspace, size_t workspace_bytes, void* stream);
 size_t gnpde_threshold_edges_workspace_bytes(int64_t n_edges, int32_t n_nodes);
 int gnpde_threshold_edges(const int64_t* edge_index, const float* score, int64_t n_edges, const float* threshold,
                           int32_t norm_idx, int32_t n_nodes, int64_t* out_edge_index, float* out_weight, int64_t* out_count,
@@ -956,6 +966,36 @@ int gnpde_gdc_threshold_fill(const gnpde_graph_t* g, int64_t j0, int32_t block, 
 int gnpde_gdc_segment_sums(float* w, const int64_t* offsets, int64_t n_segments, float* sums, int32_t divide, void* stream);
 int gnpde_gdc_dense(const gnpde_graph_t* g, const float* slab, int64_t j0, int32_t block, int32_t normalise, float* dense,
                     size_t cap_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Approximate personalised PageRank by forward push (Andersen-Chung-Lang): the `exact = False` branch of graph diffusion rewiring
+ * (reference src/graph_rewiring.py:389-392 -> torch_geometric's GDC.diffusion_matrix_approx).  g: the coalesced UNWEIGHTED graph with
+ * the self loops already added (row_begin = 0; only n, rowptr and colidx are read), deg(u) = the length of row u.  For every
+ * source s: p_s = 0, r_s = alpha e_s; a push at u with res = r_s(u) does p_s(u) += res, r_s(u) = 0, r_s(v) += (1 - alpha) res /
+ * deg(u) for every v of row u.  The source is pushed once unconditionally, then every u with r_s(u) >= alpha eps deg(u), in
+ * synchronous rounds, until none is left.  p and r are 64-bit fixed-point integers (quantum 2^-60; the two divisions of a push
+ * round DOWN, so a push loses less than deg(u) + 2 quanta of mass and never creates any) accumulated with integer atomics: the
+ * result is bit-identical from run to run and does not depend on the batch (s0, n_sources), the grid, `capacity` or `slow_groups`.
+ * The state of a source lives in an LDS hash of `capacity` distinct nodes (-1: the built-in 1536, the maximum; 0: none); a source
+ * whose support outgrows it is run again inside the same call on one of `slow_groups` per-workgroup scratch areas of the workspace
+ * (36 n bytes each, cleared by the groups that have work, reset per source through a touched list) -- same integers, same result.  Nothing of size n x n exists.
+ *   gnpde_gdc_push_count      counts[i] (int64, [n_sources]) = number of u with p_{s0 + i}(u) > 0
+ *   gnpde_gdc_push_fill       offsets [n_sources + 1] = exclusive scan of those counts (the caller's) -> out_edge_index ([2, out_ld]
+ *                             int64 row-major: row 0 = s, row 1 = u ascending) and out_p = fp32(p_s(u)) (one rounding) at offsets[i] ..
+ *   gnpde_gdc_push_residuals  residuals [n_sources, n] fp32 (dense, zero-filled here) = fp32(r_s(u)); for tests, n <= 4096
+ * info: int64[2] on the device, zeroed by the caller: info[0] += sources that took the slow path (count pass only), info[1] |=
+ * 1 (round guard reached: never expected), 2 (a column index outside [0, n)), 4 (offsets are not those of this push's counts; that
+ * source is not written).  Limits: n <= INT32_MAX, 0 < alpha < 1, eps > 0 finite, alpha eps >= 2^-60, 0 <= s0, s0 + n_sources <= n,
+ * capacity >= -1, 1 <= slow_groups <= 1024; outside them GNPDE_EINVAL / GNPDE_ESHAPE / GNPDE_EWS with gnpde_last_error set and
+ * nothing launched (gnpde_gdc_push_workspace_bytes: 0). */
+size_t gnpde_gdc_push_workspace_bytes(int64_t n, int64_t n_sources, int32_t slow_groups);
+int gnpde_gdc_push_count(const gnpde_graph_t* g, int64_t s0, int64_t n_sources, double alpha, double eps, int32_t capacity,
+                         int32_t slow_groups, int64_t* counts, int64_t* info, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_gdc_push_fill(const gnpde_graph_t* g, int64_t s0, int64_t n_sources, double alpha, double eps, int32_t capacity,
+                        int32_t slow_groups, const int64_t* offsets, int64_t* out_edge_index, int64_t out_ld, float* out_p,
+                        int64_t* info, void* workspace, size_t workspace_bytes, void* stream);
+int gnpde_gdc_push_residuals(const gnpde_graph_t* g, int64_t s0, int64_t n_sources, double alpha, double eps, int32_t capacity,
+                             int32_t slow_groups, float* residuals, int64_t* info, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-partitioned solve over the GPUs of one node: one process per GPU, RCCL point-to-point halo exchange once per

@@ -8,7 +8,14 @@ no composite exists there.  Graphs are the synthetic stand-ins of gnpde_amd.synt
 
 Per shape one JSON line (printed, and appended to --out): best-of-R event time after a warm-up call, the number of series terms, and at the
 Cora shape the composite's time, the ratio, and the share of (row, col) entries on which the two selections agree.  Nothing here asserts a
-speed."""
+speed.
+
+  python tools/gdc_ab.py --push [--shape ...] [--alpha A] [--eps EPS] [--repeats R] [--exact-repeats R2] [--out profiles/gdc_push_ab.jsonl]
+
+times the approximate pipeline GDCWrapper(approx='push', exact=False) -- forward push with tolerance EPS, threshold EPS, 'col' out, as
+apply_gdc maps opt['gdc_threshold'] -- against the exact native path (the same wrapper without approx: ops.gdc with threshold EPS) on the
+same graph: event time of the whole call, best of R after a warm-up (the exact path: best of R2, 0 skips it), edges returned by both
+and the sources that took the push's slow path."""
 import argparse
 import json
 import os
@@ -50,8 +57,46 @@ def best_ms(fn, repeats):
   return best, out
 
 
+class _Data(object):
+  def __init__(self, n, ei):
+    self.num_nodes, self.edge_index, self.edge_attr = n, ei, None
+
+
+def push_ab(args, dev):
+  W = G.graph_rewiring.GDCWrapper
+  out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, 'profiles', 'gdc_push_ab.jsonl')
+  diff = dict(method='ppr', alpha=args.alpha, eps=args.eps)
+  sparse = dict(method='threshold', eps=args.eps)
+  for name in (['cora', 'arxiv'] if args.shape == 'both' else [args.shape]):
+    ei, n = G.synthetic.make_graph(name, seed=0)
+    ei = ei.to(dev)
+    push = W(1, 'sym', 'col', diff, sparse, exact=False, approx='push')
+    t_push, res = best_ms(lambda: push(_Data(n, ei)), args.repeats)
+    _, _, info = ops.gdc_push(ei, n, args.alpha, args.eps, return_info=True)
+    out = {'tool': 'gdc_ab --push', 'shape': name, 'n': n, 'edges': int(ei.shape[1]), 'alpha': args.alpha, 'eps': args.eps,
+           'push_ms': round(t_push, 3), 'push_edges': int(res.edge_attr.numel()), 'slow_sources': info['slow_sources']}
+    del res, info
+    torch.cuda.empty_cache()
+    reps = args.repeats if args.exact_repeats is None else args.exact_repeats
+    if reps > 0:
+      exact = W(1, 'sym', 'col', diff, sparse, exact=True, tol=args.tol, block=args.block)
+      t_exact, res = best_ms(lambda: exact(_Data(n, ei)), reps)
+      out.update(exact_ms=round(t_exact, 3), exact_edges=int(res.edge_attr.numel()), exact_repeats=reps, exact_over_push=round(t_exact / t_push, 3))
+      del res
+    print(json.dumps(out), flush=True)
+    with open(out_path, 'a') as f:
+      f.write(json.dumps(out) + '\n')
+    torch.cuda.empty_cache()
+
+
+DEFAULT_OUT = os.path.join(ROOT, 'profiles', 'gdc_ab.jsonl')
+
+
 def main():
   ap = argparse.ArgumentParser()
+  ap.add_argument('--push', action='store_true', help='time the approximate push pipeline against the exact native path')
+  ap.add_argument('--eps', type=float, default=1e-4, help='--push: the push tolerance and the threshold')
+  ap.add_argument('--exact-repeats', type=int, default=None, help='--push: timed calls of the exact path (default --repeats; 0 skips it)')
   ap.add_argument('--shape', default='both', choices=['cora', 'arxiv', 'both'])
   ap.add_argument('--method', default='ppr', choices=['ppr', 'heat'])
   ap.add_argument('--alpha', type=float, default=0.05)
@@ -60,9 +105,11 @@ def main():
   ap.add_argument('--tol', type=float, default=1e-6)
   ap.add_argument('--block', type=int, default=256)
   ap.add_argument('--repeats', type=int, default=3)
-  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'gdc_ab.jsonl'))
+  ap.add_argument('--out', default=DEFAULT_OUT)
   args = ap.parse_args()
   dev = torch.device('cuda:0')
+  if args.push:
+    return push_ab(args, dev)
   param = args.alpha if args.method == 'ppr' else args.t
   kw = dict(method=args.method, k=args.k, tol=args.tol, block=args.block, **({'alpha': param} if args.method == 'ppr' else {'t': param}))
   for name in (['cora', 'arxiv'] if args.shape == 'both' else [args.shape]):
