@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 14     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 15     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
@@ -32,6 +32,7 @@ METRIC_POINCARE = 1
 TUNE_KNN_VARIANT = 20    # tile-kernel variants of the search (A/B): 1 = 32-float K chunks for k > 32, 2 = the k > 32 kernel for every k
 TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)
 SAMPLING_EMPTY_COLUMN, SAMPLING_NONFINITE, SAMPLING_ZERO_MASS, SAMPLING_INDEX_RANGE = 1, 2, 4, 8   # GNPDE_SAMPLING_* flag bits
+DEEPWALK_BAD_START, DEEPWALK_BAD_GRAPH, DEEPWALK_BAD_WALK = 1, 2, 4   # GNPDE_DEEPWALK_* flag bits
 
 ATT_TYPES = {'scaled_dot': ATT_SCALED_DOT, 'cosine_sim': ATT_COSINE, 'pearson': ATT_PEARSON,
              'exp_kernel': ATT_EXP_KERNEL}
@@ -278,6 +279,16 @@ PROTOTYPES = {
   'gnpde_select_edges_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64]),
   'gnpde_select_edges': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_full_adjacency': (ctypes.c_int, [ctypes.c_int32, c_vp, c_vp]),
+  'gnpde_random_walks': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, c_vp, c_vp, c_vp]),
+  'gnpde_negative_walks': (ctypes.c_int, [ctypes.c_int32, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32,
+                                          ctypes.c_uint32, ctypes.c_uint64, c_vp, c_vp, c_vp]),
+  'gnpde_random_permutation_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64]),
+  'gnpde_random_permutation': (ctypes.c_int, [ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_deepwalk_step_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+  'gnpde_deepwalk_step': (ctypes.c_int, [c_vp, ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_comm_load_library': (ctypes.c_int, [ctypes.c_char_p]),
   'gnpde_comm_get_unique_id': (ctypes.c_int, [c_vp]),
   'gnpde_comm_create': (ctypes.c_int, [ctypes.POINTER(c_vp), c_vp, ctypes.c_int32, ctypes.c_int32]),

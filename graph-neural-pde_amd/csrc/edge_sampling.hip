@@ -4,7 +4,7 @@
 //                  in both directions, then torch.unique(dim=1);
 //   edge_sampling  keep the columns whose mean attention is >= a quantile (the quantile itself is gnpde_quantile, rewire.hip).
 // Pieces here:
-//   Philox4x32-10  counter-based generator written out below (Random123; Salmon et al., SC'11): no state, word i of a stream is a
+//   Philox4x32-10  counter-based generator written out in philox.h (Random123; Salmon et al., SC'11): no state, word i of a stream is a
 //                  pure function of (seed, stream, call, i), so a draw does not depend on the launch shape
 //   gnpde_random_nodes     j = (word * n) >> 32
 //   gnpde_node_importance  mean of att_mean over a node's incoming edges: one wave per column of the graph's CSC view, lane l sums the
@@ -17,6 +17,7 @@
 // (gnpde_select_edges, the >= compaction, shares the compaction kernels of rewire.hip and lives there.)
 // Error conditions that depend on device data set bits of a device flag word (integer atomic OR) that the caller reads.
 #include "common.h"
+#include "philox.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -27,32 +28,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-struct Words4 {
-  unsigned w[4];
-};
-
-// Philox4x32-10: key (k0, k1), counter (c0 .. c3).  Round: (hi0, lo0) = M0 * c0, (hi1, lo1) = M1 * c2,
-// c <- (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0); the key is bumped by the Weyl constants between rounds.
-__device__ __forceinline__ Words4 philox4x32_10(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
-  constexpr unsigned kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
-    const unsigned hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
-    const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += kW0; k1 += kW1;
-  }
-  Words4 out;
-  out.w[0] = c0; out.w[1] = c1; out.w[2] = c2; out.w[3] = c3;
-  return out;
-}
-
-// block `b` of stream (seed, stream, call): key = the seed's words, counter = (b low, b high, stream, call)
-__device__ __forceinline__ Words4 stream_block(u64 seed, unsigned stream, unsigned call, u64 b) {
-  return philox4x32_10(static_cast<unsigned>(seed), static_cast<unsigned>(seed >> 32), static_cast<unsigned>(b),
-                       static_cast<unsigned>(b >> 32), stream, call);
-}
+// Philox4x32-10 and stream_block (block `b` of stream (seed, stream, call)) are in philox.h
 
 __global__ __launch_bounds__(kBlock) void philox_words_kernel(u64 seed, unsigned stream, unsigned call, u64 first_block, long long n_words,
                                                              unsigned* __restrict__ out) {

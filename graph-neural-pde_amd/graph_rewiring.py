@@ -16,7 +16,7 @@ opt['exact'] the reference's approximate branch runs instead: a forward push per
 
 Positional-distance rewiring (`--rewiring pos_enc_knn`; reference graph_rewiring.py:285-342, hyperbolic_distances.py:7-14,
 distances_kNN.py): `apply_pos_dist_rewire` with `hyperbolize`, `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold` and
-`apply_beltrami`.  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
+`apply_beltrami` (which, with opt['gnpde_generate_pos_enc'], trains a missing DW<d> pickle natively: deepwalk_embeddings.py).  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
 it or hands it to sklearn's NearestNeighbors(metric='precomputed'); here the edge set comes straight from the encodings
 (`ops.knn(metric=...)`, `ops.radius_graph`), so the helpers take ENCODINGS where the reference's take a distance matrix.
 Deliberate differences: no [n, n] distance pickle is written; the edge set is computed whether or not a cache file existed (the
@@ -289,11 +289,31 @@ def apply_dist_threshold(x, quant=POS_DIST_QUANTILE, metric='sqeuclidean'):
   return ops.radius_graph(_encodings(x), quantile=quant, metric=metric)
 
 
+DW_DEFAULTS = dict(walk_length=20, context_size=16, walks_per_node=16, num_negative_samples=1)   # the reference script's defaults
+
+
+def _generate_deepwalk(data, opt, fname):
+  """Train DW<d> encodings natively (deepwalk_embeddings.DeepWalk) and cache them in the layout of the reference's pickles."""
+  from . import deepwalk_embeddings
+  kind = opt['pos_enc_type']
+  if not kind[2:].isdigit():
+    raise ValueError('apply_beltrami: cannot read the embedding width from pos_enc_type %r (expected DW<d>)' % (kind,))
+  model = deepwalk_embeddings.DeepWalk(data.edge_index, data.num_nodes, embedding_dim=int(kind[2:]), seed=opt.get('seed', 0), **DW_DEFAULTS)
+  model.fit(opt.get('gnpde_dw_epochs', 100), batch_size=128)
+  z = model.embedding.detach().to(torch.device('cpu'))
+  os.makedirs(os.path.dirname(fname), exist_ok=True)
+  with open(fname, 'wb') as f:
+    pickle.dump({'data': z, 'acc': deepwalk_embeddings.node_classification_accuracy(z, data)}, f)
+  return z
+
+
 def apply_beltrami(data, opt, data_dir='../data'):
   """Positional encodings (reference graph_rewiring.py:244-282): the cached pickle `<data_dir>/pos_encodings/<dataset>_<type>.pkl`
   the reference loads (the 'data' entry for DW* types); otherwise, for pos_enc_type 'GDC', the native
-  `apply_gdc(type='pos_encoding')`, cached as the reference caches it.  Generating DeepWalk or hyperbolic embeddings is not
-  built: a missing pickle of such a type is an error."""
+  `apply_gdc(type='pos_encoding')`, cached as the reference caches it.  With a truthy opt['gnpde_generate_pos_enc'] a missing DW<d>
+  pickle is trained natively (deepwalk_embeddings.DeepWalk with the reference script's defaults, opt['gnpde_dw_epochs'] epochs,
+  default 100, seed opt['seed']) and cached in that layout.  Without the option a missing DW* pickle is an error, as is a missing
+  HYP* pickle always: generating hyperbolic embeddings is not built."""
   pos_enc_dir = os.path.join(data_dir, 'pos_encodings')
   fname = os.path.join(pos_enc_dir, '%s_%s.pkl' % (opt['dataset'], opt['pos_enc_type']))
   print('[i] Looking for positional encodings in %s...' % fname)
@@ -304,9 +324,13 @@ def apply_beltrami(data, opt, data_dir='../data'):
     if opt['pos_enc_type'].startswith('DW'):
       pos_encoding = pos_encoding['data']
     return pos_encoding
+  if opt['pos_enc_type'].startswith('DW') and opt.get('gnpde_generate_pos_enc'):
+    print('    Encodings not found! Training DeepWalk embeddings and caching them')
+    return _generate_deepwalk(data, opt, fname)
   if opt['pos_enc_type'] != 'GDC':
-    raise FileNotFoundError('apply_beltrami: no cached positional encodings %s, and type %r cannot be generated here'
-                            % (fname, opt['pos_enc_type']))
+    raise FileNotFoundError('apply_beltrami: no cached positional encodings %s, and type %r cannot be generated here%s'
+                            % (fname, opt['pos_enc_type'],
+                               " (set opt['gnpde_generate_pos_enc'] to train them)" if opt['pos_enc_type'].startswith('DW') else ''))
   print('    Encodings not found! Calculating and caching them')
   pos_encoding = apply_gdc(data, opt, type='pos_encoding')
   os.makedirs(pos_enc_dir, exist_ok=True)

@@ -470,6 +470,203 @@ def full_adjacency(n, device=None):
   return out
 
 
+# ---- DeepWalk positional encodings (csrc/deepwalk.hip; definitions in include/gnpde.h) -------------------------------------------
+DEEPWALK_FLAGS = ((_lib.DEEPWALK_BAD_START, 'a start node lies outside [0, n)'),
+                  (_lib.DEEPWALK_BAD_GRAPH, 'a rowptr / col entry of the walk graph lies outside the graph'),
+                  (_lib.DEEPWALK_BAD_WALK, 'a walk entry lies outside [0, n)'))
+DEEPWALK_MAX_WALK_LENGTH = 127
+DEEPWALK_MAX_DIM = 256
+DEEPWALK_LDS_FLOATS = 16384
+STREAM_POS_WALKS, STREAM_NEG_WALKS, STREAM_EPOCH_ORDER = 16, 17, 18     # graph_rewiring's edge sampling uses streams 0 and 1
+
+
+def _raise_deepwalk_flags(flag, who):
+  bits = int(flag.item())
+  if bits:
+    raise _lib.GnpdeError('%s: %s' % (who, '; '.join(text for bit, text in DEEPWALK_FLAGS if bits & bit)))
+
+
+class WalkGraph(object):
+  """CSR of the walk graph on the device: rowptr [n + 1] and col [E] int32, a node's out-neighbours with multiplicity, ascending."""
+
+  def __init__(self, rowptr, col, n):
+    self.rowptr, self.col, self.n = rowptr, col, int(n)
+
+
+def walk_csr(edge_index, n):
+  """WalkGraph of edge_index ([2, E] int64 on a HIP device): the out-neighbours of u are the dst of the edges (u, dst), with
+  multiplicity, ascending by dst.  Torch device ops, once per graph; one host read checks the index range."""
+  ei = _edge_list(edge_index, 'walk_csr: edge_index')
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('walk_csr: n = %d outside 1 .. INT32_MAX' % n)
+  E = ei.shape[1]
+  if E > INT32_MAX:
+    raise _lib.GnpdeError('walk_csr: %d edges exceed int32 positions' % E)
+  if E and (int(ei.min()) < 0 or int(ei.max()) >= n):
+    raise _lib.GnpdeError('walk_csr: an edge index lies outside [0, n)')
+  key = torch.sort(ei[0] * n + ei[1]).values
+  src = torch.div(key, n, rounding_mode='floor')
+  rowptr = torch.zeros(n + 1, dtype=torch.int64, device=ei.device)
+  if E:
+    rowptr[1:] = torch.cumsum(torch.bincount(src, minlength=n), 0)
+  return WalkGraph(rowptr.to(torch.int32), (key - src * n).to(torch.int32), n)
+
+
+def _walk_args(starts, walk_length, seed, stream, call, first_walk, repeats, who):
+  if not isinstance(starts, torch.Tensor) or starts.dim() != 1:
+    raise _lib.GnpdeError('%s: starts must be a vector' % who)
+  require_hip(starts)
+  if starts.dtype != torch.int64:
+    raise _lib.GnpdeError('%s: starts must be int64 (got %s)' % (who, starts.dtype))
+  L, repeats, first_walk = int(walk_length), int(repeats), int(first_walk)
+  if not 1 <= L <= DEEPWALK_MAX_WALK_LENGTH:
+    raise _lib.GnpdeError('%s: walk_length = %d outside 1 .. %d' % (who, L, DEEPWALK_MAX_WALK_LENGTH))
+  if repeats < 1 or not 0 <= first_walk < 2 ** 64:
+    raise _lib.GnpdeError('%s: repeats = %d / first_walk = %d out of range' % (who, repeats, first_walk))
+  _, seed, stream, call = _draw_args(0, seed, stream, call, who)
+  st = starts.detach()
+  return (st if st.is_contiguous() else st.contiguous()), L, seed, stream, call, first_walk, repeats
+
+
+def random_walks(edge_index, n, starts, walk_length, seed, stream, call, first_walk=0, *, repeats=1, dtype=torch.int64, flag=None):
+  """[R, walk_length + 1] uniform random walks (gnpde_random_walks; include/gnpde.h has the definition): walk r starts at
+  starts[r % len(starts)], R = len(starts) * repeats, and is walk first_walk + r of the Philox stream (seed, stream, call).
+  edge_index: [2, E] int64 on a HIP device, or a WalkGraph (ops.walk_csr) to build the CSR once.  flag: a device int32 the caller
+  reads itself (no host read here); otherwise a start outside [0, n) raises."""
+  who = 'random_walks'
+  st, L, seed, stream, call, first_walk, repeats = _walk_args(starts, walk_length, seed, stream, call, first_walk, repeats, who)
+  g = edge_index if isinstance(edge_index, WalkGraph) else walk_csr(edge_index, n)
+  if g.n != int(n):
+    raise _lib.GnpdeError('random_walks: the walk graph has %d nodes, not %d' % (g.n, int(n)))
+  if g.rowptr.device != st.device:
+    raise _lib.GnpdeError('random_walks: starts is on %s but the graph is on %s' % (st.device, g.rowptr.device))
+  R = st.numel() * repeats
+  out = torch.empty(R, L + 1, dtype=torch.int32, device=st.device)
+  if R:
+    own = flag is None
+    if own:
+      flag = torch.zeros(1, dtype=torch.int32, device=st.device)
+    check(_lib.lib().gnpde_random_walks(ptr(g.rowptr), ptr(g.col), g.col.numel(), g.n, ptr(st), st.numel(), R, L, seed, stream, call, first_walk,
+                                        ptr(out), ptr(flag), stream_of(st)))
+    if own:
+      _raise_deepwalk_flags(flag, who)
+  return out if dtype == torch.int32 else out.to(dtype)
+
+
+def negative_walks(n, starts, walk_length, seed, stream, call, first_walk=0, *, repeats=1, dtype=torch.int64, flag=None):
+  """[R, walk_length + 1]: column 0 the start node (starts[r % len(starts)]), every other column uniform over [0, n)
+  (gnpde_negative_walks): PyG's negative sample of Node2Vec on this package's Philox streams."""
+  who = 'negative_walks'
+  st, L, seed, stream, call, first_walk, repeats = _walk_args(starts, walk_length, seed, stream, call, first_walk, repeats, who)
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('negative_walks: n = %d outside 1 .. INT32_MAX' % n)
+  R = st.numel() * repeats
+  out = torch.empty(R, L + 1, dtype=torch.int32, device=st.device)
+  if R:
+    own = flag is None
+    if own:
+      flag = torch.zeros(1, dtype=torch.int32, device=st.device)
+    check(_lib.lib().gnpde_negative_walks(n, ptr(st), st.numel(), R, L, seed, stream, call, first_walk, ptr(out), ptr(flag), stream_of(st)))
+    if own:
+      _raise_deepwalk_flags(flag, who)
+  return out if dtype == torch.int32 else out.to(dtype)
+
+
+def random_permutation(n, seed, stream, call, device=None):
+  """A permutation of range(n) as an int64 device vector: the indices sorted by (word i of the stream) << 32 | i
+  (gnpde_random_permutation).  1 <= n <= INT32_MAX."""
+  _, seed, stream, call = _draw_args(0, seed, stream, call, 'random_permutation')
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('random_permutation: n = %d outside 1 .. INT32_MAX' % n)
+  device = _sampling_device(device, 'random_permutation')
+  L = _lib.lib()
+  out = torch.empty(n, dtype=torch.int64, device=device)
+  ws = torch.empty(int(L.gnpde_random_permutation_workspace_bytes(n)), dtype=torch.uint8, device=device)
+  check(L.gnpde_random_permutation(n, seed, stream, call, ptr(out), ptr(ws), ws.numel(), _stream_on(device)))
+  return out
+
+
+def deepwalk_check_shape(walk_length, context_size, d, who='deepwalk_step'):
+  """Raise for a shape the native step refuses (the limits of include/gnpde.h)."""
+  L, C, d = int(walk_length), int(context_size), int(d)
+  if not 1 <= L <= DEEPWALK_MAX_WALK_LENGTH:
+    raise _lib.GnpdeError('%s: walk_length = %d outside 1 .. %d' % (who, L, DEEPWALK_MAX_WALK_LENGTH))
+  if not 2 <= C <= L:
+    raise _lib.GnpdeError('%s: walk_length >= context_size >= 2 is required (walk_length %d, context_size %d)' % (who, L, C))
+  if d % 4 != 0 or not 4 <= d <= DEEPWALK_MAX_DIM:
+    raise _lib.GnpdeError('%s: the embedding width %d must be a multiple of 4 in 4 .. %d' % (who, d, DEEPWALK_MAX_DIM))
+  if (L + 1) * d + (L + 2 - C) * (C - 1) > DEEPWALK_LDS_FLOATS:
+    raise _lib.GnpdeError('%s: (walk_length + 1) * width + windows * (context_size - 1) = %d exceeds %d floats (64 KiB of LDS)'
+                          % (who, (L + 1) * d + (L + 2 - C) * (C - 1), DEEPWALK_LDS_FLOATS))
+
+
+def _state_rows(t, name):
+  if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+    raise _lib.GnpdeError('deepwalk_step: %s must be a float32 matrix' % name)
+  require_hip(t)
+  if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
+    raise _lib.GnpdeError('deepwalk_step: %s is updated in place: unit column stride, a row stride that is a multiple of 4 and '
+                          '16-byte alignment are required' % name)
+  return t
+
+
+def _walks_i32(rw, L, name):
+  if not isinstance(rw, torch.Tensor) or rw.dim() != 2 or rw.dtype not in (torch.int32, torch.int64):
+    raise _lib.GnpdeError('deepwalk_step: %s must be an int32 / int64 matrix [R, walk_length + 1]' % name)
+  require_hip(rw)
+  if L is not None and rw.shape[1] != L + 1:
+    raise _lib.GnpdeError('deepwalk_step: %s has %d columns, pos_rw has %d' % (name, rw.shape[1], L + 1))
+  rw = rw.detach().to(torch.int32)
+  return rw if rw.is_contiguous() else rw.contiguous()
+
+
+def deepwalk_workspace(r_pos, r_neg, walk_length, context_size, d, device):
+  need = int(_lib.lib().gnpde_deepwalk_step_workspace_bytes(int(r_pos), int(r_neg), int(walk_length), int(context_size), int(d)))
+  if need == 0:
+    raise _lib.GnpdeError('deepwalk_step: the workspace query failed (%s)'
+                          % (_lib.lib().gnpde_last_error().decode(errors='replace') or "the sort's temporary-storage query needs a device"))
+  return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def deepwalk_step(emb, m, v, t, pos_rw, neg_rw, context_size, lr=0.01, betas=(0.9, 0.999), eps=1e-8, *, loss_out=None, flag=None, workspace=None):
+  """One skip-gram-with-negative-sampling step with the SparseAdam update, in place on emb, m, v ([n, d] float32 on a HIP device;
+  emb may have padded rows): gnpde_deepwalk_step, include/gnpde.h has the definition.  pos_rw [R_pos, L + 1], neg_rw [R_neg, L + 1]:
+  the walks (int32 or int64).  t: the global step count from 1.  Returns the step's loss as a 0-d device tensor; nothing is read by
+  the host unless `flag` is None (then a walk entry outside [0, n) raises).  loss_out: a 1-element float32 device view to write
+  the loss to; workspace: a buffer from deepwalk_workspace to reuse."""
+  emb = _state_rows(emb, 'emb')
+  m, v = _state_rows(m, 'm'), _state_rows(v, 'v')
+  if m.shape != emb.shape or v.shape != emb.shape or m.stride(0) != v.stride(0):
+    raise _lib.GnpdeError('deepwalk_step: m and v must have the shape of emb and one row stride')
+  n, d = emb.shape
+  pos = _walks_i32(pos_rw, None, 'pos_rw')
+  L = pos.shape[1] - 1
+  neg = _walks_i32(neg_rw, L, 'neg_rw')
+  deepwalk_check_shape(L, context_size, d)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('deepwalk_step: n = %d outside 1 .. INT32_MAX' % n)
+  if pos.shape[0] < 1 or neg.shape[0] < 1:
+    raise _lib.GnpdeError('deepwalk_step: at least one positive and one negative walk are needed')
+  if not (emb.device == m.device == v.device == pos.device == neg.device):
+    raise _lib.GnpdeError('deepwalk_step: the tensors are on different devices')
+  if workspace is None:
+    workspace = deepwalk_workspace(pos.shape[0], neg.shape[0], L, context_size, d, emb.device)
+  own = flag is None
+  if own:
+    flag = torch.zeros(1, dtype=torch.int32, device=emb.device)
+  if loss_out is None:
+    loss_out = torch.empty(1, dtype=torch.float32, device=emb.device)
+  check(_lib.lib().gnpde_deepwalk_step(ptr(emb), emb.stride(0), ptr(m), ptr(v), m.stride(0), n, d, int(t), ptr(pos), pos.shape[0], ptr(neg),
+                                       neg.shape[0], L, int(context_size), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                       ptr(loss_out), ptr(flag), ptr(workspace), workspace.numel(), stream_of(emb)))
+  if own:
+    _raise_deepwalk_flags(flag, 'deepwalk_step')
+  return loss_out.reshape(())
+
+
 KNN_MAX_K = 128
 METRICS = {'sqeuclidean': _lib.METRIC_SQEUCLIDEAN, 'poincare': _lib.METRIC_POINCARE}
 

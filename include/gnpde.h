@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 14  /* 14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 15  /* 15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -903,6 +903,61 @@ size_t gnpde_select_edges_workspace_bytes(int64_t n_edges);
 int gnpde_select_edges(const int64_t* edge_index, const float* score, int64_t n_edges, const float* threshold,
                        int64_t* out_edge_index, int64_t* out_count, void* workspace, size_t workspace_bytes, void* stream);
 int gnpde_full_adjacency(int32_t n, int64_t* out_edge_index, void* stream);
+
+/* DeepWalk positional encodings (BLEND's `--pos_enc_type DW<d>`; reference src/deepwalk_embeddings.py: torch_geometric's Node2Vec
+ * with p = q = 1, sparse embedding, torch.optim.SparseAdam).  This header is the authority; PyG and torch_cluster are no dependency.
+ *
+ * Graph.  CSR over n nodes: rowptr [n + 1] and col [n_edges] int32.  The out-neighbours of u are the `dst` of the caller's edges
+ *   (u, dst), WITH multiplicity, ascending by dst (ops.walk_csr builds it).  A node of out-degree 0 stays where it is (torch_cluster).
+ * Random numbers.  The Philox4x32-10 streams defined above.  Stream ids 0 and 1 belong to the edge sampling; the trainer uses
+ *   16 (positive walks), 17 (negative walks) and 18 (epoch order).
+ * Positive walk w, step t (0 <= t < L = walk_length, 1 <= L <= 127):
+ *     word(w, t) = word (t & 3) of block  w * ceil(L / 4) + (t >> 2)  of stream (seed, stream_id, call)     (64-bit block number)
+ *     next = col[rowptr[cur] + ((word * deg(cur)) >> 32)]
+ *   out [n_walks, L + 1] int32, column 0 the start node.  Walk r of a call is w = first_walk + r and starts at starts[r % n_starts]
+ *   (PyG's batch.repeat): batches of one epoch draw from disjoint counter ranges.
+ * Negative walk: column 0 the start node, column t + 1 = (word(w, t) * n) >> 32, on a stream id of its own.
+ * Epoch order.  gnpde_random_permutation: out = the indices i in [0, n) sorted by the 64-bit key (word i of the stream) << 32 | i
+ *   (radix sort), int64.
+ * Epoch e, batch b of size B (the last may be short): the start of walk r is perm[b B + (r mod |batch|)], r < |batch| walks_per_node
+ *   positive and r < |batch| walks_per_node num_negative_samples negative walks; call = e; first_walk = b B walks_per_node for the
+ *   positive walks and that times num_negative_samples for the negative ones.
+ * Windows (C = context_size, walk_length >= C >= 2): J = L + 2 - C windows per walk; a walk contributes the position pairs (a, b)
+ *   with 0 <= a < J and a < b <= a + C - 1 -- the pairs (first column, other column) of PyG's cat([rw[:, j:j + C] for j in range(J)]).
+ * Loss of one step: x_ab = <e[rw[a]], e[rw[b]]>, EPS = 1e-15,
+ *     loss = mean over all positive pairs of -log(sigma(x) + EPS)  +  mean over all negative pairs of -log(sigma(-x) + EPS).
+ *   PyG writes the negative term as log(1 - sigma(x) + EPS); in fp32 that is log(EPS) once x > ~17.  The step follows the mathematics.
+ * Update (torch.optim.SparseAdam): g = the gradient summed per distinct touched row (a pair with rw[a] == rw[b] contributes to that
+ *   row twice); only touched rows change:  m <- m + (g - m)(1 - beta1),  v <- v + (g g - v)(1 - beta2),
+ *     e <- e - lr sqrt(1 - beta2^t) / (1 - beta1^t) * m / (sqrt(v) + eps),   t = the global step count from 1.
+ *   An untouched row keeps its e, m and v bit for bit.
+ * gnpde_deepwalk_step: emb [n, d] (row stride ld), m and v [n, d] (row stride ld_mv) float32, 16-byte aligned, strides multiples of 4;
+ *   pos_rw [r_pos, L + 1] and neg_rw [r_neg, L + 1] int32 (given, so that a test can feed walks); *loss_out (device float) = the loss.
+ *   One wave per walk stages the walk's rows in LDS and writes ONE contribution row per walk position with plain stores; a radix
+ *   sort of (node << 32 | slot) is the inverted index; per node the contribution rows are added in slot order.  No float atomics:
+ *   results are bit-identical from run to run.  Nothing is read by the host.
+ *   Limits (GNPDE_ESHAPE otherwise): d a multiple of 4 in 4 .. 256, L <= 127, 2 <= C <= L, (L + 1) d + J (C - 1) <= 16384 floats
+ *   (64 KiB of LDS: the rows and the pair coefficients), (r_pos + r_neg)(L + 1) <= INT32_MAX.
+ * `flag` is ONE device int32 that the kernels OR bits into; the caller zeroes it and reads it: a start node or a walk entry outside
+ *   [0, n) (it then counts as node 0), a rowptr / col entry outside the graph (the walk then stays).
+ * Everything runs on the caller's stream; argument errors return a code before any launch.  A workspace query returns 0 for
+ * arguments the entry point refuses. */
+#define GNPDE_DEEPWALK_BAD_START 1
+#define GNPDE_DEEPWALK_BAD_GRAPH 2
+#define GNPDE_DEEPWALK_BAD_WALK  4
+int gnpde_random_walks(const int32_t* rowptr, const int32_t* col, int64_t n_edges, int32_t n, const int64_t* starts, int64_t n_starts,
+                       int64_t n_walks, int32_t walk_length, uint64_t seed, uint32_t stream_id, uint32_t call, uint64_t first_walk,
+                       int32_t* out, int32_t* flag, void* stream);
+int gnpde_negative_walks(int32_t n, const int64_t* starts, int64_t n_starts, int64_t n_walks, int32_t walk_length, uint64_t seed,
+                         uint32_t stream_id, uint32_t call, uint64_t first_walk, int32_t* out, int32_t* flag, void* stream);
+size_t gnpde_random_permutation_workspace_bytes(int64_t n);
+int gnpde_random_permutation(int64_t n, uint64_t seed, uint32_t stream_id, uint32_t call, int64_t* out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+size_t gnpde_deepwalk_step_workspace_bytes(int64_t r_pos, int64_t r_neg, int32_t walk_length, int32_t context_size, int32_t d);
+int gnpde_deepwalk_step(float* emb, int32_t ld, float* m, float* v, int32_t ld_mv, int32_t n, int32_t d, int32_t t,
+                        const int32_t* pos_rw, int64_t r_pos, const int32_t* neg_rw, int64_t r_neg, int32_t walk_length,
+                        int32_t context_size, float lr, float beta1, float beta2, float eps, float* loss_out, int32_t* flag,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* Two-hop densification of the rewiring block (new_edges = 'k_hop_att', reference src/block_transformer_rewiring.py:68-86):
  *   S = coalesce(A ++ offdiag(A A)) / 2, i.e. torch_sparse.spspmm(A, A) -> remove_self_loops -> cat with A -> / 2 ->
