@@ -18,6 +18,7 @@
 // No PyTorch op runs inside the solve.  GRAND-l (constant weights) is the same without the attention steps.
 #include <vector>
 #include "common.h"
+#include "graph_capture.h"
 #include "rhs.h"
 #include "epilogue.h"
 
@@ -1128,8 +1129,7 @@ int enqueue_taped(gnpde_adjoint* s, float* a, float* grads, hipStream_t st) {
 }
 
 void drop_adjoint_graph(gnpde_adjoint* s) {
-  if (s->exec) { (void)hipGraphExecDestroy(s->exec); s->exec = nullptr; }
-  if (s->graph_obj) { (void)hipGraphDestroy(s->graph_obj); s->graph_obj = nullptr; }
+  drop_capture(&s->graph_obj, &s->exec);
   s->cap_y = s->cap_a = s->cap_g = nullptr;
 }
 
@@ -1232,21 +1232,8 @@ extern "C" int gnpde_adjoint_run(gnpde_adjoint_t* s, float* y, float* a, float* 
   if (!use_graph) return s->tape ? enqueue_taped(s, a, grads, st) : enqueue_adjoint(s, y, a, grads, st);
   if (s->exec == nullptr || s->cap_y != y || s->cap_a != a || s->cap_g != grads) {
     drop_adjoint_graph(s);
-    if (s->cap_stream == nullptr) GNPDE_HIP(hipStreamCreateWithFlags(&s->cap_stream, hipStreamNonBlocking));
-    GNPDE_HIP(hipStreamBeginCapture(s->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = s->tape ? enqueue_taped(s, a, grads, s->cap_stream) : enqueue_adjoint(s, y, a, grads, s->cap_stream);
-    hipGraph_t gobj = nullptr;
-    const hipError_t ec = hipStreamEndCapture(s->cap_stream, &gobj);
-    if (rc != 0) {
-      if (gobj) (void)hipGraphDestroy(gobj);
-      return rc;
-    }
-    if (ec != hipSuccess) {
-      set_error("adjoint_run: hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-      return static_cast<int>(ec);
-    }
-    s->graph_obj = gobj;
-    GNPDE_HIP(hipGraphInstantiate(&s->exec, s->graph_obj, nullptr, nullptr, 0));
+    auto enqueue = [&](hipStream_t cs) { return s->tape ? enqueue_taped(s, a, grads, cs) : enqueue_adjoint(s, y, a, grads, cs); };
+    if (int rc = capture_into(&s->cap_stream, &s->graph_obj, &s->exec, enqueue, "adjoint_run: ")) return rc;
     s->cap_y = y; s->cap_a = a; s->cap_g = grads;
   }
   GNPDE_HIP(hipGraphLaunch(s->exec, st));

@@ -12,42 +12,19 @@
 //                     per-wave dots <u_a, F_r>, <u_a, x0>;  aggregation on the transposed graph: V_r = alpha' (A^T u_a - u_a), epilogue: the same for a
 //     2 x error norm  block partial sums of ((sum_j e_j h K_j) / (atol + rtol max(|.|, |.1|)))^2 for y and for a
 //     control         folds the partial sums and every stage's dots; the scalars' step g1 = g + h sum_j c_j Ks_j, error and mid point; mixed
-//                     norm = the largest component rms (misc.py _mixed_norm: y, a and each scalar a component of its own); accept / reject; t, dt
-//                     (float64, misc.py _optimal_step_size); end point reached -> interpolation fraction, the scalars interpolated
+//                     norm = the largest component rms (misc.py _mixed_norm: y, a and each scalar a component of its own); the decision of
+//                     embedded_pair.h (step_decide, the same as the forward solve's); end point reached -> the scalars interpolated
 //     finish          commit of a rejected step (an accepted one costs nothing: two buffer parities alternate), the quartic end-point
 //                     interpolation of a (interp.py), the next trial step's first stage inputs
 // The host replays the graph and reads a 128-byte record once per batch of trial steps, exactly like gnpde_dopri5_run.
 #include <cmath>
 #include "common.h"
+#include "embedded_pair.h"
+#include "graph_capture.h"
 #include "rhs.h"
 
 namespace gnpde {
 namespace {
-
-constexpr int kMaxStages = 6;
-
-// embedded pairs of torchdiffeq 0.2.1 (adaptive_heun.py, dopri5.py): stage weights a[r] = weights of the input of stage r + 1 (row S - 1 of a
-// first-same-as-last pair is the solution), solution / error / mid-point weights over K_0..K_S
-struct Tableau {
-  int S, fsal, order;
-  double a[kMaxStages][kMaxStages];
-  double c_sol[kMaxStages + 1], c_err[kMaxStages + 1], c_mid[kMaxStages + 1];
-};
-
-const Tableau kHeun = {1, 0, 2, {{1.0}}, {0.5, 0.5}, {0.5, -0.5}, {0.5, 0.0}};
-const Tableau kDopri5 = {
-  6, 1, 5,
-  {{1.0 / 5},
-   {3.0 / 40, 9.0 / 40},
-   {44.0 / 45, -56.0 / 15, 32.0 / 9},
-   {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729},
-   {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656},
-   {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}},
-  {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0.0},
-  {35.0 / 384 - 1951.0 / 21600, 0.0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720, -2187.0 / 6784 + 12231.0 / 42400,
-   11.0 / 84 - 649.0 / 6300, -1.0 / 60},
-  {6025192743.0 / 30085553152.0 / 2, 0.0, 51252292925.0 / 65400821598.0 / 2, -2691868925.0 / 45128329728.0 / 2,
-   187940372067.0 / 1594534317056.0 / 2, -1776094331.0 / 19743644256.0 / 2, 11237099.0 / 235043384.0 / 2}};
 
 struct HCtl {             // controller record (device; copied to the host once per batch)
   double t, dt, t1;
@@ -75,34 +52,6 @@ struct HCtlArgs {
   int parity;
 };
 
-__device__ __forceinline__ float quartic(float y0, float y1, float f0, float f1, float ym, float h, float x) {
-  const float ca = 2.0f * h * (f1 - f0) - 8.0f * (y1 + y0) + 16.0f * ym;
-  const float cb = h * (5.0f * f0 - 3.0f * f1) + 18.0f * y0 + 14.0f * y1 - 32.0f * ym;
-  const float cc = h * (f1 - 4.0f * f0) - 11.0f * y0 - 5.0f * y1 + 16.0f * ym;
-  const float cd = h * f0;
-  float tot = y0 + x * cd;
-  float xp = x * x;
-  tot += xp * cc;
-  xp *= x;
-  tot += xp * cb;
-  xp *= x;
-  tot += xp * ca;
-  return tot;
-}
-
-// sum over the block, every thread gets it
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double out = red[0];
-  __syncthreads();
-  return out;
-}
-
 // Ks of one evaluation from the per-wave dots: ((1 - alpha') (<u_a, F> - beta <u_a, x0>), <u_a, x0>)
 __device__ __forceinline__ void scalars_of(double d1, double d2, const float* alpha, int sig, const float* beta, float (&ks)[2]) {
   const float a = sig ? 1.0f / (1.0f + expf(-*alpha)) : *alpha;
@@ -117,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void adaptive_init_kernel(const float* __re
   __shared__ double red[kBlock];
   double a1 = 0.0, a2 = 0.0;
   for (long long i = threadIdx.x; i < n_pairs; i += kBlock) { a1 += dots[2 * i]; a2 += dots[2 * i + 1]; }
-  const double d1 = block_sum(a1, red), d2 = block_sum(a2, red);
+  const double d1 = block_sum_double(a1, red), d2 = block_sum_double(a2, red);
   if (threadIdx.x != 0) return;
   float ks[2];
   scalars_of(d1, d2, alpha, sig, beta, ks);
@@ -129,8 +78,8 @@ __global__ __launch_bounds__(kBlock) void adaptive_init_kernel(const float* __re
   for (int j = 0; j < 2; ++j) { c->g[0][j] = g_in[j]; c->g[1][j] = g_in[j]; c->ks[0][j] = ks[j]; c->ks[1][j] = ks[j]; c->g_out[j] = g_in[j]; }
 }
 
-// The controller's arithmetic for one trial step (torchdiffeq rk_common.py _adaptive_step / misc.py _optimal_step_size and _mixed_norm over
-// the components y, a and each scalar of its own), from the folded sums `tot` = (sum err_y^2, sum err_a^2, then per new stage the dots
+// The controller's arithmetic for one trial step (torchdiffeq misc.py _mixed_norm over the components y, a and each scalar of its own, then
+// step_decide of embedded_pair.h), from the folded sums `tot` = (sum err_y^2, sum err_a^2, then per new stage the dots
 // <u_a, F>, <u_a, x0>).  L: the record this trial step started from; returns the record of the next one.  Registers and compile-time
 // indices only (round 5: the first version read and wrote the record field by field through its pointer and cost 32 us).
 template <int S>
@@ -176,33 +125,22 @@ __device__ __forceinline__ HCtl control_decide(const HCtl& L, const double* tot,
     const float ry = static_cast<float>(sqrt(tot[0] / a.count)), ra = static_cast<float>(sqrt(tot[1] / a.count));
     const float ratio32 = fmaxf(fmaxf(ry, ra), rs);
     N.ratio = ratio32;
-    const double ratio = static_cast<double>(ratio32);
-    const double dt = L.dt;
+    const StepDecision dec = step_decide(L.t, L.dt, L.t1, ratio32, a.order);
+    const int accept = dec.accept, interp = dec.done;
     N.trials = L.trials + 1;
-    int accept = 0, interp = 0;
-    if (ratio <= 1.0) {
-      const double t_next = L.t + dt;
-      if (t_next >= L.t1) {
-        N.x = static_cast<float>((L.t1 - L.t) / (t_next - L.t));
-        interp = 1;
+    if (accept) {
+      if (interp) {
+        N.x = dec.x;
         N.done = 1;
 #pragma unroll
         for (int j = 0; j < 2; ++j) N.g_out[j] = quartic(g0[j], g1[j], ks[0][j], ks[S][j], gm[j], h, N.x);
       }
-      N.t = t_next;
-      accept = 1;
+      N.t = dec.t_next;
       N.accepted = L.accepted + 1;
     } else {
       N.rejected = L.rejected + 1;
     }
-    double factor;
-    if (ratio == 0.0) {
-      factor = 10.0;
-    } else {
-      const double lo = ratio < 1.0 ? 1.0 : 0.2;
-      factor = fmin(10.0, fmax(0.9 / pow(ratio, 1.0 / a.order), lo));
-    }
-    N.dt = dt * factor;
+    N.dt = dec.dt_next;
     h_next = static_cast<float>(N.dt);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -418,17 +356,6 @@ __global__ __launch_bounds__(kBlock) void adaptive_finish2_kernel(const HCtlArgs
   }
 }
 
-__global__ __launch_bounds__(kBlock) void adaptive_copy_rows_kernel(const float* __restrict__ src, int ld_src, float* __restrict__ dst, int ld_dst,
-                                                                   long long n, int d) {
-  const long long total = n * d;
-  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
-       i += static_cast<long long>(gridDim.x) * blockDim.x) {
-    const long long r = i / d;
-    const int c = static_cast<int>(i - r * d);
-    dst[static_cast<size_t>(r) * ld_dst + c] = src[static_cast<size_t>(r) * ld_src + c];
-  }
-}
-
 __global__ void adaptive_store_g_kernel(const HCtl* c, float* g) {
   g[0] = c->g_out[0];
   g[1] = c->g_out[1];
@@ -462,10 +389,6 @@ struct gnpde_adjoint_adaptive {
 };
 
 namespace {
-
-const Tableau* tableau_of(int method) {
-  return method == GNPDE_ADAPTIVE_HEUN ? &kHeun : method == GNPDE_ADAPTIVE_DOPRI5 ? &kDopri5 : nullptr;
-}
 
 size_t adaptive_layout(const gnpde_rhs_t& r, const gnpde_rhs_t& rb, const Tableau& tab, gnpde_adjoint_adaptive* s) {
   const size_t state = align_up(static_cast<size_t>(r.graph->n) * r.ld * 4, 256);
@@ -689,13 +612,8 @@ extern "C" int gnpde_adjoint_adaptive_run(gnpde_adjoint_adaptive_t* s, const flo
     GNPDE_HIP(hipMemsetAsync(s->ws + s->off_state, 0, static_cast<size_t>(s->n_state) * s->state_bytes, st));
     s->cleared = true;
   }
-  long long cb = (n * r.d + kBlock - 1) / kBlock;
-  if (cb > 8192) cb = 8192;
-  if (cb < 1) cb = 1;
-  hipLaunchKernelGGL(adaptive_copy_rows_kernel, dim3(static_cast<unsigned>(cb)), dim3(kBlock), 0, st, y, ld_y, s->Y[0], r.ld, n, r.d);
-  GNPDE_LAUNCH_CHECK();
-  hipLaunchKernelGGL(adaptive_copy_rows_kernel, dim3(static_cast<unsigned>(cb)), dim3(kBlock), 0, st, a, ld_a, s->A[0], r.ld, n, r.d);
-  GNPDE_LAUNCH_CHECK();
+  if (int rc = launch_copy_rows(y, ld_y, s->Y[0], r.ld, n, r.d, st)) return rc;
+  if (int rc = launch_copy_rows(a, ld_a, s->A[0], r.ld, n, r.d, st)) return rc;
   // the derivative at the start (torchdiffeq: f0 of _before_integrate), the controller record, the first stage inputs
   if (int rc = enqueue_eval(s, s->Y[0], s->A[0], s->KFp[0], s->KVp[0], 0, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st))
     return rc;
@@ -715,34 +633,18 @@ extern "C" int gnpde_adjoint_adaptive_run(gnpde_adjoint_adaptive_t* s, const flo
   for (int which = 0; which < 4; ++which) {
     if (s->exec[which] != nullptr) continue;
     const int parity = which & 1;
-    if (s->cap_stream == nullptr) GNPDE_HIP(hipStreamCreateWithFlags(&s->cap_stream, hipStreamNonBlocking));
-    GNPDE_HIP(hipStreamBeginCapture(s->cap_stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_trial(s, parity, s->cap_stream);
-    if (rc == 0 && which >= 2) rc = enqueue_trial(s, 1 - parity, s->cap_stream);      // two trial steps per launch: half the launch gaps
-    hipGraph_t gobj = nullptr;
-    const hipError_t ec = hipStreamEndCapture(s->cap_stream, &gobj);
-    if (rc != 0) {
-      if (gobj) (void)hipGraphDestroy(gobj);
+    auto enqueue = [&](hipStream_t cs) {
+      int rc = enqueue_trial(s, parity, cs);
+      if (rc == 0 && which >= 2) rc = enqueue_trial(s, 1 - parity, cs);      // two trial steps per launch: half the launch gaps
       return rc;
-    }
-    if (ec != hipSuccess) {
-      set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-      return static_cast<int>(ec);
-    }
-    s->graph_obj[which] = gobj;
-    GNPDE_HIP(hipGraphInstantiate(&s->exec[which], gobj, nullptr, nullptr, 0));
+    };
+    if (int rc = capture_into(&s->cap_stream, &s->graph_obj[which], &s->exec[which], enqueue)) return rc;
   }
   bool have_record = false;
   for (;;) {
-    // as gnpde_dopri5_run: queue as many trial steps as cannot pass s1 even if each were accepted with the largest growth (x 10)
+    // as gnpde_dopri5_run: as many trial steps as cannot pass s1 (plan_batch, embedded_pair.h), then one read of the record
     const HCtl& hc = *s->host_ctl;
-    int batch = 1;
-    double reach = hc.dt, step = hc.dt;
-    while (have_record && batch < trials_per_sync && hc.t + reach < hc.t1) {
-      step *= 10.0;
-      reach += step;
-      ++batch;
-    }
+    const int batch = plan_batch(hc.t, hc.dt, hc.t1, trials_per_sync, have_record);
     for (int b = 0; b < batch;) {
       const int par = (s->n_launches + b) & 1;
       if (batch - b >= 2) { GNPDE_HIP(hipGraphLaunch(s->exec[2 + par], st)); b += 2; }
@@ -761,8 +663,7 @@ extern "C" int gnpde_adjoint_adaptive_run(gnpde_adjoint_adaptive_t* s, const flo
     GNPDE_CHECK_ARG(hc.t + hc.dt > hc.t, GNPDE_EINVAL, "adjoint_adaptive_run: underflow in dt %g at s %g", hc.dt, hc.t);
     if (max_evals > 0 && s->n_evals > max_evals) return 0;   // *finished stays 0
   }
-  hipLaunchKernelGGL(adaptive_copy_rows_kernel, dim3(static_cast<unsigned>(cb)), dim3(kBlock), 0, st, s->AOUT, r.ld, a, ld_a, n, r.d);
-  GNPDE_LAUNCH_CHECK();
+  if (int rc = launch_copy_rows(s->AOUT, r.ld, a, ld_a, n, r.d, st)) return rc;
   hipLaunchKernelGGL(adaptive_store_g_kernel, dim3(1), dim3(1), 0, st, s->ctl + (s->n_launches & 1), g);
   GNPDE_LAUNCH_CHECK();
   if (finished) *finished = 1;
@@ -772,20 +673,13 @@ extern "C" int gnpde_adjoint_adaptive_run(gnpde_adjoint_adaptive_t* s, const flo
 extern "C" int gnpde_adjoint_adaptive_stats(const gnpde_adjoint_adaptive_t* s, int32_t* n_evals, int32_t* n_accepted, int32_t* n_rejected,
                                             int32_t* n_launches, int32_t* n_syncs) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "adjoint_adaptive_stats: solver is null");
-  if (n_evals) *n_evals = s->n_evals;
-  if (n_accepted) *n_accepted = s->n_accepted;
-  if (n_rejected) *n_rejected = s->n_rejected;
-  if (n_launches) *n_launches = s->n_launches;
-  if (n_syncs) *n_syncs = s->n_syncs;
+  store_stats(s, n_evals, n_accepted, n_rejected, n_launches, n_syncs);
   return 0;
 }
 
 extern "C" int gnpde_adjoint_adaptive_destroy(gnpde_adjoint_adaptive_t* s) {
   if (!s) return 0;
-  for (int p = 0; p < 4; ++p) {
-    if (s->exec[p]) (void)hipGraphExecDestroy(s->exec[p]);
-    if (s->graph_obj[p]) (void)hipGraphDestroy(s->graph_obj[p]);
-  }
+  for (int p = 0; p < 4; ++p) drop_capture(&s->graph_obj[p], &s->exec[p]);
   if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
   if (s->host_ctl) (void)hipHostFree(s->host_ctl);
   delete s;

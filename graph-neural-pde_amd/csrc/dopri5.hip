@@ -8,8 +8,8 @@
 //     5 x f         k_i = f(u_i), the epilogue forms u_{i+1} = y + sum_j (b_ij h) k_j      (u_6 = y1; coef_scale -> h)
 //     f             k6 = f(y1)                                                              (first-same-as-last)
 //     error norm    block partial sums of ((sum_j e_j h k_j) / (atol + rtol max(|y|, |y1|)))^2
-//     control       fold -> ratio; accept = ratio <= 1; t += dt; end point reached -> interpolation fraction, done;
-//                   dt *= factor (float64); h' = fl32(dt) for the next trial step
+//     control       fold -> ratio; the decision of embedded_pair.h (step_decide: accept, end point reached -> interpolation fraction
+//                   and done, t, dt in float64); h' = fl32(dt) for the next trial step
 //     finish        (end point in this step) y_out = quartic through y, y1, y_mid, k0, k6 at t1;
 //                   u_1 = y' + (b10 h') k0' of the NEXT trial step, (y', k0') = (y1, k6) if accepted else (y, k0)
 // The graph exists in two parities that the host launches in turn: h and h' alternate between two slots of the record, and so
@@ -21,25 +21,12 @@
 #include <cmath>
 #include <vector>
 #include "common.h"
+#include "embedded_pair.h"
+#include "graph_capture.h"
 #include "rhs.h"
 
 namespace gnpde {
 namespace {
-
-// Dormand-Prince 5(4) as torchdiffeq 0.2.1 writes it (dopri5.py): stage weights, error weights (5th - 4th order solution,
-// Shampine's variant), mid-point weights of the quartic interpolant
-const double kB[6][6] = {
-  {1.0 / 5, 0, 0, 0, 0, 0},
-  {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-  {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-  {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-  {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-  {35.0 / 384, 0.0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
-const double kE[7] = {35.0 / 384 - 1951.0 / 21600, 0.0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
-                      -2187.0 / 6784 + 12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60};
-const double kMid[7] = {6025192743.0 / 30085553152.0 / 2, 0.0, 51252292925.0 / 65400821598.0 / 2,
-                        -2691868925.0 / 45128329728.0 / 2, 187940372067.0 / 1594534317056.0 / 2,
-                        -1776094331.0 / 19743644256.0 / 2, 11237099.0 / 235043384.0 / 2};
 
 struct Ctl {            // the controller record (device; copied to the host once per batch of trial steps)
   double t, dt, t1;
@@ -59,21 +46,16 @@ struct Ctl {            // the controller record (device; copied to the host onc
 };
 static_assert(sizeof(Ctl) == 96, "controller record");
 
-// fold of the error partial sums (as rk_error_final_kernel of misc.hip) + torchdiffeq rk_common.py _adaptive_step /
-// _optimal_step_size: safety 0.9, ifactor 10, dfactor 0.2, order 5
+// fold of the error partial sums (as rk_error_final_kernel of misc.hip) + the controller's decision (embedded_pair.h); around it what is
+// this solve's own: the no-op past the end point, the counters, the trial budget and the gate of the evaluator kernels
 __global__ __launch_bounds__(kBlock) void control_kernel(const double* __restrict__ ws, int nblocks, double count, Ctl* c,
-                                                        int parity, double* __restrict__ times, int times_capacity, double inv_order) {
+                                                        int parity, double* __restrict__ times, int times_capacity, int order) {
   __shared__ double red[kBlock];
   double acc = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += kBlock) acc += ws[i];      // block partials in double (misc.hip, rk_error_partial_kernel)
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  const double sum = block_sum_double(acc, red);
   if (threadIdx.x != 0) return;
-  const float ratio32 = static_cast<float>(sqrt(red[0] / count));
+  const float ratio32 = static_cast<float>(sqrt(sum / count));
   c->ratio = ratio32;
   if (c->done) {                      // replayed past the end point (never queued by gnpde_dopri5_run): change nothing
     c->accept = 0;
@@ -82,32 +64,22 @@ __global__ __launch_bounds__(kBlock) void control_kernel(const double* __restric
     c->h[1 - parity] = c->h[parity];
     return;
   }
-  const double ratio = static_cast<double>(ratio32);
-  const double dt = c->dt;
+  const StepDecision dec = step_decide(c->t, c->dt, c->t1, ratio32, order);
   c->trials += 1;
-  int accept = 0, interp = 0;
-  if (ratio <= 1.0) {
-    const double t_next = c->t + dt;
-    if (t_next >= c->t1) {
-      c->x = static_cast<float>((c->t1 - c->t) / (t_next - c->t));
-      interp = 1;
+  const int accept = dec.accept;
+  int interp = dec.done;
+  if (accept) {
+    if (dec.done) {
+      c->x = dec.x;
       c->done = 1;
     }
-    c->t = t_next;
-    accept = 1;
+    c->t = dec.t_next;
     c->accepted += 1;
   } else {
     c->rejected += 1;
   }
-  double factor;
-  if (ratio == 0.0) {
-    factor = 10.0;
-  } else {
-    const double lo = ratio < 1.0 ? 1.0 : 0.2;
-    factor = fmin(10.0, fmax(0.9 / pow(ratio, inv_order), lo));     // (1 / order: 0.2 for dopri5, 0.5 for the Heun pair)
-  }
-  c->dt = dt * factor;
-  c->h[1 - parity] = static_cast<float>(c->dt);
+  c->dt = dec.dt_next;
+  c->h[1 - parity] = static_cast<float>(dec.dt_next);
   // early stopping: which state the evaluator kernels behind this trial step see.  Accepted: the new state, tagged with the
   // number of accepted steps (its time goes to times[tag]).  Rejected: the unchanged previous state -- counted already, it
   // cannot win the strict `val > best` -- except before the first accept, when it is the INITIAL state (tag 0), once.
@@ -145,7 +117,7 @@ __global__ void init_h0_kernel(Init* q) {
   q->h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6f : 0.01f * q->d0 / q->d1;
 }
 
-__global__ void init_dt_kernel(const Init* q, Ctl* c, double t0, double t1, int max_trials, double* times, int times_capacity, float inv_order) {
+__global__ void init_dt_kernel(const Init* q, Ctl* c, double t0, double t1, int max_trials, double* times, int times_capacity, int order) {
   const double h0 = static_cast<double>(q->h0), d1 = static_cast<double>(q->d1);
   const double d2 = static_cast<double>(q->d2) / h0;
   double h1;
@@ -153,7 +125,7 @@ __global__ void init_dt_kernel(const Init* q, Ctl* c, double t0, double t1, int 
     h1 = fmax(1e-6, h0 * 1e-3);
   } else {
     const float big = static_cast<float>(fmax(d1, d2));
-    h1 = static_cast<double>(static_cast<float>(pow(static_cast<double>(0.01f / big), static_cast<double>(inv_order))));
+    h1 = static_cast<double>(static_cast<float>(pow(static_cast<double>(0.01f / big), static_cast<double>(1.0f / order))));
   }
   c->t = t0;
   c->t1 = t1;
@@ -169,19 +141,7 @@ __global__ void init_dt_kernel(const Init* q, Ctl* c, double t0, double t1, int 
   if (times != nullptr && times_capacity > 0) times[0] = t0;
 }
 
-// dst[r, 0:d] = src[r, 0:d] between two row strides (state in / result out; a pitched hipMemcpy2D is far slower)
-__global__ __launch_bounds__(kBlock) void copy_rows_kernel(const float* __restrict__ src, int ld_src, float* __restrict__ dst,
-                                                          int ld_dst, long long n, int d) {
-  const long long total = n * d;
-  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
-       i += static_cast<long long>(gridDim.x) * blockDim.x) {
-    const long long r = i / d;
-    const int c = static_cast<int>(i - r * d);
-    dst[static_cast<size_t>(r) * ld_dst + c] = src[static_cast<size_t>(r) * ld_src + c];
-  }
-}
-
-// the same copy through a row map: gather != 0: dst[r] = src[map[r]] (state in: solver row r holds the caller's row map[r]);
+// the row copy of misc.hip (launch_copy_rows) through a row map: gather != 0: dst[r] = src[map[r]] (state in: solver row r holds the caller's row map[r]);
 // gather == 0: dst[map[r]] = src[r] (result out).  Folds the node relabelling of graph.LocalityView into the two copies a solve makes
 // anyway (two index_select launches, a state-sized temporary and their host gaps per forward otherwise).
 __global__ __launch_bounds__(kBlock) void copy_rows_map_kernel(const float* __restrict__ src, int ld_src, float* __restrict__ dst, int ld_dst,
@@ -210,7 +170,7 @@ struct FinishArgs {
   int parity;
 };
 
-// torchdiffeq's quartic end-point interpolation (_interp_fit + _interp_evaluate, as dopri5_interp_kernel of misc.hip), the commit
+// torchdiffeq's quartic end-point interpolation (embedded_pair.h, as dopri5_interp_kernel of misc.hip), the commit
 // of an accepted step and the first stage input of the next trial step, one pass over the state
 __global__ __launch_bounds__(kBlock) void finish_kernel(const FinishArgs a) {
   const int accept = a.c->accept, interp = a.c->interp, stopped = a.c->stopped;
@@ -239,18 +199,7 @@ __global__ __launch_bounds__(kBlock) void finish_kernel(const FinishArgs a) {
         const float m = j < a.n_k ? a.mid[j] * h : 0.0f;
         if (m != 0.0f) ym += reinterpret_cast<const f4*>(a.k[j])[i] * m;
       }
-      const f4 ca = 2.0f * h * (fb - fa) - 8.0f * (yb + ya) + 16.0f * ym;
-      const f4 cb = h * (5.0f * fa - 3.0f * fb) + 18.0f * ya + 14.0f * yb - 32.0f * ym;
-      const f4 cc = h * (fb - 4.0f * fa) - 11.0f * ya - 5.0f * yb + 16.0f * ym;
-      const f4 cd = h * fa;
-      f4 tot = ya + x * cd;
-      float xp = x * x;
-      tot += xp * cc;
-      xp *= x;
-      tot += xp * cb;
-      xp *= x;
-      tot += xp * ca;
-      reinterpret_cast<f4*>(a.yout)[i] = tot;
+      reinterpret_cast<f4*>(a.yout)[i] = quartic(ya, yb, fa, fb, ym, h, x);
     }
     const f4 yn = accept ? yb : ya, fn = accept ? fb : fa;
     if (stopped) reinterpret_cast<f4*>(a.yout)[i] = yn;     // trial budget spent: the state where the integration stopped
@@ -310,13 +259,8 @@ __global__ __launch_bounds__(kBlock) void tape_dots_partial_kernel(const float* 
     const float2 v = reinterpret_cast<const float2*>(dots)[i];
     acc += static_cast<double>(v.x) - static_cast<double>(v.y);
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  const double sum = block_sum_double(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kTapeFoldBlocks) void tape_dots_fold_kernel(const double* __restrict__ part, float* __restrict__ out) {
@@ -416,58 +360,48 @@ int enqueue_trial(gnpde_dopri5* s, int parity, hipStream_t st) {
   const float* h = &s->ctl->h[parity];
   float* y = s->Y[parity];
   float* y1 = s->Y[1 - parity];
-  float* k[7] = {s->KA[parity], s->km[0], s->km[1], s->km[2], s->km[3], s->km[4], s->KA[1 - parity]};
+  const Tableau& tab = *tableau_of(s->pair);
+  const int S = tab.S, n_k = S + 1;
+  float* k[7];                          // K_0 (carried over), the middle stages, K_S (carried on); entries past S repeat K_S
+  k[0] = s->KA[parity];
+  for (int j = 1; j < 7; ++j) k[j] = j < S ? s->km[j - 1] : s->KA[1 - parity];
   // stage inputs u_1..u_5: two alternating buffers -- or, when the solve is recorded, five distinct ones that survive the trial step
   float* ui[5] = {s->u[0], s->u[1], s->u[0], s->u[1], s->u[0]};
   if (s->tape != nullptr) { ui[2] = s->tape_x[0]; ui[3] = s->tape_x[1]; ui[4] = s->tape_x[2]; }
-  const bool heun = s->pair == GNPDE_ADAPTIVE_HEUN;
-  int n_k = 7;
   float ce[7], cmid[7];
-  for (int j = 0; j < 7; ++j) { ce[j] = static_cast<float>(kE[j]); cmid[j] = static_cast<float>(kMid[j]); }
-  if (heun) {
-    // torchdiffeq 0.2.1's adaptive_heun (adaptive_heun.py: alpha (1), beta ((1)), c_sol (1/2, 1/2), c_error (1/2, -1/2), c_mid (1/2, 0)):
-    // ONE evaluation per trial step, k1 = f(u_1) with u_1 = y + h k0, whose epilogue forms y1 = y + h (k0 + k1) / 2; the next step's
-    // first derivative is k1 (rk_common.py takes f1 = k[..., -1] for every pair, also this one, whose last stage is not the solution)
-    n_k = 2;
-    for (int j = 1; j < 7; ++j) k[j] = s->KA[1 - parity];
-    for (int j = 0; j < 7; ++j) { ce[j] = 0.f; cmid[j] = 0.f; }
-    ce[0] = 0.5f; ce[1] = -0.5f; cmid[0] = 0.5f;
-    gnpde_epilogue_t e = base_epilogue(r);
-    e.stage = GNPDE_STAGE_LINCOMB;
-    e.y = y;
-    e.out_k = k[1];
-    e.out_y = y1;
-    e.n_prev = 1;
-    e.prev[0] = k[0];
-    e.coef[0] = 0.5f; e.coef[1] = 0.5f;
-    e.coef_scale = h;
-    if (int rc = enqueue_f(s, s->u[0], e, st)) return rc;
-  }
-  for (int i = 1; i < 6 && !heun; ++i) {       // (u_1 = y + (b10 h) k0 was written by the previous trial step's finish kernel)
-    gnpde_epilogue_t e = base_epilogue(r);
-    e.stage = GNPDE_STAGE_LINCOMB;
-    e.y = y;
-    e.out_k = k[i];
-    e.out_y = i == 5 ? y1 : ui[i];
-    // (earlier derivatives with a zero weight -- k1 in the solution row -- are not streamed: fma(k, 0, o) = o for every finite k)
-    int np = 0;
-    for (int j = 0; j < i; ++j) {
-      const float c = static_cast<float>(kB[i][j]);
-      if (c == 0.0f) continue;
-      e.prev[np] = k[j];
-      e.coef[np] = c;
-      ++np;
-    }
-    e.n_prev = np;
-    e.coef[np] = static_cast<float>(kB[i][i]);
-    e.coef_scale = h;
-    if (int rc = enqueue_f(s, ui[i - 1], e, st)) return rc;
-  }
-  if (!heun) {
+  for (int j = 0; j < 7; ++j) { ce[j] = static_cast<float>(tab.c_err[j]); cmid[j] = static_cast<float>(tab.c_mid[j]); }
+  // (u_1 = y + (a00 h) k0 was written by the previous trial step's finish kernel)
+  float* cur = s->u[0];
+  for (int rr = 1; rr <= S; ++rr) {
     gnpde_epilogue_t e = base_epilogue(r);
     e.stage = GNPDE_STAGE_RHS;
-    e.out_k = k[6];
-    if (int rc = enqueue_f(s, y1, e, st)) return rc;
+    e.out_k = k[rr];
+    const double* w = nullptr;          // weights of the state this evaluation's epilogue forms from K_0..K_rr, if any
+    if (rr < S) {                       // the input of stage rr + 1 (of a first-same-as-last pair the last one IS the solution)
+      w = tab.a[rr];
+      e.out_y = tab.fsal && rr == S - 1 ? y1 : ui[rr];
+    } else if (!tab.fsal) {             // the solution from every stage derivative
+      w = tab.c_sol;
+      e.out_y = y1;
+    }
+    if (w != nullptr) {
+      e.stage = GNPDE_STAGE_LINCOMB;
+      e.y = y;
+      // (earlier derivatives with a zero weight -- k1 in the solution row -- are not streamed: fma(k, 0, o) = o for every finite k)
+      int np = 0;
+      for (int j = 0; j < rr; ++j) {
+        const float c = static_cast<float>(w[j]);
+        if (c == 0.0f) continue;
+        e.prev[np] = k[j];
+        e.coef[np] = c;
+        ++np;
+      }
+      e.n_prev = np;
+      e.coef[np] = static_cast<float>(w[rr]);
+      e.coef_scale = h;
+    }
+    if (int rc = enqueue_f(s, cur, e, st)) return rc;
+    if (w != nullptr) cur = e.out_y;
   }
   int nblocks = 0;
   if (int rc = launch_rk_error_ratio(y, y1, k, ce, n_k, s->atol, s->rtol, n, r.d, r.ld, nullptr, s->err_ws, st, h, &nblocks))
@@ -477,7 +411,7 @@ int enqueue_trial(gnpde_dopri5* s, int parity, hipStream_t st) {
     nblocks = 1;
   }
   hipLaunchKernelGGL(control_kernel, dim3(1), dim3(kBlock), 0, st, reinterpret_cast<const double*>(s->err_ws), nblocks, s->count, s->ctl, parity,
-                     s->early ? s->times : nullptr, s->early ? s->times_capacity : 0, heun ? 0.5 : 0.2);
+                     s->early ? s->times : nullptr, s->early ? s->times_capacity : 0, tab.order);
   GNPDE_LAUNCH_CHECK();
   if (s->tape != nullptr) {
     TapeArgs ta{};
@@ -499,8 +433,8 @@ int enqueue_trial(gnpde_dopri5* s, int parity, hipStream_t st) {
     fa.k[j] = k[j];
     fa.mid[j] = cmid[j];
   }
-  fa.n_k = n_k; fa.last = n_k - 1;
-  fa.b10 = heun ? 1.0f : static_cast<float>(kB[0][0]);
+  fa.n_k = n_k; fa.last = S;
+  fa.b10 = static_cast<float>(tab.a[0][0]);
   fa.n = n; fa.d = r.d; fa.ld = r.ld; fa.c = s->ctl; fa.parity = parity;
   long long blocks = (n * r.ld / 4 + kBlock - 1) / kBlock;
   if (blocks > 4096) blocks = 4096;
@@ -675,15 +609,16 @@ extern "C" int gnpde_dopri5_run(gnpde_dopri5_t* s, const float* y0, int32_t ld_y
     GNPDE_HIP(hipMemsetAsync(s->ws + s->off_state, 0, (s->shard != nullptr ? 8 : 12) * s->state_bytes, st));
     s->padding_cleared = true;
   }
-  long long copy_blocks = (static_cast<long long>(n) * r.d + kBlock - 1) / kBlock;
-  if (copy_blocks > 8192) copy_blocks = 8192;
-  if (s->row_order != nullptr)
-    hipLaunchKernelGGL(copy_rows_map_kernel, dim3(static_cast<unsigned>(copy_blocks)), dim3(kBlock), 0, st, y0, ld_y0, s->Y[0], r.ld,
-                       static_cast<long long>(n), r.d, s->row_order, 1);
-  else
-    hipLaunchKernelGGL(copy_rows_kernel, dim3(static_cast<unsigned>(copy_blocks)), dim3(kBlock), 0, st, y0, ld_y0, s->Y[0], r.ld,
-                       static_cast<long long>(n), r.d);
-  GNPDE_LAUNCH_CHECK();
+  const Tableau& tab = *tableau_of(s->pair);
+  // state in / result out: dst rows = src rows, through the row map if one is set
+  auto copy_rows = [&](const float* src, int ld_src, float* dst, int ld_dst, int gather) -> int {
+    if (s->row_order == nullptr) return launch_copy_rows(src, ld_src, dst, ld_dst, n, r.d, st);
+    hipLaunchKernelGGL(copy_rows_map_kernel, dim3(copy_rows_grid(n, r.d)), dim3(kBlock), 0, st, src, ld_src, dst, ld_dst,
+                       static_cast<long long>(n), r.d, s->row_order, gather);
+    GNPDE_LAUNCH_CHECK();
+    return 0;
+  };
+  if (int rc = copy_rows(y0, ld_y0, s->Y[0], r.ld, 1)) return rc;
   auto feval = [&](float* src, float* dst) -> int {
     gnpde_epilogue_t e = base_epilogue(r);
     e.stage = GNPDE_STAGE_RHS;
@@ -708,43 +643,23 @@ extern "C" int gnpde_dopri5_run(gnpde_dopri5_t* s, const float* y0, int32_t ld_y
     const float cw[2] = {one, minus};
     if (int rc = scaled_rms(s, dk, cw, 2, st, &s->init->d2)) return rc;
     hipLaunchKernelGGL(init_dt_kernel, dim3(1), dim3(1), 0, st, s->init, s->ctl, t0, t1, s->early ? s->max_trials : 0,
-                       s->early ? s->times : nullptr, s->early ? s->times_capacity : 0, s->pair == GNPDE_ADAPTIVE_HEUN ? 1.0f / 2.0f : 1.0f / 5.0f);
+                       s->early ? s->times : nullptr, s->early ? s->times_capacity : 0, tab.order);
     GNPDE_LAUNCH_CHECK();
     // first stage input of the first trial step (later ones come out of the finish kernel)
-    const float c[1] = {s->pair == GNPDE_ADAPTIVE_HEUN ? 1.0f : static_cast<float>(kB[0][0])};
+    const float c[1] = {static_cast<float>(tab.a[0][0])};
     if (int rc = launch_lincomb(s->Y[0], w, c, 1, flat, s->u[0], st, &s->ctl->h[0])) return rc;
   }
   for (int parity = 0; parity < 2; ++parity) {
     if (s->exec[parity] != nullptr) continue;
-    if (s->cap_stream == nullptr) GNPDE_HIP(hipStreamCreateWithFlags(&s->cap_stream, hipStreamNonBlocking));
-    GNPDE_HIP(hipStreamBeginCapture(s->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_trial(s, parity, s->cap_stream);
-    hipGraph_t gobj = nullptr;
-    const hipError_t ec = hipStreamEndCapture(s->cap_stream, &gobj);
-    if (rc != 0) {
-      if (gobj) (void)hipGraphDestroy(gobj);
+    if (int rc = capture_into(&s->cap_stream, &s->graph_obj[parity], &s->exec[parity], [&](hipStream_t cs) { return enqueue_trial(s, parity, cs); }))
       return rc;
-    }
-    if (ec != hipSuccess) {
-      set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-      return static_cast<int>(ec);
-    }
-    s->graph_obj[parity] = gobj;
-    GNPDE_HIP(hipGraphInstantiate(&s->exec[parity], gobj, nullptr, nullptr, 0));
   }
   const int base_evals = s->n_evals;
   bool have_record = false;   // nothing is known about dt on the host before the first read: one trial step, then look
   for (;;) {
-    // Queue as many trial steps as cannot pass t1 even if each were accepted with the controller's largest growth (x10):
-    // dt (10^m - 1) / 9 < t1 - t  =>  m steps cannot finish.  At most trials_per_sync, then one read of the record.
+    // as many trial steps as cannot pass t1 (plan_batch, embedded_pair.h), then one read of the record
     const Ctl& hc = *s->host_ctl;
-    int batch = 1;
-    double reach = hc.dt, step = hc.dt;
-    while (have_record && batch < trials_per_sync && hc.t + reach < hc.t1) {
-      step *= 10.0;
-      reach += step;
-      ++batch;
-    }
+    int batch = plan_batch(hc.t, hc.dt, hc.t1, trials_per_sync, have_record);
     if (have_record && hc.max_trials > 0 && batch > hc.max_trials - hc.trials) batch = hc.max_trials - hc.trials;   // trial budget
     if (batch < 1) batch = 1;
     for (int b = 0; b < batch; ++b) GNPDE_HIP(hipGraphLaunch(s->exec[(s->n_launches + b) & 1], st));
@@ -753,7 +668,7 @@ extern "C" int gnpde_dopri5_run(gnpde_dopri5_t* s, const float* y0, int32_t ld_y
     GNPDE_HIP(hipStreamSynchronize(st));
     s->n_syncs += 1;
     have_record = true;
-    s->n_evals = base_evals + (s->pair == GNPDE_ADAPTIVE_HEUN ? 1 : 6) * hc.trials;
+    s->n_evals = base_evals + tab.S * hc.trials;
     s->n_accepted = hc.accepted;
     s->n_rejected = hc.rejected;
     if (s->shard != nullptr) {    // a peer that never arrived: its share of the norms is missing, nothing behind this point means anything
@@ -765,13 +680,7 @@ extern "C" int gnpde_dopri5_run(gnpde_dopri5_t* s, const float* y0, int32_t ld_y
     GNPDE_CHECK_ARG(hc.t + hc.dt > hc.t, GNPDE_EINVAL, "dopri5_run: underflow in dt %g at t %g", hc.dt, hc.t);
     if (max_evals > 0 && s->n_evals > max_evals) return 0;   // *finished stays 0
   }
-  if (s->row_order != nullptr)
-    hipLaunchKernelGGL(copy_rows_map_kernel, dim3(static_cast<unsigned>(copy_blocks)), dim3(kBlock), 0, st, s->yout, r.ld, y_out, ld_out,
-                       static_cast<long long>(n), r.d, s->row_order, 0);
-  else
-    hipLaunchKernelGGL(copy_rows_kernel, dim3(static_cast<unsigned>(copy_blocks)), dim3(kBlock), 0, st, s->yout, r.ld, y_out, ld_out,
-                       static_cast<long long>(n), r.d);
-  GNPDE_LAUNCH_CHECK();
+  if (int rc = copy_rows(s->yout, r.ld, y_out, ld_out, 0)) return rc;
   if (s->tape != nullptr) {
     GNPDE_CHECK_ARG(s->n_accepted <= s->tape_capacity, GNPDE_EWS, "dopri5_run: %d accepted steps do not fit the tape (%d slots)",
                     s->n_accepted, s->tape_capacity);
@@ -791,8 +700,7 @@ extern "C" int gnpde_dopri5_set_early_stop(gnpde_dopri5_t* s, const gnpde_decode
                                            int32_t trace_capacity, double* times, int32_t times_capacity, int32_t max_trial_steps) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "dopri5_set_early_stop: solver is null");
   for (int p = 0; p < 2; ++p) {      // the evaluator kernels are part of the captured trial step
-    if (s->exec[p]) { (void)hipGraphExecDestroy(s->exec[p]); s->exec[p] = nullptr; }
-    if (s->graph_obj[p]) { (void)hipGraphDestroy(s->graph_obj[p]); s->graph_obj[p] = nullptr; }
+    drop_capture(&s->graph_obj[p], &s->exec[p]);
   }
   if (dec == nullptr) {
     s->early = false;
@@ -819,8 +727,7 @@ extern "C" int gnpde_dopri5_set_pair(gnpde_dopri5_t* s, int32_t pair) {
   GNPDE_CHECK_ARG(pair == GNPDE_ADAPTIVE_DOPRI5 || s->tape == nullptr, GNPDE_ESTATE, "dopri5_set_pair: the recorded solve is Dormand-Prince's");
   if (pair == s->pair) return 0;
   for (int p = 0; p < 2; ++p) {      // the trial step is captured per pair
-    if (s->exec[p]) { (void)hipGraphExecDestroy(s->exec[p]); s->exec[p] = nullptr; }
-    if (s->graph_obj[p]) { (void)hipGraphDestroy(s->graph_obj[p]); s->graph_obj[p] = nullptr; }
+    drop_capture(&s->graph_obj[p], &s->exec[p]);
   }
   s->pair = pair;
   return 0;
@@ -836,19 +743,14 @@ extern "C" int gnpde_dopri5_set_row_order(gnpde_dopri5_t* s, const int32_t* orde
 extern "C" int gnpde_dopri5_stats(const gnpde_dopri5_t* s, int32_t* n_evals, int32_t* n_accepted, int32_t* n_rejected,
                                   int32_t* n_launches, int32_t* n_syncs) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "dopri5_stats: solver is null");
-  if (n_evals) *n_evals = s->n_evals;
-  if (n_accepted) *n_accepted = s->n_accepted;
-  if (n_rejected) *n_rejected = s->n_rejected;
-  if (n_launches) *n_launches = s->n_launches;
-  if (n_syncs) *n_syncs = s->n_syncs;
+  store_stats(s, n_evals, n_accepted, n_rejected, n_launches, n_syncs);
   return 0;
 }
 
 extern "C" int gnpde_dopri5_destroy(gnpde_dopri5_t* s) {
   if (!s) return 0;
   for (int p = 0; p < 2; ++p) {
-    if (s->exec[p]) (void)hipGraphExecDestroy(s->exec[p]);
-    if (s->graph_obj[p]) (void)hipGraphDestroy(s->graph_obj[p]);
+    drop_capture(&s->graph_obj[p], &s->exec[p]);
   }
   if (s->cap_stream) (void)hipStreamDestroy(s->cap_stream);
   if (s->host_ctl) (void)hipHostFree(s->host_ctl);
@@ -876,8 +778,7 @@ extern "C" size_t gnpde_dopri5_tape_bytes(const gnpde_rhs_t* rhs, int32_t capaci
 extern "C" int gnpde_dopri5_set_tape(gnpde_dopri5_t* s, void* tape, size_t tape_bytes, int32_t capacity_steps) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "dopri5_set_tape: solver is null");
   for (int p = 0; p < 2; ++p) {      // the store kernel and the stage-input buffers are part of the captured trial step
-    if (s->exec[p]) { (void)hipGraphExecDestroy(s->exec[p]); s->exec[p] = nullptr; }
-    if (s->graph_obj[p]) { (void)hipGraphDestroy(s->graph_obj[p]); s->graph_obj[p] = nullptr; }
+    drop_capture(&s->graph_obj[p], &s->exec[p]);
   }
   s->tape = nullptr;
   s->tape_steps = 0;
@@ -978,11 +879,7 @@ extern "C" int gnpde_dopri5_tape_backward(gnpde_dopri5_t* s, const gnpde_graph_t
   GNPDE_HIP(hipMemsetAsync(sum_g, 0, static_cast<size_t>(flat) * sizeof(float), st));
   if (graph_t->e > 0) GNPDE_HIP(hipMemsetAsync(r_t, 0, static_cast<size_t>(graph_t->e) * sizeof(float), st));
   GNPDE_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(one), 0x3f800000, 1, st));     // 1.0f: weight of the source term
-  long long copy_blocks = (n * r.d + kBlock - 1) / kBlock;
-  if (copy_blocks > 8192) copy_blocks = 8192;
-  if (copy_blocks < 1) copy_blocks = 1;
-  hipLaunchKernelGGL(copy_rows_kernel, dim3(static_cast<unsigned>(copy_blocks)), dim3(kBlock), 0, st, grad_out, ld_go, GO, r.ld, n, r.d);
-  GNPDE_LAUNCH_CHECK();
+  if (int rc = launch_copy_rows(grad_out, ld_go, GO, r.ld, n, r.d, st)) return rc;
   auto slot_u = [&](int step, int i) -> const float* {       // stage input u_i of accepted step `step` (u_6 = u_0 of the next slot)
     return i < 6 ? s->tape_slots + (static_cast<size_t>(step) * 6 + i) * stride : s->tape_slots + (static_cast<size_t>(step) + 1) * 6 * stride;
   };
@@ -1015,13 +912,13 @@ extern "C" int gnpde_dopri5_tape_backward(gnpde_dopri5_t* s, const gnpde_graph_t
       const double x = static_cast<double>(s->last_x), x2 = x * x, x3 = x2 * x, x4 = x3 * x, hd = static_cast<double>(h);
       const double p_ym = 16 * x2 - 32 * x3 + 16 * x4, p_y = 1 - 11 * x2 + 18 * x3 - 8 * x4, p_y1 = -5 * x2 + 14 * x3 - 8 * x4;
       const double p_k0 = hd * (x - 4 * x2 + 5 * x3 - 2 * x4), p_k6 = hd * (x2 - 3 * x3 + 2 * x4);
-      for (int j = 0; j < 7; ++j) cD[j] = static_cast<float>(p_ym * hd * kMid[j]);
-      cD[0] = static_cast<float>(p_ym * hd * kMid[0] + p_k0);
+      for (int j = 0; j < 7; ++j) cD[j] = static_cast<float>(p_ym * hd * kDopri5.c_mid[j]);
+      cD[0] = static_cast<float>(p_ym * hd * kDopri5.c_mid[0] + p_k0);
       cDy = static_cast<float>(p_y + p_ym);
       const float* v[1] = {GO};
       const float c1[1] = {static_cast<float>(p_y1)};
       if (int rc = launch_lincomb(Z, v, c1, 1, flat, gy_io[io], st, nullptr)) return rc;
-      const float c6[1] = {static_cast<float>(p_ym * hd * kMid[6] + p_k6)};
+      const float c6[1] = {static_cast<float>(p_ym * hd * kDopri5.c_mid[6] + p_k6)};
       if (int rc = launch_lincomb(Z, v, c6, 1, flat, gk_io[io], st, nullptr)) return rc;
     }
     float* gk_in = gk_io[io];
@@ -1029,13 +926,13 @@ extern "C" int gnpde_dopri5_tape_backward(gnpde_dopri5_t* s, const gnpde_graph_t
     float* gk_out = gk_io[1 - io];
     float* gy_out = gy_io[1 - io];
     for (int i = 6; i >= 1; --i) {
-      // after this launch: W_i, and G_{i-1} = D_{i-1} + h sum_{m >= i} a_{m,i-1} W_m   (a_{m,j} = kB[m-1][j]; row 5 of kB = b)
+      // after this launch: W_i, and G_{i-1} = D_{i-1} + h sum_{m >= i} a_{m,i-1} W_m   (a_{m,j} = kDopri5.a[m-1][j]; its row 5 = b)
       const float* prev[GNPDE_MAX_PREV];
       float coef[GNPDE_MAX_PREV + 1];
       int np = 0;
-      for (int m = 6; m > i; --m) { prev[np] = W[m]; coef[np] = static_cast<float>(kB[m - 1][i - 1]) * h; ++np; }
+      for (int m = 6; m > i; --m) { prev[np] = W[m]; coef[np] = static_cast<float>(kDopri5.a[m - 1][i - 1]) * h; ++np; }
       if (last && cD[i - 1] != 0.f) { prev[np] = GO; coef[np] = cD[i - 1]; ++np; }
-      coef[np] = static_cast<float>(kB[i - 1][i - 1]) * h;
+      coef[np] = static_cast<float>(kDopri5.a[i - 1][i - 1]) * h;
       const float* g_in = i == 6 ? gk_in : Gk[i];
       float* g_next = i == 1 ? gk_out : Gk[i - 1];
       if (int rc = stage(g_in, slot_u(step, i), i == 6 ? gy_in : nullptr, W[i], g_next, prev, coef, np)) return rc;
@@ -1059,8 +956,7 @@ extern "C" int gnpde_dopri5_tape_backward(gnpde_dopri5_t* s, const gnpde_graph_t
     const float c[1] = {1.f};
     if (int rc = launch_lincomb(sum_g, v, c, 1, flat, sum_g, st, nullptr)) return rc;
   }
-  hipLaunchKernelGGL(copy_rows_kernel, dim3(static_cast<unsigned>(copy_blocks)), dim3(kBlock), 0, st, GY0, r.ld, grad_y0, ld_gy0, n, r.d);
-  GNPDE_LAUNCH_CHECK();
+  if (int rc = launch_copy_rows(GY0, r.ld, grad_y0, ld_gy0, n, r.d, st)) return rc;
   double* fold_part = reinterpret_cast<double*>(ws + L.off_one + 64);       // (behind the 1.0f of the source weight)
   hipLaunchKernelGGL(tape_dots_partial_kernel, dim3(kTapeFoldBlocks), dim3(kBlock), 0, st, dots, static_cast<long long>(L.slots) * launch, fold_part);
   GNPDE_LAUNCH_CHECK();

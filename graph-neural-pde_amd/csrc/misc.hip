@@ -2,6 +2,7 @@
 // stand-alone diffusion epilogue (GAT mix_features path, where the aggregate passes through Wout
 // before alpha (ax - x) + beta x0 is applied; reference src/function_GAT_attention.py:33-38,56-64).
 #include "common.h"
+#include "embedded_pair.h"
 #include "epilogue.h"
 
 namespace gnpde {
@@ -136,13 +137,8 @@ __global__ __launch_bounds__(kBlock) void rk_error_final_kernel(const double* __
   __shared__ double red[kBlock];
   double acc = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += kBlock) acc += ws[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *ratio = static_cast<float>(sqrt(red[0] / count));
+  const double sum = block_sum_double(acc, red);
+  if (threadIdx.x == 0) *ratio = static_cast<float>(sqrt(sum / count));
 }
 
 struct InterpArgs {
@@ -170,22 +166,28 @@ __global__ __launch_bounds__(kBlock) void dopri5_interp_kernel(const InterpArgs 
     for (int j = 0; j < GNPDE_MAX_PREV; ++j)
       if (a.mid[j] != 0.0f) ym += a.k[j][off] * a.mid[j];
     const float fa = a.k[0][off], fb = a.k[6][off], h = a.h, x = a.x;
-    const float ca = 2.0f * h * (fb - fa) - 8.0f * (yb + ya) + 16.0f * ym;
-    const float cb = h * (5.0f * fa - 3.0f * fb) + 18.0f * ya + 14.0f * yb - 32.0f * ym;
-    const float cc = h * (fb - 4.0f * fa) - 11.0f * ya - 5.0f * yb + 16.0f * ym;
-    const float cd = h * fa;
-    float tot = ya + x * cd;
-    float xp = x * x;
-    tot += xp * cc;
-    xp *= x;
-    tot += xp * cb;
-    xp *= x;
-    tot += xp * ca;
-    a.out[off] = tot;
+    a.out[off] = quartic(ya, yb, fa, fb, ym, h, x);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void copy_rows_kernel(const float* __restrict__ src, int ld_src, float* __restrict__ dst, int ld_dst,
+                                                          long long n, int d) {
+  const long long total = n * d;
+  for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += static_cast<long long>(gridDim.x) * blockDim.x) {
+    const long long r = i / d;
+    const int c = static_cast<int>(i - r * d);
+    dst[static_cast<size_t>(r) * ld_dst + c] = src[static_cast<size_t>(r) * ld_src + c];
   }
 }
 
 }  // namespace
+
+int launch_copy_rows(const float* src, int ld_src, float* dst, int ld_dst, long long n, int d, hipStream_t st) {
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(copy_rows_grid(n, d)), dim3(kBlock), 0, st, src, ld_src, dst, ld_dst, n, d);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
 
 int launch_dopri5_interp(const float* y0, const float* y1, const float* const* k, const float* mid_coef, float h, float x,
                          int64_t n, int32_t d, int32_t ld, float* out, hipStream_t stream) {

@@ -34,6 +34,8 @@
 #include <vector>
 #include "gnpde.h"
 #include "common.h"
+#include "embedded_pair.h"
+#include "graph_capture.h"
 #include "rhs.h"
 
 namespace gnpde {
@@ -231,12 +233,7 @@ __global__ __launch_bounds__(kBlock) void p2p_sum_kernel(double* __restrict__ va
   } else {
   double acc = 0.0;
   for (int i = threadIdx.x; i < n_partials; i += kBlock) acc += value[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  (void)block_sum_double(acc, red);      // (red[0] keeps the sum)
   if (world == 1) {
     if (threadIdx.x == 0) value[0] = red[0];
     return;
@@ -681,8 +678,7 @@ int enqueue_run(gnpde_sharded_solver* s, float* y, hipStream_t st) {
 }
 
 void drop_sharded_graph(gnpde_sharded_solver* s) {
-  if (s->exec) { (void)hipGraphExecDestroy(s->exec); s->exec = nullptr; }
-  if (s->graph_obj) { (void)hipGraphDestroy(s->graph_obj); s->graph_obj = nullptr; }
+  drop_capture(&s->graph_obj, &s->exec);
   s->captured_y = nullptr;
 }
 
@@ -1094,21 +1090,7 @@ extern "C" int gnpde_sharded_solver_run(gnpde_sharded_solver_t* s, float* y, int
                   "recurses without bound on the forked send/recv stream); run it eagerly or use the P2P transport");
   if (s->exec == nullptr || s->captured_y != y) {
     drop_sharded_graph(s);
-    if (s->cap_stream == nullptr) GNPDE_HIP(hipStreamCreateWithFlags(&s->cap_stream, hipStreamNonBlocking));
-    GNPDE_HIP(hipStreamBeginCapture(s->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_run(s, y, s->cap_stream);
-    hipGraph_t gobj = nullptr;
-    const hipError_t ec = hipStreamEndCapture(s->cap_stream, &gobj);
-    if (rc != 0) {
-      if (gobj) (void)hipGraphDestroy(gobj);
-      return rc;
-    }
-    if (ec != hipSuccess) {
-      set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-      return static_cast<int>(ec);
-    }
-    s->graph_obj = gobj;
-    GNPDE_HIP(hipGraphInstantiate(&s->exec, s->graph_obj, nullptr, nullptr, 0));
+    if (int rc = capture_into(&s->cap_stream, &s->graph_obj, &s->exec, [&](hipStream_t cs) { return enqueue_run(s, y, cs); })) return rc;
     s->captured_y = y;
   }
   GNPDE_HIP(hipGraphLaunch(s->exec, st));

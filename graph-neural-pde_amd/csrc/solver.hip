@@ -9,6 +9,7 @@
 // 1 (GRAND-l) or 5 (GRAND-nl) launches per stage here and a single graph launch per forward pass.
 #include <vector>
 #include "common.h"
+#include "graph_capture.h"
 #include "rhs.h"
 
 namespace gnpde {
@@ -379,8 +380,7 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
 }
 
 void drop_graph(gnpde_solver* s) {
-  if (s->exec) { (void)hipGraphExecDestroy(s->exec); s->exec = nullptr; }
-  if (s->graph_obj) { (void)hipGraphDestroy(s->graph_obj); s->graph_obj = nullptr; }
+  drop_capture(&s->graph_obj, &s->exec);
   s->captured_y = nullptr;
 }
 
@@ -466,21 +466,7 @@ extern "C" int gnpde_solver_run(gnpde_solver_t* s, float* y, int32_t use_graph, 
   if (!use_graph) return enqueue_solve(s, y, st);
   if (s->exec == nullptr || s->captured_y != y) {
     drop_graph(s);
-    if (s->cap_stream == nullptr) GNPDE_HIP(hipStreamCreateWithFlags(&s->cap_stream, hipStreamNonBlocking));
-    GNPDE_HIP(hipStreamBeginCapture(s->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_solve(s, y, s->cap_stream);
-    hipGraph_t gobj = nullptr;
-    const hipError_t ec = hipStreamEndCapture(s->cap_stream, &gobj);
-    if (rc != 0) {
-      if (gobj) (void)hipGraphDestroy(gobj);
-      return rc;
-    }
-    if (ec != hipSuccess) {
-      set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-      return static_cast<int>(ec);
-    }
-    s->graph_obj = gobj;
-    GNPDE_HIP(hipGraphInstantiate(&s->exec, s->graph_obj, nullptr, nullptr, 0));
+    if (int rc = capture_into(&s->cap_stream, &s->graph_obj, &s->exec, [&](hipStream_t cs) { return enqueue_solve(s, y, cs); })) return rc;
     s->captured_y = y;
   }
   GNPDE_HIP(hipGraphLaunch(s->exec, st));

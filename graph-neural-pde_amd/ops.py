@@ -1378,9 +1378,33 @@ def rhs_eval(desc, u, out=None):
   return out
 
 
-class Dopri5Solver(object):
+class _NativeSolver(object):
+  """A native solver handle and the name of the entry point that destroys it."""
+  _destroy = None
+
+  def close(self):
+    if getattr(self, 'handle', None) is not None and self.handle.value:
+      try:
+        getattr(_lib.lib(), self._destroy)(self.handle)
+      except Exception:
+        pass
+      self.handle = None
+
+  def __del__(self):
+    self.close()
+
+
+def _stats(fn, handle):
+  """The counters of a device-controlled solve's last run (gnpde_*_stats)."""
+  v = [ctypes.c_int32(0) for _ in range(5)]
+  check(fn(handle, *[ctypes.byref(x) for x in v]))
+  return dict(zip(('evals', 'accepted', 'rejected', 'launches', 'syncs'), [x.value for x in v]))
+
+
+class Dopri5Solver(_NativeSolver):
   """gnpde_dopri5_t: dopri5 with the step-size controller on the device; one trial step = one hipGraph replay, the host reads
   the controller record once per `trials_per_sync` trial steps."""
+  _destroy = 'gnpde_dopri5_destroy'
 
   def __init__(self, desc, rtol, atol, device):
     self.desc = desc
@@ -1480,25 +1504,13 @@ class Dopri5Solver(object):
     return gy0, r_t, sum_g[:, :d], dot
 
   def stats(self):
-    v = [ctypes.c_int32(0) for _ in range(5)]
-    check(_lib.lib().gnpde_dopri5_stats(self.handle, *[ctypes.byref(x) for x in v]))
-    return dict(zip(('evals', 'accepted', 'rejected', 'launches', 'syncs'), [x.value for x in v]))
-
-  def close(self):
-    if getattr(self, 'handle', None) is not None and self.handle.value:
-      try:
-        _lib.lib().gnpde_dopri5_destroy(self.handle)
-      except Exception:
-        pass
-      self.handle = None
-
-  def __del__(self):
-    self.close()
+    return _stats(_lib.lib().gnpde_dopri5_stats, self.handle)
 
 
-class AdjointAdaptiveSolver(object):
+class AdjointAdaptiveSolver(_NativeSolver):
   """gnpde_adjoint_adaptive_t: one backward interval of the adjoint with an adaptive adjoint method ('adaptive_heun' / 'dopri5') on the
   Laplacian function, the controller on the device (one hipGraph replay per trial step)."""
+  _destroy = 'gnpde_adjoint_adaptive_destroy'
 
   def __init__(self, desc, graph_t, w_t, method, rtol, atol, device):
     self.desc, self.graph_t, self.w_t = desc, graph_t, w_t
@@ -1524,20 +1536,7 @@ class AdjointAdaptiveSolver(object):
     return bool(fin.value)
 
   def stats(self):
-    v = [ctypes.c_int32(0) for _ in range(5)]
-    check(_lib.lib().gnpde_adjoint_adaptive_stats(self.handle, *[ctypes.byref(x) for x in v]))
-    return dict(zip(('evals', 'accepted', 'rejected', 'launches', 'syncs'), [x.value for x in v]))
-
-  def close(self):
-    if getattr(self, 'handle', None) is not None and self.handle.value:
-      try:
-        _lib.lib().gnpde_adjoint_adaptive_destroy(self.handle)
-      except Exception:
-        pass
-      self.handle = None
-
-  def __del__(self):
-    self.close()
+    return _stats(_lib.lib().gnpde_adjoint_adaptive_stats, self.handle)
 
 
 def rhs_stage(desc, u, stage, ws=None, **kw):
@@ -1662,8 +1661,9 @@ class EarlyStopEvaluator(object):
     return out
 
 
-class FixedStepSolver(object):
+class FixedStepSolver(_NativeSolver):
   """gnpde_solver_t: euler / midpoint / rk4 over a fixed grid, the whole loop captured in one hipGraph."""
+  _destroy = 'gnpde_solver_destroy'
 
   def __init__(self, desc, method, dts, device):
     self.desc = desc
@@ -1730,20 +1730,10 @@ class FixedStepSolver(object):
     check(_lib.lib().gnpde_solver_run(self.handle, ptr(y), int(bool(use_graph)), stream_of(y)))
     return y
 
-  def close(self):
-    if getattr(self, 'handle', None) is not None and self.handle.value:
-      try:
-        _lib.lib().gnpde_solver_destroy(self.handle)
-      except Exception:
-        pass
-      self.handle = None
 
-  def __del__(self):
-    self.close()
-
-
-class AdjointSolver(object):
+class AdjointSolver(_NativeSolver):
   """gnpde_adjoint_t: the fixed-grid adjoint solve (state, adjoint and parameter gradients integrated backwards), one hipGraph."""
+  _destroy = 'gnpde_adjoint_destroy'
 
   def __init__(self, desc, graph_t, t_from_csr, proj_wt, w_t, method, dts, device):
     self.desc, self.graph_t = desc, graph_t
@@ -1787,14 +1777,3 @@ class AdjointSolver(object):
     if grads.dtype != torch.float32 or not grads.is_contiguous() or grads.numel() < self.n_grad:
       raise _lib.GnpdeError('adjoint solve: gradient buffer of %d floats needed' % self.n_grad)
     check(_lib.lib().gnpde_adjoint_run(self.handle, ptr(y), ptr(a), ptr(grads), int(bool(use_graph)), stream_of(y)))
-
-  def close(self):
-    if getattr(self, 'handle', None) is not None and self.handle.value:
-      try:
-        _lib.lib().gnpde_adjoint_destroy(self.handle)
-      except Exception:
-        pass
-      self.handle = None
-
-  def __del__(self):
-    self.close()
