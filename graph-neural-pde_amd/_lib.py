@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 15     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 16     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
@@ -30,6 +30,7 @@ TUNE_KNN_SPLITS = 19     # column splits of the k-nearest-neighbour search: 0 = 
 METRIC_SQEUCLIDEAN = 0   # GNPDE_METRIC_* of include/gnpde.h (the key of a pair in gnpde_knn_metric / gnpde_radius_*)
 METRIC_POINCARE = 1
 TUNE_KNN_VARIANT = 20    # tile-kernel variants of the search (A/B): 1 = 32-float K chunks for k > 32, 2 = the k > 32 kernel for every k
+TUNE_ATT_ONE_LAUNCH = 21  # 1: the row attention of a GRAND-nl evaluation keeps its two launches (A/B against the one-launch form)
 TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)
 SAMPLING_EMPTY_COLUMN, SAMPLING_NONFINITE, SAMPLING_ZERO_MASS, SAMPLING_INDEX_RANGE = 1, 2, 4, 8   # GNPDE_SAMPLING_* flag bits
 DEEPWALK_BAD_START, DEEPWALK_BAD_GRAPH, DEEPWALK_BAD_WALK = 1, 2, 4   # GNPDE_DEEPWALK_* flag bits
@@ -104,6 +105,7 @@ PROTOTYPES = {
   'gnpde_abi_version': (ctypes.c_int, []),
   'gnpde_last_error': (ctypes.c_char_p, []),
   'gnpde_tune': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
+  'gnpde_one_launch_evaluations': (ctypes.c_int64, []),
   'gnpde_graph_count_long': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32, c_int_p, c_int_p, c_int_p]),
   'gnpde_graph_build': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int32] + [c_vp] * 15),
   'gnpde_partition_rows': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -663,15 +663,11 @@ __global__ __launch_bounds__(kBlock) void row_attention_kernel(const AttArgs a, 
 // (scores recomputed, nothing stored).  The segments are the rows of whatever graph a.bin_rows / a.colidx describe -- the
 // transposed graph, with a.q / a.k exchanged and a.out_pos mapping its positions to the CSR positions of the weights, when the
 // reference normalises over edge[1] (attention_norm_idx = 1, function_transformer_attention.py:210-213).
+// The rows of one class (bin_rows[first_row .. first_row + n_rows)); the class's workgroups follow the first `n_hub` of the launch.  The body of
+// row_attention_sd_kernel, and of both row classes of row_attention_sd_one_kernel (same code and lane mapping per row: the weights
+// are the same bits whichever launch runs it).
 template <int H, int DK4, int GL, int RI, int PB, int NB, int MODE, bool SCATTER>
-__global__ __launch_bounds__(kBlock) void row_attention_sd_kernel(const AttArgs a, int first_row, int n_rows, int n_hub,
-                                                                 int hub_phase, float* __restrict__ part,
-                                                                 const int* __restrict__ chunk_first) {
-  if (static_cast<int>(blockIdx.x) < n_hub) {
-    if (hub_phase == 0) hub_scores_partial_heads<(MODE == 4 ? GNPDE_ATT_EXP_KERNEL : GNPDE_ATT_SCALED_DOT), true, H, MODE>(a, part, blockIdx.x);
-    else hub_normalise_body<MODE, SCATTER>(a, part, chunk_first, blockIdx.x);
-    return;
-  }
+__device__ __forceinline__ void row_attention_sd_rows(const AttArgs& a, int first_row, int n_rows, int n_hub) {
   constexpr int RPW = kWave / GL;
   constexpr int GE = GL / H;
   const int lane = threadIdx.x & (kWave - 1);
@@ -919,6 +915,40 @@ __global__ __launch_bounds__(kBlock) void row_attention_sd_kernel(const AttArgs 
     }
 }
 
+template <int H, int DK4, int GL, int RI, int PB, int NB, int MODE, bool SCATTER>
+__global__ __launch_bounds__(kBlock) void row_attention_sd_kernel(const AttArgs a, int first_row, int n_rows, int n_hub,
+                                                                 int hub_phase, float* __restrict__ part,
+                                                                 const int* __restrict__ chunk_first) {
+  if (static_cast<int>(blockIdx.x) < n_hub) {
+    if (hub_phase == 0) hub_scores_partial_heads<(MODE == 4 ? GNPDE_ATT_EXP_KERNEL : GNPDE_ATT_SCALED_DOT), true, H, MODE>(a, part, blockIdx.x);
+    else hub_normalise_body<MODE, SCATTER>(a, part, chunk_first, blockIdx.x);
+    return;
+  }
+  row_attention_sd_rows<H, DK4, GL, RI, PB, NB, MODE, SCATTER>(a, first_row, n_rows, n_hub);
+}
+
+// Row softmax of a whole graph in ONE launch, for an evaluation whose aggregation follows on the same stream: workgroups
+// [0, n_hub) score the 512-entry chunks of the hub rows and store their statistics (phase 0, as above), the next blocks64 take the
+// rows of 17..512 entries (a wave per row, longest first: bin_rows' order) and the rest the rows of <= 16 entries, which fill the
+// tail.  There is no phase 1: the grid-wide dependency between the chunk statistics and the hub entries' weights is carried by
+// the kernel boundary in front of the aggregation, whose hub-chunk items fold the statistics and form (and store) those weights
+// themselves (spmm.hip, HubDefer).  Two launches of < 20 us each paid two ramps, two tails and a boundary.
+template <int H, int DK4, int GL16, int RI16, int P16, int PB64, int NB64>
+__global__ __launch_bounds__(kBlock) void row_attention_sd_one_kernel(const AttArgs a, int n16, int n64, int n_hub,
+                                                                     float* __restrict__ part) {
+  const int b = static_cast<int>(blockIdx.x);
+  const int blocks64 = (n64 + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (b < n_hub) {
+    hub_scores_partial_heads<GNPDE_ATT_SCALED_DOT, true, H, 0>(a, part, b);
+    return;
+  }
+  if (b < n_hub + blocks64) {
+    row_attention_sd_rows<H, DK4, kWave, 1, PB64, NB64, 0, false>(a, n16, n64, n_hub);
+    return;
+  }
+  row_attention_sd_rows<H, DK4, GL16, RI16, P16, 1, 0, false>(a, 0, n16, n_hub + blocks64);
+}
+
 __global__ __launch_bounds__(kBlock) void edge_to_csr_mean_kernel(const int* __restrict__ perm, const float* __restrict__ src,
                                                                  int h, int e, float* __restrict__ w) {
   const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
@@ -1001,6 +1031,18 @@ inline void sd_sweep_waves(int h, int dk4, int n16, int n64, long long (&w)[2]) 
   w[1] = n64 > 0 ? static_cast<long long>(n64 + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock : 0;
 }
 
+// lane mapping of the two row classes of the scaled-dot row kernels (launch_rows_sd_mode explains the choices)
+template <int H, int DK4>
+struct SdShape {
+  static constexpr bool QUARTER = sd_quarter_rows(H, DK4);
+  static constexpr int GL16 = QUARTER ? 16 : ((16 * H < kWave) ? 16 * H : kWave);   // lanes per row for rows with <= 16 entries
+  static constexpr int P16 = (16 * H + GL16 - 1) / GL16;           // passes to cover 16 entries
+  static constexpr int RPW16 = kWave / GL16;
+  static constexpr int RI16 = QUARTER ? 2 : ((DK4 == 1 && P16 == 1) ? 4 : (P16 == 1 ? 2 : 1));  // rows interleaved per group
+  static constexpr int P64 = GNPDE_LONG_ROW / (kWave / H);         // passes to cover GNPDE_LONG_ROW entries
+  static constexpr int PB64 = (DK4 == 1) ? 4 : 2;
+};
+
 template <int H, int DK4, int MODE, bool SCATTER>
 void launch_rows_sd_mode(const AttArgs& a_in, int n16, int n64, hipStream_t s, int n_hub, float* part, const int* chunk_first) {
   AttArgs a = a_in;
@@ -1010,13 +1052,9 @@ void launch_rows_sd_mode(const AttArgs& a_in, int n16, int n64, hipStream_t s, i
   // (d_k = 16) 4.48 -> 3.98 ms; the other packings tried on the row softmax (half a wave x 2 passes with 8 / 4 rows per wave: 38.2; a quarter
   // with 16 rows per wave: 40.4, with 4: 37.3; half with 16 rows: 43.0; an eighth x 8 passes with 16 / 8 rows: 40.4 / 37.2) are in DESIGN.md,
   // the whole-wave form stays behind gnpde_tune(17, 9) for the row softmax (A/B).  Other head counts: 16 H lanes (at most a wave) per row.
-  constexpr bool QUARTER = sd_quarter_rows(H, DK4);
-  constexpr int GL16 = QUARTER ? 16 : ((16 * H < kWave) ? 16 * H : kWave);   // lanes per row for rows with <= 16 entries
-  constexpr int P16 = (16 * H + GL16 - 1) / GL16;           // passes to cover 16 entries
-  constexpr int RPW16 = kWave / GL16;
-  constexpr int RI16 = QUARTER ? 2 : ((DK4 == 1 && P16 == 1) ? 4 : (P16 == 1 ? 2 : 1));  // rows interleaved per group
-  constexpr int P64 = GNPDE_LONG_ROW / (kWave / H);         // passes to cover GNPDE_LONG_ROW entries
-  constexpr int PB64 = (DK4 == 1) ? 4 : 2;
+  using S = SdShape<H, DK4>;
+  constexpr bool QUARTER = S::QUARTER;
+  constexpr int GL16 = S::GL16, P16 = S::P16, RPW16 = S::RPW16, RI16 = S::RI16, P64 = S::P64, PB64 = S::PB64;
   // launch 1: hub phase 0 + rows with <= 16 entries; launch 2: hub phase 1 + rows with 17..512 entries (the maximum sweep of
   // squareplus, MODE 2, has no hub phase 1)
   bool first_done = false;
@@ -1079,6 +1117,35 @@ bool launch_sd_with_hubs(const AttArgs& c, int n16, int n64, int n_hub, float* p
     default: return false;
   }
 #undef GNPDE_SD
+}
+
+// The plain row softmax in ONE launch (row_attention_sd_one_kernel): hub phase 0, the rows of 17..512 entries, the rows of <= 16
+// entries.  The hub entries' weights are NOT written: the caller hands the chunk statistics to the aggregation (HubDefer).
+template <int H, int DK4>
+void launch_rows_sd_one(const AttArgs& a, int n16, int n64, int n_hub, float* part, hipStream_t s) {
+  using S = SdShape<H, DK4>;
+  const long long rpb16 = static_cast<long long>(S::RPW16) * S::RI16 * kWavesPerBlock;
+  const int blocks64 = (n64 + kWavesPerBlock - 1) / kWavesPerBlock;
+  const long long grid = static_cast<long long>(n_hub) + blocks64 + (n16 + rpb16 - 1) / rpb16;
+  if (grid == 0) return;
+  hipLaunchKernelGGL((row_attention_sd_one_kernel<H, DK4, S::GL16, S::RI16, S::P16, S::PB64, S::P64 / S::PB64>), dim3(static_cast<unsigned>(grid)),
+                     dim3(kBlock), 0, s, a, n16, n64, n_hub, part);
+}
+
+bool launch_sd_one(const AttArgs& c, int n16, int n64, int n_hub, float* part, hipStream_t s) {
+#define GNPDE_SD1(HH)                                                                  \
+  case HH:                                                                             \
+    if (c.dk == 4) { launch_rows_sd_one<HH, 1>(c, n16, n64, n_hub, part, s); return true; }  \
+    if (c.dk == 8) { launch_rows_sd_one<HH, 2>(c, n16, n64, n_hub, part, s); return true; }  \
+    if (c.dk == 16) { launch_rows_sd_one<HH, 4>(c, n16, n64, n_hub, part, s); return true; } \
+    return false;
+  // (8 heads keep the two launches: their long-row body needs 96 - 123 VGPRs, and one kernel would run the <= 16-entry rows -- 54 - 56
+  //  VGPRs, 8 waves per SIMD in a launch of their own -- at 4 - 5)
+  switch (c.h) {
+    GNPDE_SD1(1) GNPDE_SD1(2) GNPDE_SD1(4)
+    default: return false;
+  }
+#undef GNPDE_SD1
 }
 
 template <int TYPE, int H, bool VEC4>
@@ -1174,7 +1241,7 @@ size_t attention_workspace_bytes(const gnpde_graph_t* g, int h, bool gat);
 // kernel arguments -- the backward pass continues from there
 static int edge_attention_impl(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, float* att_edge,
                                float* prods_edge, void* ws, size_t ws_bytes, hipStream_t stream, const Fork* fork,
-                               bool stats_only, AttArgs* args_out, bool hubs_only = false, int pass_only = 0) {
+                               bool stats_only, AttArgs* args_out, bool hubs_only = false, int pass_only = 0, HubDefer* defer = nullptr) {
   GNPDE_CHECK_ARG(g && at, GNPDE_EINVAL, "edge_attention: null descriptor");
   GNPDE_CHECK_ARG(stats_only || w_mean_csr || att_edge || prods_edge, GNPDE_EINVAL, "edge_attention: no output requested");
   GNPDE_CHECK_ARG(at->heads >= 1 && at->att_dim >= at->heads && at->att_dim % at->heads == 0, GNPDE_EINVAL,
@@ -1264,6 +1331,23 @@ static int edge_attention_impl(const gnpde_graph_t* g, const gnpde_attention_t* 
       c2.sp_mode = 3;
       if (launch_sd_with_hubs(c2, g->n_bin16, g->n_bin64, g->n_long_rows > 0 ? g->n_long_chunks : 0, part, g->long_chunk_first, stream)) {
         GNPDE_LAUNCH_CHECK();
+        return 0;
+      }
+    }
+    // the caller's aggregation follows on this stream and takes the hub rows' normalisation (launch_edge_attention_deferred): one launch
+    if (defer != nullptr && a.type == GNPDE_ATT_SCALED_DOT && vec4 && fork == nullptr && a.edge_w == nullptr && w_mean_csr != nullptr &&
+        g->row_begin == 0 && at->n_key_rows == 0 && (a.dk == 4 || a.dk == 8 || a.dk == 16) &&
+        (g->n_long_rows == 0 || (g->long_chunk_first != nullptr && g->long_chunk_begin != nullptr && g->long_chunk_end != nullptr)) &&
+        g_tune[GNPDE_TUNE_ATT_ONE_LAUNCH] == 0 && g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] == 0 && g_tune[GNPDE_TUNE_ATT_ROWS16] == 0) {
+      const int n_hub = g->n_long_rows > 0 ? g->n_long_chunks : 0;
+      if (launch_sd_one(c, g->n_bin16, g->n_bin64, n_hub, part, stream)) {
+        GNPDE_LAUNCH_CHECK();
+        defer->part = part;
+        defer->scores = a.scores;
+        defer->chunk_first = g->long_chunk_first;
+        defer->w_out = w_mean_csr;
+        defer->h = a.h;
+        defer->taken = 1;
         return 0;
       }
     }
@@ -1414,6 +1498,16 @@ __global__ __launch_bounds__(kBlock) void stats_merge_kernel(float* __restrict__
 int launch_edge_attention(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, float* att_edge,
                           float* prods_edge, void* ws, size_t ws_bytes, hipStream_t stream, const Fork* fork) {
   return edge_attention_impl(g, at, w_mean_csr, att_edge, prods_edge, ws, ws_bytes, stream, fork, false, nullptr);
+}
+
+// The attention of an evaluation whose aggregation (launch_spmm_rhs with `defer`, same stream) follows.  Where the plain scaled-dot
+// row softmax runs (whole graph, no re-weighting, a specialised (heads, d_k)) it takes ONE launch, leaves the weights of the hub
+// rows' entries unwritten and sets defer->taken: the aggregation's hub-chunk items form and store them.  Everything else runs
+// launch_edge_attention's launches and leaves defer->taken == 0 (the weights are complete).
+int launch_edge_attention_deferred(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
+                                   hipStream_t stream, HubDefer* defer) {
+  *defer = HubDefer{};
+  return edge_attention_impl(g, at, w_mean_csr, nullptr, nullptr, ws, ws_bytes, stream, nullptr, false, nullptr, false, 0, defer);
 }
 
 // w_mean_csr[p] for the entries of the rows longer than GNPDE_LONG_ROW only (row softmax path); the caller attends the

@@ -114,7 +114,9 @@ enum {
                                        // elements (the fp32 mapping, 8-byte gathers), 2 = four rows per wave, 16 lanes x 8 elements (16-byte gathers; d % 8 == 0)
   GNPDE_TUNE_KNN_SPLITS = 19,         // column splits S of the k-nearest-neighbour search (knn.hip): 0 = from n and the CU count, S > 0 forces S (capped by the merge kernel's limits)
   GNPDE_TUNE_KNN_VARIANT = 20,        // A/B of the search's tile kernel: 1 = 32-float K chunks with the 256-key buffers (k > 32), 2 = the 256-key buffers for every k
-  GNPDE_TUNE_COUNT = 21
+  GNPDE_TUNE_ATT_ONE_LAUNCH = 21,     // 1: the row softmax of a GRAND-nl evaluation keeps its two launches with the hub rows normalised by the second (A/B against the one
+                                      // launch whose hub rows the aggregation's chunk items normalise)
+  GNPDE_TUNE_COUNT = 22
 };
 extern int g_tune[GNPDE_TUNE_COUNT];
 
@@ -154,10 +156,30 @@ struct LoPair {
   uint16_t* out_y_lo = nullptr;     // nullable: bf16 rounding of out_y at the same element offsets
 };
 
+// Hub rows (more than GNPDE_LONG_ROW entries) of a row softmax whose normalisation is left to the aggregation that follows it
+// (attention.hip row_attention_sd_one_kernel -> spmm.hip hub-chunk items): the attention launch stored the scores of the hub
+// entries and one (maximum, sum) pair per head and 512-entry chunk; a chunk item folds its row's pairs, forms the head-mean
+// weight of each of its entries and stores it to w_out before it gathers -- the same float sequence as the attention's own
+// second phase, so weights and results are the same bits.
+struct HubDefer {
+  const float* part = nullptr;        // [n_long_chunks, 2 h]: per chunk, h maxima then h sums
+  const float* scores = nullptr;      // [e, h] (hub entries only are read)
+  const int* chunk_first = nullptr;   // chunk -> first chunk of its row (gnpde_graph_t.long_chunk_first)
+  float* w_out = nullptr;             // [e]: the weight buffer (== w_csr of the launch)
+  int h = 0;
+  int taken = 0;                      // set by launch_edge_attention_deferred when the one-launch form ran
+};
+
 // internal launchers used by the solver (defined in the kernel translation units)
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes,
-                    hipStream_t stream, const Fork* fork = nullptr, bool padded_rows = false, const LoPair* lo = nullptr);
+                    hipStream_t stream, const Fork* fork = nullptr, bool padded_rows = false, const LoPair* lo = nullptr,
+                    const HubDefer* defer = nullptr);
+// true where launch_spmm_rhs (no fork, no bf16 operand) runs kernels whose hub-chunk items can take a HubDefer
+bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int ld, const gnpde_epilogue_t& epi, const void* ws,
+                              bool padded_rows);
+int launch_edge_attention_deferred(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
+                                   hipStream_t stream, HubDefer* defer);
 
 // fp32 [n, d] (row stride ld) -> bf16 shadow [n, ld] (misc.hip)
 int launch_to_bf16(const float* src, long long n, int d, int ld, uint16_t* dst, hipStream_t s);

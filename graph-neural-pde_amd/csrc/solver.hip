@@ -7,6 +7,7 @@
 // solver loop reached from ODEblock.forward (src/block_constant.py:57-62,
 // src/block_transformer_attention.py:58-63): ~30 launches + ~10 elementwise launches per stage there,
 // 1 (GRAND-l) or 5 (GRAND-nl) launches per stage here and a single graph launch per forward pass.
+#include <atomic>
 #include <vector>
 #include "common.h"
 #include "graph_capture.h"
@@ -73,6 +74,9 @@ int check_rhs(const gnpde_rhs_t* r) {
   return 0;
 }
 
+// evaluations enqueued in the one-launch attention form (gnpde_one_launch_evaluations: the tests read the launch decision from it)
+static std::atomic<long long> g_one_launch_evals{0};
+
 // Enqueue f(u) with the given epilogue.  `ws` follows rhs_layout.
 int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& epi, char* ws, const RhsLayout& L,
                 hipStream_t s, const Fork* fork, const RhsRecord* record, const LoPair* lo) {
@@ -125,6 +129,18 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
       rc = launch_hub_attention(g, &at, wmean, ws + L.att, L.att_bytes, s);
       if (rc) return rc;
       return launch_attn_spmm(g, &at, wmean, u, r.d, r.ld, &epi, ws + L.spmm, L.spmm_bytes, s, padded);
+    }
+    // Whole-graph GRAND-nl with the plain scaled-dot row softmax, fp32 gather, aggregation next on this stream: the row attention is
+    // ONE launch, and the hub-chunk items of the aggregation normalise the hub rows (HubDefer) -- the weight buffer is complete after the
+    // aggregation, so a recorded solve takes this form too.  Whatever the attention launcher does not cover keeps its own launches.
+    if (lo == nullptr && fork == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && r.att.type == GNPDE_ATT_SCALED_DOT && r.att.norm_idx == 0 &&
+        !r.att.square_plus && r.att.edge_w_csr == nullptr && r.proj_row_end == 0 && r.n_state_rows <= g->n && g->row_begin == 0 &&
+        g_tune[GNPDE_TUNE_ATT_ONE_LAUNCH] == 0 && spmm_hub_defer_supported(g, u, r.d, r.ld, epi, ws + L.spmm, padded)) {
+      HubDefer defer;
+      rc = launch_edge_attention_deferred(g, &at, wmean, ws + L.att, L.att_bytes, s, &defer);
+      if (rc) return rc;
+      if (defer.taken) g_one_launch_evals.fetch_add(1, std::memory_order_relaxed);
+      return launch_spmm_rhs(g, wmean, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, nullptr, padded, nullptr, &defer);
     }
     rc = launch_edge_attention(g, &at, wmean, nullptr, nullptr, ws + L.att, L.att_bytes, s, fork);
     if (rc) return rc;
@@ -385,6 +401,8 @@ void drop_graph(gnpde_solver* s) {
 }
 
 }  // namespace
+
+extern "C" int64_t gnpde_one_launch_evaluations(void) { return gnpde::g_one_launch_evals.load(std::memory_order_relaxed); }
 
 extern "C" size_t gnpde_rhs_workspace_bytes(const gnpde_rhs_t* rhs) {
   if (check_rhs(rhs)) return 0;

@@ -39,6 +39,13 @@ struct SpmmArgs {
   // own term still reads u), and the epilogue stores the bf16 rounding of out_y to out_y_lo (nullable) as well
   const uint16_t* __restrict__ u_lo;
   uint16_t* out_y_lo;
+  // hub rows whose softmax the attention launch left un-normalised (HubDefer, common.h; kernels instantiated with DEFER): the
+  // hub-chunk items form the weights of their entries themselves and store them to w_out (the buffer `w` points to)
+  const float* __restrict__ hub_part;
+  const float* __restrict__ hub_scores;
+  const int* __restrict__ hub_chunk_first;
+  float* w_out;
+  int hub_h;
 };
 
 
@@ -373,6 +380,82 @@ __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs
   }
 }
 
+// DEFER: the weights of a hub chunk's entries from the stored scores and the chunk statistics of the chunk's row -- the float sequence of
+// hub_normalise_body (attention.hip), so the same bits: per head the maximum over the row's chunks, l += sum_c * expf(max_c - m) in
+// chunk order, rcp(l + 1e-16f); per entry the sum over the heads of exp2((s - m) log2 e) * rcp in head order, then / h -- both sums as
+// the fused multiply-adds the compiler contracts them to there (written out here: left to the compiler, the four-head form below
+// became packed multiplications and separate additions, one ulp away on some entries).  Every lane
+// folds the statistics of head lane % h (h <= 8: the same addresses across the wave, one dependent chain per wave, before the first
+// gather of a 512-entry item); an entry's lane fetches them by head.  No cross-block dependency: the attention launch has ended.
+struct HubStat { float m, rinv; };
+__device__ __forceinline__ HubStat hub_row_stat(const SpmmArgs& a, int chunk, int row, int lane) {
+  const int h = a.hub_h, head = lane % h;
+  const int c0 = __builtin_amdgcn_readfirstlane(a.hub_chunk_first[chunk]);
+  const int nch = (__builtin_amdgcn_readfirstlane(a.rowptr[row + 1]) - __builtin_amdgcn_readfirstlane(a.rowptr[row]) + GNPDE_LONG_ROW - 1) /
+                  GNPDE_LONG_ROW;
+  const float* q0 = a.hub_part + static_cast<size_t>(c0) * 2 * h;
+  // four chunks per trip, their loads issued together (a slot past the end re-reads the row's last chunk: a maximum taken twice changes
+  // nothing, its share of the sum is skipped): written chunk by chunk every statistic was a dependent round trip of its own, up to
+  // 2 x 26 of them in front of the first gather of the largest hub's items
+  constexpr int B = 4;
+  float m = -INFINITY;
+  for (int i0 = 0; i0 < nch; i0 += B) {
+    float v[B];
+#pragma unroll
+    for (int j = 0; j < B; ++j) v[j] = q0[(i0 + j < nch ? i0 + j : nch - 1) * 2 * h + head];
+#pragma unroll
+    for (int j = 0; j < B; ++j) m = fmaxf(m, v[j]);
+  }
+  float l = 0.f;
+  for (int i0 = 0; i0 < nch; i0 += B) {
+    float mx[B], sm[B];
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const float* q = q0 + (i0 + j < nch ? i0 + j : nch - 1) * 2 * h;
+      mx[j] = q[head];
+      sm[j] = q[h + head];
+    }
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const float t = fmaf(sm[j], expf(mx[j] - m), l);
+      l = i0 + j < nch ? t : l;
+    }
+  }
+  HubStat st;
+  st.m = m;
+  st.rinv = __builtin_amdgcn_rcpf(l + 1e-16f);
+  return st;
+}
+// weight of entry p (a valid position for EVERY lane: the statistics travel by cross-lane reads)
+__device__ __forceinline__ float hub_entry_weight(const SpmmArgs& a, const HubStat& st, int p) {
+  const int h = a.hub_h;
+  float acc = 0.f;
+  if (h == 4) {    // (wave-uniform) the headline head count: one 16-byte load of the entry's scores
+    const float4 sc = *reinterpret_cast<const float4*>(a.hub_scores + static_cast<size_t>(p) * 4);
+    acc = fmaf(__builtin_amdgcn_exp2f((sc.x - __shfl(st.m, 0, kWave)) * 1.44269504088896341f), __shfl(st.rinv, 0, kWave), acc);
+    acc = fmaf(__builtin_amdgcn_exp2f((sc.y - __shfl(st.m, 1, kWave)) * 1.44269504088896341f), __shfl(st.rinv, 1, kWave), acc);
+    acc = fmaf(__builtin_amdgcn_exp2f((sc.z - __shfl(st.m, 2, kWave)) * 1.44269504088896341f), __shfl(st.rinv, 2, kWave), acc);
+    acc = fmaf(__builtin_amdgcn_exp2f((sc.w - __shfl(st.m, 3, kWave)) * 1.44269504088896341f), __shfl(st.rinv, 3, kWave), acc);
+  } else {
+    for (int head = 0; head < h; ++head)
+      acc = fmaf(__builtin_amdgcn_exp2f((a.hub_scores[static_cast<size_t>(p) * h + head] - __shfl(st.m, head, kWave)) * 1.44269504088896341f),
+                 __shfl(st.rinv, head, kWave), acc);
+  }
+  return acc / static_cast<float>(h);
+}
+// ids and weights of the 64 entries at `base` of an item: the weights from memory, or formed (and stored) here for a hub chunk
+template <bool DEFER>
+__device__ __forceinline__ float item_weight(const SpmmArgs& a, const HubStat& hs, int chunk, int me, bool in, int e1) {
+  if constexpr (DEFER) {
+    if (chunk >= 0) {    // wave-uniform
+      const float w = hub_entry_weight(a, hs, in ? me : e1 - 1);
+      if (in) a.w_out[me] = w;
+      return in ? w : 0.0f;
+    }
+  }
+  return in ? a.w[me] : 0.0f;
+}
+
 // U gathers of one wave (G neighbours each) from the 64 (column id, weight) pairs held one per lane in cv / wv.
 // G == 1: the entry is wave-uniform -> v_readlane, row base address in SGPRs.  TAIL: entries >= cnt are skipped.
 template <int VEC, int L, int U, bool TAIL, bool FULL, bool LO = false>
@@ -510,7 +593,7 @@ __global__ __launch_bounds__(kWave) void spmm_wide_kernel(const SpmmArgs a) {
 // Each half keeps the wide kernel's summation order -- even entries into one accumulator, odd entries into a second, in
 // CSR order, then even + odd -- so the result is bit-identical to the shared-row mode whatever row a row is paired with.
 // A pair with a longer row falls back to the shared-row mode for its two rows in turn; hub chunks are shared-row items.
-template <int VEC, int U, bool FULL, bool LO = false>
+template <int VEC, int U, bool FULL, bool LO = false, bool DEFER = false>
 __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int e0, int e1, int chunk, int lane, int sub, int col,
                                                 bool col_ok, bool pre_ok, float alpha, float beta) {
   constexpr int L = 32, G = 2;
@@ -528,11 +611,15 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
   float acc[VEC];
 #pragma unroll
   for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+  HubStat hs{};
+  if constexpr (DEFER) {
+    if (chunk >= 0) hs = hub_row_stat(a, chunk, row, lane);
+  }
   for (int base = e0; base < e1; base += kWave) {
     const int me = base + lane;
     const bool in = me < e1;
     const int cv = in ? a.colidx[me] : 0;     // ONE coalesced load of 64 column ids ...
-    const float wv = in ? a.w[me] : 0.0f;     // ... and weights per wave
+    const float wv = item_weight<DEFER>(a, hs, chunk, me, in, e1);     // ... and weights per wave
     const int cnt = (e1 - base) < kWave ? (e1 - base) : kWave;   // wave-uniform
     // full batches of G*U entries without predicates (all U gathers issue back to back), then one predicated tail
     int t0 = 0;
@@ -559,7 +646,7 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
   }
 }
 
-template <int VEC, bool FULL, bool LO = false>
+template <int VEC, bool FULL, bool LO = false, bool DEFER = false>
 __global__ __launch_bounds__(kWave) void spmm_pair_kernel(const SpmmArgs a) {
   constexpr int L = 32, U = 16;   // 16 gathers in flight per half
   const int lane = threadIdx.x & (kWave - 1);
@@ -579,7 +666,7 @@ __global__ __launch_bounds__(kWave) void spmm_pair_kernel(const SpmmArgs a) {
     const int row = __builtin_amdgcn_readfirstlane(a.lc_row[chunk]);
     const int e0 = __builtin_amdgcn_readfirstlane(a.lc_begin[chunk]);
     const int e1 = __builtin_amdgcn_readfirstlane(a.lc_end[chunk]);
-    shared_row_item<VEC, U, FULL, LO>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
+    shared_row_item<VEC, U, FULL, LO, DEFER>(a, row, e0, e1, chunk, lane, half, col, col_ok, pre_ok, alpha, beta);
     return;
   }
   const int per = rows_per_xcd(a);
@@ -911,7 +998,15 @@ inline unsigned pair_grid(const SpmmArgs& a) {
   return static_cast<unsigned>(blocks * kXcds);
 }
 
+// a launch with hub chunks whose weights are still to be formed (SpmmArgs::hub_part)
+inline bool hub_deferred(const SpmmArgs& a) { return a.hub_part != nullptr && a.chunk_end > a.chunk_begin; }
+
 void launch_pair(const SpmmArgs& a, hipStream_t s) {
+  if (hub_deferred(a)) {    // hub-chunk items that normalise their row's softmax (the row pairs: the same code)
+    if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true, false, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
+    else hipLaunchKernelGGL((spmm_pair_kernel<4, false, false, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
+    return;
+  }
   if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
   else hipLaunchKernelGGL((spmm_pair_kernel<4, false>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
 }
@@ -1550,8 +1645,9 @@ int launch_adjoint_rows(const gnpde_graph_t* g, const float* w_csr, const float*
 
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes, hipStream_t stream,
-                    const Fork* fork, bool padded_rows, const LoPair* lo) {
+                    const Fork* fork, bool padded_rows, const LoPair* lo, const HubDefer* defer) {
   if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
+  if (defer != nullptr && (defer->taken == 0 || g == nullptr || g->n_long_rows == 0)) defer = nullptr;
   // (a plain aggregation from a shadow has no fp32 table at all)
   GNPDE_CHECK_ARG(g && (u || (lo && plain_out)) && (w_csr || g->e == 0), GNPDE_EINVAL, "spmm: null pointer");
   GNPDE_CHECK_ARG(d >= 1 && ld >= d, GNPDE_EINVAL, "spmm: bad d=%d ld=%d", d, ld);
@@ -1635,6 +1731,20 @@ int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, 
     return dispatch_rows<1>(arg, st);
   };
   const bool forked = fork != nullptr && fork->aux != nullptr && g->n_long_rows > 0;
+  if (defer != nullptr) {
+    // the hub entries' weights do not exist yet: only the kernels whose chunk items form them may run (spmm_hub_defer_supported)
+    const int slots = (d + 3) / 4;
+    GNPDE_CHECK_ARG(a16 && lo == nullptr && !forked && slots > 16 && slots <= 32 && 2LL * g->n_bin16 >= g->n && g->row_begin == 0 &&
+                    g_tune[GNPDE_TUNE_SPMM_PART] == 0 &&
+                    defer->part && defer->scores && defer->chunk_first && defer->w_out == w_csr && defer->h >= 1 && defer->h <= 8 &&
+                    aligned(defer->scores, 16),
+                    GNPDE_EINVAL, "spmm: deferred hub weights need the row-pair kernel (16-byte lanes, d = 68..128, mostly short rows, the whole graph; d=%d ld=%d)", d, ld);
+    a.hub_part = defer->part;
+    a.hub_scores = defer->scores;
+    a.hub_chunk_first = defer->chunk_first;
+    a.w_out = defer->w_out;
+    a.hub_h = defer->h;
+  }
   // rows and long-row chunks in one launch, then the per-row reduction of the chunk partials (a last-arriver
   // reduction inside the kernel was measured 1.7x slower: every agent-scope release fence writes back the
   // XCD's dirty L2 lines); with a fork the chunks + reduction run as a parallel branch.  The boundary pass of a
@@ -1676,6 +1786,24 @@ int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, 
   return 0;
 }
 
+
+// the route test of launch_spmm_rhs for an epilogue launch, ahead of the attention that decides on the one-launch form
+bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int ld, const gnpde_epilogue_t& e, const void* ws,
+                              bool padded_rows) {
+  // the row-pair kernel (dispatch_rows<4>: 17..32 lanes of 16 bytes, at least half of the rows with <= 16 entries).  The wide-row kernel is
+  // left as it is: with the deferred path its instantiations need 92 - 101 VGPRs instead of 80 - 86 (a wave per SIMD less for EVERY row of
+  // the launch) and spill SGPRs, for the sake of the hub chunks alone.
+  const int slots = (d + 3) / 4;
+  if (g == nullptr || u == nullptr || slots <= 16 || slots > 32 || 2LL * g->n_bin16 < g->n || g->row_begin != 0 ||
+      g_tune[GNPDE_TUNE_SPMM_PART] != 0)
+    return false;
+  bool a16 = (d % 4 == 0 || padded_rows) && (ld % 4 == 0) && aligned(u, 16) && aligned(ws, 16);
+  if (e.stage == GNPDE_STAGE_LINCOMB)
+    for (int j = 0; j < e.n_prev && j < GNPDE_MAX_PREV; ++j) a16 = a16 && aligned(e.prev[j], 16);
+  const void* ptrs[] = {e.x0, e.y, e.k1, e.k2, e.k3, e.out_k, e.out_y};
+  for (const void* p : ptrs) a16 = a16 && aligned(p, 16);
+  return a16;
+}
 
 bool attn_spmm_supported(const gnpde_graph_t* g, const gnpde_attention_t& at, int d, int ld, const float* u,
                          const gnpde_epilogue_t& e) {
