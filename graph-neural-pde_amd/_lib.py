@@ -29,7 +29,7 @@ TUNE_ROW_FUSION, TUNE_ONE_PASS_VARIANT, TUNE_SPMM_PART, TUNE_XCD_ROWS, TUNE_HUB_
 TUNE_KNN_SPLITS = 19     # column splits of the k-nearest-neighbour search: 0 = chosen from n and the CU count, S > 0 forces S
 METRIC_SQEUCLIDEAN = 0   # GNPDE_METRIC_* of include/gnpde.h (the key of a pair in gnpde_knn_metric / gnpde_radius_*)
 METRIC_POINCARE = 1
-TUNE_KNN_VARIANT = 20    # tile-kernel variants of the search (A/B): 1 = 32-float K chunks for k > 32, 2 = the k > 32 kernel for every k
+TUNE_KNN_VARIANT = 20    # tile kernel of the search (A/B): 2 = the k > 32 kernel (256-key row buffers) for every k; 1 is removed and refused
 TUNE_ATT_ONE_LAUNCH = 21  # 1: the row attention of a GRAND-nl evaluation keeps its two launches (A/B against the one-launch form)
 TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)
 SAMPLING_EMPTY_COLUMN, SAMPLING_NONFINITE, SAMPLING_ZERO_MASS, SAMPLING_INDEX_RANGE = 1, 2, 4, 8   # GNPDE_SAMPLING_* flag bits

@@ -10,7 +10,9 @@ objs=""
 pids=""
 for f in error.cpp graph_prep.cpp spmm.hip linear.hip attention.hip fused_attn.hip backward.hip adjoint.hip solver.hip misc.hip early_stop.hip sharded.hip rewire.hip twohop.hip dopri5.hip adjoint_adaptive.hip graph_device.hip knn.hip gdc.hip gdc_push.hip posdist.hip edge_sampling.hip deepwalk.hip; do
   o="build/${f%.*}.o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ epilogue.h -nt "$o" ] || [ rhs.h -nt "$o" ] || [ wave_sort.h -nt "$o" ] || [ knn_tile.h -nt "$o" ] || [ philox.h -nt "$o" ] || [ embedded_pair.h -nt "$o" ] || [ graph_capture.h -nt "$o" ] || [ "${ROOT}/include/gnpde.h" -nt "$o" ]; then
+  stale=""
+  for h in "$f" *.h "${ROOT}/include/gnpde.h"; do if [ "$h" -nt "$o" ]; then stale=1; fi; done
+  if [ ! -f "$o" ] || [ -n "$stale" ]; then
     rm -f "$o"
     $HIPCC $FLAGS -c "$f" -o "$o" &
     pids="$pids $!"

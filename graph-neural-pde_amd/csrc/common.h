@@ -113,7 +113,7 @@ enum {
   GNPDE_TUNE_LO_MAPPING = 18,          // bf16 gather operand, rows of 17..32 16-byte lanes in graphs of mostly short rows (A/B): 1 = two rows per wave, 32 lanes x 4
                                        // elements (the fp32 mapping, 8-byte gathers), 2 = four rows per wave, 16 lanes x 8 elements (16-byte gathers; d % 8 == 0)
   GNPDE_TUNE_KNN_SPLITS = 19,         // column splits S of the k-nearest-neighbour search (knn.hip): 0 = from n and the CU count, S > 0 forces S (capped by the merge kernel's limits)
-  GNPDE_TUNE_KNN_VARIANT = 20,        // A/B of the search's tile kernel: 1 = 32-float K chunks with the 256-key buffers (k > 32), 2 = the 256-key buffers for every k
+  GNPDE_TUNE_KNN_VARIANT = 20,        // A/B of the search's tile kernel: 2 = the 256-key row buffers for every k; 1 (32-float K chunks) is decided and refused (profiles/knn_ab.jsonl)
   GNPDE_TUNE_ATT_ONE_LAUNCH = 21,     // 1: the row softmax of a GRAND-nl evaluation keeps its two launches with the hub rows normalised by the second (A/B against the one
                                       // launch whose hub rows the aggregation's chunk items normalise)
   GNPDE_TUNE_COUNT = 22

@@ -15,14 +15,13 @@
 //   loss_kernel         the partial losses (float64) summed in a fixed order by one workgroup
 #include "common.h"
 #include "philox.h"
+#include "select.h"
 
 #include <cmath>
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace gnpde {
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kMaxWalkLength = 127;
 constexpr int kMaxDim = 256;
@@ -187,8 +186,7 @@ __global__ __launch_bounds__(kBlock) void pair_kernel(const float* __restrict__ 
       if (live) st4(contrib + (static_cast<size_t>(walk) * (L + 1) + p) * d + 4 * li, acc);
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) loss += __shfl_xor(loss, off, kWave);
+  loss = wave_sum(loss);
   if (live && lane == 0) partial[walk] = loss * (positive ? mean_pos : mean_neg);
 }
 

@@ -18,6 +18,7 @@
 // Error conditions that depend on device data set bits of a device flag word (integer atomic OR) that the caller reads.
 #include "common.h"
 #include "philox.h"
+#include "select.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -25,8 +26,6 @@
 
 namespace gnpde {
 namespace {
-
-typedef unsigned long long u64;
 
 // Philox4x32-10 and stream_block (block `b` of stream (seed, stream, call)) are in philox.h
 
@@ -60,8 +59,7 @@ __global__ __launch_bounds__(kBlock) void node_importance_kernel(const int* __re
   const int b = cscptr[j], e = cscptr[j + 1];
   float sum = 0.0f;
   for (int p = b + lane; p < e; p += kWave) sum += att_mean[perm[cscpos[p]]];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, kWave);
+  sum = wave_sum(sum);
   if (lane == 0) {
     if (e == b) {
       atomicOr(flag, GNPDE_SAMPLING_EMPTY_COLUMN);
@@ -70,15 +68,6 @@ __global__ __launch_bounds__(kBlock) void node_importance_kernel(const int* __re
       out[j] = sum / static_cast<float>(e - b);
     }
   }
-}
-
-__device__ __forceinline__ unsigned key_of(float f) {   // monotone on the finite floats
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
 }
 
 // maximum of the logits as an integer maximum of their order-preserving images (order of arrival does not matter); *maxkey starts at 0
@@ -91,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void logit_max_kernel(const float* __restri
   for (long long j = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; j < n; j += stride) {
     const float v = s[j];
     if (!isfinite(v)) bad = true;
-    else best = max(best, key_of(v));
+    else best = max(best, ordered_key(v));
   }
   if (bad) atomicOr(flag, GNPDE_SAMPLING_NONFINITE);
 #pragma unroll
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void logit_weights_kernel(const float* __re
   const float v = s[j];
   u64 q = 0;
   if (mk != 0 && isfinite(v)) {
-    const float t = expf(v - value_of(mk));
+    const float t = expf(v - ordered_value(mk));
     q = static_cast<u64>(fminf(t, 1.0f) * 4294967296.0f);
   }
   w[j] = q;

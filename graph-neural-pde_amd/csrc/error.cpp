@@ -19,6 +19,8 @@ extern "C" int gnpde_tune(int32_t key, int32_t value) {
   const bool retired = key == gnpde::GNPDE_TUNE_RETIRED_0 || key == gnpde::GNPDE_TUNE_RETIRED_8 || key == gnpde::GNPDE_TUNE_RETIRED_13;
   GNPDE_CHECK_ARG(!retired || value == 0, GNPDE_EINVAL, "tune: key %d is retired: the variant %d it selected was removed (it was last in c657da7; "
                   "its measurements are in profiles/ and DESIGN.md)", key, value);
+  GNPDE_CHECK_ARG(key != gnpde::GNPDE_TUNE_KNN_VARIANT || value != 1, GNPDE_EINVAL, "tune: value 1 of key %d is retired: the 32-float K "
+                  "chunks of the neighbour search were removed, slower at both shapes (profiles/knn_ab.jsonl)", key);
   gnpde::g_tune[key] = value;
   return 0;
 }

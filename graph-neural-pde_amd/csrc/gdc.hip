@@ -19,7 +19,7 @@
 //              the threshold mode and the degree sums of the input normalisation.
 //   dense      column sums from the transposed slab, then dense[i, j0 + b] = X[i, b] / sum_b.
 #include "common.h"
-#include "wave_sort.h"
+#include "select.h"
 
 namespace gnpde {
 namespace {
@@ -30,7 +30,6 @@ constexpr int kGdcMaxTerms = 4097;       // M <= 4096
 constexpr int kGdcCap = 256;             // keys of a wave's candidate buffer: k + 64 <= CAP
 constexpr int kGdcSplitRows = 512;       // rows of a column that one wave streams before another split is opened
 constexpr int kGdcMaxSplits = 32;        // S * k <= 4096 keys in the merge (32 KiB of LDS)
-constexpr u64 kGdcPadKey = ~0ull;
 
 __host__ __device__ __forceinline__ int gdc_splits(long long n) {
   long long s = (n + kGdcSplitRows - 1) / kGdcSplitRows;
@@ -86,12 +85,7 @@ __global__ __launch_bounds__(kBlock) void gdc_transpose_kernel(const float* __re
 // sort the buffer's cnt keys, keep the k best; returns the new count, *bar = the k-th key once k are known
 __device__ __forceinline__ int gdc_prune(u64* buf, int cnt, int k, int lane, u64* bar) {
   wave_lds_sync();
-  int P = 2;
-  while (P < cnt) P <<= 1;
-  for (int p = cnt + lane; p < P; p += kWave) buf[p] = kGdcPadKey;
-  wave_lds_sync();
-  wave_sort(buf, P, lane);
-  const int nc = cnt < k ? cnt : k;
+  const int nc = wave_keep_best(buf, cnt, k, lane);
   if (nc == k) *bar = buf[k - 1];
   return nc;
 }
@@ -103,11 +97,9 @@ __global__ __launch_bounds__(kWave) void gdc_select_kernel(const float* __restri
   const int lane = threadIdx.x;
   const int b = blockIdx.x, s = blockIdx.y, S = gridDim.y;
   const float* xr = xt + static_cast<long long>(b) * n;
-  const long long begin = s * per;
-  long long end = begin + per;
-  if (end > n) end = n;
+  const long long begin = s * per, end = begin + per < n ? begin + per : n;
   int cnt = 0;
-  u64 bar = kGdcPadKey;
+  u64 bar = kPadKey;
   for (long long i = begin; i < end; i += 4 * kWave) {
     float v[4];
 #pragma unroll
@@ -121,14 +113,15 @@ __global__ __launch_bounds__(kWave) void gdc_select_kernel(const float* __restri
       const long long r = i + u * kWave + lane;
       const u64 key = (static_cast<u64>(~__float_as_uint(v[u])) << 32) | static_cast<u64>(static_cast<unsigned>(r));
       const bool ok = v[u] > 0.f && key < bar;
-      const u64 m = __ballot(ok);
-      if (ok) buf[cnt + __popcll(m & ((1ull << lane) - 1ull))] = key;
-      cnt += __popcll(m);
+      int kept;
+      const int pos = cnt + wave_rank(ok, lane, &kept);
+      if (ok) buf[pos] = key;
+      cnt += kept;
     }
   }
   cnt = gdc_prune(buf, cnt, k, lane, &bar);
   u64* out = partial + (static_cast<long long>(b) * S + s) * k;
-  for (int p = lane; p < k; p += kWave) out[p] = p < cnt ? buf[p] : kGdcPadKey;
+  for (int p = lane; p < k; p += kWave) out[p] = p < cnt ? buf[p] : kPadKey;
 }
 
 // one wave per column: the S sorted partial lists -> keys[(j0 + b) * k ..] (the k best, padded) and counts[j0 + b]
@@ -137,26 +130,16 @@ __global__ __launch_bounds__(kWave) void gdc_merge_kernel(const u64* __restrict_
   extern __shared__ __align__(16) unsigned char smem[];
   u64* buf = reinterpret_cast<u64*>(smem);
   const int lane = threadIdx.x, b = blockIdx.x;
-  const int total = S * k;
-  const u64* in = partial + static_cast<long long>(b) * total;
-  for (int p = lane; p < P; p += kWave) buf[p] = p < total ? in[p] : kGdcPadKey;
-  wave_lds_sync();
-  wave_sort(buf, P, lane);
+  wave_merge_lists(buf, P, partial + static_cast<long long>(b) * S * k, k, S, k, lane);
   u64* out = keys + (j0 + b) * k;
   int c = 0;
   for (int p0 = 0; p0 < k; p0 += kWave) {
     const int p = p0 + lane;
-    const u64 key = p < k ? buf[p] : kGdcPadKey;
+    const u64 key = p < k ? buf[p] : kPadKey;
     if (p < k) out[p] = key;
-    c += __popcll(__ballot(key != kGdcPadKey));
+    c += __popcll(__ballot(key != kPadKey));
   }
   if (lane == 0) counts[j0 + b] = c;
-}
-
-__device__ __forceinline__ float wave_sum_all(float s) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, kWave);
-  return s;
 }
 
 // one wave per column j of the whole result: keys[j * k .. + count) -> (row, j, value [/ column sum]) at offsets[j]
@@ -173,10 +156,10 @@ __global__ __launch_bounds__(kWave) void gdc_emit_kernel(const u64* __restrict__
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int p = lane + u * kWave;
-    key[u] = p < c ? in[p] : kGdcPadKey;
+    key[u] = p < c ? in[p] : kPadKey;
     v[u] = p < c ? __uint_as_float(~static_cast<unsigned>(key[u] >> 32)) : 0.f;
   }
-  const float sum = wave_sum_all(v[0] + v[1]);
+  const float sum = wave_sum(v[0] + v[1]);
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int p = lane + u * kWave;
@@ -194,13 +177,10 @@ __global__ __launch_bounds__(kWave) void gdc_count_kernel(const float* __restric
   const int lane = threadIdx.x;
   const int b = blockIdx.x, s = blockIdx.y, S = gridDim.y;
   const float* xr = xt + static_cast<long long>(b) * n;
-  const long long begin = s * per;
-  long long end = begin + per;
-  if (end > n) end = n;
+  const long long begin = s * per, end = begin + per < n ? begin + per : n;
   int c = 0;
   for (long long r = begin + lane; r < end; r += kWave) c += xr[r] >= eps ? 1 : 0;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, kWave);
+  c = wave_sum(c);
   if (lane == 0) part[b * S + s] = c;
 }
 
@@ -219,23 +199,21 @@ __global__ __launch_bounds__(kWave) void gdc_fill_kernel(const float* __restrict
   const int lane = threadIdx.x;
   const int b = blockIdx.x, s = blockIdx.y, S = gridDim.y;
   const float* xr = xt + static_cast<long long>(b) * n;
-  const long long begin = s * per;
-  long long end = begin + per;
-  if (end > n) end = n;
+  const long long begin = s * per, end = begin + per < n ? begin + per : n;
   long long pos = offsets[b];
   for (int t = 0; t < s; ++t) pos += part[b * S + t];
   for (long long i = begin; i < end; i += kWave) {
     const long long r = i + lane;
     const float v = r < end ? xr[r] : 0.f;
     const bool ok = r < end && v >= eps;
-    const u64 m = __ballot(ok);
+    int kept;
+    const long long p = pos + wave_rank(ok, lane, &kept);
     if (ok) {
-      const long long p = pos + __popcll(m & ((1ull << lane) - 1ull));
       out_ei[p] = r;
       out_ei[out_ld + p] = j0 + b;
       out_w[p] = v;
     }
-    pos += __popcll(m);
+    pos += kept;
   }
 }
 
@@ -248,7 +226,7 @@ __global__ __launch_bounds__(kWave) void gdc_segment_kernel(float* __restrict__ 
   const long long a = offsets[g], e = offsets[g + 1];
   float s = 0.f;
   for (long long p = a + lane; p < e; p += kWave) s += w[p];
-  s = wave_sum_all(s);
+  s = wave_sum(s);
   if (sums != nullptr && lane == 0) sums[g] = s;
   if (divide) {
     for (long long p = a + lane; p < e; p += kWave) w[p] = s != 0.f ? w[p] / s : 0.f;
@@ -261,7 +239,7 @@ __global__ __launch_bounds__(kWave) void gdc_colsum_kernel(const float* __restri
   const float* xr = xt + static_cast<long long>(b) * n;
   float s = 0.f;
   for (long long r = lane; r < n; r += kWave) s += xr[r];
-  s = wave_sum_all(s);
+  s = wave_sum(s);
   if (lane == 0) sums[b] = s;
 }
 
@@ -378,8 +356,7 @@ extern "C" int gnpde_gdc_topk(const gnpde_graph_t* g, const float* slab, int64_t
   if (rc != 0) return rc;
   hipLaunchKernelGGL(gdc_select_kernel, dim3(static_cast<unsigned>(ncols), static_cast<unsigned>(S)), dim3(kWave), 0, s, xt, n, per, k, partial);
   GNPDE_LAUNCH_CHECK();
-  int P = 2;
-  while (P < S * k) P <<= 1;
+  const int P = sort_length(S * k);
   hipLaunchKernelGGL(gdc_merge_kernel, dim3(static_cast<unsigned>(ncols)), dim3(kWave), static_cast<size_t>(P) * sizeof(u64), s, partial, S, k, P,
                      static_cast<long long>(j0), reinterpret_cast<u64*>(keys), reinterpret_cast<long long*>(counts));
   GNPDE_LAUNCH_CHECK();

@@ -18,7 +18,7 @@
 // tiling: bit-identical from run to run and for every S.
 #include "common.h"
 #include "knn_tile.h"
-#include "wave_sort.h"
+#include "select.h"
 
 namespace gnpde {
 namespace {
@@ -26,7 +26,6 @@ namespace {
 constexpr int kMaxK = 128;
 constexpr int kMaxMergeKeys = 4096;  // S * k of the merge kernel (32 KiB of LDS per row)
 constexpr int kMaxSplits = 32;
-constexpr u64 kPadKey = ~0ull;
 
 // sort the buffers of the wave's 16 rows, keep the k best of each, tighten the thresholds.  cnt / thr of local row 4 q + i
 // live in register i of the 16 lanes of group q.
@@ -38,12 +37,7 @@ __device__ __forceinline__ void wave_merge(u64* mybuf, int k, int lane, int (&cn
   for (int lr = 0; lr < 16; ++lr) {
     const int c = __shfl(cnt[lr & 3], (lr >> 2) * 16, kWave);
     u64* b = mybuf + lr * CAP;
-    int P = 2;
-    while (P < c) P <<= 1;
-    for (int p = c + lane; p < P; p += kWave) b[p] = kPadKey;
-    wave_lds_sync();
-    wave_sort(b, P, lane);
-    const int nc = c < k ? c : k;
+    const int nc = wave_keep_best(b, c, k, lane);
     float t = __builtin_inff();
     if (nc == k) t = __uint_as_float(static_cast<unsigned>(b[k - 1] >> 32));
     if (q == (lr >> 2)) {
@@ -55,20 +49,17 @@ __device__ __forceinline__ void wave_merge(u64* mybuf, int k, int lane, int (&cn
 
 // CAP: keys per row buffer (k <= CAP - 64 so that a step's 64 columns always fit after a merge).  The tile product and the key of
 // a pair are tile_sweep's (knn_tile.h); this kernel is the per-row streaming selection on those keys.
-template <int CAP, int KC, int METRIC>
+template <int CAP, int METRIC>
 __global__ __launch_bounds__(kBlock) void knn_tile_kernel(const float* __restrict__ x, const float* __restrict__ norms,
                                                          const float* __restrict__ ball, int n, int d, long long ldx, int k, int vec,
                                                          int tiles_per_split, long long* __restrict__ idx, float* __restrict__ dist,
                                                          u64* __restrict__ partial) {
   extern __shared__ __align__(16) unsigned char smem[];
   float* stage = reinterpret_cast<float*>(smem);                              // tile_sweep's operand chunks
-  u64* buf = reinterpret_cast<u64*>(stage + tile_lds_floats<KC>());           // [64][CAP]
+  u64* buf = reinterpret_cast<u64*>(stage + tile_lds_floats());                // [64][CAP]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
-  const long long row0 = static_cast<long long>(blockIdx.x) * kTM;
-  const long long col_begin = static_cast<long long>(blockIdx.y) * tiles_per_split * kTN;
-  long long col_end = col_begin + static_cast<long long>(tiles_per_split) * kTN;
-  if (col_end > n) col_end = n;
+  const TileRange tr = tile_range(tiles_per_split, n);
   u64* mybuf = buf + wave * 16 * CAP;
 
   float thr[4];
@@ -80,25 +71,24 @@ __global__ __launch_bounds__(kBlock) void knn_tile_kernel(const float* __restric
   }
 
   // selection.  C layout of a 16x16 tile: column = lane & 15, row = 4 * (lane >> 4) + register
-  tile_sweep<KC, METRIC>(
-      x, norms, ball, n, d, ldx, vec, row0, col_begin, col_end, stage,
+  tile_sweep<METRIC>(
+      x, norms, ball, n, d, ldx, vec, tr, stage,
       [&](long long) {
         const bool full = cnt[0] > CAP - kTN || cnt[1] > CAP - kTN || cnt[2] > CAP - kTN || cnt[3] > CAP - kTN;
         if (__any(full)) wave_merge<CAP>(mybuf, k, lane, cnt, thr);
       },
       [&](int i, int, long long, long long col, float D, bool valid) {
         const bool ok = valid && D < thr[i];
-        const u64 m = __ballot(ok);
-        const unsigned g = static_cast<unsigned>(m >> (16 * q)) & 0xffffu;
-        const int pos = cnt[i] + __popc(g & ((1u << r) - 1u));
+        int kept;
+        const int pos = cnt[i] + group16_rank(ok, q, r, &kept);
         if (ok) mybuf[(4 * q + i) * CAP + pos] = (static_cast<u64>(__float_as_uint(D)) << 32) | static_cast<unsigned>(col);
-        cnt[i] += __popc(g);
+        cnt[i] += kept;
       });
 
   wave_merge<CAP>(mybuf, k, lane, cnt, thr);
 #pragma unroll
   for (int lr = 0; lr < 16; ++lr) {
-    const long long row = row0 + 16 * wave + lr;
+    const long long row = tr.row0 + 16 * wave + lr;
     const int c = __shfl(cnt[lr & 3], (lr >> 2) * 16, kWave);
     if (row >= n) continue;
     const u64* b = mybuf + lr * CAP;
@@ -121,17 +111,7 @@ __global__ __launch_bounds__(kWave) void knn_merge_kernel(const u64* __restrict_
   u64* b = reinterpret_cast<u64*>(smem);
   const long long row = blockIdx.x;
   const int lane = threadIdx.x;
-  const int total = splits * k;
-  for (int p = lane; p < P; p += kWave) {
-    u64 key = kPadKey;
-    if (p < total) {
-      const int s = p / k, j = p - s * k;
-      key = partial[(static_cast<long long>(s) * n + row) * k + j];
-    }
-    b[p] = key;
-  }
-  wave_lds_sync();
-  wave_sort(b, P, lane);
+  wave_merge_lists(b, P, partial + row * k, static_cast<long long>(n) * k, splits, k, lane);
   for (int p = lane; p < k; p += kWave) {
     const u64 key = b[p];
     idx[row * k + p] = static_cast<long long>(key & 0xffffffffull);
@@ -142,27 +122,16 @@ __global__ __launch_bounds__(kWave) void knn_merge_kernel(const u64* __restrict_
   }
 }
 
-// Column splits: one when the row tiles alone give every CU a workgroup, otherwise enough to reach the CU count; never more
-// than the merge kernel sorts (S * k <= 4096, S <= 32) or than there are column tiles.  gnpde_tune(19, S) forces S (same caps).
+// Column splits (select.h): a workgroup per CU, never more than the merge kernel sorts (S * k <= 4096, S <= 32)
 int choose_splits(long long n, int k) {
-  const long long tiles = (n + kTM - 1) / kTM;
-  long long s = g_tune[GNPDE_TUNE_KNN_SPLITS];
-  if (s <= 0) s = tiles >= num_cus() ? 1 : (num_cus() + tiles - 1) / tiles;
-  if (s > kMaxSplits) s = kMaxSplits;
-  if (s > kMaxMergeKeys / k) s = kMaxMergeKeys / k;
-  if (s > tiles) s = tiles;
-  if (s < 1) s = 1;
-  // splits that would get no column tile are dropped
-  const long long per = (tiles + s - 1) / s;
-  s = (tiles + per - 1) / per;
-  return static_cast<int>(s);
+  return column_splits(n, 1, kMaxSplits, kMaxMergeKeys / k, num_cus(), g_tune[GNPDE_TUNE_KNN_SPLITS]);
 }
 
-template <int CAP, int KC, int METRIC>
+template <int CAP, int METRIC>
 int launch_tiles(const float* x, const float* norms, const float* ball, int n, int d, int ldx, int k, int splits, long long* idx,
                  float* dist, u64* partial, hipStream_t s) {
-  const size_t lds = static_cast<size_t>(tile_lds_floats<KC>()) * sizeof(float) + static_cast<size_t>(kTM) * CAP * sizeof(u64);
-  auto kern = knn_tile_kernel<CAP, KC, METRIC>;
+  const size_t lds = static_cast<size_t>(tile_lds_floats()) * sizeof(float) + static_cast<size_t>(kTM) * CAP * sizeof(u64);
+  auto kern = knn_tile_kernel<CAP, METRIC>;
   static bool attr_set = false;
   if (!attr_set) {
     GNPDE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -209,24 +178,16 @@ extern "C" int gnpde_knn_metric(const float* x, int32_t n, int32_t d, int32_t ld
   long long* out = reinterpret_cast<long long*>(idx);
   int rc = launch_norms(x, n, d, ldx, norms, ball, s);
   if (rc != 0) return rc;
-  // k <= 32: 128-key row buffers, 74 KiB of LDS with the 16-float chunks: two workgroups per CU.  Above: 256-key buffers fill the
-  // CU (138 KiB).  32-float chunks (twice the matrix work per barrier pair) measured SLOWER at the ogbn-arxiv shape and stay
-  // behind gnpde_tune(20, 1) for A/B (metric 0 only)
-  const int variant = g_tune[GNPDE_TUNE_KNN_VARIANT];
-  if (poincare) {
-    if (k <= 32) rc = launch_tiles<128, 16, GNPDE_METRIC_POINCARE>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
-    else rc = launch_tiles<256, 16, GNPDE_METRIC_POINCARE>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
-  } else if (k <= 32 && variant != 2) {
-    rc = launch_tiles<128, 16, GNPDE_METRIC_SQEUCLIDEAN>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
-  } else if (variant == 1) {
-    rc = launch_tiles<256, 32, GNPDE_METRIC_SQEUCLIDEAN>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
-  } else {
-    rc = launch_tiles<256, 16, GNPDE_METRIC_SQEUCLIDEAN>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
-  }
+  // k <= 32: 128-key row buffers, 74 KiB of LDS: two workgroups per CU.  Above: 256-key buffers fill the CU (138 KiB);
+  // gnpde_tune(20, 2) takes them for every k (A/B: faster at the Cora shape, slower at ogbn-arxiv, profiles/knn_ab.jsonl)
+  const bool small = k <= 32 && g_tune[GNPDE_TUNE_KNN_VARIANT] != 2;
+  with_metric(metric, [&](auto m) {
+    if (small) rc = launch_tiles<128, decltype(m)::value>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
+    else rc = launch_tiles<256, decltype(m)::value>(x, norms, ball, n, d, ldx, k, splits, out, dist, partial, s);
+  });
   if (rc != 0) return rc;
   if (splits > 1) {
-    int P = 2;
-    while (P < splits * k) P <<= 1;
+    const int P = sort_length(splits * k);
     const size_t lds = static_cast<size_t>(P) * sizeof(u64);
     hipLaunchKernelGGL(knn_merge_kernel, dim3(static_cast<unsigned>(n)), dim3(kWave), lds, s, partial, n, k, splits, P, metric, out,
                        dist);

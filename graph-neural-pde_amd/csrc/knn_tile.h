@@ -10,16 +10,19 @@
 // the same and the additions commute.  Keys are non-negative floats: their bit patterns order as unsigned integers.
 #pragma once
 #include "common.h"
+#include "select.h"
+#include <type_traits>
 
 namespace gnpde {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kTM = 64;              // rows per workgroup (16 per wave)
-constexpr int kTN = 64;              // columns per step
-// K chunk staged per barrier pair: KC = 16 or 32 floats of every row, LDS row stride KC + 4 floats (5 or 9 16-byte slots: odd, so
-// the 16 rows a ds_read_b128 touches fall on 16 different slots)
+constexpr int kTM = kKeyTile;        // rows per workgroup (16 per wave)
+constexpr int kTN = kKeyTile;        // columns per step
+// K chunk staged per barrier pair: 16 floats of every row, LDS row stride 20 floats (5 16-byte slots: odd, so the 16 rows a
+// ds_read_b128 touches fall on 16 different slots).  32-float chunks measured slower at both shapes (profiles/knn_ab.jsonl).
+constexpr int kKC = 16;
 
 // s_i = sum_c x_ic^2 (16 lanes per row, fp32); ball != nullptr: also a_i = max(1 - s_i, 2^-24), the Poincare denominator
 __global__ __launch_bounds__(kBlock) void knn_norms_kernel(const float* __restrict__ x, int n, int d, long long ldx,
@@ -98,21 +101,38 @@ __device__ __forceinline__ float4 mask_group(float4 v, int nv) {
   return v;
 }
 
-template <int KC>
-constexpr int tile_lds_floats() { return (kTM + kTN) * (KC + 4); }
+constexpr int tile_lds_floats() { return (kTM + kTN) * (kKC + 4); }
+
+// the rows and the column range of workgroup (blockIdx.x, blockIdx.y) of a sweep whose splits take tiles_per_split column tiles each
+struct TileRange { long long row0, col_begin, col_end; };
+__device__ __forceinline__ TileRange tile_range(int tiles_per_split, int n) {
+  const long long begin = static_cast<long long>(blockIdx.y) * tiles_per_split * kTN;
+  const long long end = begin + static_cast<long long>(tiles_per_split) * kTN;
+  return TileRange{static_cast<long long>(blockIdx.x) * kTM, begin, end < n ? end : n};
+}
+
+// f(the metric as a compile-time constant): the launch sites instantiate their kernel for it
+template <class F>
+inline void with_metric(int metric, F&& f) {
+  if (metric == GNPDE_METRIC_POINCARE) f(std::integral_constant<int, GNPDE_METRIC_POINCARE>());
+  else f(std::integral_constant<int, GNPDE_METRIC_SQEUCLIDEAN>());
+}
 
 // The sweep of one workgroup (all kBlock threads call it together): rows row0 .. row0 + 64 against the 64-column tiles of
 // [col_begin, col_end), ascending.  Per tile, after the products: begin_tile(col0) once, then visit(i, t, row, col, key, valid)
 // for the lane's 16 entries -- C layout of a 16x16 tile: col = col0 + 16 t + (lane & 15), row = row0 + 16 wave + 4 (lane >> 4) + i;
-// valid = row < n && col < col_end.  Both are called by every lane (ballots inside them are whole).  stage: tile_lds_floats<KC>()
+// valid = row < n && col < col_end.  Both are called by every lane (ballots inside them are whole).  stage: tile_lds_floats()
 // floats of LDS.  ball (metric 1): the a_i of knn_norms_kernel.
-template <int KC, int METRIC, class BeginTile, class Visit>
+template <int METRIC, class BeginTile, class Visit>
 __device__ __forceinline__ void tile_sweep(const float* __restrict__ x, const float* __restrict__ norms,
-                                           const float* __restrict__ ball, int n, int d, long long ldx, int vec, long long row0,
-                                           long long col_begin, long long col_end, float* stage, BeginTile&& begin_tile,
-                                           Visit&& visit) {
-  constexpr int LD = KC + 4;
-  constexpr int NP = KC / 16;          // staging passes: 256 threads cover 64 / NP rows of KC floats with one 16-byte group each
+                                           const float* __restrict__ ball, int n, int d, long long ldx, int vec, const TileRange& tr,
+                                           float* stage, BeginTile&& begin_tile, Visit&& visit) {
+  constexpr int KC = kKC, LD = KC + 4;
+  const long long row0 = tr.row0, col_begin = tr.col_begin, col_end = tr.col_end;
+  // staging passes: 256 threads cover 64 / NP rows of KC floats with one 16-byte group each.  NP is 1, and the loops over it stay:
+  // with pa / pb as plain float4s the compiler folds the two load forms of stage_loads into one and waits on them earlier
+  // (318 against 229 ms at the ogbn-arxiv shape)
+  constexpr int NP = KC / 16;
   float* As = stage;                   // [64][LD]
   float* Bs = As + kTM * LD;           // [64][LD]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

@@ -18,13 +18,11 @@
 // several workgroups share a CU and cover each other's barriers; no other tile shape has been measured.
 #include "common.h"
 #include "knn_tile.h"
+#include "select.h"
 
 namespace gnpde {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kKC = 16;
 constexpr int kBins = 2048;
 constexpr int kMaxRadiusSplits = 32;
 // a workgroup's u32 bin counts are flushed every 2^18 column tiles (64 * 64 * 2^18 = 2^30 keys at the most in one bin)
@@ -45,13 +43,10 @@ __global__ __launch_bounds__(kBlock) void radius_hist_kernel(const float* __rest
                                                             const float* __restrict__ ball, int n, int d, long long ldx, int vec,
                                                             int tiles_per_split, int pass, const RadiusRecord* __restrict__ rec,
                                                             u64* __restrict__ hist) {
-  __shared__ __align__(16) float stage[tile_lds_floats<kKC>()];
+  __shared__ __align__(16) float stage[tile_lds_floats()];
   __shared__ unsigned h[kBins];
   const int tid = threadIdx.x;
-  const long long row0 = static_cast<long long>(blockIdx.x) * kTM;
-  const long long col_begin = static_cast<long long>(blockIdx.y) * tiles_per_split * kTN;
-  long long col_end = col_begin + static_cast<long long>(tiles_per_split) * kTN;
-  if (col_end > n) col_end = n;
+  const TileRange tr = tile_range(tiles_per_split, n);
   const int shift = pass_shift(pass), mask = pass_bins(pass) - 1;
   const int hi = shift + (pass == 2 ? 10 : 11);                  // the bits above this pass's: the prefix
   const unsigned prefix = pass == 0 ? 0u : rec->prefix;
@@ -68,8 +63,8 @@ __global__ __launch_bounds__(kBlock) void radius_hist_kernel(const float* __rest
     __syncthreads();
   };
   int tiles_done = 0;
-  tile_sweep<kKC, METRIC>(
-      x, norms, ball, n, d, ldx, vec, row0, col_begin, col_end, stage,
+  tile_sweep<METRIC>(
+      x, norms, ball, n, d, ldx, vec, tr, stage,
       [&](long long) {
         if (++tiles_done == kFlushTiles) {   // (workgroup-uniform)
           flush();
@@ -101,19 +96,11 @@ __global__ __launch_bounds__(kWave) void radius_select_kernel(const u64* __restr
   for (int l = 0; l < lane; ++l) before += part[l];
   __syncthreads();                                   // rec is read above by every lane before the owner rewrites it
   if (rank >= before && rank < before + mine) {      // exactly one lane: the counts sum to more than the rank
-    u64 acc = before;
-    int bin = lane * per;
-    for (int j = 0; j < per; ++j) {
-      const u64 c = h[lane * per + j];
-      if (rank < acc + c) {
-        bin = lane * per + j;
-        break;
-      }
-      acc += c;
-    }
+    u64 inside = rank - before;
+    const int bin = rank_bin(h, lane * per, (lane + 1) * per, &inside);
     const unsigned grown = (prefix << (pass == 2 ? 10 : 11)) | static_cast<unsigned>(bin);
     rec->prefix = grown;
-    rec->rank = rank - acc;
+    rec->rank = inside;
     if (pass == 2) {
       const float key = __uint_as_float(grown);
       tau_out[0] = key;
@@ -127,24 +114,21 @@ __global__ __launch_bounds__(kBlock) void radius_count_kernel(const float* __res
                                                              const float* __restrict__ ball, int n, int d, long long ldx, int vec,
                                                              int tiles_per_split, const float* __restrict__ tau_dev, float tau_key,
                                                              long long* __restrict__ counts) {
-  __shared__ __align__(16) float stage[tile_lds_floats<kKC>()];
+  __shared__ __align__(16) float stage[tile_lds_floats()];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
-  const long long row0 = static_cast<long long>(blockIdx.x) * kTM;
-  const long long col_begin = static_cast<long long>(blockIdx.y) * tiles_per_split * kTN;
-  long long col_end = col_begin + static_cast<long long>(tiles_per_split) * kTN;
-  if (col_end > n) col_end = n;
+  const TileRange tr = tile_range(tiles_per_split, n);
   const unsigned tau = __float_as_uint(tau_dev != nullptr ? tau_dev[0] : tau_key);
   int cnt[4] = {0, 0, 0, 0};
-  tile_sweep<kKC, METRIC>(
-      x, norms, ball, n, d, ldx, vec, row0, col_begin, col_end, stage, [](long long) {},
+  tile_sweep<METRIC>(
+      x, norms, ball, n, d, ldx, vec, tr, stage, [](long long) {},
       [&](int i, int, long long, long long, float key, bool valid) { cnt[i] += (valid && __float_as_uint(key) <= tau) ? 1 : 0; });
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     int c = cnt[i];
 #pragma unroll
     for (int off = 8; off >= 1; off >>= 1) c += __shfl_xor(c, off, kWave);
-    const long long row = row0 + 16 * wave + 4 * q + i;
+    const long long row = tr.row0 + 16 * wave + 4 * q + i;
     if (r == 0 && row < n) counts[static_cast<long long>(blockIdx.y) * n + row] = c;
   }
 }
@@ -161,16 +145,8 @@ __global__ __launch_bounds__(kBlock) void radius_scan_kernel(long long* __restri
     long long tot = 0;
     if (row < n)
       for (int s = 0; s < splits; ++s) tot += counts[static_cast<long long>(s) * n + row];
-    sc[tid] = tot;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-      const long long v = tid >= off ? sc[tid - off] : 0;
-      __syncthreads();
-      sc[tid] += v;
-      __syncthreads();
-    }
+    long long o = block_scan_exclusive(tot, sc, &carry);
     if (row < n) {
-      long long o = carry + sc[tid] - tot;
       rowptr[row] = o;
       for (int s = 0; s < splits; ++s) {
         const long long c = counts[static_cast<long long>(s) * n + row];
@@ -178,8 +154,6 @@ __global__ __launch_bounds__(kBlock) void radius_scan_kernel(long long* __restri
         o += c;
       }
     }
-    carry += sc[kBlock - 1];
-    __syncthreads();
   }
   if (tid == 0) rowptr[n] = carry;
 }
@@ -190,48 +164,36 @@ __global__ __launch_bounds__(kBlock) void radius_fill_kernel(const float* __rest
                                                             int tiles_per_split, const float* __restrict__ tau_dev, float tau_key,
                                                             const long long* __restrict__ offsets, long long* __restrict__ out,
                                                             long long out_ld) {
-  __shared__ __align__(16) float stage[tile_lds_floats<kKC>()];
+  __shared__ __align__(16) float stage[tile_lds_floats()];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
-  const long long row0 = static_cast<long long>(blockIdx.x) * kTM;
-  const long long col_begin = static_cast<long long>(blockIdx.y) * tiles_per_split * kTN;
-  long long col_end = col_begin + static_cast<long long>(tiles_per_split) * kTN;
-  if (col_end > n) col_end = n;
+  const TileRange tr = tile_range(tiles_per_split, n);
   const unsigned tau = __float_as_uint(tau_dev != nullptr ? tau_dev[0] : tau_key);
   long long slot[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const long long row = row0 + 16 * wave + 4 * q + i;
+    const long long row = tr.row0 + 16 * wave + 4 * q + i;
     slot[i] = row < n ? offsets[static_cast<long long>(blockIdx.y) * n + row] : 0;
   }
   // a row's 16 lanes hold the columns col0 + 16 t + r: ascending in (t, r), the order the slots are handed out in
-  tile_sweep<kKC, METRIC>(
-      x, norms, ball, n, d, ldx, vec, row0, col_begin, col_end, stage, [](long long) {},
+  tile_sweep<METRIC>(
+      x, norms, ball, n, d, ldx, vec, tr, stage, [](long long) {},
       [&](int i, int, long long row, long long col, float key, bool valid) {
         const bool ok = valid && __float_as_uint(key) <= tau;
-        const u64 m = __ballot(ok);
-        const unsigned g = static_cast<unsigned>(m >> (16 * q)) & 0xffffu;
-        const long long pos = slot[i] + __popc(g & ((1u << r) - 1u));
+        int kept;
+        const long long pos = slot[i] + group16_rank(ok, q, r, &kept);
         if (ok && pos < out_ld) {     // (pos < out_ld always holds for the tau and the split of the count; a guard, not a path)
           out[pos] = row;
           out[out_ld + pos] = col;
         }
-        slot[i] += __popc(g);
+        slot[i] += kept;
       });
 }
 
 // Column splits of the radius sweeps: enough workgroups for two per CU (they are small), at most 32 and at most one per column
 // tile; gnpde_tune(19, S) forces S.
 int radius_splits(long long n) {
-  const long long tiles = (n + kTM - 1) / kTM;
-  long long s = g_tune[GNPDE_TUNE_KNN_SPLITS];
-  if (s <= 0) s = tiles >= 2 * num_cus() ? 1 : (2 * num_cus() + tiles - 1) / tiles;
-  if (s > kMaxRadiusSplits) s = kMaxRadiusSplits;
-  if (s > tiles) s = tiles;
-  if (s < 1) s = 1;
-  const long long per = (tiles + s - 1) / s;   // splits that would get no column tile are dropped
-  s = (tiles + per - 1) / per;
-  return static_cast<int>(s);
+  return column_splits(n, 2, kMaxRadiusSplits, kMaxRadiusSplits, num_cus(), g_tune[GNPDE_TUNE_KNN_SPLITS]);
 }
 
 size_t hist_bytes() { return 3 * kBins * sizeof(u64); }
@@ -308,12 +270,10 @@ extern "C" int gnpde_radius_quantile(const float* x, int64_t n, int32_t d, int32
   const Grid g = radius_grid(nn);
   const int vec = tile_vec(x, d, ldx);
   for (int pass = 0; pass < 3; ++pass) {
-    if (poincare)
-      hipLaunchKernelGGL(radius_hist_kernel<GNPDE_METRIC_POINCARE>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
+    with_metric(metric, [&](auto m) {
+      hipLaunchKernelGGL(radius_hist_kernel<decltype(m)::value>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
                          static_cast<long long>(ldx), vec, g.per, pass, w.rec, w.hist);
-    else
-      hipLaunchKernelGGL(radius_hist_kernel<GNPDE_METRIC_SQEUCLIDEAN>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
-                         static_cast<long long>(ldx), vec, g.per, pass, w.rec, w.hist);
+    });
     GNPDE_LAUNCH_CHECK();
     hipLaunchKernelGGL(radius_select_kernel, dim3(1), dim3(kWave), 0, s, w.hist, pass, rank, metric, w.rec, tau_out);
     GNPDE_LAUNCH_CHECK();
@@ -336,12 +296,10 @@ extern "C" int gnpde_radius_count(const float* x, int64_t n, int32_t d, int32_t 
   if (rc != 0) return rc;
   const Grid g = radius_grid(nn);
   const int vec = tile_vec(x, d, ldx);
-  if (poincare)
-    hipLaunchKernelGGL(radius_count_kernel<GNPDE_METRIC_POINCARE>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
+  with_metric(metric, [&](auto m) {
+    hipLaunchKernelGGL(radius_count_kernel<decltype(m)::value>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
                        static_cast<long long>(ldx), vec, g.per, tau_dev, tau_key, w.counts);
-  else
-    hipLaunchKernelGGL(radius_count_kernel<GNPDE_METRIC_SQEUCLIDEAN>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
-                       static_cast<long long>(ldx), vec, g.per, tau_dev, tau_key, w.counts);
+  });
   GNPDE_LAUNCH_CHECK();
   hipLaunchKernelGGL(radius_scan_kernel, dim3(1), dim3(kBlock), 0, s, w.counts, nn, static_cast<int>(g.grid.y),
                      reinterpret_cast<long long*>(rowptr));
@@ -361,17 +319,13 @@ extern "C" int gnpde_radius_fill(const float* x, int64_t n, int32_t d, int32_t l
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nn = static_cast<int>(n);
   const RadiusWs w = carve(workspace, n);
-  const bool poincare = metric == GNPDE_METRIC_POINCARE;
   const Grid g = radius_grid(nn);
   const int vec = tile_vec(x, d, ldx);
-  if (poincare)
-    hipLaunchKernelGGL(radius_fill_kernel<GNPDE_METRIC_POINCARE>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
+  with_metric(metric, [&](auto m) {
+    hipLaunchKernelGGL(radius_fill_kernel<decltype(m)::value>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
                        static_cast<long long>(ldx), vec, g.per, tau_dev, tau_key, w.counts, reinterpret_cast<long long*>(out_edge_index),
                        static_cast<long long>(out_ld));
-  else
-    hipLaunchKernelGGL(radius_fill_kernel<GNPDE_METRIC_SQEUCLIDEAN>, g.grid, dim3(kBlock), 0, s, x, w.norms, w.ball, nn, d,
-                       static_cast<long long>(ldx), vec, g.per, tau_dev, tau_key, w.counts, reinterpret_cast<long long*>(out_edge_index),
-                       static_cast<long long>(out_ld));
+  });
   GNPDE_LAUNCH_CHECK();
   return 0;
 }

@@ -14,18 +14,10 @@
 //                         the per-endpoint renormalisation (sums by float atomics, as the reference's scatter-add on a GPU).
 // 10 passes over [E] floats instead of a sort: ~40 us at the ogbn-arxiv shape.
 #include "common.h"
+#include "select.h"
 
 namespace gnpde {
 namespace {
-
-__device__ __forceinline__ unsigned key_of(float f) {   // monotone: a < b  <=>  key(a) < key(b)  (no NaNs expected)
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
 
 // select state in device memory: two ranks searched at once
 struct SelectState {
@@ -52,7 +44,7 @@ __global__ __launch_bounds__(kBlock) void select_hist_kernel(const float* __rest
   const unsigned p0 = st->prefix[0], p1 = st->prefix[1];
   const long long stride = static_cast<long long>(gridDim.x) * blockDim.x;
   for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const unsigned key = key_of(v[i]);
+    const unsigned key = ordered_key(v[i]);
     const unsigned digit = (key >> shift) & 255u;
     if ((key & hi_mask) == p0) atomicAdd(&h[0][digit], 1u);
     if ((key & hi_mask) == p1) atomicAdd(&h[1][digit], 1u);
@@ -68,15 +60,8 @@ __global__ __launch_bounds__(kBlock) void select_hist_kernel(const float* __rest
 __global__ __launch_bounds__(64) void select_pick_kernel(SelectState* st, int shift) {
   const int r = threadIdx.x;
   if (r < 2) {
-    unsigned long long k = st->k[r];
-    unsigned digit = 255;
-    for (unsigned dgt = 0; dgt < 256; ++dgt) {
-      const unsigned long long c = st->hist[r][dgt];
-      if (k < c) { digit = dgt; break; }
-      k -= c;
-    }
+    const unsigned digit = rank_bin(st->hist[r], 0, 256, &st->k[r]);
     st->prefix[r] |= digit << shift;
-    st->k[r] = k;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 512; i += blockDim.x) (&st->hist[0][0])[i] = 0;
@@ -84,7 +69,7 @@ __global__ __launch_bounds__(64) void select_pick_kernel(SelectState* st, int sh
 
 // torch's lerp of the two order statistics (aten lerp: the branch keeps it monotone and exact at both ends)
 __global__ void select_finish_kernel(const SelectState* st, float w, float* out) {
-  const float lo = value_of(st->prefix[0]), hi = value_of(st->prefix[1]);
+  const float lo = ordered_value(st->prefix[0]), hi = ordered_value(st->prefix[1]);
   const float diff = hi - lo;
   *out = w < 0.5f ? lo + w * diff : hi - diff * (1.0f - w);
 }
@@ -107,8 +92,7 @@ __global__ __launch_bounds__(kBlock) void keep_count_kernel(const float* __restr
     const long long i = base + static_cast<long long>(j) * kBlock + threadIdx.x;
     if (i < n && kept<kInclusive>(score[i], t)) ++c;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, kWave);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) counts[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -118,24 +102,12 @@ __global__ __launch_bounds__(kBlock) void keep_count_kernel(const float* __restr
 __global__ __launch_bounds__(kBlock) void keep_scan_kernel(unsigned* __restrict__ counts, int n_blocks, long long* out_count) {
   __shared__ unsigned buf[kBlock];
   __shared__ unsigned long long carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  if (threadIdx.x == 0) carry = 0;    // (read behind the scan's first barrier)
   for (int b0 = 0; b0 < n_blocks; b0 += kBlock) {
     const int i = b0 + threadIdx.x;
     const unsigned c = i < n_blocks ? counts[i] : 0;
-    buf[threadIdx.x] = c;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {   // Hillis-Steele inclusive scan
-      const unsigned add = threadIdx.x >= off ? buf[threadIdx.x - off] : 0;
-      __syncthreads();
-      buf[threadIdx.x] += add;
-      __syncthreads();
-    }
-    const unsigned incl = buf[threadIdx.x];
-    if (i < n_blocks) counts[i] = static_cast<unsigned>(carry) + incl - c;
-    __syncthreads();
-    if (threadIdx.x == kBlock - 1) carry += incl;
-    __syncthreads();
+    const unsigned long long before = block_scan_exclusive(c, buf, &carry);
+    if (i < n_blocks) counts[i] = static_cast<unsigned>(before);
   }
   if (threadIdx.x == 0) *out_count = static_cast<long long>(carry);
 }
@@ -156,9 +128,9 @@ __global__ __launch_bounds__(kBlock) void keep_scatter_kernel(const long long* _
   for (int j = 0; j < kItems; ++j) {
     const long long i = base + static_cast<long long>(j) * kBlock + threadIdx.x;
     const bool keep = i < n && kept<kInclusive>(score[i], t);
-    const unsigned long long ballot = __ballot(keep);
-    const unsigned before = __popcll(ballot & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_cnt[wave] = __popcll(ballot);
+    int wave_kept;
+    const unsigned before = wave_rank(keep, lane, &wave_kept);
+    if (lane == 0) wave_cnt[wave] = wave_kept;
     __syncthreads();
     unsigned wave_off = 0;
     for (int w = 0; w < wave; ++w) wave_off += wave_cnt[w];
@@ -233,8 +205,8 @@ extern "C" int gnpde_quantile(const float* v, int64_t n, double q, float* out, v
 // the select of gnpde_quantile with the caller's two ascending ranks, fed piece by piece (the histogram kernel ADDS to the state):
 // begin, then for pass 0 .. 3: hist over every piece, pick; then values.  Graph diffusion rewiring's threshold by avg_degree.
 __global__ void select_values_kernel(const SelectState* st, float* out) {
-  out[0] = value_of(st->prefix[0]);
-  out[1] = value_of(st->prefix[1]);
+  out[0] = ordered_value(st->prefix[0]);
+  out[1] = ordered_value(st->prefix[1]);
 }
 
 extern "C" int gnpde_rank_select_begin(int64_t k0, int64_t k1, void* workspace, size_t workspace_bytes, void* stream) {

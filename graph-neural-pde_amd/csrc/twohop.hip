@@ -16,6 +16,7 @@
 // Two passes of the same kernel: structure only (row counts -> exclusive scan = output row pointer; the caller reads the total and
 // allocates), then numbers.  Workspace: min(2048, 16 GiB / slab) slabs of ~4.2 n bytes.
 #include "common.h"
+#include "select.h"
 
 namespace gnpde {
 namespace {
@@ -174,22 +175,12 @@ __global__ __launch_bounds__(kBlock) void row_pointer_kernel(const int* __restri
   if (threadIdx.x == 0) {
     carry = 0;
     out[0] = 0;
-  }
-  __syncthreads();
+  }                                     // (carry is read behind the scan's first barrier)
   for (int b0 = 0; b0 < n; b0 += kBlock) {
     const int i = b0 + threadIdx.x;
-    buf[threadIdx.x] = i < n ? counts[i] : 0;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-      const long long add = threadIdx.x >= off ? buf[threadIdx.x - off] : 0;
-      __syncthreads();
-      buf[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (i < n) out[i + 1] = carry + buf[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == kBlock - 1) carry += buf[threadIdx.x];
-    __syncthreads();
+    const long long c = i < n ? counts[i] : 0;
+    const long long before = block_scan_exclusive(c, buf, &carry);
+    if (i < n) out[i + 1] = before + c;
   }
 }
 

@@ -86,7 +86,7 @@ class DeepWalk(object):
           ops.deepwalk_step(self.embedding, self.exp_avg, self.exp_avg_sq, self.step_count, pos[:r_pos], neg[:r_neg], self.context_size,
                             lr=self.lr, loss_out=losses[b:b + 1], flag=flag, workspace=ws[nb])
         self.epoch += 1
-        ops._raise_deepwalk_flags(flag, 'DeepWalk.fit')
+        ops._raise_flags(flag, 'DeepWalk.fit', ops.DEEPWALK_FLAGS)
         out.append(float(losses.double().mean().item()))
     return out
 

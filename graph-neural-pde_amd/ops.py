@@ -316,10 +316,18 @@ def _draw_args(count, seed, stream, call, who):
   return count, seed & (2 ** 64 - 1), stream, call
 
 
-def _raise_flags(flag, who):
+def _node_count(n, who):
+  n = int(n)
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('%s: n = %d outside 1 .. INT32_MAX' % (who, n))
+  return n
+
+
+def _raise_flags(flag, who, table=SAMPLING_FLAGS):
+  """Raise with the texts of the bits set in a kernel's device flag word (table: SAMPLING_FLAGS or DEEPWALK_FLAGS)."""
   bits = int(flag.item())
   if bits:
-    raise _lib.GnpdeError('%s: %s' % (who, '; '.join(text for bit, text in SAMPLING_FLAGS if bits & bit)))
+    raise _lib.GnpdeError('%s: %s' % (who, '; '.join(text for bit, text in table if bits & bit)))
 
 
 def _edge_list(edge_index, name):
@@ -350,9 +358,7 @@ def random_nodes(n, count, seed, stream, call, device=None):
   """count node indices uniform over [0, n) as an int64 device vector: draw i = (word i of the stream * n) >> 32
   (gnpde_random_nodes).  1 <= n <= INT32_MAX."""
   count, seed, stream, call = _draw_args(count, seed, stream, call, 'random_nodes')
-  n = int(n)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('random_nodes: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'random_nodes')
   device = _sampling_device(device, 'random_nodes')
   out = torch.empty(count, dtype=torch.int64, device=device)
   if count:
@@ -367,9 +373,7 @@ def node_importance(edge_index, att_mean, n):
   from .graph import graph_of
   ei = _edge_list(edge_index, 'node_importance: edge_index')
   require_hip(att_mean)
-  n = int(n)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('node_importance: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'node_importance')
   att = f32c(att_mean.detach().reshape(-1), 'att_mean')
   if att.numel() != ei.shape[1]:
     raise _lib.GnpdeError('node_importance: %d values for %d edges' % (att.numel(), ei.shape[1]))
@@ -395,9 +399,7 @@ def sample_nodes(logits, count, seed, stream, call):
   require_hip(logits)
   count, seed, stream, call = _draw_args(count, seed, stream, call, 'sample_nodes')
   s = f32c(logits.detach(), 'logits')
-  n = s.numel()
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('sample_nodes: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(s.numel(), 'sample_nodes')
   out = torch.empty(count, dtype=torch.int64, device=s.device)
   if count == 0:
     return out
@@ -416,9 +418,7 @@ def edge_union(a, b, n):
   b = _edge_list(b, 'edge_union: b')
   if a.device != b.device:
     raise _lib.GnpdeError('edge_union: a is on %s but b is on %s' % (a.device, b.device))
-  n = int(n)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('edge_union: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'edge_union')
   ea, eb = a.shape[1], b.shape[1]
   if ea + eb == 0:
     return torch.empty(2, 0, dtype=torch.int64, device=a.device)
@@ -480,12 +480,6 @@ DEEPWALK_LDS_FLOATS = 16384
 STREAM_POS_WALKS, STREAM_NEG_WALKS, STREAM_EPOCH_ORDER = 16, 17, 18     # graph_rewiring's edge sampling uses streams 0 and 1
 
 
-def _raise_deepwalk_flags(flag, who):
-  bits = int(flag.item())
-  if bits:
-    raise _lib.GnpdeError('%s: %s' % (who, '; '.join(text for bit, text in DEEPWALK_FLAGS if bits & bit)))
-
-
 class WalkGraph(object):
   """CSR of the walk graph on the device: rowptr [n + 1] and col [E] int32, a node's out-neighbours with multiplicity, ascending."""
 
@@ -497,9 +491,7 @@ def walk_csr(edge_index, n):
   """WalkGraph of edge_index ([2, E] int64 on a HIP device): the out-neighbours of u are the dst of the edges (u, dst), with
   multiplicity, ascending by dst.  Torch device ops, once per graph; one host read checks the index range."""
   ei = _edge_list(edge_index, 'walk_csr: edge_index')
-  n = int(n)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('walk_csr: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'walk_csr')
   E = ei.shape[1]
   if E > INT32_MAX:
     raise _lib.GnpdeError('walk_csr: %d edges exceed int32 positions' % E)
@@ -550,7 +542,7 @@ def random_walks(edge_index, n, starts, walk_length, seed, stream, call, first_w
     check(_lib.lib().gnpde_random_walks(ptr(g.rowptr), ptr(g.col), g.col.numel(), g.n, ptr(st), st.numel(), R, L, seed, stream, call, first_walk,
                                         ptr(out), ptr(flag), stream_of(st)))
     if own:
-      _raise_deepwalk_flags(flag, who)
+      _raise_flags(flag, who, DEEPWALK_FLAGS)
   return out if dtype == torch.int32 else out.to(dtype)
 
 
@@ -559,9 +551,7 @@ def negative_walks(n, starts, walk_length, seed, stream, call, first_walk=0, *, 
   (gnpde_negative_walks): PyG's negative sample of Node2Vec on this package's Philox streams."""
   who = 'negative_walks'
   st, L, seed, stream, call, first_walk, repeats = _walk_args(starts, walk_length, seed, stream, call, first_walk, repeats, who)
-  n = int(n)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('negative_walks: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'negative_walks')
   R = st.numel() * repeats
   out = torch.empty(R, L + 1, dtype=torch.int32, device=st.device)
   if R:
@@ -570,7 +560,7 @@ def negative_walks(n, starts, walk_length, seed, stream, call, first_walk=0, *, 
       flag = torch.zeros(1, dtype=torch.int32, device=st.device)
     check(_lib.lib().gnpde_negative_walks(n, ptr(st), st.numel(), R, L, seed, stream, call, first_walk, ptr(out), ptr(flag), stream_of(st)))
     if own:
-      _raise_deepwalk_flags(flag, who)
+      _raise_flags(flag, who, DEEPWALK_FLAGS)
   return out if dtype == torch.int32 else out.to(dtype)
 
 
@@ -578,9 +568,7 @@ def random_permutation(n, seed, stream, call, device=None):
   """A permutation of range(n) as an int64 device vector: the indices sorted by (word i of the stream) << 32 | i
   (gnpde_random_permutation).  1 <= n <= INT32_MAX."""
   _, seed, stream, call = _draw_args(0, seed, stream, call, 'random_permutation')
-  n = int(n)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('random_permutation: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'random_permutation')
   device = _sampling_device(device, 'random_permutation')
   L = _lib.lib()
   out = torch.empty(n, dtype=torch.int64, device=device)
@@ -646,8 +634,7 @@ def deepwalk_step(emb, m, v, t, pos_rw, neg_rw, context_size, lr=0.01, betas=(0.
   L = pos.shape[1] - 1
   neg = _walks_i32(neg_rw, L, 'neg_rw')
   deepwalk_check_shape(L, context_size, d)
-  if not 1 <= n <= INT32_MAX:
-    raise _lib.GnpdeError('deepwalk_step: n = %d outside 1 .. INT32_MAX' % n)
+  n = _node_count(n, 'deepwalk_step')
   if pos.shape[0] < 1 or neg.shape[0] < 1:
     raise _lib.GnpdeError('deepwalk_step: at least one positive and one negative walk are needed')
   if not (emb.device == m.device == v.device == pos.device == neg.device):
@@ -663,7 +650,7 @@ def deepwalk_step(emb, m, v, t, pos_rw, neg_rw, context_size, lr=0.01, betas=(0.
                                        neg.shape[0], L, int(context_size), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                        ptr(loss_out), ptr(flag), ptr(workspace), workspace.numel(), stream_of(emb)))
   if own:
-    _raise_deepwalk_flags(flag, 'deepwalk_step')
+    _raise_flags(flag, 'deepwalk_step', DEEPWALK_FLAGS)
   return loss_out.reshape(())
 
 

@@ -229,6 +229,8 @@ def _cases():
   # the hub alone are exactly tied).  Random weights break those ties: alpha = 0.3 with weights leaves 0.8 % open
   c['hub_ppr'] = dict(graph=dict(n=600, deg=4, seed=4, hub=530), weights=12, method='ppr', param=0.3, k=16, block=256)
   c['hub_heat'] = dict(graph=dict(n=600, deg=4, seed=4, hub=530), method='heat', param=3.0, k=16, block=256)
+  # two row splits (n > 512) merged with k > 64: the merge's strided loop over k and its ballot count
+  c['split_k128'] = dict(graph=dict(n=600, deg=6, seed=12), method='heat', param=3.0, k=128, block=256)
   c['directed'] = dict(graph=dict(n=300, deg=8, seed=5, directed=True), method='ppr', param=0.15, k=16, block=256)
   c['weighted_dups'] = dict(graph=dict(n=120, deg=6, seed=6, dup=60), weights=7, method='heat', param=3.0, k=16, block=64)
   c['isolated'] = dict(graph=dict(n=100, deg=4, seed=8, isolated=5), method='ppr', param=0.15, k=8, block=256, self_loop_weight=0.0)

@@ -160,7 +160,7 @@ def test_edge_union_refuses_an_index_out_of_range(dev):
 
 
 # ---- selection ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('E', [1, 255, 257, 100000])
+@pytest.mark.parametrize('E', [1, 255, 257, 100000, 1048577])   # the last: 257 blocks of 4096, the scan's carry into a second chunk
 @pytest.mark.parametrize('rmv', [0.0, 0.32, 0.8, 1.0])
 def test_select_edges_with_ties(dev, E, rmv):
   """Scores from eight dyadic values: many tie with the quantile, and `>=` keeps them all, in order."""

@@ -483,17 +483,18 @@ def test_xcd_row_map_takes_every_row_exactly_once(contiguous):
 
 
 def test_retired_tune_keys_fail_loudly():
-  """Keys 0, 8 and 13 selected aggregation / projection variants that are gone: a value other than 0 is refused (an old A/B command line
-  must not silently measure the default), 0 is accepted; the live keys keep taking their values."""
+  """Keys 0, 8 and 13 selected aggregation / projection variants that are gone, and so did value 1 of key 20 (a tile kernel of the
+  neighbour search): a value other than 0 is refused (an old A/B command line must not silently measure the default), 0 is accepted;
+  the live keys keep taking their values."""
   L = _lib.lib()
-  for key, value in ((0, 135), (8, 6), (13, 1)):
+  for key, value in ((0, 135), (8, 6), (13, 1), (20, 1)):
     assert L.gnpde_tune(key, value) == -1     # GNPDE_EINVAL
     assert 'retired' in L.gnpde_last_error().decode()
     with pytest.raises(G.GnpdeError, match='retired'):
       G.ops.tune(key, value)
   for key in (0, 8, 13):
     assert L.gnpde_tune(key, 0) == 0
-  live = ((9, 1), (9, 2), (10, 1), (10, 2), (14, 1), (15, 1), (16, 1), (17, 9), (18, 1), (18, 2), (19, 4), (20, 1), (20, 2))
+  live = ((9, 1), (9, 2), (10, 1), (10, 2), (14, 1), (15, 1), (16, 1), (17, 9), (18, 1), (18, 2), (19, 4), (20, 2))
   try:
     for key, value in live:
       assert L.gnpde_tune(key, value) == 0

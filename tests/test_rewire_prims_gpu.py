@@ -38,7 +38,7 @@ def test_quantile_beyond_torch_size_limit(dev):
 
 
 @pytest.mark.parametrize('norm_idx', [0, 1])
-@pytest.mark.parametrize('n_edges', [0, 1, 4097, 300_000])
+@pytest.mark.parametrize('n_edges', [0, 1, 4097, 300_000, 1_048_577])   # the last: 257 blocks of 4096, the scan's carry into a second chunk
 def test_threshold_edges_matches_reference_sequence(dev, norm_idx, n_edges):
   n = 5000
   g = torch.Generator().manual_seed(7 + n_edges)

@@ -7,7 +7,8 @@ at the two shapes BLEND's rewiring meets: Cora (2 708 x 80, k = 64) and ogbn-arx
 Per shape one JSON line: best-of-R event time of both (after a warm-up call each), 2 n^2 d / time in TF for the native kernel
 and its share of the 157.3 TF fp32 peak, the ratio composite / native, and the share of index entries on which the two agree
 (they differ where fp32 rounding reorders near-equal distances: the composite's cdist is a different evaluation).
---splits: gnpde_tune(19, S), the column split of the native kernel (0: the library's rule)."""
+--splits: gnpde_tune(19, S), the column split of the native kernel (0: the library's rule).  --variant 2: gnpde_tune(20, 2), the
+256-key row buffers for every k (an open lead at small n: DESIGN 4c)."""
 import argparse
 import json
 import os
@@ -51,7 +52,8 @@ def main():
   ap.add_argument('--repeats', type=int, default=5)
   ap.add_argument('--chunk-floats', type=int, default=1 << 26, help='size of one [chunk, n] distance slab of the composite')
   ap.add_argument('--splits', type=int, default=0)
-  ap.add_argument('--variant', type=int, default=0, help='gnpde_tune(20, .): tile-kernel variant (0: the default)')
+  ap.add_argument('--variant', type=int, default=0, choices=[0, 2],
+                  help='gnpde_tune(20, .): 2 = the 256-key row buffers for every k (0: the default)')
   ap.add_argument('--k', type=int, default=None, help='override k of both shapes')
   args = ap.parse_args()
   dev = torch.device('cuda:0')
