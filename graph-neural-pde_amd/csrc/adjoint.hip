@@ -18,6 +18,7 @@
 // No PyTorch op runs inside the solve.  GRAND-l (constant weights) is the same without the attention steps.
 #include <vector>
 #include "common.h"
+#include "fixed_grid.h"
 #include "graph_capture.h"
 #include "rhs.h"
 #include "epilogue.h"
@@ -993,56 +994,36 @@ int enqueue_stage(gnpde_adjoint* s, const float* uy, const float* ua, float* Fou
   return 0;
 }
 
+// The state runs backwards (y' = -F in s = -t: the schedule of fixed_grid.h with -dt) beside the adjoint (a' = +V, +dt), buffer for buffer.
+// euler alternates between the caller's y / a and uy[] / ua[].  rk4 (3/8 rule) in the COMPACT form of the forward solver (gnpde.h: stage
+// states expressed through the previous stage inputs, so no stage derivative F_j / V_j is ever stored or re-read -- the identities hold
+// for any sequence of derivatives): per stage each kernel reads one or two state-sized operands besides its own row instead of up to
+// five.  u2 = uy[0] / ua[0], u3 = uy[1] / ua[1], u4 = F[0] / V[0] (free buffers); the last stage is in place: y is not gathered in it.
 int enqueue_adjoint(gnpde_adjoint* s, float* y, float* a, float* grads, hipStream_t st) {
   const gnpde_rhs_t& r = s->rhs;
   const size_t nbytes = static_cast<size_t>(r.graph->n) * r.ld * 4;
   GNPDE_HIP(hipMemsetAsync(grads, 0, static_cast<size_t>(s->stride) * 4, st));
-  if (s->method == GNPDE_METHOD_EULER) {
-    float* cy = y; float* ca = a;
-    int flip = 0;
-    for (float dt : s->dts) {
-      gnpde_epilogue_t eF{}, eV{};
-      eF.stage = GNPDE_STAGE_EULER; eF.dt = -dt; eF.y = cy; eF.out_y = s->uy[flip];       // y' = -F in s = -t
-      eV.stage = GNPDE_STAGE_EULER; eV.dt = dt; eV.y = ca; eV.out_y = s->ua[flip];        // a' = +V
-      int rc = enqueue_stage(s, cy, ca, nullptr, eF, nullptr, eV, dt, grads, st);
+  const int m = s->method;
+  float* ychain[5] = {y, s->uy[0], s->uy[1], s->F[0], y};
+  float* achain[5] = {a, s->ua[0], s->ua[1], s->V[0], a};
+  int flip = 0;
+  for (float dt : s->dts) {
+    if (m == GNPDE_METHOD_EULER) {
+      ychain[1] = s->uy[flip]; achain[1] = s->ua[flip];
+    }
+    for (int j = 0; j < evals_per_step(m); ++j) {
+      const int rc = enqueue_stage(s, ychain[j], achain[j], nullptr, stage_epilogue({}, m, j, -dt, ychain), nullptr,
+                                   stage_epilogue({}, m, j, dt, achain), stage_weight(m, j, dt), grads, st);
       if (rc) return rc;
-      cy = s->uy[flip]; ca = s->ua[flip];
+    }
+    if (m == GNPDE_METHOD_EULER) {
+      ychain[0] = ychain[1]; achain[0] = achain[1];
       flip ^= 1;
     }
-    if (cy != y) {
-      GNPDE_HIP(hipMemcpyAsync(y, cy, nbytes, hipMemcpyDeviceToDevice, st));
-      GNPDE_HIP(hipMemcpyAsync(a, ca, nbytes, hipMemcpyDeviceToDevice, st));
-    }
-    return 0;
   }
-  // rk4 (3/8 rule) in the COMPACT form of the forward solver (gnpde.h: stage states expressed through the previous stage inputs, so no
-  // stage derivative F_j / V_j is ever stored or re-read -- the identities hold for any sequence of derivatives, here -F for the state
-  // and +V for the adjoint): per stage each kernel reads one or two state-sized operands besides its own row instead of up to five.
-  // u2 = uy[0] / ua[0], u3 = uy[1] / ua[1], u4 = F[0] / V[0] (free buffers).
-  float* y4 = s->F[0]; float* a4 = s->V[0];
-  for (float dtf : s->dts) {
-    const double dt = dtf;
-    const float c8 = static_cast<float>(dt * 0.125), c38 = static_cast<float>(3.0 * (dt * 0.125));
-    gnpde_epilogue_t eF{}, eV{};
-    eF.stage = GNPDE_STAGE_RK1C; eF.dt = -dtf; eF.out_y = s->uy[0];
-    eV.stage = GNPDE_STAGE_RK1C; eV.dt = dtf; eV.out_y = s->ua[0];
-    int rc = enqueue_stage(s, y, a, nullptr, eF, nullptr, eV, c8, grads, st);
-    if (rc) return rc;
-    eF = gnpde_epilogue_t{}; eV = gnpde_epilogue_t{};
-    eF.stage = GNPDE_STAGE_RK2C; eF.dt = -dtf; eF.y = y; eF.out_y = s->uy[1];
-    eV.stage = GNPDE_STAGE_RK2C; eV.dt = dtf; eV.y = a; eV.out_y = s->ua[1];
-    rc = enqueue_stage(s, s->uy[0], s->ua[0], nullptr, eF, nullptr, eV, c38, grads, st);
-    if (rc) return rc;
-    eF = gnpde_epilogue_t{}; eV = gnpde_epilogue_t{};
-    eF.stage = GNPDE_STAGE_RK3C; eF.dt = -dtf; eF.k1 = s->uy[0]; eF.out_y = y4;
-    eV.stage = GNPDE_STAGE_RK3C; eV.dt = dtf; eV.k1 = s->ua[0]; eV.out_y = a4;
-    rc = enqueue_stage(s, s->uy[1], s->ua[1], nullptr, eF, nullptr, eV, c38, grads, st);
-    if (rc) return rc;
-    eF = gnpde_epilogue_t{}; eV = gnpde_epilogue_t{};
-    eF.stage = GNPDE_STAGE_RK4C; eF.dt = -dtf; eF.y = y; eF.k1 = s->uy[1]; eF.out_y = y;     // in place: y is not gathered in this stage
-    eV.stage = GNPDE_STAGE_RK4C; eV.dt = dtf; eV.y = a; eV.k1 = s->ua[1]; eV.out_y = a;
-    rc = enqueue_stage(s, y4, a4, nullptr, eF, nullptr, eV, c8, grads, st);
-    if (rc) return rc;
+  if (ychain[0] != y) {
+    GNPDE_HIP(hipMemcpyAsync(y, ychain[0], nbytes, hipMemcpyDeviceToDevice, st));
+    GNPDE_HIP(hipMemcpyAsync(a, achain[0], nbytes, hipMemcpyDeviceToDevice, st));
   }
   return 0;
 }
@@ -1070,21 +1051,6 @@ int enqueue_taped(gnpde_adjoint* s, float* a, float* grads, hipStream_t st) {
     rec_store = rhs_record_at(r, const_cast<float*>(s->tape_rec), eval);
     return &rec_store;
   };
-  if (s->method == GNPDE_METHOD_EULER) {
-    float* ca = a;
-    int flip = 0;
-    for (int n = S - 1; n >= 0; --n) {
-      const float h = s->dts[n];
-      gnpde_epilogue_t eV{};
-      eV.stage = GNPDE_STAGE_EULER; eV.dt = h; eV.y = ca; eV.out_y = s->ua[flip];
-      int rc = enqueue_stage(s, slot(n), ca, nullptr, no_output(), nullptr, eV, h, grads, st, rec(n));
-      if (rc) return rc;
-      ca = s->ua[flip];
-      flip ^= 1;
-    }
-    if (ca != a) GNPDE_HIP(hipMemcpyAsync(a, ca, nbytes, hipMemcpyDeviceToDevice, st));
-    return 0;
-  }
   if (s->method == GNPDE_METHOD_MIDPOINT) {
     // y_mid = y + (h/2) f(y), y' = y + h f(y_mid):  W = J_mid^T g,  g_new = g + h W + (h^2 / 2) J_y^T W
     for (int n = S - 1; n >= 0; --n) {
@@ -1101,30 +1067,27 @@ int enqueue_taped(gnpde_adjoint* s, float* a, float* grads, hipStream_t st) {
     }
     return 0;
   }
-  float* a4 = s->V[0];
+  // euler and rk4: the cotangent runs the schedule of fixed_grid.h (euler alternating between a and ua[], rk4 over a, ua[0], ua[1],
+  // V[0], in place on a: a is not gathered in the last stage); evaluation j of the sweep pairs with evaluation E - 1 - j of the
+  // forward step, whose input and record it reads from the tape
+  const int m = s->method, E = evals_per_step(m);
+  float* achain[5] = {a, s->ua[0], s->ua[1], s->V[0], a};
+  int flip = 0;
   for (int n = S - 1; n >= 0; --n) {
-    const float dtf = s->dts[n];
-    const double dt = dtf;
-    const float c8 = static_cast<float>(dt * 0.125), c38 = static_cast<float>(3.0 * (dt * 0.125));
-    const float *u1 = slot(4 * static_cast<size_t>(n)), *u2 = u1 + stride, *u3 = u2 + stride, *u4 = u3 + stride;
-    gnpde_epilogue_t eV{};
-    eV.stage = GNPDE_STAGE_RK1C; eV.dt = dtf; eV.out_y = s->ua[0];
-    const size_t e0 = 4 * static_cast<size_t>(n);
-    int rc = enqueue_stage(s, u4, a, nullptr, no_output(), nullptr, eV, c8, grads, st, rec(e0 + 3));
-    if (rc) return rc;
-    eV = gnpde_epilogue_t{};
-    eV.stage = GNPDE_STAGE_RK2C; eV.dt = dtf; eV.y = a; eV.out_y = s->ua[1];
-    rc = enqueue_stage(s, u3, s->ua[0], nullptr, no_output(), nullptr, eV, c38, grads, st, rec(e0 + 2));
-    if (rc) return rc;
-    eV = gnpde_epilogue_t{};
-    eV.stage = GNPDE_STAGE_RK3C; eV.dt = dtf; eV.k1 = s->ua[0]; eV.out_y = a4;
-    rc = enqueue_stage(s, u2, s->ua[1], nullptr, no_output(), nullptr, eV, c38, grads, st, rec(e0 + 1));
-    if (rc) return rc;
-    eV = gnpde_epilogue_t{};
-    eV.stage = GNPDE_STAGE_RK4C; eV.dt = dtf; eV.y = a; eV.k1 = s->ua[1]; eV.out_y = a;      // in place: a is not gathered in this stage
-    rc = enqueue_stage(s, u1, a4, nullptr, no_output(), nullptr, eV, c8, grads, st, rec(e0));
-    if (rc) return rc;
+    const float h = s->dts[n];
+    if (m == GNPDE_METHOD_EULER) achain[1] = s->ua[flip];
+    for (int j = 0; j < E; ++j) {
+      const size_t e = static_cast<size_t>(E) * n + (E - 1 - j);
+      const int rc = enqueue_stage(s, slot(e), achain[j], nullptr, no_output(), nullptr, stage_epilogue({}, m, j, h, achain),
+                                   stage_weight(m, j, h), grads, st, rec(e));
+      if (rc) return rc;
+    }
+    if (m == GNPDE_METHOD_EULER) {
+      achain[0] = achain[1];
+      flip ^= 1;
+    }
   }
+  if (achain[0] != a) GNPDE_HIP(hipMemcpyAsync(a, achain[0], nbytes, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -1209,7 +1172,7 @@ extern "C" int gnpde_adjoint_create(gnpde_adjoint_t** out, const gnpde_rhs_t* rh
   s->ws = static_cast<char*>(workspace);
   s->ws_bytes = workspace_bytes;
   adjoint_layout(s->rhs, s->graph_t, method, s);
-  s->n_evals = n_steps * (method == GNPDE_METHOD_RK4 ? 4 : method == GNPDE_METHOD_MIDPOINT ? 2 : 1);
+  s->n_evals = n_steps * evals_per_step(method);
   *out = s;
   return 0;
 }
@@ -1251,7 +1214,7 @@ extern "C" int gnpde_adjoint_set_tape(gnpde_adjoint_t* s, const void* tape, size
   s->csr_from_t = nullptr;
   s->swapped = false;
   if (tape == nullptr) return 0;
-  const size_t per = s->method == GNPDE_METHOD_RK4 ? 4 : s->method == GNPDE_METHOD_MIDPOINT ? 2 : 1;
+  const size_t per = evals_per_step(s->method);
   const size_t rec_floats = rhs_record_stride(s->rhs);
   const size_t need = (per * s->dts.size() + 1) * s->state_bytes + per * s->dts.size() * rec_floats * 4;
   GNPDE_CHECK_ARG(reinterpret_cast<uintptr_t>(tape) % 256 == 0 && tape_bytes >= need, GNPDE_EWS,

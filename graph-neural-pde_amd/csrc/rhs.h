@@ -1,5 +1,6 @@
 // One right-hand-side evaluation composed from the kernels of this library (defined in solver.hip); shared by the
 // single-GPU solver and the row-partitioned solver (sharded.hip).  Internal, not part of the C ABI.
+// Which stage epilogue evaluation j of a fixed-grid step gets (euler, midpoint, compact rk4) is stated in fixed_grid.h.
 #pragma once
 #include "common.h"
 

@@ -35,6 +35,7 @@
 #include "gnpde.h"
 #include "common.h"
 #include "embedded_pair.h"
+#include "fixed_grid.h"
 #include "graph_capture.h"
 #include "rhs.h"
 
@@ -614,40 +615,21 @@ int enqueue_eval(gnpde_sharded_solver* s, float* u, gnpde_epilogue_t e, hipStrea
 
 // y_work: the stage buffer that holds the state ([n_own + n_halo, ld]); the caller's y with RCCL, shared buffer 0 with P2P
 int enqueue_sharded_solve(gnpde_sharded_solver* s, float* y, hipStream_t st) {
-  float* ua = stage_buffer(s, 1);
-  gnpde_epilogue_t base = base_epilogue(s->rhs_int);
-  if (s->method == GNPDE_METHOD_EULER) {
-    float* cur = y;
-    float* nxt = ua;
-    for (float dt : s->dts) {
-      gnpde_epilogue_t e = base;
-      e.stage = GNPDE_STAGE_EULER; e.dt = dt; e.y = cur; e.out_y = nxt;
-      const int rc = enqueue_eval(s, cur, e, st);
-      if (rc) return rc;
-      float* t = cur; cur = nxt; nxt = t;
-    }
-    if (cur != y)
-      GNPDE_HIP(hipMemcpyAsync(y, cur, static_cast<size_t>(s->n_own) * s->ld * 4, hipMemcpyDeviceToDevice, st));
-    return 0;
+  const gnpde_epilogue_t base = base_epilogue(s->rhs_int);
+  // the schedule of fixed_grid.h over the ring y, ua (euler: alternating) or y, ua, ub, uc (compact rk4: every step ends in place on y)
+  const int S = evals_per_step(s->method), B = stage_input_buffers(s->method);
+  float* bufs[4] = {y};
+  for (int b = 1; b < B; ++b) bufs[b] = stage_buffer(s, b);
+  float* u[5];
+  int first = 0;
+  for (float dt : s->dts) {
+    for (int i = 0; i <= S; ++i) u[i] = bufs[(first + i) % B];
+    const int rc = enqueue_step(base, s->method, dt, u, [&](int, float* in, const gnpde_epilogue_t& e) { return enqueue_eval(s, in, e, st); });
+    if (rc) return rc;
+    first = (first + S) % B;
   }
-  float* ub = stage_buffer(s, 2);
-  float* uc = stage_buffer(s, 3);
-  for (float dt : s->dts) {   // compact rk4 stages (gnpde.h): stage states from the previous stage inputs
-    gnpde_epilogue_t e = base;
-    e.dt = dt;
-    e.stage = GNPDE_STAGE_RK1C; e.out_y = ua;
-    int rc = enqueue_eval(s, y, e, st);
-    if (rc) return rc;
-    e.stage = GNPDE_STAGE_RK2C; e.y = y; e.out_y = ub;
-    rc = enqueue_eval(s, ua, e, st);
-    if (rc) return rc;
-    e.stage = GNPDE_STAGE_RK3C; e.k1 = ua; e.out_y = uc;
-    rc = enqueue_eval(s, ub, e, st);
-    if (rc) return rc;
-    e.stage = GNPDE_STAGE_RK4C; e.k1 = ub; e.out_y = y;
-    rc = enqueue_eval(s, uc, e, st);
-    if (rc) return rc;
-  }
+  if (bufs[first] != y)
+    GNPDE_HIP(hipMemcpyAsync(y, bufs[first], static_cast<size_t>(s->n_own) * s->ld * 4, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -754,7 +736,7 @@ int create_common(gnpde_sharded_solver** out, gnpde_comm* comm, gnpde_p2p* p2p, 
   }
   s->ws = static_cast<char*>(workspace);
   s->ws_bytes = workspace_bytes;
-  s->n_evals = n_steps * (method == GNPDE_METHOD_RK4 ? 4 : 1);
+  s->n_evals = n_steps * evals_per_step(method);
   hipError_t e = hipEventCreateWithFlags(&s->e_pack, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->e_recv, hipEventDisableTiming);
   if (e != hipSuccess) {
@@ -951,7 +933,7 @@ extern "C" int gnpde_sharded_solver_create_p2p(gnpde_sharded_solver_t** out, gnp
                                                const int64_t* peer_buffer_bytes, void* workspace, size_t workspace_bytes) {
   GNPDE_CHECK_ARG(p2p && halo && peer_halo_row0 && peer_buffer_bytes, GNPDE_EINVAL, "sharded_solver_create_p2p: null argument");
   GNPDE_CHECK_ARG(p2p->world == halo->world && p2p->rank == halo->rank, GNPDE_EINVAL, "sharded_solver_create_p2p: rank / world mismatch");
-  const int nbuf = method == GNPDE_METHOD_RK4 ? 4 : 2;
+  const int nbuf = stage_input_buffers(method);
   GNPDE_CHECK_ARG(p2p->n_buffers >= nbuf, GNPDE_EINVAL, "sharded_solver_create_p2p: %d shared buffers, need %d", p2p->n_buffers, nbuf);
   const size_t state = static_cast<size_t>(halo->n_own + halo->n_halo) * (rhs_interior ? rhs_interior->ld : 0) * 4;
   GNPDE_CHECK_ARG(p2p->buffer_bytes >= state, GNPDE_EINVAL, "sharded_solver_create_p2p: shared buffers of %zu bytes, state needs %zu",

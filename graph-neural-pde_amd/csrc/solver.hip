@@ -10,6 +10,7 @@
 #include <atomic>
 #include <vector>
 #include "common.h"
+#include "fixed_grid.h"
 #include "graph_capture.h"
 #include "rhs.h"
 
@@ -197,9 +198,8 @@ struct gnpde_solver {
 
 namespace {
 
-// shadows of the stage-input buffers: y and ua (euler, midpoint), + ub and the fourth stage input of the compact rk4
+// one bf16 shadow per stage-input buffer (stage_input_buffers of fixed_grid.h)
 size_t lo_stride(const gnpde_rhs_t& r) { return align_up(static_cast<size_t>(r.graph->n) * r.ld * 2, 256); }
-int lo_count(int method) { return method == GNPDE_METHOD_RK4 ? 4 : 2; }
 
 size_t solver_layout(const gnpde_rhs_t& r, int method, gnpde_solver* s) {
   const size_t state = align_up(static_cast<size_t>(r.graph->n) * r.ld * 4, 256);
@@ -260,86 +260,28 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
     const int crc = launch_to_bf16(y, r.graph->n, r.d, r.ld, shadow(0), st);
     if (crc) return crc;
   }
-  if (s->tape != nullptr) {
-    // Recorded solve: the same launches, every stage input written to a slot of its own instead of a recycled buffer -- the record
-    // costs no extra pass over the state.  Slot 0 = y0, slot i = the input of evaluation i (rk4: u1..u4 of step n at 4n..4n+3),
-    // the last slot = y(T), copied back into y.
-    const size_t stride = align_up(static_cast<size_t>(r.graph->n) * r.ld * 4, 256) / 4;
-    const size_t nbytes = static_cast<size_t>(r.graph->n) * r.ld * 4;
-    auto slot = [&](size_t i) { return s->tape + i * stride; };
-    GNPDE_HIP(hipMemcpyAsync(slot(0), y, nbytes, hipMemcpyDeviceToDevice, st));
-    size_t at = 0;
-    RhsRecord rec_store{};
-    auto rec = [&](size_t eval) -> const RhsRecord* {
-      if (s->tape_rec == nullptr) return nullptr;
-      rec_store = rhs_record_at(r, s->tape_rec, eval);
-      return &rec_store;
-    };
+  const size_t nbytes = static_cast<size_t>(r.graph->n) * r.ld * 4;
+  const gnpde_epilogue_t base = base_epilogue(r);
+  // y, u2 (ua), u3 (ub) and u4 (the k1 slot) of the compact rk4, whose k1..k3 are never materialised; y and ua for euler and midpoint
+  float* const bufs[4] = {y, ua, reinterpret_cast<float*>(s->ws + s->off_ub), reinterpret_cast<float*>(s->ws + s->off_k1)};
+  if (s->method == GNPDE_METHOD_RK4 && s->tape == nullptr && g_tune[GNPDE_TUNE_RK4_CLASSIC] != 0) {
+    // the classic form with k1..k3 stored (A/B against the compact one; a recorded solve is always compact)
+    float *ub = bufs[2], *k1 = bufs[3];
+    float* k2 = reinterpret_cast<float*>(s->ws + s->off_k2);
+    float* k3 = reinterpret_cast<float*>(s->ws + s->off_k3);
     for (float dt : s->dts) {
-      gnpde_epilogue_t e = base_epilogue(r);
-      e.dt = dt;
-      int rc = 0;
-      if (s->method == GNPDE_METHOD_EULER) {
-        e.stage = GNPDE_STAGE_EULER; e.y = slot(at); e.out_y = slot(at + 1);
-        rc = enqueue_rhs(r, slot(at), e, rws, s->L, st, fk, rec(at));
-        at += 1;
-      } else if (s->method == GNPDE_METHOD_MIDPOINT) {
-        e.stage = GNPDE_STAGE_LINCOMB; e.y = slot(at); e.n_prev = 0; e.out_k = nullptr;
-        e.coef[0] = 0.5f * dt; e.out_y = slot(at + 1);
-        rc = enqueue_rhs(r, slot(at), e, rws, s->L, st, fk, rec(at));
-        if (rc) return rc;
-        e.coef[0] = dt; e.out_y = slot(at + 2);
-        rc = enqueue_rhs(r, slot(at + 1), e, rws, s->L, st, fk, rec(at + 1));
-        at += 2;
-      } else {
-        float *u1 = slot(at), *u2 = slot(at + 1), *u3 = slot(at + 2), *u4 = slot(at + 3);
-        e.stage = GNPDE_STAGE_RK1C; e.out_y = u2;
-        rc = enqueue_rhs(r, u1, e, rws, s->L, st, fk, rec(at));
-        if (rc) return rc;
-        e.stage = GNPDE_STAGE_RK2C; e.y = u1; e.out_y = u3;
-        rc = enqueue_rhs(r, u2, e, rws, s->L, st, fk, rec(at + 1));
-        if (rc) return rc;
-        e.stage = GNPDE_STAGE_RK3C; e.k1 = u2; e.out_y = u4;
-        rc = enqueue_rhs(r, u3, e, rws, s->L, st, fk, rec(at + 2));
-        if (rc) return rc;
-        e.stage = GNPDE_STAGE_RK4C; e.k1 = u3; e.out_y = slot(at + 4);
-        rc = enqueue_rhs(r, u4, e, rws, s->L, st, fk, rec(at + 3));
-        at += 4;
-      }
-      if (rc) return rc;
-      rc = evaluate(slot(at));
-      if (rc) return rc;
-    }
-    GNPDE_HIP(hipMemcpyAsync(y, slot(at), nbytes, hipMemcpyDeviceToDevice, st));
-    return 0;
-  }
-  if (s->method == GNPDE_METHOD_EULER) {
-    float* cur = y;
-    float* nxt = ua;
-    int cur_lo = 0, nxt_lo = 1;
-    for (float dt : s->dts) {
-      gnpde_epilogue_t e = base_epilogue(r);
-      e.stage = GNPDE_STAGE_EULER; e.dt = dt; e.y = cur; e.out_y = nxt;
-      int rc = enqueue_rhs(r, cur, e, rws, s->L, st, fk, nullptr, pair(cur_lo, nxt_lo));
-      if (rc) return rc;
-      float* t = cur; cur = nxt; nxt = t;
-      cur_lo ^= 1; nxt_lo ^= 1;
-      rc = evaluate(cur);
-      if (rc) return rc;
-    }
-    if (cur != y)
-      GNPDE_HIP(hipMemcpyAsync(y, cur, static_cast<size_t>(r.graph->n) * r.ld * 4, hipMemcpyDeviceToDevice, st));
-    return 0;
-  }
-  if (s->method == GNPDE_METHOD_MIDPOINT) {
-    // torchdiffeq Midpoint._step_func: y_mid = y + f(y) * (dt / 2);  y += dt * f(y_mid)  (second stage row-local in place on y)
-    for (float dt : s->dts) {
-      gnpde_epilogue_t e = base_epilogue(r);
-      e.stage = GNPDE_STAGE_LINCOMB; e.y = y; e.n_prev = 0; e.out_k = nullptr;
-      e.coef[0] = 0.5f * dt; e.out_y = ua;
+      gnpde_epilogue_t e = base;
+      e.dt = dt; e.y = y;
+      e.stage = GNPDE_STAGE_RK1; e.out_k = k1; e.out_y = ua;
       int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
       if (rc) return rc;
-      e.coef[0] = dt; e.out_y = y;
+      e.stage = GNPDE_STAGE_RK2; e.k1 = k1; e.out_k = k2; e.out_y = ub;
+      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2));
+      if (rc) return rc;
+      e.stage = GNPDE_STAGE_RK3; e.k2 = k2; e.out_k = k3; e.out_y = ua;
+      rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 1));
+      if (rc) return rc;
+      e.stage = GNPDE_STAGE_RK4; e.k3 = k3; e.out_k = nullptr; e.out_y = y;
       rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0));
       if (rc) return rc;
       rc = evaluate(y);
@@ -347,51 +289,45 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
     }
     return 0;
   }
-  float* ub = reinterpret_cast<float*>(s->ws + s->off_ub);
-  float* k1 = reinterpret_cast<float*>(s->ws + s->off_k1);
-  float* k2 = reinterpret_cast<float*>(s->ws + s->off_k2);
-  float* k3 = reinterpret_cast<float*>(s->ws + s->off_k3);
-  if (g_tune[GNPDE_TUNE_RK4_CLASSIC] == 0) {
-    // compact stages: y, u2 (ua), u3 (ub), u4 (the k1 slot); k1..k3 are never materialised
-    float* uc = k1;
-    for (float dt : s->dts) {
-      gnpde_epilogue_t e = base_epilogue(r);
-      e.dt = dt;
-      e.stage = GNPDE_STAGE_RK1C; e.out_y = ua;
-      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
-      if (rc) return rc;
-      e.stage = GNPDE_STAGE_RK2C; e.y = y; e.out_y = ub;
-      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2));
-      if (rc) return rc;
-      e.stage = GNPDE_STAGE_RK3C; e.k1 = ua; e.out_y = uc;
-      rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 3));
-      if (rc) return rc;
-      e.stage = GNPDE_STAGE_RK4C; e.k1 = ub; e.out_y = y;
-      rc = enqueue_rhs(r, uc, e, rws, s->L, st, fk, nullptr, pair(3, 0));
-      if (rc) return rc;
-      rc = evaluate(y);
-      if (rc) return rc;
-    }
-    return 0;
+  // Every other solve runs the schedule of fixed_grid.h; what differs is where the stage inputs u[0..S] of a step lie.  Recycled buffers:
+  // the step starts in the buffer the last one ended in and walks the ring from there -- midpoint and rk4 end in place on y, euler
+  // alternates between y and ua; idx[] also names the bf16 shadows.  Recorded solve (s->tape): the same launches, every stage input
+  // written to a slot of its own -- the record costs no extra pass over the state.  Slot 0 = y0, slot i = the input of evaluation i
+  // (rk4: u1..u4 of step n at 4n..4n+3), the last slot = y(T), copied back into y.
+  const int S = evals_per_step(s->method), B = stage_input_buffers(s->method);
+  const size_t stride = align_up(nbytes, 256) / 4;
+  auto slot = [&](size_t i) { return s->tape + i * stride; };
+  RhsRecord rec_store{};
+  auto rec = [&](size_t eval) -> const RhsRecord* {
+    if (s->tape_rec == nullptr) return nullptr;
+    rec_store = rhs_record_at(r, s->tape_rec, eval);
+    return &rec_store;
+  };
+  float* u[5];
+  int idx[5];
+  int first = 0;     // ring position of the step's start
+  float* result = y;
+  if (s->tape != nullptr) {
+    result = slot(0);
+    GNPDE_HIP(hipMemcpyAsync(result, y, nbytes, hipMemcpyDeviceToDevice, st));
   }
+  size_t at = 0;     // evaluations so far
   for (float dt : s->dts) {
-    gnpde_epilogue_t e = base_epilogue(r);
-    e.dt = dt; e.y = y;
-    e.stage = GNPDE_STAGE_RK1; e.out_k = k1; e.out_y = ua;
-    int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
+    for (int i = 0; i <= S; ++i) {
+      idx[i] = (first + i) % B;
+      u[i] = s->tape != nullptr ? slot(at + i) : bufs[idx[i]];
+    }
+    int rc = enqueue_step(base, s->method, dt, u, [&](int j, const float* in, const gnpde_epilogue_t& e) {
+      return enqueue_rhs(r, in, e, rws, s->L, st, fk, rec(at + j), pair(idx[j], idx[j + 1]));
+    });
     if (rc) return rc;
-    e.stage = GNPDE_STAGE_RK2; e.k1 = k1; e.out_k = k2; e.out_y = ub;
-    rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2));
-    if (rc) return rc;
-    e.stage = GNPDE_STAGE_RK3; e.k2 = k2; e.out_k = k3; e.out_y = ua;
-    rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 1));
-    if (rc) return rc;
-    e.stage = GNPDE_STAGE_RK4; e.k3 = k3; e.out_k = nullptr; e.out_y = y;
-    rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0));
-    if (rc) return rc;
-    rc = evaluate(y);
+    at += S;
+    first = idx[S];
+    result = u[S];
+    rc = evaluate(result);
     if (rc) return rc;
   }
+  if (result != y) GNPDE_HIP(hipMemcpyAsync(y, result, nbytes, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -473,7 +409,7 @@ extern "C" int gnpde_solver_create(gnpde_solver_t** out, const gnpde_rhs_t* rhs,
   }
   s->ws = static_cast<char*>(workspace);
   s->ws_bytes = workspace_bytes;
-  s->n_evals = n_steps * (method == GNPDE_METHOD_RK4 ? 4 : method == GNPDE_METHOD_MIDPOINT ? 2 : 1);
+  s->n_evals = n_steps * evals_per_step(method);
   *out = s;
   return 0;
 }
@@ -495,7 +431,7 @@ extern "C" size_t gnpde_solver_tape_bytes(const gnpde_rhs_t* rhs, int32_t method
   if (check_rhs(rhs) || n_steps < 0) return 0;
   if (method != GNPDE_METHOD_EULER && method != GNPDE_METHOD_RK4 && method != GNPDE_METHOD_MIDPOINT) return 0;
   const size_t state = align_up(static_cast<size_t>(rhs->graph->n) * rhs->ld * 4, 256);
-  const size_t per = method == GNPDE_METHOD_RK4 ? 4 : method == GNPDE_METHOD_MIDPOINT ? 2 : 1;
+  const size_t per = evals_per_step(method);
   return (per * static_cast<size_t>(n_steps) + 1) * state + per * static_cast<size_t>(n_steps) * rhs_record_stride(*rhs) * 4;
 }
 
@@ -527,7 +463,7 @@ extern "C" size_t gnpde_solver_gather_bytes(const gnpde_rhs_t* rhs, int32_t meth
               "GNPDE_RHS_PADDED_ROWS; ld %% 4 == 0): d=%d ld=%d", rhs->d, rhs->ld);
     return 0;
   }
-  return lo_count(method) * lo_stride(*rhs);
+  return stage_input_buffers(method) * lo_stride(*rhs);
 }
 
 extern "C" int gnpde_solver_set_gather(gnpde_solver_t* s, int32_t dtype, void* mem, size_t bytes) {

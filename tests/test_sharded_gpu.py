@@ -260,18 +260,22 @@ def test_other_score_functions_run_partitioned(dev, tmp_path, kind):
 
 
 def test_no_exchange_world1_matches_single_gpu_solver(dev):
-  """A world-1 shard without halo (comm NULL): interior = all rows; must equal the single-GPU solver bit for bit."""
+  """A world-1 shard without halo (comm NULL): interior = all rows; the native sharded solve must agree with the oracle's solve like
+  the single-GPU solver does -- rk4, and euler with an odd number of steps (the result ends in the second stage buffer and is copied
+  back)."""
   n, d, ei, x, p, alpha, beta, rhs = _problem('transformer', seed=5)
   plan = D.PartitionPlan(ei, n, 1)
   sh = plan.shard(0)
   assert sh.n_halo == 0 and sh.n_interior == sh.n_own
   be = D.NativeBackend(sh, d, dev, 'transformer', p, alpha, beta, True)
-  solver = D.NativeShardedSolver(sh, be, 2.0, 1.0, 'rk4')     # P2P transport, world 1: no peers, nothing to exchange
   x_own = D.scatter_rows(x, sh).to(dev)
-  with torch.no_grad():
-    z = solver.integrate(x_own, x_own)
-  ref = R.odeint_fixed(rhs, x, 2.0, 1.0, 'rk4')
-  assert_parity(z, ref[sh.own_old_ids], what='world-1 native sharded solve')
+  for method, T in (('rk4', 2.0), ('euler', 3.0)):
+    solver = D.NativeShardedSolver(sh, be, T, 1.0, method)     # P2P transport, world 1: no peers, nothing to exchange
+    assert len(solver.dts) == int(T)
+    with torch.no_grad():
+      z = solver.integrate(x_own, x_own)
+    ref = R.odeint_fixed(rhs, x, T, 1.0, method)
+    assert_parity(z, ref[sh.own_old_ids], what='world-1 native sharded solve, %s' % method)
 
 
 @pytest.mark.timeout(600, method='thread')
