@@ -16,7 +16,8 @@ opt['exact'] the reference's approximate branch runs instead: a forward push per
 
 Positional-distance rewiring (`--rewiring pos_enc_knn`; reference graph_rewiring.py:285-342, hyperbolic_distances.py:7-14,
 distances_kNN.py): `apply_pos_dist_rewire` with `hyperbolize`, `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold` and
-`apply_beltrami` (which, with opt['gnpde_generate_pos_enc'], trains a missing DW<d> pickle natively: deepwalk_embeddings.py).  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
+`apply_beltrami` (which, with opt['gnpde_generate_pos_enc'], trains a missing DW<d> pickle natively: deepwalk_embeddings.py; and,
+with opt['gnpde_pos_enc_nmf_dim'], compresses a missing GDC encoding by NMF: pos_enc_factorisation.py).  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
 it or hands it to sklearn's NearestNeighbors(metric='precomputed'); here the edge set comes straight from the encodings
 (`ops.knn(metric=...)`, `ops.radius_graph`), so the helpers take ENCODINGS where the reference's take a distance matrix.
 Deliberate differences: no [n, n] distance pickle is written; the edge set is computed whether or not a cache file existed (the
@@ -307,13 +308,44 @@ def _generate_deepwalk(data, opt, fname):
   return z
 
 
+NMF_DEFAULTS = dict(max_iter=100, tol=0.002)     # the reference script's defaults (pos_enc_factorisation.py --max_iter, --tol)
+
+
+def _generate_compressed_gdc(data, opt, fname):
+  """GDC encodings compressed to opt['gnpde_pos_enc_nmf_dim'] columns (pos_enc_factorisation.NMF) and cached as a CPU tensor where the
+  reference's script leaves its W.  While the dense [n, n] matrix fits ops.GDC_DENSE_CAP the input is apply_gdc(type='pos_encoding'),
+  the reference's literal input; above it the sparse GDC graph of apply_gdc(type='combined') (transposed for orientation 'col')."""
+  import copy
+  from . import pos_enc_factorisation
+  n = data.num_nodes[0] if isinstance(data.num_nodes, list) else data.num_nodes
+  if 4 * int(n) * int(n) <= ops.GDC_DENSE_CAP:
+    print('    NMF input: the dense %d x %d GDC matrix' % (n, n))
+    x = apply_gdc(data, opt, type='pos_encoding').contiguous()
+  else:
+    print('    NMF input: the sparse GDC graph (the dense %d x %d matrix exceeds %d bytes)' % (n, n, ops.GDC_DENSE_CAP))
+    sparse = apply_gdc(copy.copy(data), opt, type='combined')
+    ei = sparse.edge_index if opt['pos_enc_orientation'] == 'row' else sparse.edge_index.flip(0)
+    x = (ei.contiguous(), sparse.edge_attr, (int(n), int(n)))
+  model = pos_enc_factorisation.NMF(n_components=int(opt['gnpde_pos_enc_nmf_dim']), init='random', random_state=0,
+                                    max_iter=opt.get('gnpde_pos_enc_nmf_iters', NMF_DEFAULTS['max_iter']),
+                                    tol=opt.get('gnpde_pos_enc_nmf_tol', NMF_DEFAULTS['tol']), verbose=1)
+  w = model.fit_transform(x).to(torch.device('cpu'))
+  os.makedirs(os.path.dirname(fname), exist_ok=True)
+  with open(fname, 'wb') as f:
+    pickle.dump(w, f)
+  return w
+
+
 def apply_beltrami(data, opt, data_dir='../data'):
   """Positional encodings (reference graph_rewiring.py:244-282): the cached pickle `<data_dir>/pos_encodings/<dataset>_<type>.pkl`
   the reference loads (the 'data' entry for DW* types); otherwise, for pos_enc_type 'GDC', the native
   `apply_gdc(type='pos_encoding')`, cached as the reference caches it.  With a truthy opt['gnpde_generate_pos_enc'] a missing DW<d>
   pickle is trained natively (deepwalk_embeddings.DeepWalk with the reference script's defaults, opt['gnpde_dw_epochs'] epochs,
   default 100, seed opt['seed']) and cached in that layout.  Without the option a missing DW* pickle is an error, as is a missing
-  HYP* pickle always: generating hyperbolic embeddings is not built."""
+  HYP* pickle always: generating hyperbolic embeddings is not built.  With opt['gnpde_pos_enc_nmf_dim'] = r a missing GDC pickle is
+  generated AND compressed to [n, r] by the native NMF (the reference's pos_enc_factorisation.py; opt['gnpde_pos_enc_nmf_iters'],
+  default 100, and opt['gnpde_pos_enc_nmf_tol'], default 0.002), from the sparse GDC graph once the dense matrix exceeds
+  ops.GDC_DENSE_CAP, and W is cached as a CPU tensor at the same path."""
   pos_enc_dir = os.path.join(data_dir, 'pos_encodings')
   fname = os.path.join(pos_enc_dir, '%s_%s.pkl' % (opt['dataset'], opt['pos_enc_type']))
   print('[i] Looking for positional encodings in %s...' % fname)
@@ -331,6 +363,9 @@ def apply_beltrami(data, opt, data_dir='../data'):
     raise FileNotFoundError('apply_beltrami: no cached positional encodings %s, and type %r cannot be generated here%s'
                             % (fname, opt['pos_enc_type'],
                                " (set opt['gnpde_generate_pos_enc'] to train them)" if opt['pos_enc_type'].startswith('DW') else ''))
+  if opt.get('gnpde_pos_enc_nmf_dim'):
+    print('    Encodings not found! Calculating, compressing and caching them')
+    return _generate_compressed_gdc(data, opt, fname)
   print('    Encodings not found! Calculating and caching them')
   pos_encoding = apply_gdc(data, opt, type='pos_encoding')
   os.makedirs(pos_enc_dir, exist_ok=True)

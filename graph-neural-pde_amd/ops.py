@@ -1241,6 +1241,149 @@ def tall_skinny_gram(a, b, slabs=512):
   return out
 
 
+NMF_MAX_COMPONENTS = 256
+NMF_X_NONFINITE, NMF_X_NEGATIVE, NMF_INIT_NONFINITE, NMF_INIT_NEGATIVE, NMF_INDEX_RANGE = 1, 2, 4, 8, 16
+NMF_FLAGS = ((NMF_X_NONFINITE, 'X has a non-finite entry'), (NMF_X_NEGATIVE, 'X has a negative entry'),
+             (NMF_INIT_NONFINITE, 'the initial W or H has a non-finite entry'), (NMF_INIT_NEGATIVE, 'the initial W or H has a negative entry'),
+             (NMF_INDEX_RANGE, 'an edge index lies outside [0, n)'))
+
+
+def _nmf_rows(t, name):
+  """A float32 device matrix with unit column stride (its rows may be padded), as the sweep takes it."""
+  if not isinstance(t, torch.Tensor) or t.dim() != 2:
+    raise _lib.GnpdeError('nmf: %s must be a 2-d tensor' % name)
+  if not t.is_cuda:
+    raise _lib.GnpdeError('nmf: %s is a %s tensor; the factorisation runs only on a HIP device, there is no CPU fallback' % (name, t.device.type))
+  if t.dtype != torch.float32:
+    raise _lib.GnpdeError('nmf: %s must be float32 (got %s)' % (name, t.dtype))
+  if t.shape[1] > 1 and t.stride(1) != 1:
+    raise _lib.GnpdeError('nmf: %s must have unit column stride (strides %s)' % (name, tuple(t.stride())))
+  return t
+
+
+def nmf_cd_sweep(W, G, P, workspace=None):
+  """One half-sweep of sklearn's coordinate-descent NMF (gnpde_nmf_cd_sweep, include/gnpde.h has the definition): W [n, k] is updated
+  in place from G [k, k] (symmetric) and P [n, k]; W and P may be column slices of wider buffers (padded rows).  Returns the
+  projected-gradient violation as a 0-d float64 device tensor; nothing is read by the host."""
+  W, G, P = _nmf_rows(W, 'W'), _nmf_rows(G, 'G'), _nmf_rows(P, 'P')
+  n, k = W.shape
+  if not 1 <= k <= NMF_MAX_COMPONENTS:
+    raise _lib.GnpdeError('nmf: k = %d components outside 1 .. %d' % (k, NMF_MAX_COMPONENTS))
+  if not 1 <= n <= INT32_MAX:
+    raise _lib.GnpdeError('nmf: n = %d rows outside 1 .. INT32_MAX' % n)
+  if tuple(G.shape) != (k, k) or tuple(P.shape) != (n, k) or G.device != W.device or P.device != W.device:
+    raise _lib.GnpdeError('nmf: W is %s but G is %s and P is %s (want [k, k] and [n, k] on one device)' % (tuple(W.shape), tuple(G.shape), tuple(P.shape)))
+  if not G.is_contiguous():
+    G = G.contiguous()
+  L = _lib.lib()
+  need = int(L.gnpde_nmf_cd_sweep_workspace_bytes(n))
+  if workspace is None or workspace.numel() < need:
+    workspace = torch.empty(need, dtype=torch.uint8, device=W.device)
+  out = torch.empty((), dtype=torch.float64, device=W.device)
+  check(L.gnpde_nmf_cd_sweep(ptr(W), W.stride(0) if n > 1 else k, ptr(G), ptr(P), P.stride(0) if n > 1 else k, n, k, ptr(out), ptr(workspace),
+                             workspace.numel(), stream_of(W)))
+  return out
+
+
+def _nmf_operand(X):
+  """(n, m, X H^T product, X^T W product, sum of entries, sum of squares (double), flag bits) of a dense matrix or a sparse triple."""
+  if isinstance(X, torch.Tensor):
+    X = _nmf_rows(X, 'X')
+    if not X.is_contiguous():
+      X = X.contiguous()
+    n, m = X.shape
+    Xt = X.t()
+    bad = (~torch.isfinite(X)).any().to(torch.int32) * NMF_X_NONFINITE + (X < 0).any().to(torch.int32) * NMF_X_NEGATIVE
+    return n, m, (lambda Ht: X.mm(Ht)), (lambda W: Xt.mm(W)), X.sum(dtype=torch.float64), (X.double() ** 2).sum(), bad
+  if not (isinstance(X, (tuple, list)) and len(X) == 3):
+    raise _lib.GnpdeError('nmf: X is a dense float32 [n, m] tensor or (edge_index, weight, (n, m))')
+  from .graph import CSRGraph
+  edge_index, w, shape = X
+  ei = _edge_list(edge_index, 'nmf: edge_index')
+  n, m = int(shape[0]), int(shape[1])
+  if n != m:
+    raise _lib.GnpdeError('nmf: a sparse X must be square (got %d x %d): its products run on the aggregation kernel' % (n, m))
+  if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.numel() != ei.shape[1]:
+    raise _lib.GnpdeError('nmf: weight must be a vector with one value per edge')
+  require_hip(w)
+  w = f32c(w.detach(), 'nmf: weight')
+  bad = (~torch.isfinite(w)).any().to(torch.int32) * NMF_X_NONFINITE + (w < 0).any().to(torch.int32) * NMF_X_NEGATIVE
+  if ei.numel():
+    bad = bad + ((ei < 0) | (ei >= n)).any().to(torch.int32) * NMF_INDEX_RANGE
+    ei = ei.clamp(0, n - 1)
+  # one entry per (row, col), sorted by (row, col) as ops.gdc returns them
+  key, inverse = torch.unique(ei[0] * n + ei[1], return_inverse=True)
+  if key.numel() != w.numel():
+    raise _lib.GnpdeError('nmf: the sparse X repeats %d (row, col) pairs; coalesce it first' % (w.numel() - key.numel()))
+  if w.numel():
+    w = torch.empty_like(w).index_copy_(0, inverse, w)
+  ei = torch.stack([torch.div(key, n, rounding_mode='floor'), key % n])
+  graph = CSRGraph(ei, n, ei.device)
+  graph_t, t_from_csr = graph.transposed_positions()
+  w_csr = w[graph.perm_long].contiguous() if w.numel() else w
+  w_t = w_csr[t_from_csr.long()[:graph.e]].contiguous() if w.numel() else w
+  return n, m, (lambda Ht: spmm(graph, w_csr, Ht)), (lambda W: spmm(graph_t, w_t, W)), w.sum(dtype=torch.float64), (w.double() ** 2).sum(), bad
+
+
+def nmf_iteration(x_ht, xt_w, W, Ht, workspace=None):
+  """One iteration in place on W [n, k] and Ht [m, k]: the W half-sweep with G = H H^T, P = x_ht(Ht), then the H half-sweep with
+  G = W^T W, P = xt_w(W); returns the summed violation (0-d float64 device tensor).  x_ht, xt_w: the two products with X."""
+  v = nmf_cd_sweep(W, tall_skinny_gram(Ht, Ht), x_ht(Ht), workspace)
+  return v + nmf_cd_sweep(Ht, tall_skinny_gram(W, W), xt_w(W), workspace)
+
+
+def nmf(X, n_components, *, W=None, H=None, max_iter=200, tol=1e-4, seed=0, check_every=1):
+  """X ~ W H with W [n, k], H [k, m] >= 0: sklearn.decomposition.NMF(solver='cd', beta_loss='frobenius', shuffle=False) without
+  regularisation (include/gnpde.h has the definition).  X: a dense float32 [n, m] device tensor, or (edge_index [2, E] int64, weight
+  [E], (n, n)) -- a square sparse matrix, every (row, col) pair once.  X H^T and X^T W run on the aggregation kernel (`spmm`;
+  torch.mm for a dense X), the k x k Grams through `tall_skinny_gram`, the updates in `nmf_cd_sweep`.
+  W and H together: the initial factors (sklearn's init='custom'); neither: avg |N(0, 1)| with avg = sqrt(mean(X) / k) from a
+  torch.Generator on the device seeded with `seed` (sklearn's init='random' on another generator).
+  The fit stops after iteration `it` when violation_it / violation_1 <= tol, or at once when violation_1 == 0; the host reads the
+  two violations once per `check_every` iterations and nothing else.  Returns (W, H, n_iter, reconstruction_err):
+  reconstruction_err = sqrt(max(0, |X|^2 - 2 <W, X H^T> + <W^T W, H H^T>)) as a 0-d float64 device tensor, summed in double.
+  Refused: a CPU tensor, negative or non-finite entries in X, W or H, more than 256 components."""
+  k = int(n_components)
+  if not 1 <= k <= NMF_MAX_COMPONENTS:
+    raise _lib.GnpdeError('nmf: n_components = %d outside 1 .. %d' % (k, NMF_MAX_COMPONENTS))
+  max_iter, check_every = int(max_iter), int(check_every)
+  if max_iter < 1 or check_every < 1:
+    raise _lib.GnpdeError('nmf: max_iter = %d and check_every = %d must be positive' % (max_iter, check_every))
+  if (W is None) != (H is None):
+    raise _lib.GnpdeError('nmf: give both W and H (a custom init) or neither (the random init)')
+  n, m, x_ht, xt_w, x_sum, x_sq, bad = _nmf_operand(X)
+  dev = bad.device
+  if W is None:
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    avg = torch.sqrt(x_sum / (float(n) * float(m) * k)).to(torch.float32)
+    Ht = (avg * torch.randn(k, m, generator=gen, dtype=torch.float32, device=dev).abs()).t().contiguous()
+    W = avg * torch.randn(n, k, generator=gen, dtype=torch.float32, device=dev).abs()
+  else:
+    W, H = _nmf_rows(W, 'W'), _nmf_rows(H, 'H')
+    if tuple(W.shape) != (n, k) or tuple(H.shape) != (k, m) or W.device != dev or H.device != dev:
+      raise _lib.GnpdeError('nmf: the initial W is %s and H is %s; want [%d, %d] and [%d, %d] on %s' % (tuple(W.shape), tuple(H.shape), n, k, k, m, dev))
+    bad = bad + ((~torch.isfinite(W)).any() | (~torch.isfinite(H)).any()).to(torch.int32) * NMF_INIT_NONFINITE
+    bad = bad + ((W < 0).any() | (H < 0).any()).to(torch.int32) * NMF_INIT_NEGATIVE
+    W, Ht = W.detach().clone().contiguous(), H.detach().t().contiguous()
+  _raise_flags(bad, 'nmf', NMF_FLAGS)
+  L = _lib.lib()
+  ws = torch.empty(int(L.gnpde_nmf_cd_sweep_workspace_bytes(max(n, m))), dtype=torch.uint8, device=dev)
+  first = None
+  n_iter = max_iter
+  for it in range(1, max_iter + 1):
+    v = nmf_iteration(x_ht, xt_w, W, Ht, ws)
+    if it == 1:
+      first = v
+    if it % check_every == 0 or it == 1:
+      v_now, v_first = torch.stack([v, first]).tolist()
+      if v_first == 0.0 or v_now / v_first <= tol:
+        n_iter = it
+        break
+  Wd, Hd = W.double(), Ht.double()
+  err2 = x_sq - 2.0 * (Wd * x_ht(Ht).double()).sum() + (Wd.t().mm(Wd) * Hd.t().mm(Hd)).sum()
+  return W, Ht.t().contiguous(), n_iter, torch.sqrt(torch.clamp(err2, min=0.0))
+
+
 def head_spmm(graph, ds_csr, feat, heads, dk, scale, by_column, out=None):
   """Head-wise weighted segment sum (gnpde_head_spmm): [N, heads*dk] (optionally into a column slice `out`)."""
   require_hip(ds_csr, feat)

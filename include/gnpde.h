@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 16  /* 16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 17  /* 17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -963,6 +963,27 @@ int gnpde_deepwalk_step(float* emb, int32_t ld, float* m, float* v, int32_t ld_m
                         const int32_t* pos_rw, int64_t r_pos, const int32_t* neg_rw, int64_t r_neg, int32_t walk_length,
                         int32_t context_size, float lr, float beta1, float beta2, float eps, float* loss_out, int32_t* flag,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* NMF compression of positional encodings (reference src/pos_enc_factorisation.py: sklearn.decomposition.NMF(solver='cd',
+ * beta_loss='frobenius'), no regularisation, shuffle off).  This header is the authority; sklearn is no dependency.
+ *   X [n, m] >= 0 is approximated by W [n, k] H [k, m], W, H >= 0.  One iteration is two half-sweeps of one kind:
+ *     update W  with  G = H H^T [k, k]  and  P = X H^T [n, k];      update H^T [m, k]  with  G = W^T W  and  P = X^T W.
+ *   gnpde_nmf_cd_sweep is one half-sweep: for each component t = 0 .. k - 1 in order and for every row i
+ *       grad = -P[i, t] + sum_r G[t, r] W[i, r]                   (W already updated for the components < t)
+ *       pg   = W[i, t] == 0 ? min(0, grad) : grad;   *violation += |pg|
+ *       if G[t, t] != 0:  W[i, t] = max(W[i, t] - grad / G[t, t], 0)                           (one IEEE division)
+ *   Rows are independent.  The kernel keeps q = W_i G - P_i in registers (one wave per row, lane l the components l, l + 64, ...) and
+ *   adds G[t, :] (new - old) to it after each component: the same mathematics with another float32 summation order.  G is a Gram
+ *   matrix: the kernel reads row t of G where the update of q names column t, so G is to be symmetric.
+ *   *violation (device double) = the sum over rows and components: per row in double in component order, one double per row in
+ *   the workspace, then chunks of 4096 rows and the chunk sums in a fixed order.  No atomics: bit-identical from run to run.
+ *   W [n, k] (row stride ldw, in place), G [k, k] contiguous, P [n, k] (row stride ldp), float32, unit column stride.
+ *   Limits: 1 <= k <= 256 and 1 <= n <= INT32_MAX (GNPDE_ESHAPE); the byte range of W may meet neither P's nor G's (GNPDE_EINVAL;
+ *   two column slices of ONE wider buffer count as meeting).  Inputs are to be finite and W, G[t, t] >= 0: nothing is checked on the
+ *   device.  Everything runs on the caller's stream; the workspace query returns 0 for an n the entry point refuses. */
+size_t gnpde_nmf_cd_sweep_workspace_bytes(int64_t n);
+int gnpde_nmf_cd_sweep(float* W, int64_t ldw, const float* G, const float* P, int64_t ldp, int64_t n, int32_t k, double* violation,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* Two-hop densification of the rewiring block (new_edges = 'k_hop_att', reference src/block_transformer_rewiring.py:68-86):
  *   S = coalesce(A ++ offdiag(A A)) / 2, i.e. torch_sparse.spspmm(A, A) -> remove_self_loops -> cat with A -> / 2 ->
