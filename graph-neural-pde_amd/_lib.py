@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 17     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 18     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
@@ -49,6 +49,28 @@ class GraphStruct(ctypes.Structure):
               ('n_long_cols', ctypes.c_int32), ('n_bin16', ctypes.c_int32), ('n_bin64', ctypes.c_int32),
               ('max_row_len', ctypes.c_int32), ('max_col_len', ctypes.c_int32), ('row_begin', ctypes.c_int32), ('long_cols', c_vp), ('bin_rows', c_vp), ('long_chunk_first', c_vp),
               ('xcd_deal', ctypes.c_int32), ('n_bin_le64', ctypes.c_int32)]
+
+
+class LinearLaunchStruct(ctypes.Structure):
+  """gnpde_linear_launch_t: one launch of the projection's plan (gnpde_linear_plan)."""
+  _fields_ = [('family', ctypes.c_int32), ('mt', ctypes.c_int32), ('param', ctypes.c_int32), ('split', ctypes.c_int32),
+              ('col_base', ctypes.c_int32), ('cols', ctypes.c_int32),
+              ('grid_x', ctypes.c_uint32), ('grid_y', ctypes.c_uint32), ('block', ctypes.c_uint32)]
+
+  @property
+  def line(self):
+    """The kernel instantiation as the dispatch table of csrc/linear.hip names it, e.g. 'staged<2,4>' or 'tile<8,1,0>'."""
+    fam = LINEAR_FAMILIES[self.family]
+    if fam == 'small':
+      return 'small<%d>' % self.mt
+    if fam == 'staged2':
+      return 'staged2<%d>%s' % (self.param, '+split' if self.split else '')
+    if fam == 'tile':
+      return 'tile<%d,%d,%d>' % (self.mt, self.param >> 1, self.param & 1)
+    return '%s<%d,%d>' % (fam, self.mt, self.param)
+
+
+LINEAR_FAMILIES = ('small', 'staged2', 'staged', 'persistent', 'lds', 'tile')     # GNPDE_LINEAR_* of include/gnpde.h
 
 
 class EpilogueStruct(ctypes.Structure):
@@ -162,6 +184,10 @@ PROTOTYPES = {
                                           ctypes.c_int32, c_float_p, ctypes.c_int32, c_vp, ctypes.c_size_t]),
   'gnpde_adjoint_run': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_linear_split_supported': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+  'gnpde_linear_plan': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(LinearLaunchStruct), ctypes.c_int32]),
+  'gnpde_linear_split_plan': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(LinearLaunchStruct)]),
   'gnpde_linear_split': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp,
                                         ctypes.c_int32, c_vp]),
   'gnpde_adjoint_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]),

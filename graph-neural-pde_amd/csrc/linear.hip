@@ -471,82 +471,68 @@ __global__ __launch_bounds__(kBlock) void linear_staged2_kernel(const float* __r
   }
 }
 
-template <int MT, bool ALIGNED>
-void launch_tile(const float* x, int n, int d, int ldx, const float* W, int m, int ldw, const float* b, float* out,
-                 int ldo, int col, hipStream_t s, int relu) {
+// ---- The launch decision -----------------------------------------------------------------------------------------------------
+// ONE function decides which kernel instantiation a launch takes, over which columns and on what grid; the launchers below switch on
+// its result and gnpde_linear_plan hands the same result to tests and A/B scripts, so the two cannot drift apart.  A launch is
+// (family, mt, param): the template arguments of the kernel (gnpde_linear_launch_t in include/gnpde.h).
+struct LinearShape {
+  long long n;
+  int d, m, ldo;
+  bool aligned;        // 16-byte operand loads: ldx % 4 == 0, ldw % 4 == 0, x and W 16-byte aligned
+  uintptr_t out;       // only its alignment is read
+};
+
+unsigned capped_grid(long long blocks, long long need) { return static_cast<unsigned>(blocks > need ? need : blocks); }
+
+// the launch of MT column tiles from column `col` on
+gnpde_linear_launch_t plan_tile(const LinearShape& p, int MT, int col) {
+  gnpde_linear_launch_t L = {};
+  L.mt = MT;
+  L.col_base = col;
+  L.cols = p.m - col < 16 * MT ? p.m - col : 16 * MT;
+  L.grid_y = 1;
+  L.block = kBlock;
   // complete 16-row tiles with complete column tiles and d % 16 == 0 take the unguarded kernel
-  const bool full_cols = ALIGNED && (d % 16 == 0) && (col + 16 * MT <= m);
-  const long long tiles = (static_cast<long long>(n) + 15) / 16;
-  if constexpr (MT <= 2) {
-    if (full_cols && d <= 128) {
-      // persistent grid: enough wavefronts to fill the chip (8 per SIMD at these register counts would be
-      // ideal; W fragments + double-buffered A cost ~150 VGPRs -> 3 per SIMD), each striding over tiles
-      long long blocks = 256LL * 3;
-      const long long need = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-      if (blocks > need) blocks = need;
-      const unsigned pg = static_cast<unsigned>(blocks);
-      // d = 64 / 128 (4 or 8 chunks per lane and tile): full-line loads transposed through LDS (linear_staged_kernel)
-      if (d == 128 || d == 64) {
-        if constexpr (MT == 2) {
-          if (ldo % 2 == 0 && col % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0) {
-            // paired columns on a grid of 4 workgroups per CU (3 resident: the fourth starts as one ends) -- 24.4 -> 24.0 us in the
-            // headline solve, 26.9 -> 25.8 us stand-alone (profiles/r06_linear_*.txt)
-            long long pg2 = 256LL * 4;
-            if (pg2 > need) pg2 = need;
-            const unsigned g2 = static_cast<unsigned>(pg2);
-            if (d == 128)
-              hipLaunchKernelGGL((linear_staged2_kernel<8>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
-            else
-              hipLaunchKernelGGL((linear_staged2_kernel<4>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
-            return;
-          }
-        }
-        if (d == 128)
-          hipLaunchKernelGGL((linear_staged_kernel<MT, 8>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
-        else
-          hipLaunchKernelGGL((linear_staged_kernel<MT, 4>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu);
-        return;
-      }
-#define GNPDE_LP(KBV) \
-  hipLaunchKernelGGL((linear_persistent_kernel<MT, KBV>), dim3(pg), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu)
-      switch (d / 16) {
-        case 1: GNPDE_LP(1); return;
-        case 2: GNPDE_LP(2); return;
-        case 3: GNPDE_LP(3); return;
-        case 4: GNPDE_LP(4); return;
-        case 5: GNPDE_LP(5); return;
-        case 6: GNPDE_LP(6); return;
-        case 7: GNPDE_LP(7); return;
-        case 8: GNPDE_LP(8); return;
-        default: break;
-      }
-#undef GNPDE_LP
-    }
-  }
-  if constexpr (MT >= 4 && ALIGNED) {
-    if (full_cols && d <= 256) {   // W staged in LDS, persistent workgroups
-      const long long need = (tiles + 7) / 8;
-      if (d <= 128) {
-        long long blocks = 256LL * (MT == 4 ? 4 : 2);
-        if (blocks > need) blocks = need;
-        hipLaunchKernelGGL((linear_lds_kernel<MT, 128>), dim3(static_cast<unsigned>(blocks)), dim3(512), 0, s, x, n, d, ldx, W, ldw, b,
-                           out, ldo, col, relu);
+  const bool full_cols = p.aligned && (p.d % 16 == 0) && (col + 16 * MT <= p.m);
+  const long long tiles = (p.n + 15) / 16;
+  const long long need = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (MT <= 2 && full_cols && p.d <= 128) {
+    // persistent grid: enough wavefronts to fill the chip (8 per SIMD at these register counts would be
+    // ideal; W fragments + double-buffered A cost ~150 VGPRs -> 3 per SIMD), each striding over tiles
+    L.grid_x = capped_grid(256LL * 3, need);
+    L.param = p.d / 16;
+    // d = 64 / 128 (4 or 8 chunks per lane and tile): full-line loads transposed through LDS (linear_staged_kernel)
+    if (p.d == 128 || p.d == 64) {
+      if (MT == 2 && p.ldo % 2 == 0 && col % 2 == 0 && p.out % 8 == 0) {
+        // paired columns on a grid of 4 workgroups per CU (3 resident: the fourth starts as one ends) -- 24.4 -> 24.0 us in the
+        // headline solve, 26.9 -> 25.8 us stand-alone (profiles/r06_linear_*.txt)
+        L.family = GNPDE_LINEAR_STAGED2;
+        L.grid_x = capped_grid(256LL * 4, need);
       } else {
-        long long blocks = 256LL * (MT == 4 ? 2 : 1);
-        if (blocks > need) blocks = need;
-        hipLaunchKernelGGL((linear_lds_kernel<MT, 256>), dim3(static_cast<unsigned>(blocks)), dim3(512), 0, s, x, n, d, ldx, W, ldw, b,
-                           out, ldo, col, relu);
+        L.family = GNPDE_LINEAR_STAGED;
       }
-      return;
+    } else {
+      L.family = GNPDE_LINEAR_PERSISTENT;
     }
+    return L;
   }
-  const unsigned grid = static_cast<unsigned>((tiles + kWavesPerBlock - 1) / kWavesPerBlock);
-  if (full_cols)
-    hipLaunchKernelGGL((linear_kernel<MT, ALIGNED, true>), dim3(grid), dim3(kBlock), 0, s, x, n, d, ldx, W, m, ldw, b, out, ldo,
-                       col, 0, relu);
-  else
-    hipLaunchKernelGGL((linear_kernel<MT, ALIGNED, false>), dim3(grid), dim3(kBlock), 0, s, x, n, d, ldx, W, m, ldw, b, out,
-                       ldo, col, 0, relu);
+  if (MT >= 4 && full_cols && p.d <= 256) {   // W staged in LDS, persistent workgroups of 8 waves
+    const long long need8 = (tiles + 7) / 8;
+    L.family = GNPDE_LINEAR_LDS;
+    L.block = 512;
+    if (p.d <= 128) {
+      L.param = 128;
+      L.grid_x = capped_grid(256LL * (MT == 4 ? 4 : 2), need8);
+    } else {
+      L.param = 256;
+      L.grid_x = capped_grid(256LL * (MT == 4 ? 2 : 1), need8);
+    }
+    return L;
+  }
+  L.family = GNPDE_LINEAR_TILE;
+  L.param = 2 * (p.aligned ? 1 : 0) + (full_cols ? 1 : 0);
+  L.grid_x = static_cast<unsigned>(need);
+  return L;
 }
 
 // Small n (Cora: 2 708 rows, [n,80] x [80,256]): the persistent / LDS-staged kernels above are built to stream a tall x -- at 170 row
@@ -558,37 +544,128 @@ void launch_tile(const float* x, int n, int d, int ldx, const float* W, int m, i
 // every other variant (bit-identical results).
 constexpr long long kSmallLinearTiles = 2048;      // n <= 32 768 rows
 
-template <bool ALIGNED>
-void launch_linear(const float* x, int n, int d, int ldx, const float* W, int m, int ldw, const float* b, float* out,
-                   int ldo, hipStream_t s, int relu) {
-  if constexpr (ALIGNED) {
-    const long long tiles = (static_cast<long long>(n) + 15) / 16;
-    if (tiles <= kSmallLinearTiles && d % 16 == 0 && m % 16 == 0) {
-      const unsigned gx = static_cast<unsigned>((tiles + kWavesPerBlock - 1) / kWavesPerBlock);
-      if (m % 32 == 0)
-        hipLaunchKernelGGL((linear_kernel<2, true, true, 8>), dim3(gx, m / 32), dim3(kBlock), 0, s, x, n, d, ldx, W, m, ldw, b, out, ldo, 0, 0, relu);
-      else
-        hipLaunchKernelGGL((linear_kernel<1, true, true, 8>), dim3(gx, m / 16), dim3(kBlock), 0, s, x, n, d, ldx, W, m, ldw, b, out, ldo, 0, 0, relu);
-      return;
-    }
+// The launch that starts at column `col` (col < m); the next one starts at col + 16 * mt of what this returns, until that reaches m.
+gnpde_linear_launch_t plan_next(const LinearShape& p, int col) {
+  const long long tiles = (p.n + 15) / 16;
+  if (p.aligned && col == 0 && tiles <= kSmallLinearTiles && p.d % 16 == 0 && p.m % 16 == 0) {
+    gnpde_linear_launch_t L = {};
+    L.family = GNPDE_LINEAR_SMALL;
+    L.mt = p.m % 32 == 0 ? 2 : 1;
+    L.cols = p.m;
+    L.grid_x = static_cast<unsigned>((tiles + kWavesPerBlock - 1) / kWavesPerBlock);
+    L.grid_y = static_cast<unsigned>(p.m / (16 * L.mt));
+    L.block = kBlock;
+    return L;
   }
-  int col = 0;
-  while (col < m) {
-    const int rem = (m - col + 15) / 16;
-    if (rem >= 8) {
-      launch_tile<8, ALIGNED>(x, n, d, ldx, W, m, ldw, b, out, ldo, col, s, relu);
-      col += 128;
-    } else if (rem >= 4) {
-      launch_tile<4, ALIGNED>(x, n, d, ldx, W, m, ldw, b, out, ldo, col, s, relu);
-      col += 64;
-    } else if (rem >= 2) {
-      launch_tile<2, ALIGNED>(x, n, d, ldx, W, m, ldw, b, out, ldo, col, s, relu);
-      col += 32;
-    } else {
-      launch_tile<1, ALIGNED>(x, n, d, ldx, W, m, ldw, b, out, ldo, col, s, relu);
-      col += 16;
-    }
+  const int rem = (p.m - col + 15) / 16;
+  return plan_tile(p, rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1, col);
+}
+
+int columns_advanced(const gnpde_linear_launch_t& L) { return L.family == GNPDE_LINEAR_SMALL ? L.cols : 16 * L.mt; }
+
+// Launch what the plan says: nothing here looks at the shape again.
+int launch_planned(const gnpde_linear_launch_t& L, const float* x, int n, int d, int ldx, const float* W, int m, int ldw, const float* b,
+                   float* out, int ldo, hipStream_t s, int relu, float* out2 = nullptr, int split = 0) {
+  const dim3 grid(L.grid_x, L.grid_y), block(L.block);
+  const int col = L.col_base;
+  const int key = L.mt * 1000 + L.param;
+#define GNPDE_LK(KEY, ...) \
+  case KEY: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, x, n, d, ldx, W, m, ldw, b, out, ldo, col, 0, relu); return 0
+#define GNPDE_LP(KEY, ...) \
+  case KEY: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu); return 0
+#define GNPDE_LL(KEY, ...) \
+  case KEY: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, x, n, d, ldx, W, ldw, b, out, ldo, col, relu); return 0
+  switch (L.family) {
+    case GNPDE_LINEAR_SMALL:
+      switch (key) {
+        GNPDE_LK(1000, linear_kernel<1, true, true, 8>);
+        GNPDE_LK(2000, linear_kernel<2, true, true, 8>);
+        default: break;
+      }
+      break;
+    case GNPDE_LINEAR_STAGED2:
+      switch (key) {
+        case 2004: hipLaunchKernelGGL((linear_staged2_kernel<4>), grid, block, 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu, out2, split); return 0;
+        case 2008: hipLaunchKernelGGL((linear_staged2_kernel<8>), grid, block, 0, s, x, n, ldx, W, ldw, b, out, ldo, col, relu, out2, split); return 0;
+        default: break;
+      }
+      break;
+    case GNPDE_LINEAR_STAGED:
+      switch (key) {
+        GNPDE_LP(1004, linear_staged_kernel<1, 4>);
+        GNPDE_LP(1008, linear_staged_kernel<1, 8>);
+        GNPDE_LP(2004, linear_staged_kernel<2, 4>);
+        GNPDE_LP(2008, linear_staged_kernel<2, 8>);
+        default: break;
+      }
+      break;
+    case GNPDE_LINEAR_PERSISTENT:
+      switch (key) {
+        GNPDE_LP(1001, linear_persistent_kernel<1, 1>);
+        GNPDE_LP(1002, linear_persistent_kernel<1, 2>);
+        GNPDE_LP(1003, linear_persistent_kernel<1, 3>);
+        GNPDE_LP(1005, linear_persistent_kernel<1, 5>);
+        GNPDE_LP(1006, linear_persistent_kernel<1, 6>);
+        GNPDE_LP(1007, linear_persistent_kernel<1, 7>);
+        GNPDE_LP(2001, linear_persistent_kernel<2, 1>);
+        GNPDE_LP(2002, linear_persistent_kernel<2, 2>);
+        GNPDE_LP(2003, linear_persistent_kernel<2, 3>);
+        GNPDE_LP(2005, linear_persistent_kernel<2, 5>);
+        GNPDE_LP(2006, linear_persistent_kernel<2, 6>);
+        GNPDE_LP(2007, linear_persistent_kernel<2, 7>);
+        default: break;
+      }
+      break;
+    case GNPDE_LINEAR_LDS:
+      switch (key) {
+        GNPDE_LL(4128, linear_lds_kernel<4, 128>);
+        GNPDE_LL(4256, linear_lds_kernel<4, 256>);
+        GNPDE_LL(8128, linear_lds_kernel<8, 128>);
+        GNPDE_LL(8256, linear_lds_kernel<8, 256>);
+        default: break;
+      }
+      break;
+    case GNPDE_LINEAR_TILE:
+      switch (key) {   // param = 2 * ALIGNED + FULL
+        GNPDE_LK(1003, linear_kernel<1, true, true>);
+        GNPDE_LK(1002, linear_kernel<1, true, false>);
+        GNPDE_LK(1000, linear_kernel<1, false, false>);
+        GNPDE_LK(2003, linear_kernel<2, true, true>);
+        GNPDE_LK(2002, linear_kernel<2, true, false>);
+        GNPDE_LK(2000, linear_kernel<2, false, false>);
+        GNPDE_LK(4003, linear_kernel<4, true, true>);
+        GNPDE_LK(4002, linear_kernel<4, true, false>);
+        GNPDE_LK(4000, linear_kernel<4, false, false>);
+        GNPDE_LK(8003, linear_kernel<8, true, true>);
+        GNPDE_LK(8002, linear_kernel<8, true, false>);
+        GNPDE_LK(8000, linear_kernel<8, false, false>);
+        default: break;
+      }
+      break;
+    default: break;
   }
+#undef GNPDE_LK
+#undef GNPDE_LP
+#undef GNPDE_LL
+  set_error("linear: the plan names no kernel (family %d, mt %d, param %d)", L.family, L.mt, L.param);
+  return GNPDE_ESHAPE;
+}
+
+bool operands_aligned(uintptr_t x, int ldx, uintptr_t W, int ldw) { return ldx % 4 == 0 && ldw % 4 == 0 && x % 16 == 0 && W % 16 == 0; }
+
+// the one launch of gnpde_linear_split: the paired-column staged kernel over both tables
+gnpde_linear_launch_t plan_split(long long n, int d) {
+  gnpde_linear_launch_t L = {};
+  const long long tiles = (n + 15) / 16;
+  L.family = GNPDE_LINEAR_STAGED2;
+  L.mt = 2;
+  L.param = d / 16;
+  L.split = 1;
+  L.cols = 32;
+  L.grid_x = capped_grid(256LL * 4, (tiles + kWavesPerBlock - 1) / kWavesPerBlock);
+  L.grid_y = 1;
+  L.block = kBlock;
+  return L;
 }
 
 }  // namespace
@@ -597,8 +674,8 @@ void launch_linear(const float* x, int n, int d, int ldx, const float* W, int m,
 // take the staged kernel anyway (tall x, d = 64 / 128, 2A = 32 output columns, 16-byte aligned operands).
 bool linear_split_supported(const float* x, long long n, int d, int ldx, const float* W, int m, int ldw, int split) {
   const long long tiles = (n + 15) / 16;
-  return m == 32 && split == 16 && (d == 64 || d == 128) && tiles > kSmallLinearTiles && ldx % 4 == 0 && ldw % 4 == 0 &&
-         reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0 && g_tune[GNPDE_TUNE_KEY_TABLE] != 1;
+  return m == 32 && split == 16 && (d == 64 || d == 128) && tiles > kSmallLinearTiles &&
+         operands_aligned(reinterpret_cast<uintptr_t>(x), ldx, reinterpret_cast<uintptr_t>(W), ldw) && g_tune[GNPDE_TUNE_KEY_TABLE] != 1;
 }
 
 int launch_linear_split(const float* x, int n, int d, int ldx, const float* W, int m, int ldw, const float* b, float* out_q, float* out_k,
@@ -606,13 +683,7 @@ int launch_linear_split(const float* x, int n, int d, int ldx, const float* W, i
   GNPDE_CHECK_ARG(x && W && out_q && out_k && linear_split_supported(x, n, d, ldx, W, m, ldw, split) &&
                   reinterpret_cast<uintptr_t>(out_q) % 8 == 0 && reinterpret_cast<uintptr_t>(out_k) % 8 == 0, GNPDE_ESHAPE,
                   "linear_split: shape without a two-table kernel (see linear_split_supported)");
-  const long long tiles = (static_cast<long long>(n) + 15) / 16;
-  long long blocks = 256LL * 4;
-  const long long need = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-  if (blocks > need) blocks = need;
-  const unsigned g2 = static_cast<unsigned>(blocks);
-  if (d == 128) hipLaunchKernelGGL((linear_staged2_kernel<8>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out_q, split, 0, 0, out_k, split);
-  else hipLaunchKernelGGL((linear_staged2_kernel<4>), dim3(g2), dim3(kBlock), 0, s, x, n, ldx, W, ldw, b, out_q, split, 0, 0, out_k, split);
+  if (int rc = launch_planned(plan_split(n, d), x, n, d, ldx, W, m, ldw, b, out_q, split, s, 0, out_k, split)) return rc;
   GNPDE_LAUNCH_CHECK();
   return 0;
 }
@@ -623,12 +694,40 @@ int launch_linear_any(const float* x, int n, int d, int ldx, const float* W, int
   GNPDE_CHECK_ARG(n >= 0 && d >= 1 && m >= 1 && ldx >= d && ldw >= d && ldo >= m, GNPDE_EINVAL,
                   "linear: bad shape n=%d d=%d m=%d ldx=%d ldw=%d ldo=%d", n, d, m, ldx, ldw, ldo);
   if (n == 0) return 0;
-  const bool al = (ldx % 4 == 0) && (ldw % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
-                  (reinterpret_cast<uintptr_t>(W) % 16 == 0);
-  if (al) launch_linear<true>(x, n, d, ldx, W, m, ldw, b, out, ldo, s, relu);
-  else launch_linear<false>(x, n, d, ldx, W, m, ldw, b, out, ldo, s, relu);
+  const LinearShape p = {n, d, m, ldo, operands_aligned(reinterpret_cast<uintptr_t>(x), ldx, reinterpret_cast<uintptr_t>(W), ldw),
+                         reinterpret_cast<uintptr_t>(out)};
+  for (int col = 0; col < m;) {
+    const gnpde_linear_launch_t L = plan_next(p, col);
+    if (int rc = launch_planned(L, x, n, d, ldx, W, m, ldw, b, out, ldo, s, relu)) return rc;
+    col += columns_advanced(L);
+  }
   GNPDE_LAUNCH_CHECK();
   return 0;
+}
+
+int linear_plan(uintptr_t x, int n, int d, int ldx, uintptr_t W, int m, int ldw, uintptr_t out, int ldo, gnpde_linear_launch_t* plan, int cap) {
+  GNPDE_CHECK_ARG(n >= 0 && d >= 1 && m >= 1 && ldx >= d && ldw >= d && ldo >= m, GNPDE_EINVAL,
+                  "linear_plan: bad shape n=%d d=%d m=%d ldx=%d ldw=%d ldo=%d", n, d, m, ldx, ldw, ldo);
+  GNPDE_CHECK_ARG(cap >= 0 && (plan != nullptr || cap == 0), GNPDE_EINVAL, "linear_plan: cap = %d entries without a buffer", cap);
+  if (n == 0) return 0;
+  const LinearShape p = {n, d, m, ldo, operands_aligned(x, ldx, W, ldw), out};
+  int count = 0;
+  for (int col = 0; col < m; ++count) {
+    const gnpde_linear_launch_t L = plan_next(p, col);
+    if (count < cap) plan[count] = L;
+    col += columns_advanced(L);
+  }
+  return count;
+}
+
+int linear_split_plan(uintptr_t x, int n, int d, int ldx, uintptr_t W, int m, int ldw, uintptr_t out_q, uintptr_t out_k, int split,
+                      gnpde_linear_launch_t* plan) {
+  GNPDE_CHECK_ARG(plan != nullptr, GNPDE_EINVAL, "linear_split_plan: null plan");
+  GNPDE_CHECK_ARG(linear_split_supported(reinterpret_cast<const float*>(x), n, d, ldx, reinterpret_cast<const float*>(W), m, ldw, split) &&
+                  out_q % 8 == 0 && out_k % 8 == 0, GNPDE_ESHAPE,
+                  "linear_split_plan: shape without a two-table kernel (see linear_split_supported)");
+  *plan = plan_split(n, d);
+  return 1;
 }
 
 }  // namespace gnpde
@@ -645,6 +744,18 @@ extern "C" int gnpde_linear_split_supported(const float* x, int64_t n, int32_t d
 extern "C" int gnpde_linear_split(const float* x, int32_t n, int32_t d, int32_t ldx, const float* W, int32_t m, int32_t ldw, const float* b,
                                   float* out_q, float* out_k, int32_t split, void* stream) {
   return gnpde::launch_linear_split(x, n, d, ldx, W, m, ldw, b, out_q, out_k, split, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int gnpde_linear_plan(uint64_t x_addr, int32_t n, int32_t d, int32_t ldx, uint64_t w_addr, int32_t m, int32_t ldw, uint64_t out_addr,
+                                 int32_t ldo, gnpde_linear_launch_t* plan, int32_t cap) {
+  return gnpde::linear_plan(static_cast<uintptr_t>(x_addr), n, d, ldx, static_cast<uintptr_t>(w_addr), m, ldw, static_cast<uintptr_t>(out_addr), ldo,
+                            plan, cap);
+}
+
+extern "C" int gnpde_linear_split_plan(uint64_t x_addr, int32_t n, int32_t d, int32_t ldx, uint64_t w_addr, int32_t m, int32_t ldw,
+                                       uint64_t out_q_addr, uint64_t out_k_addr, int32_t split, gnpde_linear_launch_t* plan) {
+  return gnpde::linear_split_plan(static_cast<uintptr_t>(x_addr), n, d, ldx, static_cast<uintptr_t>(w_addr), m, ldw,
+                                  static_cast<uintptr_t>(out_q_addr), static_cast<uintptr_t>(out_k_addr), split, plan);
 }
 
 extern "C" int gnpde_relu_linear(const float* x, int32_t n, int32_t d, int32_t ldx, const float* W, int32_t m, int32_t ldw,

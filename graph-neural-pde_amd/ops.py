@@ -18,9 +18,9 @@ def _scalar_dev(t, like):
 _PAD_X, _PAD_W = {}, {}
 
 
-def linear(x, weight, bias=None, out=None, relu_input=False):
-  """out = x @ weight.T + bias on the fp32 matrix cores (gnpde_linear); relu_input: out = relu(x) @ weight.T + bias
-  (gnpde_relu_linear, the decoder of GNN.forward).  x may have padded rows (unit column stride)."""
+def _linear_operands(x, weight, bias, out):
+  """(x, weight, b, out, n, d, m) as the projection kernels get them: validated, out allocated, and for n >= 4096 with a K the 16-byte
+  loads do not cover the zero-padded copies of both operands."""
   require_hip(x, weight, bias)
   x, weight = _lib.f32rows(x, 'x'), f32c(weight, 'weight')
   n, d = x.shape
@@ -29,8 +29,17 @@ def linear(x, weight, bias=None, out=None, relu_input=False):
     raise _lib.GnpdeError('linear: weight is %s but x has %d features' % (tuple(weight.shape), d))
   if out is None:
     out = torch.empty(n, m, dtype=torch.float32, device=x.device)
+  else:
+    # the kernels get out's address and row stride as they are: anything they would not write as [n, m] rows is refused before a launch
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+      raise _lib.GnpdeError('linear: out must be a float32 tensor (got %s)' % (getattr(out, 'dtype', type(out).__name__),))
+    if out.device != x.device:
+      raise _lib.GnpdeError('linear: out is on %s but x is on %s' % (out.device, x.device))
+    if tuple(out.shape) != (n, m):
+      raise _lib.GnpdeError('linear: out is %s, the product is [%d, %d]' % (tuple(out.shape), n, m))
+    if m > 1 and out.stride(1) != 1:
+      raise _lib.GnpdeError('linear: out must have unit column stride (strides %s)' % (tuple(out.stride()),))
   b = None if bias is None else f32c(bias, 'bias')
-  fn = _lib.lib().gnpde_relu_linear if relu_input else _lib.lib().gnpde_linear
   if n >= 4096 and (d % 16 != 0 or x.stride(0) % 4 != 0 or weight.stride(0) % 4 != 0):
     # a width the 16-byte operand loads / complete 16-wide K blocks of the MFMA kernels do not cover (BLEND: d = 162) takes their
     # guarded scalar-load variant -- 383 us against ~60 at the ogbn-arxiv shape.  Zero-padded copies of both operands (K up to the
@@ -55,8 +64,39 @@ def linear(x, weight, bias=None, out=None, relu_input=False):
       wp = _PAD_W[wkey] = torch.zeros(m, d16, dtype=torch.float32, device=x.device)
     wp[:, :d].copy_(weight)
     x, weight, d = xp, wp, d16
+  return x, weight, b, out, n, d, m
+
+
+def linear(x, weight, bias=None, out=None, relu_input=False):
+  """out = x @ weight.T + bias on the fp32 matrix cores (gnpde_linear); relu_input: out = relu(x) @ weight.T + bias
+  (gnpde_relu_linear, the decoder of GNN.forward).  x may have padded rows (unit column stride).  out, when given, is a float32
+  [n, m] tensor on x's device with unit column stride (a column window of a wider matrix is fine); anything else raises GnpdeError
+  before a launch."""
+  x, weight, b, out, n, d, m = _linear_operands(x, weight, bias, out)
+  fn = _lib.lib().gnpde_relu_linear if relu_input else _lib.lib().gnpde_linear
   check(fn(ptr(x), n, d, x.stride(0), ptr(weight), m, weight.stride(0), ptr(b), ptr(out), out.stride(0), stream_of(x)))
   return out
+
+
+def linear_launches(x, weight, out=None):
+  """The launches linear(x, weight, out=out) makes (gnpde_linear_plan), as _lib.LinearLaunchStruct records in launch order: the same
+  operand preparation, zero-padded copies included, and no launch."""
+  x, weight, _, out, n, d, m = _linear_operands(x, weight, None, out)
+  L = _lib.lib()
+  args = (x.data_ptr(), n, d, x.stride(0), weight.data_ptr(), m, weight.stride(0), out.data_ptr(), out.stride(0))
+  count = L.gnpde_linear_plan(*args, None, 0)
+  if count < 0:
+    check(count)
+  plan = (_lib.LinearLaunchStruct * max(count, 1))()
+  if L.gnpde_linear_plan(*args, plan, count) != count:
+    raise _lib.GnpdeError('linear_plan: the launch count changed between two calls')
+  return list(plan[:count])
+
+
+def linear_plan(x, weight, out=None):
+  """Names of the kernel instantiations linear(x, weight, out=out) launches, in order ('small<2>', 'staged2<8>', 'lds<4,128>',
+  'tile<1,1,0>', ...: the dispatch table of csrc/linear.hip).  The launch decision, for tests and A/B scripts."""
+  return [l.line for l in linear_launches(x, weight, out)]
 
 
 def qk_tables(x, weight, bias, att_dim, out=None):
@@ -78,6 +118,27 @@ def qk_tables(x, weight, bias, att_dim, out=None):
     return q, k, att_dim, out
   qk = linear(x, weight, bias, out=flat.view(n, m))
   return qk, qk[:, att_dim:], m, out
+
+
+def qk_tables_plan(x, weight, att_dim, out=None):
+  """Names of the launches of qk_tables(x, weight, ., att_dim, out): ['staged2<KB>+split'] where the two tables are written
+  (gnpde_linear_split_plan), else linear_plan of the interleaved product."""
+  require_hip(x, weight)
+  x, weight = _lib.f32rows(x, 'x'), f32c(weight, 'weight')
+  n, d = x.shape
+  m = weight.shape[0]
+  L = _lib.lib()
+  if out is None:
+    out = torch.empty(n * m, dtype=torch.float32, device=x.device)
+  flat = out.reshape(-1)
+  if m == 2 * att_dim and L.gnpde_linear_split_supported(ptr(x), n, d, x.stride(0), ptr(weight), m, weight.stride(0), att_dim):
+    one = _lib.LinearLaunchStruct()
+    rc = L.gnpde_linear_split_plan(x.data_ptr(), n, d, x.stride(0), weight.data_ptr(), m, weight.stride(0), flat.data_ptr(),
+                                   flat[n * att_dim:].data_ptr(), att_dim, ctypes.byref(one))
+    if rc != 1:
+      check(rc)
+    return [one.line]
+  return linear_plan(x, weight, out=flat.view(n, m))
 
 
 def edge_to_csr_mean(graph, src_edge, out=None):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 17  /* 17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 18  /* 18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -505,6 +505,46 @@ int    gnpde_solver_set_gather(gnpde_solver_t* s, int32_t dtype, void* mem, size
 int gnpde_linear_split_supported(const float* x, int64_t n, int32_t d, int32_t ldx, const float* W, int32_t m, int32_t ldw, int32_t split);
 int gnpde_linear_split(const float* x, int32_t n, int32_t d, int32_t ldx, const float* W, int32_t m, int32_t ldw, const float* b,
                        float* out_q, float* out_k, int32_t split, void* stream);
+
+/* The launch decision of gnpde_linear / gnpde_relu_linear, for tests and A/B scripts: which kernel instantiation each launch of a call
+ * with these operands takes, over which output columns and on what grid.  Nothing is launched and no address is dereferenced: x_addr,
+ * w_addr and out_addr are the operand addresses as integers and only their alignment is read (16 bytes for x and W, 8 for out).  The
+ * launchers of the library switch on the very same result, so a plan is what runs.  A launch is (family, mt, param):
+ *   GNPDE_LINEAR_SMALL       n <= 32 768, aligned operands, d % 16 == 0 and m % 16 == 0: ONE launch over all of [n, m] on a 2-D grid
+ *                            (grid_y walks groups of 16 * mt columns); mt = 2 when m % 32 == 0, else 1; param 0
+ *   GNPDE_LINEAR_STAGED2     d = 64 / 128, 32 complete columns, even ldo and column base, 8-byte aligned out: x in whole lines through
+ *                            LDS, paired output columns in 8-byte stores; mt = 2, param = KB = d / 16; split = 1 when it writes two
+ *                            tables (gnpde_linear_split)
+ *   GNPDE_LINEAR_STAGED      d = 64 / 128 otherwise (16 or 32 complete columns); mt = 1 / 2, param = KB = d / 16
+ *   GNPDE_LINEAR_PERSISTENT  every other d = 16 * KB <= 128 on 16 or 32 complete columns: W in registers; mt = 1 / 2, param = KB
+ *   GNPDE_LINEAR_LDS         64 or 128 complete columns, d % 16 == 0, d <= 256: W staged in LDS by workgroups of 512; mt = 4 / 8,
+ *                            param = DMAX = 128 (d <= 128) or 256
+ *   GNPDE_LINEAR_TILE        everything else, one wavefront per 16-row tile; mt = 1 / 2 / 4 / 8, param = 2 * ALIGNED + FULL: 3 = 16-byte
+ *                            loads without guards (complete columns, d % 16 == 0), 2 = 16-byte loads with guards (ragged columns or
+ *                            ragged K), 0 = scalar loads (operands without 16-byte alignment)
+ * A call whose rows exceed the small rule covers its columns left to right in launches of 128, 64, 32 or 16 (mt = 8, 4, 2, 1) by the
+ * number of 16-column tiles still to go.  gnpde_linear_plan writes the first min(count, cap) launches in launch order to plan and
+ * returns count (0 for n = 0), or GNPDE_EINVAL for a shape gnpde_linear refuses.  gnpde_linear_split_plan writes the one launch of
+ * gnpde_linear_split and returns 1, or GNPDE_ESHAPE where gnpde_linear_split refuses. */
+#define GNPDE_LINEAR_SMALL      0
+#define GNPDE_LINEAR_STAGED2    1
+#define GNPDE_LINEAR_STAGED     2
+#define GNPDE_LINEAR_PERSISTENT 3
+#define GNPDE_LINEAR_LDS        4
+#define GNPDE_LINEAR_TILE       5
+typedef struct gnpde_linear_launch_t {
+  int32_t  family;    /* GNPDE_LINEAR_* */
+  int32_t  mt;        /* 16-column tiles per wavefront */
+  int32_t  param;     /* KB, DMAX or 2 * ALIGNED + FULL, by family (above) */
+  int32_t  split;     /* 1: the two-table form of gnpde_linear_split */
+  int32_t  col_base;  /* first output column of the launch */
+  int32_t  cols;      /* output columns it writes */
+  uint32_t grid_x, grid_y, block;
+} gnpde_linear_launch_t;
+int gnpde_linear_plan(uint64_t x_addr, int32_t n, int32_t d, int32_t ldx, uint64_t w_addr, int32_t m, int32_t ldw, uint64_t out_addr,
+                      int32_t ldo, gnpde_linear_launch_t* plan, int32_t cap);
+int gnpde_linear_split_plan(uint64_t x_addr, int32_t n, int32_t d, int32_t ldx, uint64_t w_addr, int32_t m, int32_t ldw,
+                            uint64_t out_q_addr, uint64_t out_k_addr, int32_t split, gnpde_linear_launch_t* plan);
 
 /* One un-fused evaluation out = f(u) of the same descriptor (what ODEFunc.forward returns). */
 int gnpde_rhs_eval(const gnpde_rhs_t* rhs, const float* u, float* out, void* workspace,

@@ -382,6 +382,19 @@ def test_new_entry_points_validate_their_arguments():
   assert L.gnpde_relu_linear(None, 4, 4, 4, None, 4, 4, None, None, 4, None) != 0
   assert L.gnpde_quantile(None, 5, 0.5, None, None, 0, None) != 0
   assert L.gnpde_threshold_edges(None, None, 5, None, 0, 4, None, None, None, None, 0, None) != 0
+  # the projection's launch decision: integers in, nothing dereferenced or launched -- a shape gnpde_linear refuses is refused here too
+  plan = (_lib.LinearLaunchStruct * 2)()
+  for bad in ((256, -1, 64, 64, 256, 32, 64, 256, 32), (256, 10, 0, 64, 256, 32, 64, 256, 32), (256, 10, 64, 64, 256, 0, 64, 256, 32),
+              (256, 10, 64, 63, 256, 32, 64, 256, 32), (256, 10, 64, 64, 256, 32, 63, 256, 32), (256, 10, 64, 64, 256, 32, 64, 256, 31)):
+    assert L.gnpde_linear_plan(*bad, plan, 2) == -1 and b'linear_plan: bad shape' in L.gnpde_last_error(), bad
+  assert L.gnpde_linear_plan(256, 10, 64, 64, 256, 32, 64, 256, 32, None, 2) == -1 and b'without a buffer' in L.gnpde_last_error()
+  assert L.gnpde_linear_plan(256, 10, 64, 64, 256, 32, 64, 256, 32, plan, -1) == -1
+  assert L.gnpde_linear_plan(256, 10, 64, 64, 256, 32, 64, 256, 32, plan, 2) == 1 and plan[0].line == 'small<2>'
+  assert L.gnpde_linear_plan(0, 10, 64, 64, 0, 32, 64, 0, 32, None, 0) == 1          # addresses are numbers: only their alignment is read
+  assert L.gnpde_linear_split_plan(256, 40000, 64, 64, 256, 32, 64, 256, 512, 16, None) == -1 and b'null plan' in L.gnpde_last_error()
+  assert L.gnpde_linear_split_plan(256, 40000, 64, 64, 256, 32, 64, 256, 516, 16, plan) == -2        # out_k 4 bytes off
+  assert L.gnpde_linear_split_plan(256, 100, 64, 64, 256, 32, 64, 256, 512, 16, plan) == -2 and b'linear_split_plan' in L.gnpde_last_error()
+  assert L.gnpde_linear_split_plan(256, 40000, 64, 64, 256, 32, 64, 256, 512, 16, plan) == 1 and plan[0].line == 'staged2<4>+split'
 
 
 def test_dropin_launcher_serves_the_reference_module_names(tmp_path):
