@@ -25,6 +25,7 @@ from .GNN_KNN import GNN_KNN
 from .GNN_FA import GNN_FA
 from . import graph_rewiring
 from . import deepwalk_embeddings
+from . import hyperbolic_embeddings
 from . import pos_enc_factorisation
 from . import synthetic
 
@@ -32,4 +33,4 @@ __all__ = ['GnpdeError', 'build', 'lib', 'CSRGraph', 'graph_of', 'partition_rows
            'get_rw_adj', 'gcn_norm_fill_val', 'add_remaining_self_loops', 'odeint', 'odeint_adjoint', 'time_grid',
            'ODEFunc', 'ODEblock', 'LaplacianODEFunc', 'ODEFuncTransformerAtt', 'SpGraphTransAttentionLayer',
            'ODEFuncAtt', 'SpGraphAttentionLayer', 'ConstantODEblock', 'AttODEblock', 'MixedODEblock', 'HardAttODEblock', 'RewireAttODEblock', 'EarlyStopInt', 'EarlyStopRK4', 'EarlyStopDopri5', 'set_block', 'set_function',
-           'GNN_KNN', 'GNN_FA', 'graph_rewiring', 'deepwalk_embeddings', 'pos_enc_factorisation', 'synthetic']
+           'GNN_KNN', 'GNN_FA', 'graph_rewiring', 'deepwalk_embeddings', 'hyperbolic_embeddings', 'pos_enc_factorisation', 'synthetic']

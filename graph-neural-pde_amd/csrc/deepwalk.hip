@@ -13,12 +13,13 @@
 //   adam_kernel         one lane group per sorted entry; the head of a run adds the run's contribution rows in slot order and
 //                       updates m, v and e of that row.  No float atomics anywhere: bit-identical from run to run.
 //   loss_kernel         the partial losses (float64) summed in a fixed order by one workgroup
+// walk_step.h holds what the step shares with hyperbolic.hip: the step's workspace layout, the sort's key bits and loss_kernel.
 #include "common.h"
 #include "philox.h"
 #include "select.h"
+#include "walk_step.h"
 
 #include <cmath>
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace gnpde {
 namespace {
@@ -90,9 +91,6 @@ struct StepShape {
   int L, C, J, P, d, d4, G, waves;     // P = J (C - 1) pairs per walk; G lanes per pair / position; waves per workgroup
   int lds_floats;                      // per wave: rows (L + 1) d, then the P coefficients (rounded up to a multiple of 4)
 };
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 // one wave per walk; every wave of a workgroup runs the same trip counts (the barriers below are workgroup barriers), a wave past the
 // last walk recomputes the last walk and stores nothing
@@ -224,20 +222,6 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(const u64* __restrict__ so
   st4(pv, make_float4(vv[0], vv[1], vv[2], vv[3]));
 }
 
-// one workgroup: thread t adds the partials t, t + 256, ... in order, then a fixed tree
-__global__ __launch_bounds__(kBlock) void loss_kernel(const double* __restrict__ partial, long long r_pos, long long r_neg, float* __restrict__ out) {
-  __shared__ double red[kBlock];
-  double s = 0.0;
-  for (long long i = threadIdx.x; i < r_pos + r_neg; i += kBlock) s += partial[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = kBlock >> 1; w >= 1; w >>= 1) {
-    if (static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = static_cast<float>(red[0]);
-}
-
 // the limits of the step; returns nullptr when the shape is supported, else the message
 const char* step_shape(int L, int C, int d, StepShape* sh) {
   if (L < 1 || L > kMaxWalkLength) return "walk_length outside 1 .. 127";
@@ -255,28 +239,6 @@ const char* step_shape(int L, int C, int d, StepShape* sh) {
   sh->waves = kLdsFloats / sh->lds_floats;
   if (sh->waves > kWavesPerBlock) sh->waves = kWavesPerBlock;
   return nullptr;
-}
-
-struct StepLayout {
-  size_t keys, sorted, contrib, partial, temp, temp_bytes, total;   // total == 0: the temp-size query failed
-};
-
-StepLayout step_layout(long long r_tot, int L, int d) {
-  StepLayout Y{};
-  const size_t S = static_cast<size_t>(r_tot) * (L + 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  Y.keys = take(S * 8);
-  Y.sorted = take(S * 8);
-  Y.contrib = take(S * d * 4);
-  Y.partial = take(static_cast<size_t>(r_tot) * 8);
-  size_t t = 0;
-  u64* p = nullptr;
-  if (rocprim::radix_sort_keys(nullptr, t, p, p, S, 0, 64, nullptr) != hipSuccess) return Y;
-  Y.temp_bytes = align_up(t + 256, 256);
-  Y.temp = take(Y.temp_bytes);
-  Y.total = off;
-  return Y;
 }
 
 struct PermLayout {
@@ -409,10 +371,8 @@ extern "C" int gnpde_deepwalk_step(float* emb, int32_t ld, float* m, float* v, i
                      static_cast<unsigned>(n), pos_rw, static_cast<long long>(r_pos), neg_rw, static_cast<long long>(r_neg), sh, scale_pos,
                      scale_neg, mean_pos, mean_neg, contrib, keys, partial, flag);
   GNPDE_LAUNCH_CHECK();
-  unsigned bits = 1;
-  while (bits < 32 && ((static_cast<u64>(n) - 1) >> bits) != 0) ++bits;
   size_t tb = Y.temp_bytes;
-  GNPDE_HIP(rocprim::radix_sort_keys(ws + Y.temp, tb, keys, sorted, static_cast<size_t>(S), 0, 32 + bits, s));
+  GNPDE_HIP(rocprim::radix_sort_keys(ws + Y.temp, tb, keys, sorted, static_cast<size_t>(S), 0, slot_key_bits(n), s));
   const double bc1 = 1.0 - std::pow(static_cast<double>(beta1), t), bc2 = 1.0 - std::pow(static_cast<double>(beta2), t);
   const float step_size = static_cast<float>(static_cast<double>(lr) * std::sqrt(bc2) / bc1);
   const int per = kBlock / sh.G;

@@ -16,8 +16,8 @@ opt['exact'] the reference's approximate branch runs instead: a forward push per
 
 Positional-distance rewiring (`--rewiring pos_enc_knn`; reference graph_rewiring.py:285-342, hyperbolic_distances.py:7-14,
 distances_kNN.py): `apply_pos_dist_rewire` with `hyperbolize`, `apply_feat_KNN`, `apply_dist_KNN`, `apply_dist_threshold` and
-`apply_beltrami` (which, with opt['gnpde_generate_pos_enc'], trains a missing DW<d> pickle natively: deepwalk_embeddings.py; and,
-with opt['gnpde_pos_enc_nmf_dim'], compresses a missing GDC encoding by NMF: pos_enc_factorisation.py).  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
+`apply_beltrami` (which, with opt['gnpde_generate_pos_enc'], trains a missing DW<d> pickle natively: deepwalk_embeddings.py; with
+opt['gnpde_generate_hyp_enc'], a missing HYPS<dd> pickle: hyperbolic_embeddings.py; and, with opt['gnpde_pos_enc_nmf_dim'], compresses a missing GDC encoding by NMF: pos_enc_factorisation.py).  The reference builds a dense float64 [n, n] distance matrix (scipy pdist + squareform), takes np.quantile over
 it or hands it to sklearn's NearestNeighbors(metric='precomputed'); here the edge set comes straight from the encodings
 (`ops.knn(metric=...)`, `ops.radius_graph`), so the helpers take ENCODINGS where the reference's take a distance matrix.
 Deliberate differences: no [n, n] distance pickle is written; the edge set is computed whether or not a cache file existed (the
@@ -308,6 +308,24 @@ def _generate_deepwalk(data, opt, fname):
   return z
 
 
+def _generate_hyperbolic(data, opt, fname):
+  """Train HYPS<dd> encodings natively (hyperbolic_embeddings.PoincareEmbedding with its defaults) and cache them as the CPU tensor
+  [n, dd] that the reference's pickles of this type hold."""
+  from . import hyperbolic_embeddings
+  try:
+    d = hyperbolic_embeddings.embedding_dim_of(opt['pos_enc_type'])
+  except ValueError as err:
+    raise ValueError('apply_beltrami: %s' % err)
+  n = data.num_nodes[0] if isinstance(data.num_nodes, list) else data.num_nodes
+  model = hyperbolic_embeddings.PoincareEmbedding(data.edge_index, n, embedding_dim=d, seed=opt.get('seed', 0))
+  model.fit(opt.get('gnpde_hyp_epochs', 100), batch_size=128)
+  z = model.embedding.detach().to(torch.device('cpu'))
+  os.makedirs(os.path.dirname(fname), exist_ok=True)
+  with open(fname, 'wb') as f:
+    pickle.dump(z, f)
+  return z
+
+
 NMF_DEFAULTS = dict(max_iter=100, tol=0.002)     # the reference script's defaults (pos_enc_factorisation.py --max_iter, --tol)
 
 
@@ -341,8 +359,10 @@ def apply_beltrami(data, opt, data_dir='../data'):
   the reference loads (the 'data' entry for DW* types); otherwise, for pos_enc_type 'GDC', the native
   `apply_gdc(type='pos_encoding')`, cached as the reference caches it.  With a truthy opt['gnpde_generate_pos_enc'] a missing DW<d>
   pickle is trained natively (deepwalk_embeddings.DeepWalk with the reference script's defaults, opt['gnpde_dw_epochs'] epochs,
-  default 100, seed opt['seed']) and cached in that layout.  Without the option a missing DW* pickle is an error, as is a missing
-  HYP* pickle always: generating hyperbolic embeddings is not built.  With opt['gnpde_pos_enc_nmf_dim'] = r a missing GDC pickle is
+  default 100, seed opt['seed']) and cached in that layout.  With a truthy opt['gnpde_generate_hyp_enc'] a missing HYPS<dd> pickle is
+  trained natively (hyperbolic_embeddings.PoincareEmbedding with its defaults, opt['gnpde_hyp_epochs'] epochs, default 100, seed
+  opt['seed']) and cached as a CPU tensor [n, dd]; each key covers its own type only.  Without its option a missing DW* or HYP*
+  pickle is an error, and HYP* types other than HYPS<dd> are never generated.  With opt['gnpde_pos_enc_nmf_dim'] = r a missing GDC pickle is
   generated AND compressed to [n, r] by the native NMF (the reference's pos_enc_factorisation.py; opt['gnpde_pos_enc_nmf_iters'],
   default 100, and opt['gnpde_pos_enc_nmf_tol'], default 0.002), from the sparse GDC graph once the dense matrix exceeds
   ops.GDC_DENSE_CAP, and W is cached as a CPU tensor at the same path."""
@@ -359,10 +379,17 @@ def apply_beltrami(data, opt, data_dir='../data'):
   if opt['pos_enc_type'].startswith('DW') and opt.get('gnpde_generate_pos_enc'):
     print('    Encodings not found! Training DeepWalk embeddings and caching them')
     return _generate_deepwalk(data, opt, fname)
+  if opt['pos_enc_type'].startswith('HYP') and opt.get('gnpde_generate_hyp_enc'):
+    print('    Encodings not found! Training Poincare embeddings and caching them')
+    return _generate_hyperbolic(data, opt, fname)
   if opt['pos_enc_type'] != 'GDC':
+    hint = ''
+    if opt['pos_enc_type'].startswith('DW'):
+      hint = " (set opt['gnpde_generate_pos_enc'] to train them)"
+    elif opt['pos_enc_type'].startswith('HYPS'):
+      hint = " (set opt['gnpde_generate_hyp_enc'] to train them)"
     raise FileNotFoundError('apply_beltrami: no cached positional encodings %s, and type %r cannot be generated here%s'
-                            % (fname, opt['pos_enc_type'],
-                               " (set opt['gnpde_generate_pos_enc'] to train them)" if opt['pos_enc_type'].startswith('DW') else ''))
+                            % (fname, opt['pos_enc_type'], hint))
   if opt.get('gnpde_pos_enc_nmf_dim'):
     print('    Encodings not found! Calculating, compressing and caching them')
     return _generate_compressed_gdc(data, opt, fname)

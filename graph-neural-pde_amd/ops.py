@@ -715,8 +715,82 @@ def deepwalk_step(emb, m, v, t, pos_rw, neg_rw, context_size, lr=0.01, betas=(0.
   return loss_out.reshape(())
 
 
+# ---- hyperbolic positional encodings (csrc/hyperbolic.hip; definitions in include/gnpde.h) ---------------------------------------
+POINCARE_MAX_DIM = 128
+STREAM_HYP_POS_WALKS, STREAM_HYP_NEG_WALKS, STREAM_HYP_EPOCH_ORDER = 19, 20, 21     # DeepWalk's streams are 16, 17, 18
+POINCARE_BALL_EDGE = 1 - 1e-5
+
+
+def _up4(x):
+  return (x + 3) // 4 * 4
+
+
+def poincare_check_shape(walk_length, context_size, d, who='poincare_step'):
+  """Raise for a shape the native Poincare step refuses (the limits of include/gnpde.h)."""
+  L, C, d = int(walk_length), int(context_size), int(d)
+  if not 1 <= L <= DEEPWALK_MAX_WALK_LENGTH:
+    raise _lib.GnpdeError('%s: walk_length = %d outside 1 .. %d' % (who, L, DEEPWALK_MAX_WALK_LENGTH))
+  if not 2 <= C <= L:
+    raise _lib.GnpdeError('%s: walk_length >= context_size >= 2 is required (walk_length %d, context_size %d)' % (who, L, C))
+  if d != 2 and (d % 4 != 0 or not 4 <= d <= POINCARE_MAX_DIM):
+    raise _lib.GnpdeError('%s: the embedding width %d must be 2 or a multiple of 4 in 4 .. %d' % (who, d, POINCARE_MAX_DIM))
+  floats = (L + 1) * max(d, 4) + _up4(L + 1) + 2 * _up4((L + 2 - C) * (C - 1))
+  if floats > DEEPWALK_LDS_FLOATS:
+    raise _lib.GnpdeError('%s: (walk_length + 1) * width + the walk_length + 1 norms + 2 * windows * (context_size - 1) = %d exceeds %d '
+                          'floats (64 KiB of LDS)' % (who, floats, DEEPWALK_LDS_FLOATS))
+
+
+def poincare_workspace(r_pos, r_neg, walk_length, context_size, d, device):
+  need = int(_lib.lib().gnpde_poincare_step_workspace_bytes(int(r_pos), int(r_neg), int(walk_length), int(context_size), int(d)))
+  if need == 0:
+    raise _lib.GnpdeError('poincare_step: the workspace query failed (%s)'
+                          % (_lib.lib().gnpde_last_error().decode(errors='replace') or "the sort's temporary-storage query needs a device"))
+  return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def poincare_step(emb, pos_rw, neg_rw, context_size, lr=1.0, radius=2.0, temperature=1.0, *, loss_out=None, flag=None, workspace=None):
+  """One row-normalised Riemannian SGD step on the Poincare ball, in place on emb ([n, d] float32 on a HIP device, every row inside
+  the unit ball; padded rows allowed): gnpde_poincare_step, include/gnpde.h has the definition.  pos_rw [R_pos, L + 1], neg_rw
+  [R_neg, L + 1]: the walks (int32 or int64).  Returns the step's loss as a 0-d device tensor; nothing is read by the host unless
+  `flag` is None (then a walk entry outside [0, n) raises).  loss_out: a 1-element float32 device view to write the loss to;
+  workspace: a buffer from poincare_workspace to reuse."""
+  who = 'poincare_step'
+  if not isinstance(emb, torch.Tensor) or emb.dim() != 2 or emb.dtype != torch.float32:
+    raise _lib.GnpdeError('poincare_step: emb must be a float32 matrix')
+  require_hip(emb)
+  n, d = emb.shape
+  pos = _walks_i32(pos_rw, None, 'pos_rw')
+  L = pos.shape[1] - 1
+  neg = _walks_i32(neg_rw, L, 'neg_rw')
+  poincare_check_shape(L, context_size, d)
+  quantum = 2 if d == 2 else 4
+  if emb.stride(1) != 1 or emb.stride(0) < d or emb.stride(0) % quantum != 0 or emb.data_ptr() % (4 * quantum) != 0:
+    raise _lib.GnpdeError('poincare_step: emb is updated in place: unit column stride, a row stride that is a multiple of %d and '
+                          '%d-byte alignment are required' % (quantum, 4 * quantum))
+  n = _node_count(n, who)
+  if pos.shape[0] < 1 or neg.shape[0] < 1:
+    raise _lib.GnpdeError('poincare_step: at least one positive and one negative walk are needed')
+  if not (emb.device == pos.device == neg.device):
+    raise _lib.GnpdeError('poincare_step: the tensors are on different devices')
+  if not (float(lr) >= 0 and float(temperature) > 0):
+    raise _lib.GnpdeError('poincare_step: lr >= 0 and temperature > 0 are required (lr %r, temperature %r)' % (lr, temperature))
+  if workspace is None:
+    workspace = poincare_workspace(pos.shape[0], neg.shape[0], L, context_size, d, emb.device)
+  own = flag is None
+  if own:
+    flag = torch.zeros(1, dtype=torch.int32, device=emb.device)
+  if loss_out is None:
+    loss_out = torch.empty(1, dtype=torch.float32, device=emb.device)
+  check(_lib.lib().gnpde_poincare_step(ptr(emb), emb.stride(0), n, d, ptr(pos), pos.shape[0], ptr(neg), neg.shape[0], L, int(context_size),
+                                       float(lr), float(radius), float(temperature), ptr(loss_out), ptr(flag), ptr(workspace),
+                                       workspace.numel(), stream_of(emb)))
+  if own:
+    _raise_flags(flag, who, DEEPWALK_FLAGS)
+  return loss_out.reshape(())
+
+
 KNN_MAX_K = 128
-METRICS = {'sqeuclidean': _lib.METRIC_SQEUCLIDEAN, 'poincare': _lib.METRIC_POINCARE}
+METRICS ={'sqeuclidean': _lib.METRIC_SQEUCLIDEAN, 'poincare': _lib.METRIC_POINCARE}
 
 
 def _metric(metric, who):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 18  /* 18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 19  /* 19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -1003,6 +1003,47 @@ int gnpde_deepwalk_step(float* emb, int32_t ld, float* m, float* v, int32_t ld_m
                         const int32_t* pos_rw, int64_t r_pos, const int32_t* neg_rw, int64_t r_neg, int32_t walk_length,
                         int32_t context_size, float lr, float beta1, float beta2, float eps, float* loss_out, int32_t* flag,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* Hyperbolic positional encodings (BLEND's `--pos_enc_type HYPS<dd>`; the reference loads such files and ships no program that
+ * writes them).  This header is the authority: an embedding of the nodes in the Poincare ball, trained on DeepWalk's walks.
+ *
+ * State.  e [n, d] float32, every row strictly inside the unit ball.  No optimiser state.
+ * Walks, negative walks, epoch order, batches and windows: the DeepWalk definitions above, word for word (gnpde_random_walks,
+ *   gnpde_negative_walks, gnpde_random_permutation, the position pairs (a, b)), on stream ids of their own: 19 (positive walks),
+ *   20 (negative walks), 21 (epoch order), so that a DeepWalk run and a hyperbolic run of one seed share no random numbers.
+ * Pair (u, v) = (rw[a], rw[b]):
+ *     s_u = |e_u|^2,  alpha = 1 - s_u,  beta = 1 - s_v,  q = |e_u - e_v|^2,  r = q / (alpha beta)     (the key of gnpde_knn_metric's
+ *                                                                                                      GNPDE_METRIC_POINCARE)
+ *     dist = arccosh(1 + 2 r), evaluated as 2 log(sqrt(r) + sqrt(1 + r))                               (no cancellation at small r)
+ *     x = (R - dist) / T                                                                                (radius R, temperature T)
+ *     d dist / d e_u = 1 / sqrt(r (1 + r)) * 2 / (alpha beta) * [(e_u - e_v) + (q / alpha) e_u],   and with u, v and alpha, beta
+ *       exchanged for e_v.
+ *   A pair with r == 0 exactly (the same node, or identical coordinates) has a zero gradient; its loss term counts with dist = 0.
+ * Loss of one step (reported only), EPS = 1e-15:
+ *     mean over all positive pairs of -log(sigma(x) + EPS)  +  mean over all negative pairs of -log(sigma(-x) + EPS).
+ * Update: row-normalised Riemannian SGD.  For every touched row u
+ *     g_u = the sum over all pair ends at u, positive and negative, of the derivative of THAT PAIR'S OWN loss term (EPS included,
+ *           no 1 / count factor) with respect to e_u, added in a fixed order;
+ *     c_u = the number of pair ends at u (a pair with rw[a] == rw[b] counts twice);
+ *     e_u <- proj(e_u - lr (alpha_u^2 / 4) g_u / c_u),     proj(y) = y if |y| < 1 - 1e-5, else y (1 - 1e-5) / |y|.
+ *   alpha_u^2 / 4 is the inverse of the ball's metric; the Euclidean length of d dist / d e_u is 2 / alpha_u and |d loss / d x| < 1,
+ *   so one update moves a row by less than lr alpha_u / (2 T), whatever the batch size and however often the node occurs.
+ *   An untouched row keeps its bits.
+ * gnpde_poincare_step: emb [n, d] (row stride ld) float32; d = 2 (ld even, emb 8-byte aligned) or a multiple of 4 (ld a multiple
+ *   of 4, emb 16-byte aligned); pos_rw [r_pos, L + 1] and neg_rw [r_neg, L + 1] int32; *loss_out (device float) = the loss.
+ *   The layout of gnpde_deepwalk_step: one wave per walk stages the walk's rows in LDS (a width of 2 padded to 4), forms s per
+ *   position and (q, coefficient) per pair, and writes ONE contribution row per walk position with plain stores; a radix sort of
+ *   (node << 32 | slot) is the inverted index; per node the contribution rows are added in slot order and c_u is the sum of the
+ *   slots' pair-end counts, a function of (position, L, C) alone.  No float atomics: results are bit-identical from run to run.
+ *   Nothing is read by the host.  sqrt and the divisions are IEEE.  A walk entry outside [0, n) sets GNPDE_DEEPWALK_BAD_WALK in
+ *   `flag` and counts as node 0.
+ *   Limits (GNPDE_ESHAPE otherwise): d = 2 or a multiple of 4 in 4 .. 128, L <= 127, 2 <= C <= L, DeepWalk's 64 KiB of LDS per walk,
+ *   which here hold (L + 1) max(d, 4) row floats, L + 1 norms and 2 J (C - 1) pair coefficients, each of the four blocks rounded up
+ *   to 4 floats: at most 16384 floats together; (r_pos + r_neg)(L + 1) <= INT32_MAX.  lr >= 0 and T > 0 (GNPDE_EINVAL otherwise). */
+size_t gnpde_poincare_step_workspace_bytes(int64_t r_pos, int64_t r_neg, int32_t walk_length, int32_t context_size, int32_t d);
+int gnpde_poincare_step(float* emb, int32_t ld, int32_t n, int32_t d, const int32_t* pos_rw, int64_t r_pos, const int32_t* neg_rw,
+                        int64_t r_neg, int32_t walk_length, int32_t context_size, float lr, float radius, float temperature,
+                        float* loss_out, int32_t* flag, void* workspace, size_t workspace_bytes, void* stream);
 
 /* NMF compression of positional encodings (reference src/pos_enc_factorisation.py: sklearn.decomposition.NMF(solver='cd',
  * beta_loss='frobenius'), no regularisation, shuffle off).  This header is the authority; sklearn is no dependency.
