@@ -18,10 +18,10 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 19     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 20     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
-METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT = range(3)
+METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
 ADAPTIVE_HEUN, ADAPTIVE_DOPRI5 = range(2)
 # gnpde_tune keys (csrc/common.h); 0, 8 and 13 are retired slots: the library refuses any value but 0 for them
 TUNE_FUSED_BLOCKS_PER_CU, TUNE_ONE_PASS, TUNE_FORK, TUNE_ATT_GENERIC_ROWS, TUNE_RK4_CLASSIC = range(1, 6)
@@ -192,6 +192,7 @@ PROTOTYPES = {
                                         ctypes.c_int32, c_vp]),
   'gnpde_adjoint_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]),
   'gnpde_adjoint_tape_swapped': (ctypes.c_int, [c_vp]),
+  'gnpde_adjoint_set_dopri5_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_float_p, ctypes.c_int32, ctypes.c_float, c_vp]),
   'gnpde_solver_tape_bytes': (ctypes.c_size_t, [ctypes.POINTER(RhsStruct), ctypes.c_int32, ctypes.c_int32]),
   'gnpde_solver_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t]),
   'gnpde_to_bf16': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
@@ -255,6 +256,7 @@ PROTOTYPES = {
   'gnpde_dopri5_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, ctypes.c_int32]),
   'gnpde_dopri5_tape_steps': (ctypes.c_int, [c_vp]),
   'gnpde_dopri5_tape_record': (ctypes.c_int, [c_vp, c_float_p, ctypes.c_int32, c_float_p]),
+  'gnpde_dopri5_tape_slots': (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_size_t)]),
   'gnpde_dopri5_tape_backward_workspace_bytes': (ctypes.c_size_t, [c_vp, ctypes.POINTER(GraphStruct)]),
   'gnpde_dopri5_tape_backward': (ctypes.c_int, [c_vp, ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp,
                                                 ctypes.c_size_t, c_vp]),

@@ -19,6 +19,7 @@
 #include <vector>
 #include "common.h"
 #include "fixed_grid.h"
+#include "tape_reverse.h"
 #include "graph_capture.h"
 #include "rhs.h"
 #include "epilogue.h"
@@ -632,6 +633,10 @@ struct gnpde_adjoint {
   int dots_capacity = 0;
   const float* tape_rec = nullptr;   // one RhsRecord (q||k, head-mean weights) per forward evaluation, behind the stage inputs (rhs.h), or null
   float* r_acc = nullptr;    // [e] or null: sum over the evaluations of (b_j h) u_a[row] . u_y[col] in CSR order (GRAND-l weight gradients)
+  // recorded Dormand-Prince solve (gnpde_adjoint_set_dopri5_tape): `tape` = the slots of the forward record, slot_stride floats apart,
+  // dts = the accepted steps' sizes, last_x = the fraction of the last one at which the end time lies
+  size_t slot_stride = 0;
+  float last_x = 0.f;
 };
 
 namespace {
@@ -647,8 +652,11 @@ int check_adjoint(const gnpde_rhs_t* rhs, const gnpde_graph_t* gt, int method) {
   if (rc) return rc;
   GNPDE_CHECK_ARG(gt != nullptr && gt->n == rhs->graph->n && gt->e == rhs->graph->e, GNPDE_EINVAL,
                   "adjoint: the transposed graph does not match the descriptor's graph");
-  GNPDE_CHECK_ARG(method == GNPDE_METHOD_EULER || method == GNPDE_METHOD_RK4 || method == GNPDE_METHOD_MIDPOINT, GNPDE_EINVAL,
-                  "adjoint: bad method %d", method);     // (midpoint: as the reverse sweep of a recorded solve only)
+  GNPDE_CHECK_ARG(method == GNPDE_METHOD_EULER || method == GNPDE_METHOD_RK4 || method == GNPDE_METHOD_MIDPOINT ||
+                  method == GNPDE_METHOD_DOPRI5_TAPE, GNPDE_EINVAL,
+                  "adjoint: bad method %d", method);     // (midpoint, dopri5: as the reverse sweep of a recorded solve only)
+  GNPDE_CHECK_ARG(method != GNPDE_METHOD_DOPRI5_TAPE || rhs->kind == GNPDE_RHS_TRANSFORMER || rhs->kind == GNPDE_RHS_GAT, GNPDE_ESHAPE,
+                  "adjoint: the sweep over a recorded dopri5 solve is GRAND-nl's and GAT's (GRAND-l: gnpde_dopri5_tape_backward)");
   GNPDE_CHECK_ARG(rhs->kind == GNPDE_RHS_LAPLACIAN || rhs->kind == GNPDE_RHS_TRANSFORMER || rhs->kind == GNPDE_RHS_GAT, GNPDE_ESHAPE,
                   "adjoint: GRAND-l, GRAND-nl and the GAT function");
   if (rhs->kind == GNPDE_RHS_GAT) {
@@ -692,7 +700,9 @@ size_t adjoint_layout(const gnpde_rhs_t& r, const gnpde_graph_t& gt, int method,
   auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
   size_t o_uy[2], o_ua[2], o_F[4], o_V[3], o_P = 0, o_qk = 0, o_dqk = 0, o_w = 0, o_wt = 0, o_r = 0, o_ds = 0, o_hub = 0, o_inv = 0, o_dts = 0, o_dtd = 0;
   for (int i = 0; i < 2; ++i) { o_uy[i] = take(state); o_ua[i] = take(state); }
-  const int nF = method == GNPDE_METHOD_RK4 ? 1 : 0, nV = method == GNPDE_METHOD_RK4 ? 1 : 0;     // (u4 of the state / of the adjoint)
+  // (rk4: u4 of the state / of the adjoint; the sweep over a recorded dopri5 solve: seven more buffers of its walk, enqueue_dopri5_taped)
+  const int nF = method == GNPDE_METHOD_RK4 ? 1 : method == GNPDE_METHOD_DOPRI5_TAPE ? 4 : 0;
+  const int nV = method == GNPDE_METHOD_RK4 ? 1 : method == GNPDE_METHOD_DOPRI5_TAPE ? 3 : 0;
   for (int i = 0; i < 4; ++i) o_F[i] = i < nF ? take(state) : 0;
   for (int i = 0; i < 3; ++i) o_V[i] = i < nV ? take(state) : 0;
   const size_t o_one = take(256);
@@ -1091,6 +1101,61 @@ int enqueue_taped(gnpde_adjoint* s, float* a, float* grads, hipStream_t st) {
   return 0;
 }
 
+// Reverse sweep through a RECORDED Dormand-Prince solve (gnpde_dopri5_set_tape: u_0..u_5 of every accepted step, y1 as u_0 of the next
+// slot) for the functions with an attention per evaluation: the walk of tape_reverse.h, one enqueue_stage per recorded evaluation --
+// projection and attention recomputed at u_i, the V epilogue a GNPDE_STAGE_LINCOMB that forms the next cotangent from the later W's --
+// and one linear combination per step for G_y.  Un-normalised cotangents, parameter weight 1.  A plain sequence of launches: the number
+// of accepted steps changes from run to run.  `a`: dL/d(out) in, dL/dy0 out.
+struct Dopri5TapeOps {
+  gnpde_adjoint* s;
+  float* buf[kTrBuffers];
+  float* grads;
+  long long flat;
+  hipStream_t st;
+
+  int scale(int dst, float c) {
+    const float* v[1] = {buf[kTrOut]};
+    return launch_lincomb(buf[kTrZero], v, &c, 1, flat, buf[dst], st, nullptr);
+  }
+  int stage(const TapeStage<float>& t) {
+    gnpde_epilogue_t eF{};
+    eF.stage = GNPDE_STAGE_LINCOMB;
+    gnpde_epilogue_t eV{};
+    eV.stage = GNPDE_STAGE_LINCOMB;
+    eV.y = buf[t.base];
+    eV.n_prev = t.n_terms;
+    for (int j = 0; j < t.n_terms; ++j) { eV.prev[j] = buf[t.term[j]]; eV.coef[j] = t.coef[j]; }
+    eV.coef[t.n_terms] = t.coef[t.n_terms];
+    eV.out_y = buf[t.out];
+    return enqueue_stage(s, s->tape + static_cast<size_t>(t.slot) * s->slot_stride, buf[t.g_in], nullptr, eF, t.w_out >= 0 ? buf[t.w_out] : nullptr,
+                         eV, 1.0f, grads, st, nullptr);
+  }
+  int sum(const TapeSum<float>& t) {
+    const float* v[kTrMaxTerms];
+    for (int j = 0; j < t.n_terms; ++j) v[j] = buf[t.term[j]];
+    return launch_lincomb(buf[kTrGy], v, t.coef, t.n_terms, flat, buf[kTrGy], st, nullptr);
+  }
+};
+
+int enqueue_dopri5_taped(gnpde_adjoint* s, float* a, float* grads, hipStream_t st) {
+  const gnpde_rhs_t& r = s->rhs;
+  GNPDE_HIP(hipMemsetAsync(grads, 0, static_cast<size_t>(s->stride) * 4, st));
+  Dopri5TapeOps ops{};
+  ops.s = s; ops.grads = grads; ops.st = st;
+  ops.flat = static_cast<long long>(r.graph->n) * r.ld;
+  // uy[0] is the stage's own scratch (S of the cotangent-side form).  uy[1] is kTrZero, the zeros every combination starts from: it relies
+  // on the zero-fill of the workspace in the object's first gnpde_adjoint_run, and NOTHING of this method may ever write it (no stage
+  // output, no scratch) -- a kernel that did would corrupt every later cotangent silently.
+  ops.buf[kTrOut] = a;
+  ops.buf[kTrZero] = s->uy[1];
+  ops.buf[kTrGy] = s->ua[0];
+  ops.buf[kTrGk0] = s->ua[1];
+  ops.buf[kTrGk0 + 1] = s->F[0];
+  float* w[6] = {s->F[1], s->F[2], s->F[3], s->V[0], s->V[1], s->V[2]};
+  for (int m = 0; m < 6; ++m) ops.buf[kTrW1 + m] = w[m];
+  return tape_reverse_walk<float>(static_cast<int>(s->dts.size()), s->dts.data(), s->last_x, ops);
+}
+
 void drop_adjoint_graph(gnpde_adjoint* s) {
   drop_capture(&s->graph_obj, &s->exec);
   s->cap_y = s->cap_a = s->cap_g = nullptr;
@@ -1192,6 +1257,11 @@ extern "C" int gnpde_adjoint_run(gnpde_adjoint_t* s, float* y, float* a, float* 
   }
   GNPDE_CHECK_ARG(s->tape != nullptr || s->method != GNPDE_METHOD_MIDPOINT, GNPDE_EINVAL,
                   "adjoint_run: midpoint runs as the reverse sweep of a recorded solve only (gnpde_adjoint_set_tape)");
+  if (s->method == GNPDE_METHOD_DOPRI5_TAPE) {
+    GNPDE_CHECK_ARG(s->tape != nullptr && !s->dts.empty(), GNPDE_EINVAL, "adjoint_run: no recorded dopri5 solve (gnpde_adjoint_set_dopri5_tape)");
+    GNPDE_CHECK_ARG(!use_graph, GNPDE_EINVAL, "adjoint_run: the sweep over a recorded dopri5 solve is not captured (its length changes from run to run)");
+    return enqueue_dopri5_taped(s, a, grads, st);
+  }
   if (!use_graph) return s->tape ? enqueue_taped(s, a, grads, st) : enqueue_adjoint(s, y, a, grads, st);
   if (s->exec == nullptr || s->cap_y != y || s->cap_a != a || s->cap_g != grads) {
     drop_adjoint_graph(s);
@@ -1207,6 +1277,8 @@ extern "C" int gnpde_adjoint_tape_swapped(const gnpde_adjoint_t* s) { return s !
 
 extern "C" int gnpde_adjoint_set_tape(gnpde_adjoint_t* s, const void* tape, size_t tape_bytes, float* r_acc, const int32_t* csr_from_t) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "adjoint_set_tape: solver is null");
+  GNPDE_CHECK_ARG(s->method != GNPDE_METHOD_DOPRI5_TAPE, GNPDE_EINVAL, "adjoint_set_tape: a fixed-grid record; this object sweeps a recorded dopri5 solve "
+                  "(gnpde_adjoint_set_dopri5_tape)");
   drop_adjoint_graph(s);
   s->tape = nullptr;
   s->tape_rec = nullptr;
@@ -1229,6 +1301,32 @@ extern "C" int gnpde_adjoint_set_tape(gnpde_adjoint_t* s, const void* tape, size
   s->tape = static_cast<const float*>(tape);
   s->tape_rec = rec_floats > 0 ? s->tape + (per * s->dts.size() + 1) * (s->state_bytes / 4) : nullptr;
   s->r_acc = r_acc;
+  return 0;
+}
+
+extern "C" int gnpde_adjoint_set_dopri5_tape(gnpde_adjoint_t* s, const float* slots, size_t slot_stride, const float* h, int32_t n_steps,
+                                             float x_last, const int32_t* csr_from_t) {
+  GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "adjoint_set_dopri5_tape: solver is null");
+  GNPDE_CHECK_ARG(s->method == GNPDE_METHOD_DOPRI5_TAPE, GNPDE_EINVAL, "adjoint_set_dopri5_tape: the object was created for method %d", s->method);
+  s->tape = nullptr;
+  s->csr_from_t = nullptr;
+  s->swapped = false;
+  s->dts.clear();
+  s->n_evals = 0;
+  if (slots == nullptr) return 0;
+  GNPDE_CHECK_ARG(h != nullptr && n_steps >= 1, GNPDE_EINVAL, "adjoint_set_dopri5_tape: no accepted step to differentiate");
+  GNPDE_CHECK_ARG(reinterpret_cast<uintptr_t>(slots) % 256 == 0 && slot_stride % 64 == 0 && slot_stride * 4 >= s->state_bytes, GNPDE_EINVAL,
+                  "adjoint_set_dopri5_tape: slots 256-byte aligned and at least one state buffer (%zu bytes) apart", s->state_bytes);
+  GNPDE_CHECK_ARG(x_last > 0.0f && x_last <= 1.0f, GNPDE_EINVAL, "adjoint_set_dopri5_tape: the end point lies at the fraction %g of the last step", x_last);
+  for (int i = 0; i < n_steps; ++i)
+    GNPDE_CHECK_ARG(h[i] > 0.0f && h[i] < INFINITY, GNPDE_EINVAL, "adjoint_set_dopri5_tape: step %d has size %g", i, h[i]);
+  s->dts.assign(h, h + n_steps);
+  s->slot_stride = slot_stride;
+  s->last_x = x_last;
+  s->csr_from_t = csr_from_t;
+  s->swapped = g_tune[GNPDE_TUNE_SWEEP_UNSWAPPED] != 1 && csr_from_t != nullptr;       // (as gnpde_adjoint_set_tape)
+  s->tape = slots;
+  s->n_evals = 6 * n_steps + 1;
   return 0;
 }
 

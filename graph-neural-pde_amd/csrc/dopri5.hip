@@ -767,7 +767,9 @@ extern "C" int gnpde_dopri5_destroy(gnpde_dopri5_t* s) {
 // on the transposed graph forms W_i = a (A^T G_i - G_i) (+ the incoming dL/dy1 as its source term in stage 6), the next G_{i-1} =
 // h sum_m a_{m,i-1} W_m in its epilogue, the edge products r_e += u_i[row'] . G_i[col'] and the dot <u_i, W_i> = <G_i, k_i - b x0>.
 // The algebra is written out and pinned against torch autograd in oracle/tape_reverse.py / tests/test_tape_reverse_cpu.py.
-// GRAND-l only (f linear in u; the weights are constants of the solve that carry gradients: attention block).
+// The record (gnpde_dopri5_set_tape, _tape_bytes, _tape_slots, _tape_record) serves the Laplacian, transformer and GAT functions alike: stage
+// inputs only.  The sweep below is GRAND-l's (f linear in u; the weights are constants of the solve that carry gradients: attention
+// block); GRAND-nl and GAT records are swept by csrc/adjoint.hip (gnpde_adjoint_set_dopri5_tape, the walk of tape_reverse.h).
 // ------------------------------------------------------------------------------------------------
 extern "C" size_t gnpde_dopri5_tape_bytes(const gnpde_rhs_t* rhs, int32_t capacity_steps) {
   if (check_rhs(rhs) || capacity_steps < 1) return 0;
@@ -785,7 +787,10 @@ extern "C" int gnpde_dopri5_set_tape(gnpde_dopri5_t* s, void* tape, size_t tape_
   if (tape == nullptr) return 0;
   GNPDE_CHECK_ARG(s->shard == nullptr, GNPDE_ESTATE, "dopri5_set_tape: not on a row-partitioned solve");
   GNPDE_CHECK_ARG(s->pair == GNPDE_ADAPTIVE_DOPRI5, GNPDE_ESTATE, "dopri5_set_tape: the recorded solve is Dormand-Prince's");
-  GNPDE_CHECK_ARG(s->rhs.kind == GNPDE_RHS_LAPLACIAN, GNPDE_EINVAL, "dopri5_set_tape: the recorded solve covers the Laplacian function (f linear in the state)");
+  // (the store kernel copies stage inputs whatever f is; GRAND-nl / GAT records are swept by gnpde_adjoint_set_dopri5_tape, which
+  //  recomputes q||k and the weights of every evaluation -- nothing of an evaluation is recorded inside a trial step that may be rejected)
+  GNPDE_CHECK_ARG(s->rhs.kind == GNPDE_RHS_LAPLACIAN || s->rhs.kind == GNPDE_RHS_TRANSFORMER || s->rhs.kind == GNPDE_RHS_GAT, GNPDE_EINVAL,
+                  "dopri5_set_tape: the recorded solve covers the Laplacian, transformer and GAT functions");
   GNPDE_CHECK_ARG(capacity_steps >= 1 && reinterpret_cast<uintptr_t>(tape) % 256 == 0, GNPDE_EINVAL, "dopri5_set_tape: bad capacity or alignment");
   const size_t need = gnpde_dopri5_tape_bytes(&s->rhs, capacity_steps);
   GNPDE_CHECK_ARG(tape_bytes >= need, GNPDE_EWS, "dopri5_set_tape: %zu bytes (need %zu)", tape_bytes, need);
@@ -808,6 +813,13 @@ extern "C" int gnpde_dopri5_set_tape(gnpde_dopri5_t* s, void* tape, size_t tape_
 }
 
 extern "C" int gnpde_dopri5_tape_steps(const gnpde_dopri5_t* s) { return s ? s->tape_steps : 0; }
+
+extern "C" int gnpde_dopri5_tape_slots(const gnpde_dopri5_t* s, const float** slots, size_t* slot_stride) {
+  GNPDE_CHECK_ARG(s != nullptr && s->tape != nullptr && slots != nullptr && slot_stride != nullptr, GNPDE_EINVAL, "dopri5_tape_slots: no recorded solve");
+  *slots = s->tape_slots;
+  *slot_stride = s->state_bytes / 4;
+  return 0;
+}
 
 extern "C" int gnpde_dopri5_tape_record(const gnpde_dopri5_t* s, float* h_out, int32_t capacity, float* x_out) {
   GNPDE_CHECK_ARG(s != nullptr && s->tape != nullptr && (h_out != nullptr || capacity == 0), GNPDE_EINVAL, "dopri5_tape_record: no recorded solve");
@@ -851,6 +863,8 @@ extern "C" int gnpde_dopri5_tape_backward(gnpde_dopri5_t* s, const gnpde_graph_t
   GNPDE_CHECK_ARG(s && graph_t && grad_out && grad_y0 && r_t && sum_g && dot_out && (w_t || graph_t->e == 0), GNPDE_EINVAL,
                   "dopri5_tape_backward: null argument");
   GNPDE_CHECK_ARG(s->tape != nullptr && s->tape_steps >= 1, GNPDE_EINVAL, "dopri5_tape_backward: no recorded solve to differentiate");
+  GNPDE_CHECK_ARG(s->rhs.kind == GNPDE_RHS_LAPLACIAN, GNPDE_EINVAL, "dopri5_tape_backward: the Laplacian function's sweep (f linear in the state); "
+                  "GRAND-nl and GAT records: gnpde_adjoint_set_dopri5_tape");
   const gnpde_rhs_t& r = s->rhs;
   GNPDE_CHECK_ARG(graph_t->n == r.graph->n && graph_t->e == r.graph->e, GNPDE_ESHAPE, "dopri5_tape_backward: the transposed graph does not match");
   GNPDE_CHECK_ARG(ld_go >= r.d && ld_gy0 >= r.d && r.ld % 4 == 0 && r.d <= 256, GNPDE_ESHAPE, "dopri5_tape_backward: bad strides / width");

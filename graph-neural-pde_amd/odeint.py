@@ -577,16 +577,24 @@ _TAPE_BUDGET_BYTES = 8 << 30     # first tape allocation (it grows when a solve 
 
 
 def _recorded_ok(func, y0, t, options):
-  """The differentiated dopri5 solve runs as ONE recorded device solve + ONE native reverse sweep (csrc/dopri5.hip,
-  gnpde_dopri5_set_tape / _tape_backward) for the Laplacian function -- f is linear in the state, its weights are constants of
-  the solve that may carry gradients (attention block) -- with alpha' = sigmoid(alpha_train).  Everything else keeps the host
-  loop `_solve_dopri5` over the kernel-backed autograd Functions of autograd.py."""
-  if func.__class__.__name__ != 'LaplacianODEFunc' or not hasattr(func, '_descriptor'):
+  """The differentiated dopri5 solve runs as ONE recorded device solve + ONE native reverse sweep.  The Laplacian function -- f linear
+  in the state, its weights constants of the solve that may carry gradients (attention block), alpha' = sigmoid(alpha_train) -- is
+  swept by csrc/dopri5.hip (gnpde_dopri5_set_tape / _tape_backward); GRAND-nl and GAT within the limits of the native VJP stage
+  (_transformer_stage_native / _gat_stage_native; raw alpha too: the stage sums that form itself) by csrc/adjoint.hip
+  (gnpde_adjoint_set_dopri5_tape: one stage per recorded evaluation, q||k and the weights recomputed at the recorded stage input).
+  Everything else keeps the host loop `_solve_dopri5` over the kernel-backed autograd Functions of autograd.py."""
+  kind = func.__class__.__name__
+  if kind not in ('LaplacianODEFunc', 'ODEFuncTransformerAtt', 'ODEFuncAtt') or not hasattr(func, '_descriptor'):
     return False
   if not (y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32 and y0.shape[1] <= 256 and len(t) == 2 and t.dtype == torch.float32):
     return False
   opt = func.opt
-  if opt.get('no_alpha_sigmoid') or opt.get('gnpde_host_dopri5_training') or opt.get('gnpde_composite_backward'):
+  if opt.get('gnpde_host_dopri5_training') or opt.get('gnpde_composite_backward'):
+    return False
+  if kind == 'LaplacianODEFunc':
+    if opt.get('no_alpha_sigmoid'):
+      return False
+  elif opt.get('gnpde_shard') or not (_transformer_stage_native(func) if kind == 'ODEFuncTransformerAtt' else _gat_stage_native(func)):
     return False
   if os.environ.get('GNPDE_HOST_DOPRI5_TRAINING', '0') == '1':      # A/B runs (bench.py --config cora-epoch)
     return False
@@ -698,6 +706,139 @@ class _RecordedDopri5(torch.autograd.Function):
     return dy0, dw, dalpha, dbeta, None, None, None, None, None
 
 
+def _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out1, room):
+  """One recorded run into out1; a tape that is too short doubles (up to _TAPE_GROWTH_CAP_BYTES) and the solve runs again.  Counts the
+  evaluations into func.nfe as the host loop would and raises MaxNFEException where it would.  (The loop of _RecordedDopri5.forward,
+  which keeps its own copy: the Laplacian path is left as it is.)"""
+  from .utils import MaxNFEException
+  n = y0c.shape[0]
+  tps = 8 if y0c.numel() < (1 << 22) else 1
+  while True:
+    try:
+      finished = sol.run(y0c, t0, t1, out1, trials_per_sync=tps, max_evals=room)
+      break
+    except _lib.GnpdeError as exc:
+      if 'do not fit the tape' not in str(exc):
+        raise
+      torch.cuda.synchronize(y0c.device)
+      state_bytes = max(n * desc.struct.ld * 4, 1)
+      if 2 * sol.tape_capacity * 6 * state_bytes > _TAPE_GROWTH_CAP_BYTES:
+        raise _TapeTooLong('recorded dopri5: %d accepted steps do not fit a tape of %.0f GB' % (sol.tape_capacity, _TAPE_GROWTH_CAP_BYTES / 1e9))
+      sol.set_tape(2 * sol.tape_capacity)           # more accepted steps than slots: a longer tape, and the solve again
+  stats = sol.stats()
+  func._dopri5_stats = dict(stats, recorded=True)
+  spent = stats['evals']
+  if not finished or spent > room:
+    func.nfe += min(spent, room)
+    raise MaxNFEException
+  func.nfe += spent
+
+
+class _RecordedDopri5NL(torch.autograd.Function):
+  """GRAND-nl / GAT.  Forward: the recorded device-controlled dopri5 solve of _RecordedDopri5 (stage inputs of the accepted steps only).
+  Backward: the walk of csrc/tape_reverse.h -- per recorded evaluation the VJP stage of the native adjoint solve at the recorded stage
+  input (projection, attention, row kernel, normaliser backward, d q / d k, projection term, parameter-gradient pass), its epilogue
+  forming the next cotangent -- as a plain sequence of launches, no PyTorch op and no host synchronisation inside.  The parameters are
+  inputs (as in _RecordedFixedGrid), so their gradients come back through autograd; the backward counts no evaluation, as the
+  reference's does not."""
+
+  @staticmethod
+  def forward(ctx, y0, func, t0, t1, rtol, atol, *params):
+    from . import ops
+    from .utils import MaxNFEException
+    room = func.opt['max_nfe'] + 1 - func.nfe
+    if room <= 0:
+      raise MaxNFEException
+    y0c = _lib.f32c(y0.detach())
+    n, d = y0c.shape
+    st = func.__dict__.setdefault('_tape_state', {})
+    key = (n, d, str(y0c.device), float(rtol), float(atol))
+    ent = st.get(key)
+    if ent is None:
+      for old in st.values():
+        for name in ('solver', 'sweep'):
+          if old.get(name) is not None:
+            old[name].close()
+      st.clear()
+      ent = st[key] = {'y': _lib.alloc_state(n, d, y0c.device), 'a': _lib.alloc_state(n, d, y0c.device),
+                       'x0': _lib.alloc_state(n, d, y0c.device) if func.opt['add_source'] else None,
+                       'solver': None, 'sweep': None, 'sig': None, 'sweep_sig': None, 'extra': {}}
+    if ent['x0'] is not None:
+      if func.x0 is None:
+        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
+      ent['x0'].copy_(func.x0.detach())
+    graph = func._graph(y0c)
+    desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=graph)
+    sig = func._descriptor_signature(desc)
+    if ent['solver'] is None or ent['sig'] != sig:
+      for name in ('solver', 'sweep'):
+        if ent[name] is not None:
+          ent[name].close()
+      ent['sweep'] = None
+      ent['solver'] = ops.Dopri5Solver(desc, rtol, atol, y0c.device)
+      ent['sig'] = sig
+      state_bytes = max(n * desc.struct.ld * 4, 1)
+      ent['solver'].set_tape(int(max(8, min(64, _TAPE_BUDGET_BYTES // (6 * state_bytes)))))
+    sol = ent['solver']
+    out = torch.empty((2, n, d), dtype=torch.float32, device=y0c.device)
+    out[0].copy_(y0c)
+    _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out[1], room)
+    sol.tape_generation += 1
+    ctx.func, ctx.ent, ctx.sol, ctx.gen, ctx.desc, ctx.graph, ctx.params = func, ent, sol, sol.tape_generation, desc, graph, params
+    ctx.x0_version = None if ent['x0'] is None else ent['x0']._version
+    lay = getattr(func, 'multihead_att_layer', None)
+    ctx.split_sig = lay.split_operands()[0] if getattr(lay, 'split_kernel', False) else None      # (the derived operands this solve ran with)
+    func._last_train_solve = 'native recorded-tape dopri5 (VJP stage per recorded evaluation)'
+    _tape_claim(func, '_tape_live_dopri5', ctx)
+    return out
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    from . import ops
+    func, ent, sol, graph, desc = ctx.func, ctx.ent, ctx.sol, ctx.graph, ctx.desc
+    ctx.gnpde_consumed = True
+    if sol.handle is None or sol.tape_generation != ctx.gen:
+      raise _lib.GnpdeError('recorded dopri5: the tape of this forward pass was overwritten by a later solve of the same function '
+                            '(backward must run before the next training forward; opt["gnpde_host_dopri5_training"] = True keeps a tape per forward)')
+    if ent['x0'] is not None and ent['x0']._version != ctx.x0_version:
+      raise _lib.GnpdeError('recorded dopri5: the source term of this forward pass was overwritten before its backward')
+    need = ctx.needs_input_grad
+    with torch.no_grad():
+      n, d = grad_out.shape[1], grad_out.shape[2]
+      dev = grad_out.device
+      gt, t_from_csr = graph.transposed_positions()
+      ex = ent['extra']
+      if ctx.split_sig is not None and func.multihead_att_layer.split_operands()[0] != ctx.split_sig:
+        raise _lib.GnpdeError('recorded dopri5: the derived split-kernel projection of this forward pass was re-derived from updated '
+                              'parameters by a later evaluation (backward must run before the next use of the function)')
+      proj_wt = _stage_projection_t(func, ex, dev, forward_values=True)
+      sweep_sig = (ent['sig'], id(gt))
+      if ent['sweep'] is None or ent['sweep_sig'] != sweep_sig:
+        if ent['sweep'] is not None:
+          ent['sweep'].close()
+        ent['sweep'] = ops.AdjointSolver(desc, gt, t_from_csr, proj_wt, None, 'dopri5_tape', (), dev)
+        ent['grads'] = torch.zeros(ent['sweep'].n_grad, dtype=torch.float32, device=dev)
+        ent['sweep_sig'] = sweep_sig
+      csr_from_t = None
+      if graph.e > 0:       # the inverse position map: lets the sweep gather the cotangent rows only (csrc/adjoint.hip)
+        csr_from_t = graph.__dict__.get('_csr_from_t')
+        if csr_from_t is None:
+          csr_from_t = torch.empty_like(t_from_csr)
+          csr_from_t[t_from_csr.long()] = torch.arange(graph.e, dtype=t_from_csr.dtype, device=dev)
+          graph.__dict__['_csr_from_t'] = csr_from_t
+      ent['sweep'].set_dopri5_tape(sol, csr_from_t)      # (the accepted steps differ from one iteration to the next)
+      ab = ent['a']
+      ab.copy_(grad_out[1])
+      ent['sweep'].run(ent['y'], ab, ent['grads'], use_graph=False)      # (y is not read: the state comes from the tape)
+      dy0 = ab + grad_out[0] if need[0] else None
+      by_param = _grad_vector_by_param(func, ent['grads'], d, ex)
+      gparams = []
+      for i, p in enumerate(ctx.params):
+        g = by_param.get(id(p)) if need[6 + i] else None
+        gparams.append(None if g is None else g.clone(memory_format=torch.contiguous_format))
+    return (dy0, None, None, None, None, None) + tuple(gparams)
+
+
 def _solve_dopri5_recorded(func, y0, t, rtol, atol):
   if _tape_busy(func, '_tape_live_dopri5'):
     func._last_train_solve = 'differentiable host loop (the record of an earlier forward pass still awaits its backward)'
@@ -705,6 +846,9 @@ def _solve_dopri5_recorded(func, y0, t, rtol, atol):
   t0_, t1_ = end_points(t)
   nfe0 = func.nfe
   try:
+    if func.__class__.__name__ != 'LaplacianODEFunc':
+      params = tuple(p for p in func.parameters() if p.requires_grad)
+      return _RecordedDopri5NL.apply(y0, func, t0_, t1_, float(rtol), float(atol), *params)
     return _RecordedDopri5.apply(y0, func._edge_values(), func.alpha_train, func.beta_train, func, t0_, t1_, float(rtol),
                                  float(atol))
   except _TapeTooLong as exc:

@@ -1747,6 +1747,12 @@ class Dopri5Solver(_NativeSolver):
     check(_lib.lib().gnpde_dopri5_tape_record(self.handle, hs, n, ctypes.byref(x)))
     return [float(hs[i]) for i in range(n)], float(x.value)
 
+  def tape_slots(self):
+    """(address of buffer 0 of the record, floats between consecutive buffers): buffer 6 s + i = u_i of accepted step s."""
+    slots, stride = ctypes.c_void_p(), ctypes.c_size_t(0)
+    check(_lib.lib().gnpde_dopri5_tape_slots(self.handle, ctypes.byref(slots), ctypes.byref(stride)))
+    return slots, int(stride.value)
+
   def tape_backward(self, graph_t, w_t, grad_out):
     """(dL/dy0 [n, d], r_t [e] in graph_t's CSR order, sum_g [n, ld], dot [1]) of the last recorded run; no host synchronisation."""
     require_hip(grad_out, w_t)
@@ -2003,7 +2009,9 @@ class AdjointSolver(_NativeSolver):
   def __init__(self, desc, graph_t, t_from_csr, proj_wt, w_t, method, dts, device):
     self.desc, self.graph_t = desc, graph_t
     self.keep = [t_from_csr, proj_wt, w_t]
-    self.method = {'euler': _lib.METHOD_EULER, 'rk4': _lib.METHOD_RK4, 'midpoint': _lib.METHOD_MIDPOINT}[method]
+    # ('dopri5_tape': no grid -- the sweep over a recorded dopri5 solve, set_dopri5_tape before every run)
+    self.method = {'euler': _lib.METHOD_EULER, 'rk4': _lib.METHOD_RK4, 'midpoint': _lib.METHOD_MIDPOINT,
+                   'dopri5_tape': _lib.METHOD_DOPRI5_TAPE}[method]
     self.dts = [float(v) for v in dts]
     L = _lib.lib()
     nbytes = L.gnpde_adjoint_workspace_bytes(desc.ref(), graph_t.ref(), self.method)
@@ -2031,6 +2039,18 @@ class AdjointSolver(_NativeSolver):
       check(L.gnpde_adjoint_set_tape(self.handle, ptr(tape), tape.numel(), ptr(r_acc), ptr(csr_from_t)))
     self.tape, self.r_acc, self.csr_from_t = tape, r_acc, csr_from_t
     self.swapped = bool(L.gnpde_adjoint_tape_swapped(self.handle))
+
+  def set_dopri5_tape(self, forward, csr_from_t=None):
+    """Reverse sweep through the last recorded run of `forward` (a Dopri5Solver with a tape, GRAND-nl / GAT): run(use_graph=False)
+    then maps a = dL/d(out) to dL/dy0 with one VJP stage per recorded evaluation (gnpde_adjoint_set_dopri5_tape).  The step record is
+    host data the forward run already read; nothing synchronises here."""
+    hs, x = forward.tape_record()
+    slots, stride = forward.tape_slots()
+    arr = (ctypes.c_float * max(len(hs), 1))(*hs)
+    check(_lib.lib().gnpde_adjoint_set_dopri5_tape(self.handle, slots, stride, arr, len(hs), float(x), ptr(csr_from_t)))
+    self.tape, self.csr_from_t = forward.tape, csr_from_t
+    self.swapped = bool(_lib.lib().gnpde_adjoint_tape_swapped(self.handle))
+    self.n_rhs_evals = _lib.lib().gnpde_adjoint_num_rhs_evals(self.handle)
 
   def run(self, y, a, grads, use_graph=True):
     """y, a [n, ld] integrated backwards in place; grads [n_grad] receives the parameter gradients."""

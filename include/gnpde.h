@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 19  /* 19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 20  /* 20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -434,8 +434,10 @@ enum { GNPDE_RHS_LAPLACIAN = 0, GNPDE_RHS_TRANSFORMER = 1, GNPDE_RHS_GAT = 2 };
  * 4 (BLEND ogbn-arxiv: d = 162, reference best_params feat_hidden_dim 64 + pos_enc_hidden_dim 98) use 16-byte lanes. */
 #define GNPDE_RHS_PADDED_ROWS 1
 /* MIDPOINT (torchdiffeq fixed_grid.py Midpoint, advertised by the reference at src/run_GNN.py:330): y + dt f(y + (dt / 2) f(y)),
- * two evaluations per step, both as GNPDE_STAGE_LINCOMB stages; gnpde_solver_* only. */
-enum { GNPDE_METHOD_EULER = 0, GNPDE_METHOD_RK4 = 1, GNPDE_METHOD_MIDPOINT = 2 };
+ * two evaluations per step, both as GNPDE_STAGE_LINCOMB stages; gnpde_solver_* only.
+ * DOPRI5_TAPE: no method of a solve -- gnpde_adjoint_create only: the object sweeps a recorded Dormand-Prince solve
+ * (gnpde_adjoint_set_dopri5_tape). */
+enum { GNPDE_METHOD_EULER = 0, GNPDE_METHOD_RK4 = 1, GNPDE_METHOD_MIDPOINT = 2, GNPDE_METHOD_DOPRI5_TAPE = 3 };
 
 typedef struct gnpde_rhs {
   int32_t kind;               /* GNPDE_RHS_*                                                   */
@@ -589,6 +591,26 @@ int    gnpde_adjoint_set_tape(gnpde_adjoint_t* s, const void* tape, size_t tape_
  * the stage algebra with S + P; the recorded state rows are read as own rows, never gathered.  gnpde_adjoint_tape_swapped: 1 when that
  * form runs -- r_acc then holds the products in GRAPH_T's order. */
 int    gnpde_adjoint_tape_swapped(const gnpde_adjoint_t* s);
+/* Reverse sweep through a RECORDED DORMAND-PRINCE solve of GRAND-nl or GAT  [replaces what torch autograd does when the reference trains
+ * `--function transformer` (or GAT) with its defaults -- opt['adjoint'] = False, method dopri5 (src/run_GNN.py:336, best_params) --
+ * i.e. loss.backward() through every accepted step of torchdiffeq's dopri5 loop (rk_common.py _runge_kutta_step, interp.py) and, per
+ * evaluation, through ODEFuncTransformerAtt.forward / ODEFuncAtt.forward; the step sizes are constants of the backward pass].  The
+ * object is created with method GNPDE_METHOD_DOPRI5_TAPE (dts NULL, n_steps 0; GNPDE_RHS_TRANSFORMER / GNPDE_RHS_GAT descriptors within
+ * the limits above, t_from_csr and proj_wt as there) and given, per run and without being re-created, the record of the forward solve:
+ *   slots        the stage inputs gnpde_dopri5_set_tape left (gnpde_dopri5_tape_slots): buffer 6 s + i = u_i of accepted step s, [n, ld]
+ *                each, slot_stride floats apart (a multiple of 64, at least one state buffer), 256-byte aligned, device;
+ *   h[n_steps]   HOST array, the accepted steps' sizes (copied);  x_last in (0, 1]: the fraction of the last step at which t1 lies
+ *                (gnpde_dopri5_tape_record);   csr_from_t  as gnpde_adjoint_set_tape (nullable).
+ * gnpde_adjoint_run (use_graph = 0: the number of accepted steps changes from run to run, nothing is captured; y is not read) then maps
+ * a [n, ld] = dL/d(y_out) to dL/dy0 in place and fills grads as above (GAT: d W^T [A, d], d a in the first 2 d_k of the A slots behind it)
+ * with one VJP stage per recorded evaluation, 6 n_steps + 1 in all -- projection and attention RECOMPUTED at u_i (nothing but stage inputs
+ * is recorded), the next cotangent formed in the stage's GNPDE_STAGE_LINCOMB epilogue -- and one linear combination per step: a plain
+ * sequence of launches on `stream`, no allocation, no float atomics (bit-identical from run to run), and -- after the object's first run,
+ * which zero-fills the workspace and synchronises once as every gnpde_adjoint_run does -- no host synchronisation.  The walk is
+ * stated in csrc/tape_reverse.h.  slots == NULL detaches.  Refused: an object of another method, GNPDE_RHS_LAPLACIAN (its sweep is
+ * gnpde_dopri5_tape_backward), n_steps < 1, x_last outside (0, 1], use_graph != 0; gnpde_adjoint_set_tape refuses such an object. */
+int    gnpde_adjoint_set_dopri5_tape(gnpde_adjoint_t* s, const float* slots, size_t slot_stride, const float* h, int32_t n_steps,
+                                     float x_last, const int32_t* csr_from_t);
 int    gnpde_adjoint_num_rhs_evals(const gnpde_adjoint_t* s);
 int    gnpde_adjoint_destroy(gnpde_adjoint_t* s);
 
@@ -732,8 +754,9 @@ int gnpde_dopri5_destroy(gnpde_dopri5_t* s);
 /* Recorded solve + reverse sweep  [replaces what torch autograd does when the reference trains with opt['adjoint'] = False -- its
  * default, and its Cora / Citeseer best_params (src/base_classes.py:44-47, src/best_params.py) -- i.e. `loss.backward()` through
  * every accepted step of torchdiffeq's dopri5 (rk_common.py _runge_kutta_step, interp.py), with the step sizes constants of the
- * backward pass (misc.py _optimal_step_size runs under torch.no_grad)].  GRAND-l descriptors only (f linear in the state; the
- * edge weights are constants of the solve that carry gradients: src/block_transformer_attention.py:36-72).
+ * backward pass (misc.py _optimal_step_size runs under torch.no_grad)].  The sweep here is GRAND-l's (f linear in the state; the
+ * edge weights are constants of the solve that carry gradients: src/block_transformer_attention.py:36-72); a GRAND-nl / GAT solve is
+ * recorded the same way -- stage inputs only -- and swept by gnpde_adjoint_set_dopri5_tape + gnpde_adjoint_run.
  *   gnpde_dopri5_set_tape       ZERO-FILLED device memory of gnpde_dopri5_tape_bytes(rhs, capacity_steps) bytes, 256-byte aligned;
  *                               every ACCEPTED trial step of the following runs leaves its stage inputs u_0..u_5 (and y1 as u_0 of
  *                               the next slot) and its step size there (one copy kernel inside the captured trial step, gated by the
@@ -752,6 +775,9 @@ int gnpde_dopri5_set_tape(gnpde_dopri5_t* s, void* tape, size_t tape_bytes, int3
 int gnpde_dopri5_tape_steps(const gnpde_dopri5_t* s);
 /* host arrays: the float32 step sizes of the accepted steps of the last recorded run and the fraction of the last step at which t1 lies */
 int gnpde_dopri5_tape_record(const gnpde_dopri5_t* s, float* h_out, int32_t capacity, float* x_out);
+/* where the record lies: *slots = buffer 0 of the attached tape (buffer 6 s + i = u_i of accepted step s), *slot_stride = floats between
+ * consecutive buffers; GNPDE_EINVAL without a tape */
+int gnpde_dopri5_tape_slots(const gnpde_dopri5_t* s, const float** slots, size_t* slot_stride);
 size_t gnpde_dopri5_tape_backward_workspace_bytes(const gnpde_dopri5_t* s, const gnpde_graph_t* graph_t);
 int gnpde_dopri5_tape_backward(gnpde_dopri5_t* s, const gnpde_graph_t* graph_t, const float* w_t, const float* grad_out,
                                int32_t ld_go, float* grad_y0, int32_t ld_gy0, float* r_t, float* sum_g, float* dot_out,
