@@ -171,6 +171,27 @@ class ODEFunc(nn.Module):
       raise MaxNFEException
     self.nfe += 1
 
+  # The fused solves count their evaluations in bulk, with the same outcome as _check_nfe once per evaluation: the reference raises at
+  # the first evaluation that finds nfe > max_nfe, and nfe then stands at max_nfe + 1 (or where it already stood beyond that).
+  def _nfe_room(self):
+    """Evaluations the reference would still allow before it raises."""
+    return self.opt['max_nfe'] + 1 - self.nfe
+
+  def _charge_fixed_nfe(self, n_evals):
+    """Before a fixed-grid solve of n_evals evaluations: raises where the reference would raise inside it, counting the evaluations it
+    would have made until then.  A solve that fits is counted by the caller once it has run (`func.nfe += n_evals`)."""
+    room = self._nfe_room()
+    if n_evals > room:
+      self.nfe += max(room, 0)
+      raise MaxNFEException
+
+  def _settle_adaptive_nfe(self, room, finished, spent):
+    """After an adaptive device solve that was allowed `room` evaluations (_nfe_room() before it ran) and made `spent`."""
+    if not finished or spent > room:
+      self.nfe += min(spent, room)
+      raise MaxNFEException
+    self.nfe += spent
+
   def _needs_grad(self, x):
     if not torch.is_grad_enabled():
       return False

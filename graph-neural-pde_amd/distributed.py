@@ -1105,11 +1105,7 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
     grid = time_grid(t.detach().to('cpu'), step_size)
     dts = tuple((grid[1:] - grid[:-1]).tolist())
     n_evals = len(dts) * (4 if method == 'rk4' else 1)
-    room = func.opt['max_nfe'] + 1 - func.nfe
-    if n_evals > room:
-      func.nfe += max(room, 0)
-      from .utils import MaxNFEException
-      raise MaxNFEException
+    func._charge_fixed_nfe(n_evals)
   kind, params = _sharded_problem(func)
   ei = func.edge_index
   st = func.__dict__.setdefault('_shard_state', {})
@@ -1164,6 +1160,14 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
     local['edge_weight'] = params['edge_weight'][shard.edge_ids.to(params['edge_weight'].device)]
   be.refresh(func.alpha_train, func.beta_train, local)
   with_source = bool(func.opt['add_source'])
+
+  def source_rows():
+    """This rank's rows of the source term (a fresh contiguous tensor: indexing by ids copies), or None."""
+    if not with_source:
+      return None
+    if func.x0 is None:
+      raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
+    return func.x0.detach()[ent['own_ids']]
   skey = (method, dts, with_source)
   sol = ent['solvers'].get(skey)
   in_graph = (adaptive and ent['ctx'] is not None and d % 4 == 0 and t.dtype == torch.float32 and
@@ -1172,8 +1176,8 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
     # dopri5 / adaptive_heun with the controller on every rank's device: trial steps as per-rank hipGraphs, the error norm summed over the ranks
     # inside the stream (NativeShardedDopri5) -- every rank holds the same controller record, reads it once per batch of trial steps
     from .utils import MaxNFEException
-    from .odeint import end_points
-    room = func.opt['max_nfe'] + 1 - func.nfe
+    from .odeint import default_trials_per_sync, end_points
+    room = func._nfe_room()
     if room <= 0:
       raise MaxNFEException
     skey = (method, float(rtol), float(atol), with_source)
@@ -1186,23 +1190,15 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
       sol = NativeShardedDopri5(shard, be, rtol, atol, n, with_source=with_source, ctx=ent['ctx'], group=group, pair=method)
       ent['solvers'][skey] = sol
     y_own = y0.detach()[ent['own_ids']]
-    x0_own = None
-    if with_source:
-      if func.x0 is None:
-        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-      x0_own = func.x0.detach()[ent['own_ids']]
-    tps = 8 if n * d < (1 << 22) else 1        # (the same rule as on one GPU, over the WHOLE state: the same batches on every rank)
+    x0_own = source_rows()
+    tps = default_trials_per_sync(n * d)       # (the same rule as on one GPU, over the WHOLE state: the same batches on every rank)
     if os.environ.get('GNPDE_DOPRI5_TRIALS_PER_SYNC'):
       tps = max(1, int(os.environ['GNPDE_DOPRI5_TRIALS_PER_SYNC']))
     t0_, t1_ = end_points(t)
     z_own, finished = sol.integrate(y_own, x0_own, t0_, t1_, trials_per_sync=tps, max_evals=room)
     stats = sol.stats()
     func._dopri5_stats = stats
-    spent = stats['evals']
-    if not finished or spent > room:
-      func.nfe += min(spent, room)
-      raise MaxNFEException
-    func.nfe += spent
+    func._settle_adaptive_nfe(room, finished, stats['evals'])
     return _gather_full(z_own, y0, plan, shard, world, n, d, dev, group, func, 0)
   if adaptive:
     # where the in-graph solver does not apply (normalisers with exchanges between the attention passes, rows that are no multiple of
@@ -1215,11 +1211,7 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
       sol = ShardedSolver(shard, be, group)
       ent['solvers'][skey] = sol
     y_own = y0.detach()[ent['own_ids']]
-    x0_own = None
-    if with_source:
-      if func.x0 is None:
-        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-      x0_own = func.x0.detach()[ent['own_ids']].contiguous()
+    x0_own = source_rows()
     z_own = sol.integrate_adaptive(y_own, x0_own, t, rtol, atol, n, method=method, on_eval=func._check_nfe).clone()
     return _gather_full(z_own, y0, plan, shard, world, n, d, dev, group, func, 0)
   if getattr(be, 'general', False) and ent['ctx'] is None:
@@ -1228,11 +1220,7 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
       sol = ShardedSolver(shard, be, group)
       ent['solvers'][skey] = sol
     y_own = y0.detach()[ent['own_ids']]
-    x0_own = None
-    if with_source:
-      if func.x0 is None:
-        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-      x0_own = func.x0.detach()[ent['own_ids']].contiguous()
+    x0_own = source_rows()
     # the Python-driven loop builds its own grid from (T, step_size) starting at 0: it must be the grid the caller asked for
     T_loop = float(sum(dts))
     grid_loop = time_grid(torch.tensor([0.0, T_loop]), step_size)
@@ -1253,12 +1241,7 @@ def solve_sharded(func, y0, t, method, step_size, use_graph=True, group=None, rt
       raise _lib.GnpdeError('sharded solve: internal time grid mismatch')
     ent['solvers'][skey] = sol
   y_own = y0.detach()[ent['own_ids']]
-  x0_own = None
-  if with_source:
-    if func.x0 is None:
-      raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-    x0_own = func.x0.detach()[ent['own_ids']]
-  z_own = sol.integrate(y_own, x0_own, use_graph=use_graph)
+  z_own = sol.integrate(y_own, source_rows(), use_graph=use_graph)
   sol.check()                                       # synchronises; a lost peer raises here, on every rank that saw it
   return _gather_full(z_own, y0, plan, shard, world, n, d, dev, group, func, n_evals)
 

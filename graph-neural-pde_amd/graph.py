@@ -285,6 +285,19 @@ class CSRGraph(object):
       hit = self.__dict__['_t_from_csr'] = (gt, t_from_csr)
     return hit
 
+  def csr_positions(self):
+    """csr_from_t, the inverse of transposed_positions()[1]: for every CSR position of this graph the position of the same entry in
+    graph_t (lets a reverse sweep gather the cotangent rows only, csrc/adjoint.hip).  None for a graph without entries."""
+    if self.e == 0:
+      return None
+    csr_from_t = self.__dict__.get('_csr_from_t')
+    if csr_from_t is None:
+      t_from_csr = self.transposed_positions()[1]
+      csr_from_t = torch.empty_like(t_from_csr)
+      csr_from_t[t_from_csr.long()] = torch.arange(self.e, dtype=t_from_csr.dtype, device=t_from_csr.device)
+      self.__dict__['_csr_from_t'] = csr_from_t
+    return csr_from_t
+
   def locality_view(self, row_bytes, mode='auto'):
     """LocalityView of this graph (the same operator with its nodes relabelled), or None when it does not apply / does not
     pay.  row_bytes: bytes of one row of the table the aggregation gathers from.  Two orders are candidates:

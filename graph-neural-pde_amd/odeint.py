@@ -32,41 +32,118 @@ def time_grid(t, step_size):
 _GRID_CACHE = {}
 
 
-def step_sizes(t, step_size):
-  """The step sizes of torchdiffeq's fixed grid over `t` as host floats.  The blocks pass the SAME device tensor `block.t` on every forward
-  pass: reading it back costs a device -> host synchronisation per solve (~25 us of a 150-us Cora forward), so the result is kept per
-  (tensor object, version, storage address, dtype, step size); tensors without a version counter are read every time."""
+def _cached_host_read(t, tag, read):
+  """read(t) -- a device -> host synchronisation -- kept per (tensor object, version, storage address, dtype, tag); tensors without a
+  version counter are read every time."""
   try:
-    key = (id(t), t._version, t.data_ptr(), t.dtype, float(step_size))
+    key = (id(t), t._version, t.data_ptr(), t.dtype, tag)
   except RuntimeError:
     key = None
   hit = _GRID_CACHE.get(key) if key is not None else None
   if hit is not None and hit[0] is t:
     return hit[1]
-  grid = time_grid(t.detach().to('cpu'), step_size)
-  dts = tuple((grid[1:] - grid[:-1]).tolist())
+  val = read(t)
   if key is not None:
     if len(_GRID_CACHE) >= 64:
       _GRID_CACHE.clear()
-    _GRID_CACHE[key] = (t, dts)        # (holds `t`: its id cannot be handed to another tensor while it is a key)
-  return dts
+    _GRID_CACHE[key] = (t, val)        # (holds `t`: its id cannot be handed to another tensor while it is a key)
+  return val
+
+
+def step_sizes(t, step_size):
+  """The step sizes of torchdiffeq's fixed grid over `t` as host floats.  The blocks pass the SAME device tensor `block.t` on every forward
+  pass: reading it back costs a device -> host synchronisation per solve (~25 us of a 150-us Cora forward), so the result is cached."""
+  def read(t):
+    grid = time_grid(t.detach().to('cpu'), step_size)
+    return tuple((grid[1:] - grid[:-1]).tolist())
+  return _cached_host_read(t, float(step_size), read)
 
 
 def end_points(t):
   """(float(t[0]), float(t[-1])) with the same cache as step_sizes: the adaptive device solves read them once per `block.t`."""
-  try:
-    key = (id(t), t._version, t.data_ptr(), t.dtype, 'ends')
-  except RuntimeError:
-    key = None
-  hit = _GRID_CACHE.get(key) if key is not None else None
-  if hit is not None and hit[0] is t:
-    return hit[1]
-  ends = (float(t[0]), float(t[-1]))
-  if key is not None:
-    if len(_GRID_CACHE) >= 64:
-      _GRID_CACHE.clear()
-    _GRID_CACHE[key] = (t, ends)
-  return ends
+  return _cached_host_read(t, 'ends', lambda t: (float(t[0]), float(t[-1])))
+
+
+def default_trials_per_sync(numel):
+  """Trial steps of a device-controlled adaptive solve between two host reads of its record, by the size of the WHOLE state.  Launch-bound
+  sizes: keep the queue full between reads; large states: a read per trial step costs nothing next to the evaluations and nothing is
+  replayed past the end point."""
+  return 8 if numel < (1 << 22) else 1
+
+
+# --------------------------------------------------------------------------------------------------
+# plumbing shared by the native solve paths: every path keeps its solver objects and state-sized buffers on the function object, in a
+# slot of its own (func.__dict__[slot] = {key: entry}): _solver_state (fixed-step inference), _dopri5_device (adaptive inference),
+# _tape_state / _fixed_tape_state (recorded dopri5 / fixed-grid training), _adjoint_state (fixed-grid adjoint)
+# --------------------------------------------------------------------------------------------------
+def _close_slot(func, slot):
+  st = func.__dict__.get(slot)
+  if st:
+    for old in st.values():
+      for name in ('solver', 'sweep'):
+        if old.get(name) is not None:
+          old[name].close()
+    st.clear()
+
+
+def _entry(func, slot, key, n, d, device, bufs=('y',), siblings=(), view=None):
+  """The entry of `key` in the slot.  One live entry per slot: a miss closes what the slot holds -- its solvers' buffers are state-sized
+  -- and what the `siblings` hold (an eval that alternates methods must not hold a fixed-step AND a 12-buffer dopri5 workspace), then
+  allocates the state buffers named in `bufs`, and `x0` where the function has a source term (rows padded to a multiple of 4 floats
+  when the width is not one: 16-byte lanes for d = 162 etc.).  The entry holds `view`, so that the id in the caller's key stays its."""
+  st = func.__dict__.setdefault(slot, {})
+  ent = st.get(key)
+  if ent is None:
+    _close_slot(func, slot)
+    for name in siblings:
+      _close_slot(func, name)
+    ent = st[key] = {'solver': None, 'sweep': None, 'sig': None, 'sweep_sig': None, 'view': view, 'extra': {}, 'grads': None}
+    for name in bufs:
+      ent[name] = _lib.alloc_state(n, d, device)
+    ent['x0'] = _lib.alloc_state(n, d, device) if func.opt['add_source'] else None
+  return ent
+
+
+def _solver_for(ent, sig, build):
+  """ent['solver'], rebuilt by build() when the descriptor signature is another one; a sweep over the old solver goes with it."""
+  if ent['solver'] is None or ent['sig'] != sig:
+    for name in ('solver', 'sweep'):
+      if ent[name] is not None:
+        ent[name].close()
+        ent[name] = None
+    ent['solver'] = build()
+    ent['sig'] = sig
+  return ent['solver']
+
+
+def _rows_in(view, src, dst):
+  """dst = the rows of src in the order the solver runs in (relabelled graph, graph.LocalityView: src[order])."""
+  return dst.copy_(src) if view is None else view.enter(src, out=dst)
+
+
+def _rows_out(view, src, dst):
+  """dst = the rows of src back in the caller's order (src[inv])."""
+  return dst.copy_(src) if view is None else view.leave(src, out=dst)
+
+
+def _copy_source(func, dst, view=None):
+  """The solver's copy of the source term, refreshed from func.x0."""
+  if func.x0 is None:
+    raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
+  _rows_in(view, func.x0.detach(), dst)
+
+
+def _weights_t(func, graph, out=None):
+  """The Laplacian weights in the entry order of the transposed graph; out: a buffer with a persistent address (captured graphs keep
+  the pointer), at least one element long."""
+  w_csr = func._weights_csr(graph)
+  if graph.e == 0:
+    return w_csr if out is None else out
+  t_from_csr = graph.transposed_positions()[1]
+  if out is None:
+    return torch.index_select(w_csr[:graph.e], 0, t_from_csr[:graph.e].long())
+  torch.index_select(w_csr[:graph.e], 0, t_from_csr[:graph.e].long(), out=out[:graph.e])
+  return out
 
 
 # --------------------------------------------------------------------------------------------------
@@ -117,66 +194,31 @@ def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None
     gather = 'fp32'                                   # method, keep the fp32 operand (scope of the option: INTEGRATION.md)
   dts = list(step_sizes(t, step_size))
   n_evals = len(dts) * _EVALS_PER_STEP[method]
-  # NFE guard with the reference's semantics (raise at the first evaluation that finds nfe > max_nfe)
-  room = func.opt['max_nfe'] + 1 - func.nfe
-  if n_evals > room:
-    func.nfe += max(room, 0)
-    from .utils import MaxNFEException
-    raise MaxNFEException
-  st = func.__dict__.setdefault('_solver_state', {})
+  func._charge_fixed_nfe(n_evals)
   # relabelled graph (graph.LocalityView): the state enters as y0[order] and leaves as y[inv]; the in-graph early-stopping
   # evaluator gets its labels and split masks in the same order (EarlyStopEvaluator.relabelled: shared counters and trace)
   view = func._locality_view(y0) if hasattr(func, '_locality_view') else None
   if evaluator is not None and view is not None:
     evaluator = evaluator.relabelled(view)
   key = (method, tuple(dts), tuple(y0.shape), str(y0.device), id(view), gather)
-  ent = st.get(key)
   y0c = y0.detach()
-  if ent is None:
-    # (rows padded to a multiple of 4 floats when the width is not one: 16-byte lanes for d = 162 etc.)
-    ent = {'y': _lib.alloc_state(y0c.shape[0], y0c.shape[1], y0c.device),
-           'x0': _lib.alloc_state(y0c.shape[0], y0c.shape[1], y0c.device) if func.opt['add_source'] else None,
-           'solver': None, 'sig': None, 'view': view}
-    for old in st.values():     # one live solver per function object: its buffers are state-sized
-      if old.get('solver') is not None:
-        old['solver'].close()
-    st.clear()
-    dd = func.__dict__.get('_dopri5_device')      # ... shared with the adaptive path: an eval that alternates methods
-    if dd:                                        # must not hold a fixed-step AND a 12-buffer dopri5 workspace
-      for old in dd.values():
-        if old.get('solver') is not None:
-          old['solver'].close()
-      dd.clear()
-    st[key] = ent
-  if view is None:
-    ent['y'].copy_(y0c)
-  else:
-    view.enter(y0c, out=ent['y'])
+  ent = _entry(func, '_solver_state', key, y0c.shape[0], y0c.shape[1], y0c.device, siblings=('_dopri5_device',), view=view)
+  _rows_in(view, y0c, ent['y'])
   if ent['x0'] is not None:
-    if func.x0 is None:
-      raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
     # the solver's copy of the source term is refreshed only when the caller's tensor is another one or was written to (keyed on
     # the tensor OBJECT, kept alive here so that its address cannot be handed to another tensor, and its version counter)
     src = func.x0
     # (inference tensors have no version counter -- reading it raises -- and writes through .data / set_() do not bump it: the
     #  key also holds the storage address, and anything that cannot be keyed is copied every solve)
     try:
-      stamp = (src._version, src.data_ptr())
+      stamp = None if src is None else (src._version, src.data_ptr())
     except RuntimeError:
       stamp = None
     if stamp is None or ent.get('x0_src') is not src or ent.get('x0_version') != stamp:
-      if view is None:
-        ent['x0'].copy_(src)
-      else:
-        view.enter(src.detach(), out=ent['x0'])
+      _copy_source(func, ent['x0'], view)
       ent['x0_src'], ent['x0_version'] = src, stamp
   desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=None if view is None else view.graph)
-  sig = func._descriptor_signature(desc)
-  if ent['solver'] is None or ent['sig'] != sig:
-    if ent['solver'] is not None:
-      ent['solver'].close()
-    ent['solver'] = ops.FixedStepSolver(desc, method, dts, y0.device)
-    ent['sig'] = sig
+  _solver_for(ent, func._descriptor_signature(desc), lambda: ops.FixedStepSolver(desc, method, dts, y0.device))
   if getattr(ent['solver'], 'evaluator', None) is not evaluator:
     ent['solver'].set_early_stop(evaluator)     # per-step early-stopping evaluation inside the same hipGraph
   if getattr(ent['solver'], 'gather_dtype', 'fp32') != gather:
@@ -186,10 +228,7 @@ def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None
   func.nfe += n_evals
   out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
   out[0].copy_(y0c)
-  if view is None:
-    out[1].copy_(ent['y'])
-  else:
-    view.leave(ent['y'], out=out[1])
+  _rows_out(view, ent['y'], out[1])
   return out
 
 
@@ -466,10 +505,9 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
   (gnpde_dopri5_set_early_stop); returns (out, times of the accepted steps) then."""
   from . import ops
   from .utils import MaxNFEException
-  room = func.opt['max_nfe'] + 1 - func.nfe          # evaluations the reference would still allow before it raises
+  room = func._nfe_room()
   if room <= 0:
     raise MaxNFEException
-  st = func.__dict__.setdefault('_dopri5_device', {})
   # Relabelled graph (graph.LocalityView) under the same rule as the fixed-step solves (opt['gnpde_reorder'] / GNPDE_REORDER, 'auto' by
   # default).  The error norm of a trial step is a sum over the rows; its squares are accumulated in double (csrc/misc.hip), so the
   # float32 ratio -- and with it every accept / reject decision and step size -- is the same on the relabelled graph as on the graph as
@@ -478,39 +516,13 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
   if evaluator is not None and view is not None:
     evaluator = evaluator.relabelled(view)
   key = (tuple(y0.shape), str(y0.device), float(rtol), float(atol), id(view))
-  ent = st.get(key)
   y0c = y0.detach()
-  if ent is None:
-    ent = {'y': _lib.alloc_state(y0c.shape[0], y0c.shape[1], y0c.device),
-           'x0': _lib.alloc_state(y0c.shape[0], y0c.shape[1], y0c.device) if func.opt['add_source'] else None,
-           'solver': None, 'sig': None, 'view': view}
-    for old in st.values():
-      if old['solver'] is not None:
-        old['solver'].close()
-    st.clear()   # one live solver per function object: its workspace is 12 state-sized buffers
-    fs = func.__dict__.get('_solver_state')       # ... shared with the fixed-step path
-    if fs:
-      for old in fs.values():
-        if old.get('solver') is not None:
-          old['solver'].close()
-      fs.clear()
-    st[key] = ent
+  ent = _entry(func, '_dopri5_device', key, y0c.shape[0], y0c.shape[1], y0c.device, siblings=('_solver_state',), view=view)
   if ent['x0'] is not None:
-    if func.x0 is None:
-      raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-    if view is None:
-      ent['x0'].copy_(func.x0)
-    else:
-      view.enter(func.x0.detach(), out=ent['x0'])
+    _copy_source(func, ent['x0'], view)
   # (ent['y'] only fixes the row stride; the solver owns its buffers)
   desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=None if view is None else view.graph)
-  sig = func._descriptor_signature(desc)
-  if ent['solver'] is None or ent['sig'] != sig:
-    if ent['solver'] is not None:
-      ent['solver'].close()
-    ent['solver'] = ops.Dopri5Solver(desc, rtol, atol, y0.device)
-    ent['sig'] = sig
-  sol = ent['solver']
+  sol = _solver_for(ent, func._descriptor_signature(desc), lambda: ops.Dopri5Solver(desc, rtol, atol, y0.device))
   if getattr(sol, 'pair', 'dopri5') != pair:      # (`pair`: 'dopri5' or torchdiffeq's 'adaptive_heun' -- the same controller, another trial step)
     sol.set_pair(pair)
   if evaluator is not None:
@@ -519,9 +531,7 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
   elif getattr(sol, 'evaluator', None) is not None:
     sol.set_early_stop(None)
   if trials_per_sync is None:
-    # launch-bound sizes: keep the queue full between reads; large states: a read per trial step costs nothing next to six
-    # evaluations and nothing is replayed past the end point
-    trials_per_sync = 8 if y0c.numel() < (1 << 22) else 1
+    trials_per_sync = default_trials_per_sync(y0c.numel())
     if os.environ.get('GNPDE_DOPRI5_TRIALS_PER_SYNC'):          # A/B runs
       trials_per_sync = max(1, int(os.environ['GNPDE_DOPRI5_TRIALS_PER_SYNC']))
   out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
@@ -539,10 +549,7 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
   finished = ent['solver'].run(y0c, t0_, t1_, out[1], trials_per_sync=trials_per_sync, max_evals=room)
   spent = ent['solver'].stats()['evals']
   func._dopri5_stats = ent['solver'].stats()
-  if not finished or spent > room:
-    func.nfe += min(spent, room)
-    raise MaxNFEException
-  func.nfe += spent
+  func._settle_adaptive_nfe(room, finished, spent)
   if evaluator is not None:
     n_acc = ent['solver'].stats()['accepted']
     return out, ent['solver'].times[:n_acc + 1].tolist()
@@ -603,6 +610,80 @@ def _recorded_ok(func, y0, t, options):
   return torch.is_grad_enabled() and func._needs_grad(y0)
 
 
+def _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out1, room):
+  """One recorded run into out1; a tape that is too short doubles (up to _TAPE_GROWTH_CAP_BYTES) and the solve runs again.  Counts the
+  evaluations into func.nfe as the host loop would and raises MaxNFEException where it would."""
+  n = y0c.shape[0]
+  tps = default_trials_per_sync(y0c.numel())
+  while True:
+    try:
+      finished = sol.run(y0c, t0, t1, out1, trials_per_sync=tps, max_evals=room)
+      break
+    except _lib.GnpdeError as exc:
+      if 'do not fit the tape' not in str(exc):
+        raise
+      torch.cuda.synchronize(y0c.device)
+      state_bytes = max(n * desc.struct.ld * 4, 1)
+      if 2 * sol.tape_capacity * 6 * state_bytes > _TAPE_GROWTH_CAP_BYTES:
+        raise _TapeTooLong('recorded dopri5: %d accepted steps do not fit a tape of %.0f GB' % (sol.tape_capacity, _TAPE_GROWTH_CAP_BYTES / 1e9))
+      sol.set_tape(2 * sol.tape_capacity)           # more accepted steps than slots: a longer tape, and the solve again
+  stats = sol.stats()
+  func._dopri5_stats = dict(stats, recorded=True)
+  func._settle_adaptive_nfe(room, finished, stats['evals'])
+
+
+def _recorded_dopri5_forward(func, y0, t0, t1, rtol, atol, bufs):
+  """The forward pass of both recorded dopri5 Functions: the device-controlled solve with a tape, in the function's `_tape_state` entry
+  (state buffers `bufs`).  Returns (entry, graph, descriptor, solver, [2, n, d] output)."""
+  from . import ops
+  from .utils import MaxNFEException
+  room = func._nfe_room()
+  if room <= 0:
+    raise MaxNFEException
+  y0c = _lib.f32c(y0.detach())
+  n, d = y0c.shape
+  ent = _entry(func, '_tape_state', (n, d, str(y0c.device), float(rtol), float(atol)), n, d, y0c.device, bufs)
+  if ent['x0'] is not None:
+    _copy_source(func, ent['x0'])
+  graph = func._graph(y0c)
+  desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=graph)      # (refreshes the CSR-ordered weights in place)
+
+  def build():
+    sol = ops.Dopri5Solver(desc, rtol, atol, y0c.device)
+    state_bytes = max(n * desc.struct.ld * 4, 1)
+    sol.set_tape(int(max(8, min(64, _TAPE_BUDGET_BYTES // (6 * state_bytes)))))
+    return sol
+  sol = _solver_for(ent, func._descriptor_signature(desc), build)
+  out = torch.empty((2, n, d), dtype=torch.float32, device=y0c.device)
+  out[0].copy_(y0c)
+  _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out[1], room)
+  sol.tape_generation += 1
+  return ent, graph, desc, sol, out
+
+
+def _check_tape(sol, gen, what, hint):
+  """Backward of a recorded solve: the solver's tape must still hold the record of the forward pass stamped `gen`."""
+  if sol is None or sol.handle is None or sol.tape_generation != gen:
+    raise _lib.GnpdeError('%s: the tape of this forward pass was overwritten by a later solve of the same function '
+                          '(backward must run before the next training forward; %s)' % (what, hint))
+
+
+def _check_split_operands(func, split_sig, what):
+  """Backward of a recorded solve on the BLEND split kernel: the derived operands must still be the ones its forward pass ran with."""
+  if split_sig is not None and func.multihead_att_layer.split_operands()[0] != split_sig:
+    raise _lib.GnpdeError('%s: the derived split-kernel projection of this forward pass was re-derived from updated parameters by a '
+                          'later evaluation (backward must run before the next use of the function)' % what)
+
+
+def _param_grads(by_param, params, need):
+  """The gradient of every entry of `params` whose flag in `need` is set (None otherwise), cloned out of the sweep's gradient vector."""
+  gparams = []
+  for p, wanted in zip(params, need):
+    g = by_param.get(id(p)) if wanted else None
+    gparams.append(None if g is None else g.clone(memory_format=torch.contiguous_format))
+  return tuple(gparams)
+
+
 class _RecordedDopri5(torch.autograd.Function):
   """Forward: the device-controlled dopri5 solve (one hipGraph per trial step) that leaves the stage inputs of every ACCEPTED step
   on a tape.  Backward: what autograd does through torchdiffeq's accepted steps (step sizes constants: misc.py _optimal_step_size
@@ -611,64 +692,9 @@ class _RecordedDopri5(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, y0, edge_values, alpha_train, beta_train, func, t0, t1, rtol, atol):
-    from . import ops
-    from .utils import MaxNFEException
-    room = func.opt['max_nfe'] + 1 - func.nfe
-    if room <= 0:
-      raise MaxNFEException
-    y0c = _lib.f32c(y0.detach())
-    n, d = y0c.shape
-    st = func.__dict__.setdefault('_tape_state', {})
-    key = (n, d, str(y0c.device), float(rtol), float(atol))
-    ent = st.get(key)
-    if ent is None:
-      for old in st.values():
-        if old.get('solver') is not None:
-          old['solver'].close()
-      st.clear()
-      ent = st[key] = {'y': _lib.alloc_state(n, d, y0c.device),
-                       'x0': _lib.alloc_state(n, d, y0c.device) if func.opt['add_source'] else None, 'solver': None, 'sig': None}
-    if ent['x0'] is not None:
-      if func.x0 is None:
-        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-      ent['x0'].copy_(func.x0.detach())
-    graph = func._graph(y0c)
-    desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=graph)      # (refreshes the CSR-ordered weights in place)
-    sig = func._descriptor_signature(desc)
-    if ent['solver'] is None or ent['sig'] != sig:
-      if ent['solver'] is not None:
-        ent['solver'].close()
-      ent['solver'] = ops.Dopri5Solver(desc, rtol, atol, y0c.device)
-      ent['sig'] = sig
-      state_bytes = max(n * desc.struct.ld * 4, 1)
-      ent['solver'].set_tape(int(max(8, min(64, _TAPE_BUDGET_BYTES // (6 * state_bytes)))))
-    sol = ent['solver']
-    out = torch.empty((2, n, d), dtype=torch.float32, device=y0c.device)
-    out[0].copy_(y0c)
-    tps = 8 if y0c.numel() < (1 << 22) else 1
-    while True:
-      try:
-        finished = sol.run(y0c, t0, t1, out[1], trials_per_sync=tps, max_evals=room)
-        break
-      except _lib.GnpdeError as exc:
-        if 'do not fit the tape' not in str(exc):
-          raise
-        torch.cuda.synchronize(y0c.device)
-        state_bytes = max(n * desc.struct.ld * 4, 1)
-        if 2 * sol.tape_capacity * 6 * state_bytes > _TAPE_GROWTH_CAP_BYTES:
-          raise _TapeTooLong('recorded dopri5: %d accepted steps do not fit a tape of %.0f GB' % (sol.tape_capacity, _TAPE_GROWTH_CAP_BYTES / 1e9))
-        sol.set_tape(2 * sol.tape_capacity)           # more accepted steps than slots: a longer tape, and the solve again
-    stats = sol.stats()
-    func._dopri5_stats = dict(stats, recorded=True)
-    spent = stats['evals']
-    if not finished or spent > room:
-      func.nfe += min(spent, room)
-      raise MaxNFEException
-    func.nfe += spent
-    sol.tape_generation += 1
-    gt, t_from_csr = graph.transposed_positions()
-    w_csr = func._weights_csr(graph)
-    w_t = torch.index_select(w_csr[:graph.e], 0, t_from_csr[:graph.e].long()) if graph.e > 0 else w_csr
+    ent, graph, desc, sol, out = _recorded_dopri5_forward(func, y0, t0, t1, rtol, atol, ('y',))
+    gt = graph.transposed_positions()[0]
+    w_t = _weights_t(func, graph)
     ctx.func, ctx.sol, ctx.gen, ctx.gt, ctx.e = func, sol, sol.tape_generation, gt, graph.e
     ctx.x0 = ent['x0']
     ctx.x0_version = None if ent['x0'] is None else ent['x0']._version
@@ -683,9 +709,7 @@ class _RecordedDopri5(torch.autograd.Function):
     w_t, alpha_train, beta_train = ctx.saved_tensors
     sol, gt, E = ctx.sol, ctx.gt, ctx.e
     ctx.gnpde_consumed = True
-    if sol.handle is None or sol.tape_generation != ctx.gen:
-      raise _lib.GnpdeError('recorded dopri5: the tape of this forward pass was overwritten by a later solve of the same function '
-                            '(backward must run before the next training forward; opt["gnpde_host_dopri5_training"] = True keeps a tape per forward)')
+    _check_tape(sol, ctx.gen, 'recorded dopri5', 'opt["gnpde_host_dopri5_training"] = True keeps a tape per forward')
     need = ctx.needs_input_grad
     with torch.no_grad():
       g1 = grad_out[1].contiguous()
@@ -706,34 +730,6 @@ class _RecordedDopri5(torch.autograd.Function):
     return dy0, dw, dalpha, dbeta, None, None, None, None, None
 
 
-def _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out1, room):
-  """One recorded run into out1; a tape that is too short doubles (up to _TAPE_GROWTH_CAP_BYTES) and the solve runs again.  Counts the
-  evaluations into func.nfe as the host loop would and raises MaxNFEException where it would.  (The loop of _RecordedDopri5.forward,
-  which keeps its own copy: the Laplacian path is left as it is.)"""
-  from .utils import MaxNFEException
-  n = y0c.shape[0]
-  tps = 8 if y0c.numel() < (1 << 22) else 1
-  while True:
-    try:
-      finished = sol.run(y0c, t0, t1, out1, trials_per_sync=tps, max_evals=room)
-      break
-    except _lib.GnpdeError as exc:
-      if 'do not fit the tape' not in str(exc):
-        raise
-      torch.cuda.synchronize(y0c.device)
-      state_bytes = max(n * desc.struct.ld * 4, 1)
-      if 2 * sol.tape_capacity * 6 * state_bytes > _TAPE_GROWTH_CAP_BYTES:
-        raise _TapeTooLong('recorded dopri5: %d accepted steps do not fit a tape of %.0f GB' % (sol.tape_capacity, _TAPE_GROWTH_CAP_BYTES / 1e9))
-      sol.set_tape(2 * sol.tape_capacity)           # more accepted steps than slots: a longer tape, and the solve again
-  stats = sol.stats()
-  func._dopri5_stats = dict(stats, recorded=True)
-  spent = stats['evals']
-  if not finished or spent > room:
-    func.nfe += min(spent, room)
-    raise MaxNFEException
-  func.nfe += spent
-
-
 class _RecordedDopri5NL(torch.autograd.Function):
   """GRAND-nl / GAT.  Forward: the recorded device-controlled dopri5 solve of _RecordedDopri5 (stage inputs of the accepted steps only).
   Backward: the walk of csrc/tape_reverse.h -- per recorded evaluation the VJP stage of the native adjoint solve at the recorded stage
@@ -744,46 +740,7 @@ class _RecordedDopri5NL(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, y0, func, t0, t1, rtol, atol, *params):
-    from . import ops
-    from .utils import MaxNFEException
-    room = func.opt['max_nfe'] + 1 - func.nfe
-    if room <= 0:
-      raise MaxNFEException
-    y0c = _lib.f32c(y0.detach())
-    n, d = y0c.shape
-    st = func.__dict__.setdefault('_tape_state', {})
-    key = (n, d, str(y0c.device), float(rtol), float(atol))
-    ent = st.get(key)
-    if ent is None:
-      for old in st.values():
-        for name in ('solver', 'sweep'):
-          if old.get(name) is not None:
-            old[name].close()
-      st.clear()
-      ent = st[key] = {'y': _lib.alloc_state(n, d, y0c.device), 'a': _lib.alloc_state(n, d, y0c.device),
-                       'x0': _lib.alloc_state(n, d, y0c.device) if func.opt['add_source'] else None,
-                       'solver': None, 'sweep': None, 'sig': None, 'sweep_sig': None, 'extra': {}}
-    if ent['x0'] is not None:
-      if func.x0 is None:
-        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-      ent['x0'].copy_(func.x0.detach())
-    graph = func._graph(y0c)
-    desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=graph)
-    sig = func._descriptor_signature(desc)
-    if ent['solver'] is None or ent['sig'] != sig:
-      for name in ('solver', 'sweep'):
-        if ent[name] is not None:
-          ent[name].close()
-      ent['sweep'] = None
-      ent['solver'] = ops.Dopri5Solver(desc, rtol, atol, y0c.device)
-      ent['sig'] = sig
-      state_bytes = max(n * desc.struct.ld * 4, 1)
-      ent['solver'].set_tape(int(max(8, min(64, _TAPE_BUDGET_BYTES // (6 * state_bytes)))))
-    sol = ent['solver']
-    out = torch.empty((2, n, d), dtype=torch.float32, device=y0c.device)
-    out[0].copy_(y0c)
-    _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out[1], room)
-    sol.tape_generation += 1
+    ent, graph, desc, sol, out = _recorded_dopri5_forward(func, y0, t0, t1, rtol, atol, ('y', 'a'))
     ctx.func, ctx.ent, ctx.sol, ctx.gen, ctx.desc, ctx.graph, ctx.params = func, ent, sol, sol.tape_generation, desc, graph, params
     ctx.x0_version = None if ent['x0'] is None else ent['x0']._version
     lay = getattr(func, 'multihead_att_layer', None)
@@ -797,9 +754,7 @@ class _RecordedDopri5NL(torch.autograd.Function):
     from . import ops
     func, ent, sol, graph, desc = ctx.func, ctx.ent, ctx.sol, ctx.graph, ctx.desc
     ctx.gnpde_consumed = True
-    if sol.handle is None or sol.tape_generation != ctx.gen:
-      raise _lib.GnpdeError('recorded dopri5: the tape of this forward pass was overwritten by a later solve of the same function '
-                            '(backward must run before the next training forward; opt["gnpde_host_dopri5_training"] = True keeps a tape per forward)')
+    _check_tape(sol, ctx.gen, 'recorded dopri5', 'opt["gnpde_host_dopri5_training"] = True keeps a tape per forward')
     if ent['x0'] is not None and ent['x0']._version != ctx.x0_version:
       raise _lib.GnpdeError('recorded dopri5: the source term of this forward pass was overwritten before its backward')
     need = ctx.needs_input_grad
@@ -808,9 +763,7 @@ class _RecordedDopri5NL(torch.autograd.Function):
       dev = grad_out.device
       gt, t_from_csr = graph.transposed_positions()
       ex = ent['extra']
-      if ctx.split_sig is not None and func.multihead_att_layer.split_operands()[0] != ctx.split_sig:
-        raise _lib.GnpdeError('recorded dopri5: the derived split-kernel projection of this forward pass was re-derived from updated '
-                              'parameters by a later evaluation (backward must run before the next use of the function)')
+      _check_split_operands(func, ctx.split_sig, 'recorded dopri5')
       proj_wt = _stage_projection_t(func, ex, dev, forward_values=True)
       sweep_sig = (ent['sig'], id(gt))
       if ent['sweep'] is None or ent['sweep_sig'] != sweep_sig:
@@ -819,24 +772,13 @@ class _RecordedDopri5NL(torch.autograd.Function):
         ent['sweep'] = ops.AdjointSolver(desc, gt, t_from_csr, proj_wt, None, 'dopri5_tape', (), dev)
         ent['grads'] = torch.zeros(ent['sweep'].n_grad, dtype=torch.float32, device=dev)
         ent['sweep_sig'] = sweep_sig
-      csr_from_t = None
-      if graph.e > 0:       # the inverse position map: lets the sweep gather the cotangent rows only (csrc/adjoint.hip)
-        csr_from_t = graph.__dict__.get('_csr_from_t')
-        if csr_from_t is None:
-          csr_from_t = torch.empty_like(t_from_csr)
-          csr_from_t[t_from_csr.long()] = torch.arange(graph.e, dtype=t_from_csr.dtype, device=dev)
-          graph.__dict__['_csr_from_t'] = csr_from_t
-      ent['sweep'].set_dopri5_tape(sol, csr_from_t)      # (the accepted steps differ from one iteration to the next)
+      ent['sweep'].set_dopri5_tape(sol, graph.csr_positions())      # (the accepted steps differ from one iteration to the next)
       ab = ent['a']
       ab.copy_(grad_out[1])
       ent['sweep'].run(ent['y'], ab, ent['grads'], use_graph=False)      # (y is not read: the state comes from the tape)
       dy0 = ab + grad_out[0] if need[0] else None
-      by_param = _grad_vector_by_param(func, ent['grads'], d, ex)
-      gparams = []
-      for i, p in enumerate(ctx.params):
-        g = by_param.get(id(p)) if need[6 + i] else None
-        gparams.append(None if g is None else g.clone(memory_format=torch.contiguous_format))
-    return (dy0, None, None, None, None, None) + tuple(gparams)
+      gparams = _param_grads(_grad_vector_by_param(func, ent['grads'], d, ex), ctx.params, need[6:])
+    return (dy0, None, None, None, None, None) + gparams
 
 
 def _solve_dopri5_recorded(func, y0, t, rtol, atol):
@@ -1005,59 +947,29 @@ class _RecordedFixedGrid(torch.autograd.Function):
   @staticmethod
   def forward(ctx, y0, edge_values, func, method, dts, *params):
     from . import ops
-    from .utils import MaxNFEException
     n_evals = len(dts) * _EVALS_PER_STEP[method]
-    room = func.opt['max_nfe'] + 1 - func.nfe
-    if n_evals > room:
-      func.nfe += max(room, 0)
-      raise MaxNFEException
+    func._charge_fixed_nfe(n_evals)
     y0c = _lib.f32c(y0.detach())
     n, d = y0c.shape
     view = func._locality_view(y0c) if hasattr(func, '_locality_view') else None
-    st = func.__dict__.setdefault('_fixed_tape_state', {})
-    key = (method, tuple(dts), n, d, str(y0c.device), id(view))
-    ent = st.get(key)
-    if ent is None:
-      for old in st.values():
-        for name in ('solver', 'sweep'):
-          if old.get(name) is not None:
-            old[name].close()
-      st.clear()
-      ent = st[key] = {'y': _lib.alloc_state(n, d, y0c.device), 'a': _lib.alloc_state(n, d, y0c.device),
-                       'x0': _lib.alloc_state(n, d, y0c.device) if func.opt['add_source'] else None,
-                       'solver': None, 'sweep': None, 'sig': None, 'sweep_sig': None, 'view': view, 'extra': {}}
-    if view is None:
-      ent['y'].copy_(y0c)
-    else:
-      view.enter(y0c, out=ent['y'])
+    ent = _entry(func, '_fixed_tape_state', (method, tuple(dts), n, d, str(y0c.device), id(view)), n, d, y0c.device, ('y', 'a'), view=view)
+    _rows_in(view, y0c, ent['y'])
     if ent['x0'] is not None:
-      if func.x0 is None:
-        raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-      if view is None:
-        ent['x0'].copy_(func.x0.detach())
-      else:
-        view.enter(func.x0.detach(), out=ent['x0'])
+      _copy_source(func, ent['x0'], view)
     graph = func._graph(y0c) if view is None else view.graph
     desc = func._descriptor(ent['y'], x0_override=ent['x0'], graph=graph)      # (refreshes the CSR-ordered weights in place)
-    sig = func._descriptor_signature(desc)
-    if ent['solver'] is None or ent['sig'] != sig:
-      for name in ('solver', 'sweep'):
-        if ent[name] is not None:
-          ent[name].close()
-      ent['sweep'] = None
-      ent['solver'] = ops.FixedStepSolver(desc, method, dts, y0c.device)
-      ent['solver'].set_tape(True)
-      ent['sig'] = sig
-    sol = ent['solver']
+
+    def build():
+      sol = ops.FixedStepSolver(desc, method, dts, y0c.device)
+      sol.set_tape(True)
+      return sol
+    sol = _solver_for(ent, func._descriptor_signature(desc), build)
     sol.run(ent['y'])
     func.nfe += n_evals
     sol.tape_generation += 1
     out = torch.empty((2, n, d), dtype=torch.float32, device=y0c.device)
     out[0].copy_(y0c)
-    if view is None:
-      out[1].copy_(ent['y'])
-    else:
-      view.leave(ent['y'], out=out[1])
+    _rows_out(view, ent['y'], out[1])
     ctx.func, ctx.ent, ctx.gen, ctx.desc, ctx.graph, ctx.view = func, ent, sol.tape_generation, desc, graph, view
     lay = getattr(func, 'multihead_att_layer', None)
     ctx.split_sig = lay.split_operands()[0] if getattr(lay, 'split_kernel', False) else None      # (the derived operands this solve ran with)
@@ -1074,9 +986,7 @@ class _RecordedFixedGrid(torch.autograd.Function):
     func, ent, graph, view, desc = ctx.func, ctx.ent, ctx.graph, ctx.view, ctx.desc
     ctx.gnpde_consumed = True
     sol = ent['solver']
-    if sol is None or sol.handle is None or sol.tape_generation != ctx.gen:
-      raise _lib.GnpdeError('recorded fixed-grid solve: the tape of this forward pass was overwritten by a later solve of the same function '
-                            '(backward must run before the next training forward; opt["gnpde_host_fixed_training"] = True keeps a graph per forward)')
+    _check_tape(sol, ctx.gen, 'recorded fixed-grid solve', 'opt["gnpde_host_fixed_training"] = True keeps a graph per forward')
     need = ctx.needs_input_grad
     nl = func.__class__.__name__ in ('ODEFuncTransformerAtt', 'ODEFuncAtt')
     with torch.no_grad():
@@ -1086,48 +996,29 @@ class _RecordedFixedGrid(torch.autograd.Function):
       ex = ent['extra']
       proj_wt = w_t = None
       if nl:
-        if ctx.split_sig is not None and func.multihead_att_layer.split_operands()[0] != ctx.split_sig:
-          raise _lib.GnpdeError('recorded fixed-grid solve: the derived split-kernel projection of this forward pass was re-derived from '
-                                'updated parameters by a later evaluation (backward must run before the next use of the function)')
+        _check_split_operands(func, ctx.split_sig, 'recorded fixed-grid solve')
         proj_wt = _stage_projection_t(func, ex, dev, forward_values=True)
       else:
-        w_csr = func._weights_csr(graph)
         if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
           ex['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=dev)
           ex['r_acc'] = torch.zeros(max(graph.e, 1), dtype=torch.float32, device=dev)
-        if graph.e > 0:
-          torch.index_select(w_csr[:graph.e], 0, t_from_csr.long(), out=ex['w_t'][:graph.e])
-        w_t = ex['w_t']
+        w_t = _weights_t(func, graph, out=ex['w_t'])
       want_dw = (not nl) and ctx.has_edge_values and need[1] and graph.e > 0
       sweep_sig = (ent['sig'], id(gt), bool(want_dw), id(sol))
       if ent['sweep'] is None or ent['sweep_sig'] != sweep_sig:
         if ent['sweep'] is not None:
           ent['sweep'].close()
         ent['sweep'] = ops.AdjointSolver(desc, gt, t_from_csr if nl else None, proj_wt, w_t, ctx.method, ctx.dts, dev)
-        csr_from_t = None
-        if nl and graph.e > 0:       # the inverse position map: lets the sweep gather the cotangent rows only (csrc/adjoint.hip)
-          csr_from_t = graph.__dict__.get('_csr_from_t')
-          if csr_from_t is None:
-            csr_from_t = torch.empty_like(t_from_csr)
-            csr_from_t[t_from_csr.long()] = torch.arange(graph.e, dtype=t_from_csr.dtype, device=dev)
-            graph.__dict__['_csr_from_t'] = csr_from_t
-        ent['sweep'].set_tape(sol.tape, ex['r_acc'] if want_dw else None, csr_from_t)
+        ent['sweep'].set_tape(sol.tape, ex['r_acc'] if want_dw else None, graph.csr_positions() if nl else None)
         ent['grads'] = torch.zeros(ent['sweep'].n_grad, dtype=torch.float32, device=dev)
         ent['sweep_sig'] = sweep_sig
       ab = ent['a']
       g1 = grad_out[1]
-      if view is None:
-        ab.copy_(g1)
-      else:
-        view.enter(g1.contiguous(), out=ab)
+      _rows_in(view, g1 if view is None else g1.contiguous(), ab)
       ent['sweep'].run(ent['y'], ab, ent['grads'])      # (y is not read in the taped mode: the state comes from the tape)
       dy0 = None
       if need[0]:
-        dy0 = torch.empty((n, d), dtype=torch.float32, device=dev)
-        if view is None:
-          dy0.copy_(ab)
-        else:
-          view.leave(ab, out=dy0)
+        dy0 = _rows_out(view, ab, torch.empty((n, d), dtype=torch.float32, device=dev))
         dy0 += grad_out[0]
       dw = None
       if want_dw:
@@ -1139,12 +1030,8 @@ class _RecordedFixedGrid(torch.autograd.Function):
         order = gt.perm_long if ent['sweep'].swapped else graph.perm_long      # (the products lie in the order of the graph the row kernel ran on)
         dw_e[order] = a * ex['r_acc'][:E]
         dw = (dw_e / ctx.heads).unsqueeze(1).expand(E, ctx.heads).contiguous() if ctx.heads else dw_e
-      by_param = _grad_vector_by_param(func, ent['grads'], d, ex)
-      gparams = []
-      for i, p in enumerate(ctx.params):
-        g = by_param.get(id(p)) if need[5 + i] else None
-        gparams.append(None if g is None else g.clone(memory_format=torch.contiguous_format))
-    return (dy0, dw, None, None, None) + tuple(gparams)
+      gparams = _param_grads(_grad_vector_by_param(func, ent['grads'], d, ex), ctx.params, need[5:])
+    return (dy0, dw, None, None, None) + gparams
 
 
 _FIXED_TAPE_BUDGET_BYTES = 96 << 30     # a recorded fixed-grid solve that would need more than this (or more than 70 % of the free device memory) runs the host loop
@@ -1172,7 +1059,8 @@ def _solve_fixed_recorded(func, y0, t, method, step_size):
   if _tape_busy(func, '_tape_live_fixed'):
     func._last_train_solve = 'differentiable host loop (the record of an earlier forward pass still awaits its backward)'
     return _solve_fixed_host(func, y0, t, method, step_size)
-  cached = func.__dict__.get('_fixed_tape_state')          # (a tape of this shape that already exists is not allocated again)
+  # (a tape of this method, grid and shape that already exists is not allocated again: the key of _RecordedFixedGrid.forward)
+  cached = any(key[:4] == (method, tuple(dts), y0.shape[0], y0.shape[1]) for key in func.__dict__.get('_fixed_tape_state', ()))
   if not cached and need > min(_FIXED_TAPE_BUDGET_BYTES, 0.7 * free):
     func._last_train_solve = 'differentiable host loop (the record of %d evaluations would take %.1f GB)' % (len(dts) * _EVALS_PER_STEP[method], need / 1e9)
     return _solve_fixed_host(func, y0, t, method, step_size)
@@ -1360,41 +1248,18 @@ def _adjoint_native_ok(func, y, method):
 def _adjoint_native(func, params, y, a, span, method, step_size):
   """(a at the earlier time, [gradient contribution per entry of `params`]) of one backward interval, by the native solver."""
   from . import ops
-  from .utils import MaxNFEException
   grid = time_grid(span.detach().to('cpu'), step_size)
   dts = (grid[1:] - grid[:-1]).tolist()
   n_evals = len(dts) * (4 if method == 'rk4' else 1)
-  room = func.opt['max_nfe'] + 1 - func.nfe
-  if n_evals > room:
-    func.nfe += max(room, 0)
-    raise MaxNFEException
-  st = func.__dict__.setdefault('_adjoint_state', {})
+  func._charge_fixed_nfe(n_evals)
   view = func._locality_view(y, forward_solve=False) if hasattr(func, '_locality_view') else None
   key = (method, tuple(dts), tuple(y.shape), str(y.device), id(view))
-  ent = st.get(key)
-  if ent is None:
-    for old in st.values():
-      if old.get('solver') is not None:
-        old['solver'].close()
-    st.clear()
-    n, d = y.shape
-    ent = st[key] = {'y': _lib.alloc_state(n, d, y.device), 'a': _lib.alloc_state(n, d, y.device),
-                     'x0': _lib.alloc_state(n, d, y.device) if func.opt['add_source'] else None,
-                     'solver': None, 'sig': None, 'view': view, 'extra': {}}
+  ent = _entry(func, '_adjoint_state', key, y.shape[0], y.shape[1], y.device, ('y', 'a'), view=view)
   yb, ab = ent['y'], ent['a']
-  if view is None:
-    yb.copy_(y.detach())
-    ab.copy_(a.detach())
-  else:
-    view.enter(y.detach(), out=yb)
-    view.enter(a.detach(), out=ab)
+  _rows_in(view, y.detach(), yb)
+  _rows_in(view, a.detach(), ab)
   if ent['x0'] is not None:
-    if func.x0 is None:
-      raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-    if view is None:
-      ent['x0'].copy_(func.x0.detach())
-    else:
-      view.enter(func.x0.detach(), out=ent['x0'])
+    _copy_source(func, ent['x0'], view)
   graph = func._graph(y) if view is None else view.graph
   desc = func._descriptor(yb, x0_override=ent['x0'], graph=graph)
   gt, t_from_csr = graph.transposed_positions()
@@ -1404,27 +1269,18 @@ def _adjoint_native(func, params, y, a, span, method, step_size):
   if nl:
     proj_wt = _stage_projection_t(func, ex, y.device)
   else:
-    w_csr = func._weights_csr(graph)
     if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
       ex['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=y.device)
-    if graph.e > 0:
-      torch.index_select(w_csr[:graph.e], 0, t_from_csr.long(), out=ex['w_t'][:graph.e])
-    w_t = ex['w_t']
-  sig = (func._descriptor_signature(desc), id(gt))
-  if ent['solver'] is None or ent['sig'] != sig:
-    if ent['solver'] is not None:
-      ent['solver'].close()
-    ent['solver'] = ops.AdjointSolver(desc, gt, t_from_csr if nl else None, proj_wt, w_t, method, dts, y.device)
-    ent['grads'] = torch.zeros(ent['solver'].n_grad, dtype=torch.float32, device=y.device)
-    ent['sig'] = sig
-  sol = ent['solver']
+    w_t = _weights_t(func, graph, out=ex['w_t'])
+
+  def build():
+    sol = ops.AdjointSolver(desc, gt, t_from_csr if nl else None, proj_wt, w_t, method, dts, y.device)
+    ent['grads'] = torch.zeros(sol.n_grad, dtype=torch.float32, device=y.device)
+    return sol
+  sol = _solver_for(ent, (func._descriptor_signature(desc), id(gt)), build)
   sol.run(yb, ab, ent['grads'])
   func.nfe += n_evals
-  a_out = torch.empty_like(a, memory_format=torch.contiguous_format)
-  if view is None:
-    a_out.copy_(ab)
-  else:
-    view.leave(ab, out=a_out)
+  a_out = _rows_out(view, ab, torch.empty_like(a, memory_format=torch.contiguous_format))
   by_param = _grad_vector_by_param(func, ent['grads'], y.shape[1], ex)
   return a_out, [by_param.get(id(p)) for p in params]
 
@@ -1460,7 +1316,7 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
   dev = y.device
   n, d = y.shape
   graph = func._graph(y)
-  gt, t_from_csr = graph.transposed_positions()
+  gt = graph.transposed_positions()[0]
   cache = func.__dict__.setdefault('_adjoint_adaptive', {})
   key = (n, d, str(dev), method)
   if cache.get('key') != key:
@@ -1474,12 +1330,9 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
   A_.copy_(a.detach())
   has_src = bool(func.opt['add_source'])
   if has_src:
-    if func.x0 is None:
-      raise _lib.GnpdeError('add_source is set but x0 was never assigned (call ODEblock.set_x0)')
-    X0.copy_(func.x0.detach())
+    _copy_source(func, X0)
   desc_f = func._descriptor(Y, x0_override=X0 if has_src else None, graph=graph)
-  w_csr = func._weights_csr(graph)
-  w_t = torch.index_select(w_csr[:graph.e], 0, t_from_csr[:graph.e].long()) if graph.e > 0 else w_csr
+  w_t = _weights_t(func, graph)
   alpha_d = ops._scalar_dev(func.alpha_train, Y)
   desc_b = ops.RhsDescriptor(_lib.RHS_LAPLACIAN, gt, d, Y.stride(0), alpha_d, None, None, True, w_csr=w_t, padded_rows=_lib.is_padded(Y))
   one_minus_a = 1 - torch.sigmoid(func.alpha_train.detach().reshape(()))
@@ -1560,16 +1413,13 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
       cache['solver'] = ops.AdjointAdaptiveSolver(desc_f, gt, cache['w_t'], method, rt, at, dev)
       cache['solver_sig'] = sig
     sol = cache['solver']
-    room = func.opt['max_nfe'] + 1 - func.nfe
+    room = func._nfe_room()
     if room <= 0:
       raise MaxNFEException
-    finished = sol.run(Y, A_, g, T0, T1, dt, trials_per_sync=8 if Y.numel() < (1 << 22) else 1, max_evals=room)
+    finished = sol.run(Y, A_, g, T0, T1, dt, trials_per_sync=default_trials_per_sync(Y.numel()), max_evals=room)
     spent = sol.stats()['evals']
     func._adjoint_adaptive_stats = sol.stats()
-    if not finished or spent > room:
-      func.nfe += min(spent, room)
-      raise MaxNFEException
-    func.nfe += spent
+    func._settle_adaptive_nfe(room, finished, spent)
     new = {ia: g[0].reshape(gparams[ia].shape)}
     if ib is not None:
       new[ib] = g[1].reshape(gparams[ib].shape)

@@ -451,6 +451,34 @@ def test_recorded_fixed_grid_falls_back_to_the_host_loop_beyond_its_memory_budge
   assert torch.isfinite(gx).all()
 
 
+def test_cached_tape_of_another_grid_does_not_waive_the_memory_budget(dev, monkeypatch):
+  """The budget check is skipped only for a record that already exists: a cached tape of ANOTHER grid does not let a longer grid through
+  (it would be allocated unchecked), while the grid the tape was made for keeps the recorded path."""
+  kw = dict(kind='laplacian', block_kind='attention', n=64, d=8, heads=2, A=8, method='rk4', time=2.0)
+  block, x = _fixed_block(dev, seed=67, **kw)
+  c = torch.randn(x.shape, generator=torch.Generator().manual_seed(11)).to(dev)
+  t_short, t_long = block.t, torch.tensor([0.0, 4.0]).to(dev)
+  _train_once(block, x, dev, c)                          # 2 steps: recorded, the tape stays cached
+  assert str(block.odefunc._last_train_solve).startswith('native recorded fixed-grid'), block.odefunc._last_train_solve
+  monkeypatch.setattr(O, '_FIXED_TAPE_BUDGET_BYTES', 1)
+  block.t = t_long                                       # 4 steps: no tape of this grid exists, and none fits the budget
+  z1, gx1, g1, nfe1 = _train_once(block, x, dev, c)
+  assert str(block.odefunc._last_train_solve).startswith('differentiable host loop'), block.odefunc._last_train_solve
+  fresh, _ = _fixed_block(dev, seed=67, **kw)
+  fresh.t = t_long
+  z2, gx2, g2, nfe2 = _train_once(fresh, x, dev, c)
+  assert str(fresh.odefunc._last_train_solve).startswith('differentiable host loop'), fresh.odefunc._last_train_solve
+  assert nfe1 == nfe2 == 16, (nfe1, nfe2)
+  assert_parity(z1, z2, 1e-5, 'z')
+  assert_parity(gx1, gx2, 2e-4, 'grad_x')
+  refs = {k: v for k, v in g2.items() if v is not None}
+  assert refs, 'the host loop produced no parameter gradients'
+  _module_scaled(g1, refs, 2e-4, 'host loop beside a cached tape')
+  block.t = t_short                                      # the cached tape's own grid: recorded again, budget or not
+  _train_once(block, x, dev, c)
+  assert str(block.odefunc._last_train_solve).startswith('native recorded fixed-grid'), block.odefunc._last_train_solve
+
+
 @pytest.mark.parametrize('case', ['nl_hubs_rk4', 'nl_d22_euler', 'nl_midpoint', 'l_attention_rk4_hubs', 'gat_rk4_hubs', 'nl_pearson_rk4'])
 def test_cotangent_side_sweep_equals_the_first_form(dev, case):
   """Round 6: the reverse sweep gathers the COTANGENT rows only (row kernel on the transposed graph with the roles exchanged, then one pass
