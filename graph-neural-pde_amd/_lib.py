@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 20     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 21     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
@@ -139,8 +139,13 @@ PROTOTYPES = {
   'gnpde_push_order': (ctypes.c_int, [c_int_p, ctypes.c_int32, c_int_p]),
   'gnpde_xcd_row_map': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_int_p, c_int_p, c_vp]),
   'gnpde_spmm_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(GraphStruct), ctypes.c_int32]),
+  'gnpde_spmm_ticket_bytes': (ctypes.c_size_t, [ctypes.POINTER(GraphStruct)]),
+  'gnpde_in_kernel_fold_launches': (ctypes.c_int64, []),
+  'gnpde_agg_fold_launch': (ctypes.c_int, [ctypes.c_int32]),
   'gnpde_spmm_rhs': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(EpilogueStruct), c_vp, ctypes.c_size_t, c_vp]),
+  'gnpde_spmm_rhs_tickets': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.POINTER(EpilogueStruct), c_vp, ctypes.c_size_t, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_spmm': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, ctypes.c_int32,
                                 c_vp, c_vp, ctypes.c_size_t, c_vp]),
   'gnpde_sddmm': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32,

@@ -119,6 +119,9 @@ enum {
   GNPDE_TUNE_COUNT = 22
 };
 extern int g_tune[GNPDE_TUNE_COUNT];
+// gnpde_agg_fold_launch(1): the hub rows of the row-pair aggregation are folded by spmm_long_reduce4_kernel in a launch of its own where the
+// solver would let the last chunk item of each row fold it inside the aggregation launch (A/B and bit reference of the in-kernel fold)
+extern int g_agg_fold_launch;
 
 // Optional second stream for the hub-row work of a launch sequence.  The long-row passes touch rows
 // disjoint from the main kernels', so they run as a parallel branch: fork_begin makes `aux` wait for
@@ -174,7 +177,9 @@ struct HubDefer {
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes,
                     hipStream_t stream, const Fork* fork = nullptr, bool padded_rows = false, const LoPair* lo = nullptr,
-                    const HubDefer* defer = nullptr);
+                    const HubDefer* defer = nullptr, void* tickets = nullptr, size_t ticket_bytes = 0);
+// tickets (optional, gnpde_spmm_ticket_bytes(g) bytes, all zero when the launch starts and again when it ends): lets the launch fold the hub
+// rows inside the row-pair kernel where launch_spmm_rhs says it may; every other route ignores them and keeps the fold launch
 // true where launch_spmm_rhs (no fork, no bf16 operand) runs kernels whose hub-chunk items can take a HubDefer
 bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int ld, const gnpde_epilogue_t& epi, const void* ws,
                               bool padded_rows);

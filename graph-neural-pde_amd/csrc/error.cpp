@@ -12,7 +12,7 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace gnpde
 
-namespace gnpde { int g_tune[GNPDE_TUNE_COUNT] = {0}; }
+namespace gnpde { int g_tune[GNPDE_TUNE_COUNT] = {0}; int g_agg_fold_launch = 0; }
 
 extern "C" int gnpde_tune(int32_t key, int32_t value) {
   GNPDE_CHECK_ARG(key >= 0 && key < gnpde::GNPDE_TUNE_COUNT, GNPDE_EINVAL, "tune: bad key %d", key);
@@ -22,6 +22,12 @@ extern "C" int gnpde_tune(int32_t key, int32_t value) {
   GNPDE_CHECK_ARG(key != gnpde::GNPDE_TUNE_KNN_VARIANT || value != 1, GNPDE_EINVAL, "tune: value 1 of key %d is retired: the 32-float K "
                   "chunks of the neighbour search were removed, slower at both shapes (profiles/knn_ab.jsonl)", key);
   gnpde::g_tune[key] = value;
+  return 0;
+}
+
+extern "C" int gnpde_agg_fold_launch(int32_t keep) {
+  GNPDE_CHECK_ARG(keep == 0 || keep == 1, GNPDE_EINVAL, "agg_fold_launch: %d is neither 0 nor 1", keep);
+  gnpde::g_agg_fold_launch = keep;
   return 0;
 }
 

@@ -10,8 +10,8 @@ namespace gnpde {
 // descriptors over the same state rows (interior / boundary pass of a partitioned graph) that are handed the same
 // workspace see the SAME q||k buffer; the regions behind it are scratch that each pass overwrites.
 struct RhsLayout {
-  size_t proj, wmean, att, spmm, fused, total;
-  size_t att_bytes, spmm_bytes, fused_bytes;
+  size_t proj, wmean, att, spmm, tickets, fused, total;
+  size_t att_bytes, spmm_bytes, ticket_bytes, fused_bytes;     // tickets: gnpde_spmm_ticket_bytes, the last region
 };
 
 // Recorded solve (gnpde_solver_set_tape) of GRAND-nl: the evaluation writes its q||k projection and its head-mean weights into buffers
@@ -49,7 +49,10 @@ RhsLayout rhs_layout(const gnpde_rhs_t& r);
 int check_rhs(const gnpde_rhs_t* r);
 // Enqueue f(u) with the given epilogue; `ws` follows rhs_layout(r).
 int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& epi, char* ws, const RhsLayout& L,
-                hipStream_t s, const Fork* fork = nullptr, const RhsRecord* record = nullptr, const LoPair* lo = nullptr);
+                hipStream_t s, const Fork* fork = nullptr, const RhsRecord* record = nullptr, const LoPair* lo = nullptr,
+                bool tickets = false);
+// tickets: the caller zeroed the layout's ticket region on this stream (once, ahead of any number of evaluations): the aggregation may
+// fold its hub rows inside its own launch (launch_spmm_rhs).  The fixed-step solver does; every other caller keeps the fold launch.
 // lo (optional bf16 gather operand): the aggregation gathers the neighbour rows from lo->u_lo and writes the shadow of epi.out_y to
 // lo->out_y_lo; projection, attention and the row's own term read the fp32 `u`, and the attention stays in launches of its own.
 // Offered for whole-graph descriptors on 16-byte lanes:

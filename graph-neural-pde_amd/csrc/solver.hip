@@ -55,6 +55,10 @@ RhsLayout rhs_layout(const gnpde_rhs_t& r) {
       off += align_up(L.fused_bytes, 256);
     }
   }
+  // the aggregation's hub-row tickets (they belong to the partials; LAST, so that every other region keeps its offset)
+  L.tickets = off;
+  L.ticket_bytes = gnpde_spmm_ticket_bytes(&g);
+  off += align_up(L.ticket_bytes, 256);
   L.total = off;
   return L;
 }
@@ -80,8 +84,9 @@ static std::atomic<long long> g_one_launch_evals{0};
 
 // Enqueue f(u) with the given epilogue.  `ws` follows rhs_layout.
 int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& epi, char* ws, const RhsLayout& L,
-                hipStream_t s, const Fork* fork, const RhsRecord* record, const LoPair* lo) {
+                hipStream_t s, const Fork* fork, const RhsRecord* record, const LoPair* lo, bool tickets) {
   const gnpde_graph_t* g = r.graph;
+  void* const tk = tickets && L.ticket_bytes > 0 ? ws + L.tickets : nullptr;
   const float* w = r.w_csr;
   if (record != nullptr && rhs_record_stride(r) == 0) record = nullptr;
   if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
@@ -141,14 +146,14 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
       rc = launch_edge_attention_deferred(g, &at, wmean, ws + L.att, L.att_bytes, s, &defer);
       if (rc) return rc;
       if (defer.taken) g_one_launch_evals.fetch_add(1, std::memory_order_relaxed);
-      return launch_spmm_rhs(g, wmean, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, nullptr, padded, nullptr, &defer);
+      return launch_spmm_rhs(g, wmean, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, nullptr, padded, nullptr, &defer, tk, L.ticket_bytes);
     }
     rc = launch_edge_attention(g, &at, wmean, nullptr, nullptr, ws + L.att, L.att_bytes, s, fork);
     if (rc) return rc;
     w = wmean;
   }
   return launch_spmm_rhs(g, w, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, fork,
-                         (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0, lo);
+                         (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0, lo, nullptr, tk, L.ticket_bytes);
 }
 
 bool rhs_gather_lo_supported(const gnpde_rhs_t& r) {
@@ -245,6 +250,9 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
                                    s->early_trace, s->early_trace_capacity, st);
   };
   if (s->early) GNPDE_HIP(hipMemsetAsync(s->early_state, 0, 8 * sizeof(int32_t), st));
+  // hub-row tickets of the aggregation launches: zero at the head of the solve (a memset node of a captured one); every launch that uses
+  // them leaves them zero
+  if (s->L.ticket_bytes > 0) GNPDE_HIP(hipMemsetAsync(rws + s->L.tickets, 0, s->L.ticket_bytes, st));
   // bf16 gather operand: shadow b belongs to one stage-input buffer; the kernel that writes a stage input writes its shadow, so
   // only y0's is filled by a pass of its own.  pair(from, to): gather from shadow `from`, write the shadow of out_y to `to`.
   const bool lo_on = s->lo != nullptr;
@@ -273,16 +281,16 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       gnpde_epilogue_t e = base;
       e.dt = dt; e.y = y;
       e.stage = GNPDE_STAGE_RK1; e.out_k = k1; e.out_y = ua;
-      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1));
+      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1), true);
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK2; e.k1 = k1; e.out_k = k2; e.out_y = ub;
-      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2));
+      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2), true);
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK3; e.k2 = k2; e.out_k = k3; e.out_y = ua;
-      rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 1));
+      rc = enqueue_rhs(r, ub, e, rws, s->L, st, fk, nullptr, pair(2, 1), true);
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK4; e.k3 = k3; e.out_k = nullptr; e.out_y = y;
-      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0));
+      rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0), true);
       if (rc) return rc;
       rc = evaluate(y);
       if (rc) return rc;
@@ -318,7 +326,7 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       u[i] = s->tape != nullptr ? slot(at + i) : bufs[idx[i]];
     }
     int rc = enqueue_step(base, s->method, dt, u, [&](int j, const float* in, const gnpde_epilogue_t& e) {
-      return enqueue_rhs(r, in, e, rws, s->L, st, fk, rec(at + j), pair(idx[j], idx[j + 1]));
+      return enqueue_rhs(r, in, e, rws, s->L, st, fk, rec(at + j), pair(idx[j], idx[j + 1]), true);
     });
     if (rc) return rc;
     at += S;

@@ -11,6 +11,7 @@
 // are in flight per lane.  The G partial sums are combined with an xor butterfly (deterministic, no
 // atomics).  Rows longer than GNPDE_LONG_ROW are processed as independent chunks into a partial
 // buffer and summed by a second small kernel, so a 13k-degree hub does not serialise on one wave.
+#include <atomic>
 #include "common.h"
 #include "epilogue.h"
 
@@ -46,6 +47,11 @@ struct SpmmArgs {
   const int* __restrict__ hub_chunk_first;
   float* w_out;
   int hub_h;
+  // in-kernel fold of the hub rows (row-pair kernel, epilogue launches; fold_ticket below): one arrival counter per long row, in
+  // long_rows order, and the chunk list the counter's index is found in.  null: spmm_long_reduce4_kernel folds in a launch of its own.
+  unsigned* tickets;
+  const int* __restrict__ long_chunk_ptr;
+  int n_long_rows;
 };
 
 
@@ -329,18 +335,84 @@ __device__ __forceinline__ void epilogue_pre(const gnpde_epilogue_t& ep, float a
 // The long-row fold on 16-byte lanes: one wavefront per long row, the epilogue operands requested before the chunk loop and the
 // chunk partials fetched eight at a time (the scalar kernel above walks a chain of dependent-latency loads: 8.4 us for the 204
 // hub rows of the ogbn-arxiv shape, 99 us for the 27 896 of the R-MAT shape).  Same summation: the chunks of a row in chunk order.
-template <bool LO>
-__global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs a, const int* __restrict__ long_rows,
-                                                                 const int* __restrict__ long_chunk_ptr) {
+//
+// One body (fold_long_row) for the fold launch and for the last-arriving chunk item of the row-pair kernel (fold_ticket): the same loads in
+// the same order, the same float sequence (fold_stage), the same bits.  HANDOFF: the partials were published by other waves of the SAME
+// launch -- they are read past this CU's L1 (agent-scope relaxed 8-byte loads: global_load_dwordx2 sc1), never by a plain load.
+template <bool HANDOFF>
+__device__ __forceinline__ void load_partial4(const float* p, float (&v)[4]) {
+  if constexpr (HANDOFF) {
+    const unsigned long long* q = reinterpret_cast<const unsigned long long*>(p);
+    const unsigned long long lo = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long hi = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v[0] = __uint_as_float(static_cast<unsigned>(lo));
+    v[1] = __uint_as_float(static_cast<unsigned>(lo >> 32));
+    v[2] = __uint_as_float(static_cast<unsigned>(hi));
+    v[3] = __uint_as_float(static_cast<unsigned>(hi >> 32));
+  } else {
+    load_vec<4>(p, v);
+  }
+}
+
+// The prefetchable stages on a folded hub row with every rounding written out.  epilogue_pre leaves the contraction of a x + b y to the
+// compiler, whose choice depends on the code around it -- the same source inlined in the fold launch and in the row-pair kernel gave sums
+// one ulp apart -- and what it chose for the fold launch was not even uniform across the four floats of a lane.  A body that is inlined
+// in two places must not depend on where it is inlined, and the stored results hold the fold launch's sequence, so that sequence is
+// stated here float by float (v = position in the lane's 16 bytes).  Compared once with the launch as it was before this body existed,
+// bit for bit on every hub row: RHS, EULER and RK1C..RK4C, each with and without x0, at d = 128 and d = 96, on the whole-graph route and
+// behind the wide-row kernel (d = 256); the stages outside this list (classic rk4) still take epilogue<> and were compared the same way:
+//   k      = fma(beta, x0, rn(alpha (ax - u)))                        (no x0: the rounded product)
+//   EULER  = fma(dt, k, y)            RK1C = fma(rn(dt k), 1/3, u)
+//   RK2C   = (2 y - u) + dt k         fused but for v = 0: rn(2 y - u) + rn(dt k)
+//   RK3C   = (2 k1 - u) + dt k        fused for v = 1, 2; v = 0, 3: rn(2 k1 - u) + rn(dt k)
+//   RK4C   = (fma(dt, k, t - y)) / 8  t = rn(3 u) + rn(6 k1) for v = 0, 3; fma(3, u, rn(6 k1)) for v = 1; fma(6, k1, rn(3 u)) for v = 2
+__device__ __forceinline__ void fold_stage(const gnpde_epilogue_t& ep, float alpha, float beta, size_t off, const float (&ax)[4],
+                                           const Pre<4, false>& p) {
+  const float dt = ep.dt;
+  float o[4];
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    float k = __fmul_rn(alpha, __fsub_rn(ax[v], p.ui[v]));
+    if (ep.x0 != nullptr) k = fmaf(beta, p.x0[v], k);
+    float t;
+    switch (ep.stage) {
+      case GNPDE_STAGE_EULER:
+        o[v] = fmaf(dt, k, p.y[v]);
+        break;
+      case GNPDE_STAGE_RK1C:
+        o[v] = fmaf(__fmul_rn(dt, k), 1.0f / 3.0f, p.ui[v]);
+        break;
+      case GNPDE_STAGE_RK2C:
+        t = __fsub_rn(__fmul_rn(2.0f, p.y[v]), p.ui[v]);
+        o[v] = v == 0 ? __fadd_rn(t, __fmul_rn(dt, k)) : fmaf(dt, k, t);
+        break;
+      case GNPDE_STAGE_RK3C:
+        t = __fsub_rn(__fmul_rn(2.0f, p.k1[v]), p.ui[v]);
+        o[v] = (v == 0 || v == 3) ? __fadd_rn(t, __fmul_rn(dt, k)) : fmaf(dt, k, t);
+        break;
+      case GNPDE_STAGE_RK4C:
+        if (v == 1) t = fmaf(3.0f, p.ui[v], __fmul_rn(6.0f, p.k1[v]));
+        else if (v == 2) t = fmaf(6.0f, p.k1[v], __fmul_rn(3.0f, p.ui[v]));
+        else t = __fadd_rn(__fmul_rn(3.0f, p.ui[v]), __fmul_rn(6.0f, p.k1[v]));
+        o[v] = __fmul_rn(fmaf(dt, k, __fsub_rn(t, p.y[v])), 0.125f);
+        break;
+      default:      // GNPDE_STAGE_RHS
+        o[v] = k;
+        break;
+    }
+  }
+  store_vec<4>((ep.stage == GNPDE_STAGE_RHS ? ep.out_k : ep.out_y) + off, o);
+}
+
+// fp32 table.  HANDOFF (the row-pair kernel's last arriver): prefetchable stages only -- launch_spmm_rhs keeps the fold launch otherwise
+template <bool HANDOFF>
+__device__ __forceinline__ void fold_long_row(const SpmmArgs& a, int row, int c0, int c1, int lane) {
   constexpr int VEC = 4;
-  const int lr = blockIdx.x;
-  const int row = long_rows[lr];
-  const int c0 = long_chunk_ptr[lr], c1 = long_chunk_ptr[lr + 1];
   const bool plain = a.plain_out != nullptr;
   const float alpha = plain ? 0.0f : alpha_of(a.ep);
   const float beta = (!plain && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
   const bool pre_ok = !plain && stage_prefetchable<VEC, false>(a.ep.stage);
-  for (int col = static_cast<int>(threadIdx.x) * VEC; col < a.d; col += kWave * VEC) {
+  for (int col = lane * VEC; col < a.d; col += kWave * VEC) {
     const size_t off = static_cast<size_t>(row) * a.ld + col;
     Pre<VEC, false> pre;
     if (pre_ok) {
@@ -356,7 +428,7 @@ __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs
     for (; c + 8 <= c1; c += 8, p += 8 * static_cast<size_t>(a.ldp)) {
       float v[8][VEC];
 #pragma unroll
-      for (int t = 0; t < 8; ++t) load_vec<VEC>(p + t * static_cast<size_t>(a.ldp), v[t]);
+      for (int t = 0; t < 8; ++t) load_partial4<HANDOFF>(p + t * static_cast<size_t>(a.ldp), v[t]);
 #pragma unroll
       for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -364,20 +436,125 @@ __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs
     }
     for (; c < c1; ++c, p += a.ldp) {
       float v[VEC];
-      load_vec<VEC>(p, v);
+      load_partial4<HANDOFF>(p, v);
 #pragma unroll
       for (int q = 0; q < VEC; ++q) acc[q] += v[q];
     }
-    if (plain) {
-      store_vec<VEC>(a.plain_out + off, acc);
-    } else if (pre_ok) {
-      epilogue_pre<VEC, false, LO>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
-    } else {
-      float ui[VEC];
-      load_vec<VEC>(a.u + off, ui);
-      epilogue<VEC, false, LO>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
+    if (pre_ok) {
+      fold_stage(a.ep, alpha, beta, off, acc, pre);
+      continue;
+    }
+    if constexpr (!HANDOFF) {
+      if (plain) {
+        store_vec<VEC>(a.plain_out + off, acc);
+      } else {
+        float ui[VEC];
+        load_vec<VEC>(a.u + off, ui);
+        epilogue<VEC, false, false>(a.ep, alpha, beta, off, acc, ui, nullptr);
+      }
     }
   }
+}
+
+// fp32 table: fold_long_row.  bf16 gather operand (never folded inside the aggregation launch): the fold as this launch always had it, in
+// its own text, so that its compiled float sequence stays what it was.
+template <bool LO>
+__global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs a, const int* __restrict__ long_rows,
+                                                                 const int* __restrict__ long_chunk_ptr) {
+  constexpr int VEC = 4;
+  const int lr = blockIdx.x;
+  const int row = long_rows[lr];
+  const int c0 = long_chunk_ptr[lr], c1 = long_chunk_ptr[lr + 1];
+  if constexpr (!LO) {
+    fold_long_row<false>(a, row, c0, c1, static_cast<int>(threadIdx.x));
+  } else {
+    const bool plain = a.plain_out != nullptr;
+    const float alpha = plain ? 0.0f : alpha_of(a.ep);
+    const float beta = (!plain && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
+    const bool pre_ok = !plain && stage_prefetchable<VEC, false>(a.ep.stage);
+    for (int col = static_cast<int>(threadIdx.x) * VEC; col < a.d; col += kWave * VEC) {
+      const size_t off = static_cast<size_t>(row) * a.ld + col;
+      Pre<VEC, false> pre;
+      if (pre_ok) {
+        load_vec<VEC>(a.u + off, pre.ui);
+        if (a.ep.x0 != nullptr) load_vec<VEC>(a.ep.x0 + off, pre.x0);
+        const int st = a.ep.stage;
+        if (st == GNPDE_STAGE_EULER || st == GNPDE_STAGE_RK2C || st == GNPDE_STAGE_RK4C) load_vec<VEC>(a.ep.y + off, pre.y);
+        if (st == GNPDE_STAGE_RK3C || st == GNPDE_STAGE_RK4C) load_vec<VEC>(a.ep.k1 + off, pre.k1);
+      }
+      float acc[VEC] = {0.0f, 0.0f, 0.0f, 0.0f};
+      const float* p = a.partial + static_cast<size_t>(c0) * a.ldp + col;
+      int c = c0;
+      for (; c + 8 <= c1; c += 8, p += 8 * static_cast<size_t>(a.ldp)) {
+        float v[8][VEC];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) load_vec<VEC>(p + t * static_cast<size_t>(a.ldp), v[t]);
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+#pragma unroll
+          for (int q = 0; q < VEC; ++q) acc[q] += v[t][q];
+      }
+      for (; c < c1; ++c, p += a.ldp) {
+        float v[VEC];
+        load_vec<VEC>(p, v);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) acc[q] += v[q];
+      }
+      if (plain) {
+        store_vec<VEC>(a.plain_out + off, acc);
+      } else if (pre_ok) {
+        epilogue_pre<VEC, false, true>(a.ep, alpha, beta, off, acc, pre, a.out_y_lo);
+      } else {
+        float ui[VEC];
+        load_vec<VEC>(a.u + off, ui);
+        epilogue<VEC, false, true>(a.ep, alpha, beta, off, acc, ui, a.out_y_lo);
+      }
+    }
+  }
+}
+
+// The fold without a launch of its own (row-pair kernel, epilogue launches with SpmmArgs::tickets).  A hub-chunk item publishes its partial
+// so that it leaves the XCD (agent-scope relaxed 8-byte stores: write-through, sc1), drains its stores, and adds one to the ticket of its
+// row: one unsharded counter per row, so the wave whose add returns n_chunks - 1 knows that every other chunk of the row was published
+// before its own add was -- it is the row's consumer and folds.  Every other wave ends: nothing polls, spins or waits for another wave.
+// The consumer loads the partials only after its add has returned, behind an agent-scope acquire (twelve one-wave workgroups share a CU
+// here, so its L1 is not known to be free of these lines), with loads that pass L1 (load_partial4<true>); it puts its ticket back to 0,
+// so the next launch -- a replay of a captured solve, or the next evaluation -- needs no memset in between.  No release fence anywhere:
+// a fence per chunk wave writes back the XCD's dirty L2 lines (the gathered state's epilogue outputs) and cost 1.7x on the whole launch.
+// Index of the row in long_rows order: the chunk lists are in that order, so it is the position of the row's first chunk c0 in
+// long_chunk_ptr -- halved by scalar loads until 64 candidates are left, which one load per lane and a ballot settle.
+__device__ __forceinline__ int long_row_index(const SpmmArgs& a, int c0, int lane) {
+  int lo = 0, hi = a.n_long_rows;     // long_chunk_ptr[lo] <= c0 < long_chunk_ptr[hi]
+  while (hi - lo > kWave) {
+    const int mid = (lo + hi) >> 1;
+    if (__builtin_amdgcn_readfirstlane(a.long_chunk_ptr[mid]) <= c0) lo = mid; else hi = mid;
+  }
+  const int i = lo + lane;
+  const bool le = i < hi && a.long_chunk_ptr[i] <= c0;
+  return lo + static_cast<int>(__popcll(__ballot(le))) - 1;
+}
+
+// returns true for the wave that goes on to fold the row [c0, c0 + nch)
+__device__ __forceinline__ bool fold_ticket(const SpmmArgs& a, int c0, int nch, int lane) {
+  const int lr = long_row_index(a, c0, lane);
+  // the stores of every lane of this wave have left for memory before the one add that signals for them (written as inline assembly:
+  // a wait the compiler can prove redundant from its own scoreboard is dropped)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  unsigned old = 0;
+  if (lane == 0) old = __hip_atomic_fetch_add(a.tickets + lr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  old = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(old)));
+  if (old != static_cast<unsigned>(nch - 1)) return false;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  if (lane == 0) __hip_atomic_store(a.tickets + lr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return true;
+}
+
+__device__ __forceinline__ void store_partial4(float* p, const float (&v)[4]) {
+  unsigned long long* q = reinterpret_cast<unsigned long long*>(p);
+  __hip_atomic_store(q, static_cast<unsigned long long>(__float_as_uint(v[0])) | (static_cast<unsigned long long>(__float_as_uint(v[1])) << 32),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(q + 1, static_cast<unsigned long long>(__float_as_uint(v[2])) | (static_cast<unsigned long long>(__float_as_uint(v[3])) << 32),
+                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // DEFER: the weights of a hub chunk's entries from the stored scores and the chunk statistics of the chunk's row -- the float sequence of
@@ -628,6 +805,16 @@ __device__ __forceinline__ void shared_row_item(const SpmmArgs& a, int row, int 
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) acc[v] += __shfl_xor(acc[v], L, kWave);
+  if constexpr (VEC == 4 && !LO) {
+    if (chunk >= 0 && a.tickets != nullptr) {   // (wave-uniform) the last chunk item of a row to arrive folds the row: fold_ticket
+      if (sub == 0 && col_ok) store_partial4(a.partial + static_cast<size_t>(chunk) * a.ldp + col, acc);
+      const int rs = __builtin_amdgcn_readfirstlane(a.rowptr[row]), re = __builtin_amdgcn_readfirstlane(a.rowptr[row + 1]);
+      const int nch = (re - rs + GNPDE_LONG_ROW - 1) / GNPDE_LONG_ROW;
+      const int c0 = chunk - (e0 - rs) / GNPDE_LONG_ROW;
+      if (fold_ticket(a, c0, nch, lane)) fold_long_row<true>(a, row, c0, c0 + nch, lane);
+      return;
+    }
+  }
   if (sub != 0 || !col_ok) return;
   if (chunk >= 0) {
     store_vec<VEC>(a.partial + static_cast<size_t>(chunk) * a.ldp + col, acc);
@@ -1016,11 +1203,25 @@ void launch_rows(const SpmmArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((spmm_rows_kernel<VEC, L, K, U>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
 }
 
+// THE route test of the row-pair kernel, given 16-byte lanes of the fp32 table (dispatch_rows<4>): rows of 17..32 lanes in a graph of mostly
+// short rows.  The dispatch below, the deferred hub weights and the in-kernel hub fold all ask here -- the last two hand the launch work
+// that only spmm_pair_kernel does (hub weights, the fold), so a second copy of the condition that drifted would leave it undone silently.
+inline bool mostly_short_rows(const gnpde_graph_t* g) { return 2LL * g->n_bin16 >= g->n; }
+inline bool pair_kernel_route(int d, bool short_rows) {
+  const int slots = (d + 3) / 4;
+  return slots > 16 && slots <= 32 && short_rows;
+}
+
 // One line per width class (slots = lanes of VEC floats that cover a row); what every class takes was measured, the alternatives that
 // lost are recorded in DESIGN.md section 3 and profiles/.
 template <int VEC>
 int dispatch_rows(const SpmmArgs& a, hipStream_t s) {
   const int slots = (a.d + VEC - 1) / VEC;
+  const bool pair = VEC == 4 && pair_kernel_route(a.d, a.short_rows != 0);
+  if ((a.tickets != nullptr || hub_deferred(a)) && !pair) {     // (work of the row-pair kernel alone: never reached while the callers ask the same test)
+    set_error("spmm: hub-row tickets / deferred hub weights handed to a kernel other than the row-pair kernel (d=%d)", a.d);
+    return GNPDE_EINVAL;
+  }
   if (slots <= 8) launch_rows<VEC, 8, 1, 4>(a, s);
   else if (slots <= 16) launch_rows<VEC, 16, 1, 4>(a, s);
   else if (slots <= 64) {
@@ -1031,7 +1232,7 @@ int dispatch_rows(const SpmmArgs& a, hipStream_t s) {
       // Rows of 17..32 lanes (d = 68..128) in graphs whose rows are mostly short (the ogbn-arxiv shape: median 8 entries): two rows
       // per wave, 16 gathers in flight per half (spmm_pair_kernel; bit-identical results): 171 vs 184 us at the ogbn-arxiv shape,
       // 193 vs 230 us on a uniform degree-8 graph, but 2 % slower at degree 24 -- hence the hint (profiles/r02_ab_row_pairs.txt)
-      if (slots <= 32 && a.short_rows) launch_pair(a, s);
+      if (pair) launch_pair(a, s);
       else if (slots <= 32) launch_wide<32>(a, s);
       else launch_wide<64>(a, s);
     } else {
@@ -1643,15 +1844,20 @@ int launch_adjoint_rows(const gnpde_graph_t* g, const float* w_csr, const float*
   return 0;
 }
 
+// aggregation launches whose hub rows were folded inside the row-pair kernel (gnpde_in_kernel_fold_launches)
+static std::atomic<long long> g_in_kernel_folds{0};
+
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes, hipStream_t stream,
-                    const Fork* fork, bool padded_rows, const LoPair* lo, const HubDefer* defer) {
+                    const Fork* fork, bool padded_rows, const LoPair* lo, const HubDefer* defer, void* tickets, size_t ticket_bytes) {
   if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
   if (defer != nullptr && (defer->taken == 0 || g == nullptr || g->n_long_rows == 0)) defer = nullptr;
   // (a plain aggregation from a shadow has no fp32 table at all)
   GNPDE_CHECK_ARG(g && (u || (lo && plain_out)) && (w_csr || g->e == 0), GNPDE_EINVAL, "spmm: null pointer");
   GNPDE_CHECK_ARG(d >= 1 && ld >= d, GNPDE_EINVAL, "spmm: bad d=%d ld=%d", d, ld);
   GNPDE_CHECK_ARG((epi != nullptr) != (plain_out != nullptr), GNPDE_EINVAL, "spmm: need exactly one of epilogue / plain output");
+  GNPDE_CHECK_ARG(tickets == nullptr || (ticket_bytes >= gnpde_spmm_ticket_bytes(g) && aligned(tickets, 4)), GNPDE_EWS,
+                  "spmm: tickets %zu < %zu bytes (one 32-bit word per long row)", ticket_bytes, gnpde_spmm_ticket_bytes(g));
   if (g->n == 0) return 0;
   SpmmArgs a{};
   a.n = g->n;
@@ -1733,8 +1939,7 @@ int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, 
   const bool forked = fork != nullptr && fork->aux != nullptr && g->n_long_rows > 0;
   if (defer != nullptr) {
     // the hub entries' weights do not exist yet: only the kernels whose chunk items form them may run (spmm_hub_defer_supported)
-    const int slots = (d + 3) / 4;
-    GNPDE_CHECK_ARG(a16 && lo == nullptr && !forked && slots > 16 && slots <= 32 && 2LL * g->n_bin16 >= g->n && g->row_begin == 0 &&
+    GNPDE_CHECK_ARG(a16 && lo == nullptr && !forked && pair_kernel_route(d, mostly_short_rows(g)) && g->row_begin == 0 &&
                     g_tune[GNPDE_TUNE_SPMM_PART] == 0 &&
                     defer->part && defer->scores && defer->chunk_first && defer->w_out == w_csr && defer->h >= 1 && defer->h <= 8 &&
                     aligned(defer->scores, 16),
@@ -1745,23 +1950,39 @@ int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, 
     a.w_out = defer->w_out;
     a.hub_h = defer->h;
   }
-  // rows and long-row chunks in one launch, then the per-row reduction of the chunk partials (a last-arriver
-  // reduction inside the kernel was measured 1.7x slower: every agent-scope release fence writes back the
-  // XCD's dirty L2 lines); with a fork the chunks + reduction run as a parallel branch.  The boundary pass of a
-  // partitioned graph covers rows [row_begin, n) only (its chunks belong to those rows).
+  // rows and long-row chunks in one launch, then the per-row reduction of the chunk partials; with a fork the chunks + reduction
+  // run as a parallel branch.  The boundary pass of a partitioned graph covers rows [row_begin, n) only (its chunks belong to those rows).
+  // Where the row-pair kernel runs an epilogue launch over the whole graph on one stream from the fp32 table and the caller gave
+  // tickets, the last chunk item of a hub row to arrive folds the row inside that launch (fold_ticket: write-through partials, a
+  // drained store queue and one counter add per chunk wave; a first form with an agent-scope release fence in every chunk wave was
+  // measured 1.7x slower on the whole launch, every fence writing back the XCD's dirty L2 lines) and the reduction launch is not
+  // enqueued.  gnpde_agg_fold_launch(1) keeps the launch (A/B and bit reference), as does every other route.
   GNPDE_CHECK_ARG(g->row_begin >= 0 && g->row_begin <= g->n, GNPDE_EINVAL, "spmm: bad row_begin %d", g->row_begin);
   GNPDE_CHECK_ARG(!(forked && g->row_begin > 0), GNPDE_EINVAL, "spmm: fork with row_begin");
   a.chunk_begin = 0;
   a.chunk_end = forked ? 0 : g->n_long_chunks;
-  a.short_rows = 2LL * g->n_bin16 >= g->n ? 1 : 0;
+  a.short_rows = mostly_short_rows(g) ? 1 : 0;
   a.row_begin = g->row_begin;
   a.row_end = g->n;
   a.row_shift = choose_row_shift(static_cast<long long>(a.row_end) - a.row_begin, g->xcd_deal);
   if (g_tune[GNPDE_TUNE_SPMM_PART] == 1) a.row_end = a.row_begin;       // (timing the two kinds of work items separately)
   if (g_tune[GNPDE_TUNE_SPMM_PART] == 2) a.chunk_end = 0;
+  const bool fold_in_kernel = tickets != nullptr && epi != nullptr && g->n_long_rows > 0 && !forked && lo == nullptr && g->row_begin == 0 &&
+                              a16 && pair_kernel_route(d, a.short_rows != 0) &&
+                              (epi->stage == GNPDE_STAGE_RHS || epi->stage == GNPDE_STAGE_EULER || (epi->stage >= GNPDE_STAGE_RK1C && epi->stage <= GNPDE_STAGE_RK4C)) &&   // (the stages fold_stage states)
+                              g_tune[GNPDE_TUNE_SPMM_PART] == 0 && g_agg_fold_launch == 0;
+  if (fold_in_kernel) {
+    a.tickets = static_cast<unsigned*>(tickets);
+    a.long_chunk_ptr = g->long_chunk_ptr;
+    a.n_long_rows = g->n_long_rows;
+  }
   int rc = run(a, stream);
   if (rc != 0) return rc;
   GNPDE_LAUNCH_CHECK();
+  if (fold_in_kernel) {
+    g_in_kernel_folds.fetch_add(1, std::memory_order_relaxed);
+    return 0;
+  }
   if (g->n_long_rows > 0) {
     hipStream_t br = stream;
     if (forked) { const int frc = fork_begin(fork, stream, &br); if (frc) return frc; }
@@ -1793,8 +2014,7 @@ bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int
   // the row-pair kernel (dispatch_rows<4>: 17..32 lanes of 16 bytes, at least half of the rows with <= 16 entries).  The wide-row kernel is
   // left as it is: with the deferred path its instantiations need 92 - 101 VGPRs instead of 80 - 86 (a wave per SIMD less for EVERY row of
   // the launch) and spill SGPRs, for the sake of the hub chunks alone.
-  const int slots = (d + 3) / 4;
-  if (g == nullptr || u == nullptr || slots <= 16 || slots > 32 || 2LL * g->n_bin16 < g->n || g->row_begin != 0 ||
+  if (g == nullptr || u == nullptr || !pair_kernel_route(d, mostly_short_rows(g)) || g->row_begin != 0 ||
       g_tune[GNPDE_TUNE_SPMM_PART] != 0)
     return false;
   bool a16 = (d % 4 == 0 || padded_rows) && (ld % 4 == 0) && aligned(u, 16) && aligned(ws, 16);
@@ -1889,6 +2109,22 @@ extern "C" int gnpde_xcd_row_map(int32_t row_begin, int32_t row_end, int32_t dea
 extern "C" size_t gnpde_spmm_workspace_bytes(const gnpde_graph_t* g, int32_t d) {
   if (!g || d < 1) return 0;
   return static_cast<size_t>(g->n_long_chunks) * gnpde::align_up(static_cast<size_t>(d), 4) * sizeof(float);
+}
+
+extern "C" size_t gnpde_spmm_ticket_bytes(const gnpde_graph_t* g) {
+  if (!g || g->n_long_rows < 0) return 0;
+  return static_cast<size_t>(g->n_long_rows) * sizeof(uint32_t);
+}
+
+extern "C" int64_t gnpde_in_kernel_fold_launches(void) { return gnpde::g_in_kernel_folds.load(std::memory_order_relaxed); }
+
+extern "C" int gnpde_spmm_rhs_tickets(const gnpde_graph_t* g, const float* w_csr, const float* u, int32_t d, int32_t ld,
+                                      const gnpde_epilogue_t* epi, void* workspace, size_t workspace_bytes, void* tickets,
+                                      size_t ticket_bytes, void* stream) {
+  GNPDE_CHECK_ARG(epi != nullptr, GNPDE_EINVAL, "spmm_rhs: epilogue is null");
+  GNPDE_CHECK_ARG(tickets != nullptr || ticket_bytes == 0, GNPDE_EINVAL, "spmm_rhs: ticket bytes without tickets");
+  return gnpde::launch_spmm_rhs(g, w_csr, u, d, ld, epi, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
+                                nullptr, false, nullptr, nullptr, tickets, ticket_bytes);
 }
 
 extern "C" int gnpde_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int32_t d, int32_t ld,

@@ -214,8 +214,10 @@ def spmm_lo(graph, w_csr, u_lo, out=None):
   return out
 
 
-def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out=None, gather_lo=None, **stage_kw):
+def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out=None, gather_lo=None, tickets=None, **stage_kw):
   """f = alpha' (A u - u) + beta x0 with A given by (graph, w_csr); optional fused solver stage.
+  tickets (optional): a zeroed device buffer of gnpde_spmm_ticket_bytes(graph) bytes; where the row-pair kernel runs, the launch then
+  folds its hub rows itself instead of enqueuing the fold launch (gnpde_spmm_rhs_tickets) and leaves the buffer zero again.
   gather_lo = (u_lo, out_y_lo): the neighbour rows are gathered from the bf16 shadow u_lo of u (ops.to_bf16) instead of u, and the
   bf16 rounding of the stage's out_y is written to out_y_lo (None: not written) by the same launch (gnpde_spmm_rhs_lo)."""
   require_hip(u, w_csr, x0)
@@ -242,6 +244,11 @@ def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out
       _check_shadow(out_y_lo, u, 'gather_lo[1]')
     check(L.gnpde_spmm_rhs_lo(graph.ref(), ptr(w_csr), ptr(u), ptr(u_lo), d, u.stride(0), ctypes.byref(epi), ptr(out_y_lo), ptr(ws),
                               ws.numel(), stream_of(u)))
+    return out
+  if tickets is not None:
+    require_hip(tickets)
+    check(L.gnpde_spmm_rhs_tickets(graph.ref(), ptr(w_csr), ptr(u), d, u.stride(0), ctypes.byref(epi), ptr(ws), ws.numel(), ptr(tickets),
+                                   tickets.numel() * tickets.element_size(), stream_of(u)))
     return out
   check(L.gnpde_spmm_rhs(graph.ref(), ptr(w_csr), ptr(u), d, u.stride(0), ctypes.byref(epi), ptr(ws), ws.numel(),
                          stream_of(u)))
@@ -1591,6 +1598,12 @@ def attn_rhs_fused(graph, att, proj_w, proj_b, u, alpha, beta=None, x0=None, alp
 def tune(key, value):
   """Kernel-variant knob for A/B measurements (gnpde_tune)."""
   check(_lib.lib().gnpde_tune(int(key), int(value)))
+
+
+def agg_fold_launch(keep):
+  """1: the row-pair aggregation keeps the fold launch for its hub rows where it would fold them inside its own launch (A/B and bit
+  reference, gnpde_agg_fold_launch); 0: the default."""
+  check(_lib.lib().gnpde_agg_fold_launch(int(keep)))
 
 
 class RhsDescriptor(object):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 20  /* 20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 21  /* 21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -236,6 +236,21 @@ int gnpde_xcd_row_map(int32_t row_begin, int32_t row_end, int32_t deal, int32_t*
 
 /* Bytes of scratch gnpde_spmm_rhs needs for the long-row partial sums (0 if no long rows). */
 size_t gnpde_spmm_workspace_bytes(const gnpde_graph_t* g, int32_t d);
+
+/* Hub-row tickets of an aggregation launch that folds its long rows itself: one 32-bit arrival counter per long row, in long_rows
+ * order (0 bytes without long rows).  The caller zeroes them once; a launch that uses them leaves them zero again.  Where the
+ * row-pair kernel runs (16-byte lanes, d = 68..128, a graph of mostly short rows) with an epilogue over the whole graph from the fp32
+ * table, the chunk items of a hub row publish their partial sums, count themselves on the row's ticket, and the item that arrives last
+ * folds the row in chunk order -- the float sequence of the fold launch, so the same bits -- and that launch is not enqueued;
+ * gnpde_agg_fold_launch(1) keeps it (0, the default: fold in the kernel; a process-wide switch for A/B runs and bit references, as gnpde_tune).  Every other route ignores the tickets.  gnpde_in_kernel_fold_launches: aggregation launches enqueued
+ * so far in this process that took the in-kernel form (a captured solve counts once per enqueued launch, not per replay). */
+size_t  gnpde_spmm_ticket_bytes(const gnpde_graph_t* g);
+int64_t gnpde_in_kernel_fold_launches(void);
+int     gnpde_agg_fold_launch(int32_t keep);
+/* gnpde_spmm_rhs with tickets (NULL: exactly gnpde_spmm_rhs); GNPDE_EWS when ticket_bytes < gnpde_spmm_ticket_bytes(g). */
+int gnpde_spmm_rhs_tickets(const gnpde_graph_t* g, const float* w_csr, const float* u, int32_t d, int32_t ld,
+                           const gnpde_epilogue_t* epi, void* workspace, size_t workspace_bytes, void* tickets, size_t ticket_bytes,
+                           void* stream);
 
 /* K7+K8 of SURVEY.md: ax[i] = sum_{e in row i} w[e] * u[col_e]  (torch_sparse.spmm, src/
  * function_laplacian_diffusion.py:31-35, function_transformer_attention.py:35) followed by the
