@@ -9,10 +9,12 @@ with the best validation accuracy.
 What is different underneath: the reference leaves the solver after each step for relu -> linear -> argmax ->
 three masked accuracies with `.item()` (early_stop_solver.py:178-218).  Here the evaluation is two kernels
 appended to the step inside the solver's hipGraph (csrc/early_stop.hip) and the four numbers are read back
-once, after the solve.  dopri5 keeps its host step-size controller (one scalar read per trial step) and runs the
-same device evaluator after each accepted step; a rejected trial leaves the state -- hence the accuracies and,
-with the strict comparison, the best -- unchanged, but still counts towards `max_test_steps` (trials rejected
-before the first accept evaluate the initial state once, at t0, as the reference does).
+once, after the solve.  dopri5 runs its step-size controller on the device by default, with the evaluator inside the
+trial-step graph (odeint._solve_dopri5_device); options `eager_stages` / `host_controller` keep the controller on the
+host (one scalar read per trial step) and run the same device evaluator after each accepted step.  Either way a
+rejected trial leaves the state -- hence the accuracies and, with the strict comparison, the best -- unchanged, but
+still counts towards `max_test_steps` (trials rejected before the first accept evaluate the initial state once, at
+t0, as the reference does).
 """
 import torch
 

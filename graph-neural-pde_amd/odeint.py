@@ -74,7 +74,8 @@ def default_trials_per_sync(numel):
 # --------------------------------------------------------------------------------------------------
 # plumbing shared by the native solve paths: every path keeps its solver objects and state-sized buffers on the function object, in a
 # slot of its own (func.__dict__[slot] = {key: entry}): _solver_state (fixed-step inference), _dopri5_device (adaptive inference),
-# _tape_state / _fixed_tape_state (recorded dopri5 / fixed-grid training), _adjoint_state (fixed-grid adjoint)
+# _tape_state / _fixed_tape_state (recorded dopri5 / fixed-grid training), _adjoint_state (fixed-grid adjoint), _dopri5_host (eager
+# dopri5 with the host controller), _adjoint_adaptive (adaptive adjoint: host-controlled stages and the device solver)
 # --------------------------------------------------------------------------------------------------
 def _close_slot(func, slot):
   st = func.__dict__.get(slot)
@@ -410,97 +411,200 @@ def _solve_dopri5(func, y0, t, rtol, atol, max_num_steps=2 ** 31 - 1, safety=0.9
   return out
 
 
-def _solve_dopri5_native(func, y0, t, rtol, atol, safety=0.9, ifactor=10.0, dfactor=0.2, on_accept=None,
-                         stop_after=None, on_reject=None):
-  """dopri5 with torchdiffeq 0.2.1's controller on the host (one scalar read per trial step) and everything
-  state-sized on the device: each stage is ONE right-hand-side launch whose epilogue also forms the next stage
-  input  y + sum_j (beta_ij dt) k_j  (GNPDE_STAGE_LINCOMB), the error ratio is a device reduction.  Same
-  accept / reject rule, step-size update (float64), FSAL and quartic end-point interpolation as the host loop
-  `_solve_dopri5` (which stays the path for foreign callables)."""
+# --------------------------------------------------------------------------------------------------
+# the embedded pair with torchdiffeq 0.2.1's controller on the host (one scalar read per trial step) and everything state-sized on the
+# device, over a list of components: the eager forward dopri5 is one component, the adaptive adjoint two and a pair of scalars
+# --------------------------------------------------------------------------------------------------
+class _StageComponent(object):
+  """One state-sized component of _solve_pair_host, on native stages: K_j = f(stage input) is ONE right-hand-side launch of `desc`
+  whose epilogue also forms the next stage input  y + sign sum_m c_m K_m  (GNPDE_STAGE_LINCOMB; sign -1: the component runs in
+  reversed time, the sign applied by negating the coefficients), the scaled rms is a device reduction.  `bufs`: y, y1, two stage
+  inputs, stages + 1 derivatives (_component_bufs); `scratch`: the (one-element result, workspace) of the reduction."""
+
+  def __init__(self, desc, sign, bufs, rtol, atol, scratch):
+    self.desc, self.sign, self.tols, self.scratch = desc, sign, (float(atol), float(rtol)), scratch
+    self.y, self.y1, self.u, self.K = bufs[0], bufs[1], bufs[2:4], list(bufs[4:])
+    self.ws = desc.graph.workspace('rhs%d_%d' % (desc.struct.kind, desc.struct.d), _lib.lib().gnpde_rhs_workspace_bytes(desc.ref()))
+
+  def signed(self, coefs):
+    return [-c for c in coefs] if self.sign < 0 else list(coefs)
+
+  def stage(self, j, src, dst=None, row=()):
+    """K_j = f(src); dst = y + sign sum_m row_m K_m (m < j), the next stage input, in the same launch."""
+    from . import ops
+    if dst is None:
+      ops.rhs_stage(self.desc, src, _lib.STAGE_LINCOMB, ws=self.ws, out_k=self.K[j])
+    else:
+      ops.rhs_stage(self.desc, src, _lib.STAGE_LINCOMB, ws=self.ws, y=self.y, out_k=self.K[j], out_y=dst, prev=self.K[:j],
+                    coef=self.signed(row))
+
+  def scaled_rms(self, terms, coefs, y1=None):
+    """rms(sum_j c_j v_j / (atol + rtol max(|y|, |y1|))) in one fused pass, as a one-element tensor (overwritten by the next call)."""
+    from . import ops
+    return ops.rk_error_ratio(self.y, self.y if y1 is None else y1, terms, coefs, self.tols[0], self.tols[1], *self.scratch)
+
+  def axpys(self, coefs, out):
+    """out = y + sign sum_j c_j K_j, zeros skipped (views of padded rows are fine: plain torch ops)"""
+    first = True
+    for kj, c in zip(self.K, self.signed(coefs)):
+      if c == 0.0:
+        continue
+      if first:
+        torch.add(self.y, kj, alpha=c, out=out)
+        first = False
+      else:
+        out.add_(kj, alpha=c)
+    if first:
+      out.copy_(self.y)
+    return out
+
+  def accept(self):
+    """The trial step becomes the state; its last derivative is carried over as the next step's first."""
+    self.y, self.y1 = self.y1, self.y
+    self.K[0], self.K[-1] = self.K[-1], self.K[0]
+
+
+def _component_bufs(prefix, stages):
+  """The names of a component's buffers in an _entry."""
+  return tuple(prefix + s for s in ('', '1', 'u0', 'u1')) + tuple('%sk%d' % (prefix, j) for j in range(stages + 1))
+
+
+def _host_pair_entry(func, slot, key, n, d, device, bufs):
+  """_entry of a host-controlled embedded-pair solve; its `extra` also keeps the scratch of the norm reductions between solves."""
+  ent = _entry(func, slot, key, n, d, device, bufs)
+  if 'ratio_dev' not in ent['extra']:
+    ent['extra']['ratio_dev'] = torch.zeros(1, dtype=torch.float32, device=device)
+    ent['extra']['err_ws'] = torch.empty(4096, dtype=torch.float32, device=device)
+  return ent
+
+
+def _solve_pair_host(method, comps, T0, T1, check, scalars=None, interp=None, on_accept=None, on_reject=None, stop_after=None,
+                     initial_step_only=False, safety=0.9, ifactor=10.0, dfactor=0.2):
+  """The embedded pair `method` of _TABLEAUS from T0 to T1 on the components `comps` (the _StageComponent protocol: y, y1, u, K,
+  stage, scaled_rms, axpys, accept), with the accept / reject rule, step-size update (float64), carried-over derivative and
+  Hairer-Norsett-Wanner initial step of `_solve_dopri5` (which stays the path for foreign callables); time and step size are host
+  floats, every coefficient is float(float32(c) * float32(dt)).  The norm is torchdiffeq's mixed one, the largest component's scaled
+  rms: one component alone is read straight from its one-element tensor.  `check()` runs once per stage, before its launches.
+
+  scalars: an optional extra component of a few numbers in ONE small tensor -- attributes g (the state), g1, K (stages + 1 slots),
+  stage(j, src) -> K_j given every component's stage input, ratio(v, g0, g1) -> the one-element largest |v| / tolerance.
+  interp(x, h, c_mid): called before an accepted step that reaches T1 is committed (y, y1, K still those of the step) with the
+  end-point fraction, float32(dt) and the mid-point coefficients; the interpolation is the caller's.
+  on_accept / on_reject(first component's y, t), stop_after: as in `_solve_dopri5`; every trial step is appended to _TRIAL_TRACE
+  when that is a list.  initial_step_only: stop after the initial step (two stages: K[0] holds f(y)).
+  Returns (the step size the next trial step would take, trial steps made)."""
   import numpy as np
-  from . import ops
-  dev = y0.device
   f32 = np.float32
-  T0, T1 = float(t[0]), float(t[-1])
-  # state-sized buffers (rows padded when d % 4 != 0) are kept on the function object between solves
-  cache = func.__dict__.setdefault('_dopri5_buffers', {})
-  bkey = (tuple(y0.shape), str(dev))
-  if cache.get('key') != bkey:
-    cache.clear()
-    cache['key'] = bkey
-    cache['bufs'] = [_lib.alloc_state(y0.shape[0], y0.shape[1], dev) for _ in range(12)]
-  bufs = cache['bufs']
-  y, y1, u, K, y_out = bufs[0], bufs[1], bufs[2:4], bufs[4:11], bufs[11]
-  y.copy_(y0.detach())
-  ratio_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-  err_ws = torch.empty(4096, dtype=torch.float32, device=dev)
-  desc = func._descriptor(y)
-  L = _lib.lib()
-  ws = desc.graph.workspace('rhs%d_%d' % (desc.struct.kind, desc.struct.d), L.gnpde_rhs_workspace_bytes(desc.ref()))
+  tab = _TABLEAUS[method]
+  order, stages = tab['order'], len(tab['alpha'])
+  sc = scalars
 
-  def feval(src, out_k=None, out_y=None, ybase=None, prev=(), coef=()):
-    func._check_nfe()
-    ops.rhs_stage(desc, src, _lib.STAGE_LINCOMB, ws=ws, y=ybase, out_k=out_k, out_y=out_y, prev=prev, coef=coef)
+  def norm(of_comp, of_scalars):
+    if len(comps) == 1 and sc is None:
+      return float(of_comp(comps[0]).item())
+    parts = [of_comp(c).clone() for c in comps]
+    return float(torch.cat(parts + ([of_scalars()] if sc is not None else [])).max().item())
 
-  rtol64, atol64 = float(rtol), float(atol)
-  feval(y, out_k=K[0])
-  # initial step (order 4 estimate), a handful of reductions once per solve
-  def scaled_rms(terms, coefs):
-    """rms(sum_j c_j v_j / (atol + rtol |y|)) in one fused pass (the error-ratio kernel with y0 = y1 = y)."""
-    ops.rk_error_ratio(y, y, terms, coefs, atol64, rtol64, ratio_dev, err_ws)
-    return float(ratio_dev.item())
+  def stage(j, src, dst=None, row=()):
+    check()
+    for i, c in enumerate(comps):
+      c.stage(j, src[i], None if dst is None else dst[i], row)
+    if sc is not None:
+      sc.K[j] = sc.stage(j, src)
 
-  d0, d1 = scaled_rms([y], [1.0]), scaled_rms([K[0]], [1.0])
+  def lincomb(coefs):
+    return sum(sc.K[j] * coefs[j] for j in range(len(coefs)) if coefs[j] != 0.0)
+
+  # initial step (Hairer, Norsett & Wanner), as misc.py _select_initial_step over the mixed norm
+  stage(0, [c.y for c in comps])
+  d0 = norm(lambda c: c.scaled_rms([c.y], [1.0]), lambda: sc.ratio(sc.g, sc.g, sc.g))
+  d1 = norm(lambda c: c.scaled_rms(c.K[:1], [1.0]), lambda: sc.ratio(sc.K[0], sc.g, sc.g))
   h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else float(f32(0.01) * f32(d0) / f32(d1))
-  torch.add(y, K[0], alpha=h0, out=u[0])
-  feval(u[0], out_k=K[1])
-  d2 = scaled_rms([K[1], K[0]], [1.0, -1.0]) / h0
-  h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else float(f32(f32(0.01) / f32(max(d1, d2))) ** f32(1.0 / 5.0))
+  src = [c.axpys([h0], c.u[0]) for c in comps]
+  stage(1, src)
+  d2 = norm(lambda c: c.scaled_rms([c.K[1], c.K[0]], [1.0, -1.0]), lambda: sc.ratio(sc.K[1] - sc.K[0], sc.g, sc.g)) / h0
+  h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else float(f32(f32(0.01) / f32(max(d1, d2))) ** f32(1.0 / order))
   dt = float(min(100 * h0, h1))
-  t_cur = T0
-  out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=dev)
-  out[0].copy_(y0)
-  n_steps = 0
-  while T1 > t_cur and (stop_after is None or n_steps < stop_after):
+  t_cur, n_steps = T0, 0
+  while not initial_step_only and T1 > t_cur and (stop_after is None or n_steps < stop_after):
     assert t_cur + dt > t_cur, 'underflow in dt {}'.format(dt)
     dty = f32(dt)
-    w = [[f32(b) * dty for b in row] for row in _DP_B]
-    torch.add(y, K[0], alpha=float(w[0][0]), out=u[0])              # first stage input (k0 is FSAL)
-    for i in range(1, 6):                                            # k_i = f(u_i);  u_{i+1} in the same launch
-      dst = y1 if i == 5 else u[i % 2]
-      feval(u[(i - 1) % 2], out_k=K[i], out_y=dst, ybase=y, prev=K[:i], coef=w[i])
-    feval(y1, out_k=K[6])                                            # f(y1): next step's k0 if accepted
-    ops.rk_error_ratio(y, y1, K, [f32(e) * dty for e in _DP_E], atol64, rtol64, ratio_dev, err_ws)
-    ratio = float(ratio_dev.item())                                  # the one host sync of the step
+    rows = [[float(f32(b) * dty) for b in row] for row in tab['beta']]
+    # first stage input from the derivative carried over (rk_common: f1 = k[..., -1], also for the non-FSAL Heun pair)
+    src = [c.axpys(rows[0], c.u[0]) for c in comps]
+    for r in range(1, stages + 1):               # K_r at stage input u_r; its epilogue forms u_{r+1}
+      if r < stages:
+        last = r == stages - 1 and tab['fsal']    # (first-same-as-last: the last stage input IS the solution)
+        dst = [c.y1 if last else c.u[r % 2] for c in comps]
+        stage(r, src, dst, rows[r])
+        src = dst
+      else:
+        stage(r, src)
+    if tab['fsal']:
+      sol = rows[stages - 1]
+    else:
+      sol = [float(f32(c) * dty) for c in tab['c_sol']]
+      for c in comps:
+        c.axpys(sol, c.y1)
+    cerr = [float(f32(e) * dty) for e in tab['c_err']]
+    if sc is not None:
+      sc.g1 = sc.g + lincomb(sol)
+      err_s = lincomb(cerr)
+    ratio = norm(lambda c: c.scaled_rms(c.K, cerr, c.y1), lambda: sc.ratio(err_s, sc.g, sc.g1))   # the one host sync of the step
+    if _TRIAL_TRACE is not None:
+      _TRIAL_TRACE.append((t_cur, dt, ratio))
     if ratio <= 1:
       t_next = t_cur + dt
-      if t_next >= T1:   # end point inside this step: quartic interpolation (torchdiffeq _interp_fit / _interp_evaluate)
-        xf = float(f32((T1 - t_cur) / (t_next - t_cur)))
-        ops.dopri5_interp(y, y1, K, [f32(c) * dty for c in _DP_MID], float(dty), xf, y_out)
-        out[1].copy_(y_out)
-      y, y1 = y1, y
-      K[0], K[6] = K[6], K[0]
+      if t_next >= T1 and interp is not None:   # the end point lies in this step (torchdiffeq _interp_fit / _interp_evaluate)
+        interp(float(f32((T1 - t_cur) / (t_next - t_cur))), float(dty), [float(f32(c) * dty) for c in tab['c_mid']])
+      for c in comps:
+        c.accept()
+      if sc is not None:
+        sc.K[0], sc.g = sc.K[stages], sc.g1
       t_cur = t_next
       if on_accept is not None:
-        on_accept(y, t_cur)
+        on_accept(comps[0].y, t_cur)
     elif on_reject is not None:
-      on_reject(y, t_cur)
+      on_reject(comps[0].y, t_cur)
     if ratio == 0:
       dt = dt * ifactor
     else:
       lo = 1.0 if ratio < 1 else dfactor
-      dt = dt * min(ifactor, max(safety / ratio ** (1.0 / 5.0), lo))
+      dt = dt * min(ifactor, max(safety / ratio ** (1.0 / order), lo))
     n_steps += 1
+  return dt, n_steps
+
+
+def _solve_dopri5_native(func, y0, t, rtol, atol, on_accept=None, stop_after=None, on_reject=None):
+  """dopri5 by _solve_pair_host on ONE native component of sign +1, the end point by the fused quartic interpolation
+  (options eager_stages; EarlyStopDopri5's host loop).  Buffers: slot _dopri5_host.  Like the other host-controlled solves it now
+  appends its trial steps to _TRIAL_TRACE when that is a list."""
+  from . import ops
+  names = _component_bufs('y', 6)
+  ent = _host_pair_entry(func, '_dopri5_host', (tuple(y0.shape), str(y0.device)), y0.shape[0], y0.shape[1], y0.device, names + ('out',))
+  ent['y'].copy_(y0.detach())
+  if ent['x0'] is not None:
+    _copy_source(func, ent['x0'])
+  ex = ent['extra']
+  comp = _StageComponent(func._descriptor(ent['y'], x0_override=ent['x0']), 1, [ent[nm] for nm in names], rtol, atol,
+                         (ex['ratio_dev'], ex['err_ws']))
+  out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+  out[0].copy_(y0)
+
+  def interp(x, h, c_mid):
+    out[1].copy_(ops.dopri5_interp(comp.y, comp.y1, comp.K, c_mid, h, x, ent['out']))
+  n_steps = _solve_pair_host('dopri5', [comp], float(t[0]), float(t[-1]), func._check_nfe, interp=interp, on_accept=on_accept,
+                             on_reject=on_reject, stop_after=stop_after)[1]
   if stop_after is not None and n_steps >= stop_after:   # EarlyStopDopri5.advance: the state where it stopped
-    out[1].copy_(y)
+    out[1].copy_(comp.y)
   return out
 
 
 def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluator=None, stop_after=None, pair='dopri5'):
   """dopri5 with the controller on the device (csrc/dopri5.hip): a trial step is one hipGraph replay; accept / reject, the
   step-size update, the end-point interpolation and the commit are decided by kernels from a record in device memory, which the
-  host reads once per `trials_per_sync` trial steps.  Same arithmetic as `_solve_dopri5_native` (which stays for callers that
-  hook into every step).  evaluator + stop_after: the early-stopping test integrator -- the decoder / arg-max / split counts run
+  host reads once per `trials_per_sync` trial steps.  Same arithmetic as `_solve_pair_host` with one component (`_solve_dopri5_native`,
+  which stays for A/B runs and for callers that hook into every step).  evaluator + stop_after: the early-stopping test integrator -- the decoder / arg-max / split counts run
   as kernels behind every trial step, gated by the controller, and the solve gives up after `stop_after` trial steps
   (gnpde_dopri5_set_early_stop); returns (out, times of the accepted steps) then."""
   from . import ops
@@ -1297,41 +1401,35 @@ def _adjoint_adaptive_ok(func, y, method):
   return not (opt.get('no_alpha_sigmoid') or opt.get('gnpde_composite_backward') or opt.get('gnpde_host_adjoint'))
 
 
-def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, atol, safety=0.9, ifactor=10.0, dfactor=0.2):
+def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, atol):
   """One backward interval of torchdiffeq's adjoint with an ADAPTIVE adjoint method, for f(u) = alpha' (A u - u) + beta x0: the augmented
   system (vjp_t, y, a, g_theta) in reversed time s = -t is
 
       y' = -f(y),   a' = alpha' (A^T a - a),   g_alpha' = (1 - alpha') <a, f(y) - beta x0>,   g_beta' = <a, x0>,   everything else 0,
 
-  integrated by the embedded pair with torchdiffeq 0.2.1's controller (host, float64; mixed norm = the largest component rms, the
-  scalars being components of their own) exactly as `_solve_dopri5` does on the flat vector -- but on the components: per stage ONE
-  launch of the aggregation on the graph (f, its epilogue forming the next stage input of y) and ONE on the transposed graph (the
-  same for a), two dot products, no autograd graph; per trial step two error-norm launches and one host read.  Returns (a at the earlier
-  time, new accumulated gradients of alpha_train / beta_train as a dict by parameter id)."""
-  import numpy as np
+  integrated by the embedded pair with torchdiffeq 0.2.1's controller (mixed norm = the largest component rms, the scalars being
+  components of their own) exactly as `_solve_dopri5` does on the flat vector -- but by _solve_pair_host on the components: a
+  y-component of sign -1 on the graph, an a-component of sign +1 on the transposed graph, the scalar pair (two dot products per
+  stage), no autograd graph; per trial step two error-norm launches and one host read.  The initial step always runs there; the rest
+  of the interval runs on the device controller where that has the case.  Buffers and the device solver: slot _adjoint_adaptive.
+  Returns (a at the earlier time, new accumulated gradients of alpha_train / beta_train as a dict by parameter id)."""
+  import types
   from . import ops
-  f32 = np.float32
-  tab = _TABLEAUS[method]
-  order, stages = tab['order'], len(tab['alpha'])
+  stages = len(_TABLEAUS[method]['alpha'])
   dev = y.device
   n, d = y.shape
   graph = func._graph(y)
   gt = graph.transposed_positions()[0]
-  cache = func.__dict__.setdefault('_adjoint_adaptive', {})
-  key = (n, d, str(dev), method)
-  if cache.get('key') != key:
-    cache.clear()
-    cache['key'] = key
-    cache['bufs'] = [_lib.alloc_state(n, d, dev) for _ in range(2 * (stages + 1) + 9)]
-  bufs = cache['bufs']
-  KF, KV = bufs[:stages + 1], bufs[stages + 1:2 * (stages + 1)]
-  Y, Y1, A_, A1, UY0, UY1, UA0, UA1, X0 = bufs[2 * (stages + 1):]
+  ynames, anames = _component_bufs('y', stages), _component_bufs('a', stages)
+  ent = _host_pair_entry(func, '_adjoint_adaptive', (n, d, str(dev), method), n, d, dev, ynames + anames)
+  ex = ent['extra']
+  Y, A_, X0 = ent['y'], ent['a'], ent['x0']
   Y.copy_(y.detach())
   A_.copy_(a.detach())
-  has_src = bool(func.opt['add_source'])
+  has_src = X0 is not None
   if has_src:
     _copy_source(func, X0)
-  desc_f = func._descriptor(Y, x0_override=X0 if has_src else None, graph=graph)
+  desc_f = func._descriptor(Y, x0_override=X0, graph=graph)
   w_t = _weights_t(func, graph)
   alpha_d = ops._scalar_dev(func.alpha_train, Y)
   desc_b = ops.RhsDescriptor(_lib.RHS_LAPLACIAN, gt, d, Y.stride(0), alpha_d, None, None, True, w_csr=w_t, padded_rows=_lib.is_padded(Y))
@@ -1345,32 +1443,21 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
     g[0] = gparams[ia].reshape(())
   if ib is not None:
     g[1] = gparams[ib].reshape(())
-  ratio_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-  err_ws = torch.empty(4096, dtype=torch.float32, device=dev)
   rt, at = float(rtol), float(atol)
+  scratch = (ex['ratio_dev'], ex['err_ws'])
+  # (the descriptor of f reads y-independent operands only: alpha, beta, x0, the weights -- its `ld` is every buffer's)
+  cy = _StageComponent(desc_f, -1, [ent[nm] for nm in ynames], rt, at, scratch)       # y' = -f(y)
+  ca = _StageComponent(desc_b, 1, [ent[nm] for nm in anames], rt, at, scratch)        # a' = alpha' (A^T a - a)
 
   def dot(u, v):
     return (u * v).sum()
 
-  def feval(uy, ua, j, nxt=None):
-    """K_j of every component at the stage inputs (uy, ua); nxt = (out_uy, out_ua, coefficient row) forms the next stage inputs in the
-    epilogues: u + sum_m (row_m dt) K_m with K_y = -F."""
-    func._check_nfe()
-    if nxt is None:
-      ops.rhs_stage(desc_f, uy, _lib.STAGE_LINCOMB, out_k=KF[j])
-      ops.rhs_stage(desc_b, ua, _lib.STAGE_LINCOMB, out_k=KV[j])
-    else:
-      out_uy, out_ua, row = nxt
-      ops.rhs_stage(desc_f, uy, _lib.STAGE_LINCOMB, y=Y, out_k=KF[j], out_y=out_uy, prev=KF[:j], coef=[-c for c in row])
-      ops.rhs_stage(desc_b, ua, _lib.STAGE_LINCOMB, y=A_, out_k=KV[j], out_y=out_ua, prev=KV[:j], coef=list(row))
-    dx0 = dot(ua, X0) if has_src else torch.zeros((), device=dev)
-    dF = dot(ua, KF[j])
+  def scal_stage(j, src):
+    """(g_alpha', g_beta') at the stage inputs src = (uy, ua), after K_j of y"""
+    dx0 = dot(src[1], X0) if has_src else torch.zeros((), device=dev)
+    dF = dot(src[1], cy.K[j])
     ka = one_minus_a * (dF - beta * dx0) if has_src else one_minus_a * dF
     return torch.stack([ka, dx0])
-
-  def comp_rms(base0, base1, ks, coefs):
-    ops.rk_error_ratio(base0, base1, ks, coefs, at, rt, ratio_dev, err_ws)
-    return ratio_dev.clone()
 
   def scal_ratio(v, g0, g1):
     tol = at + rt * torch.max(g0.abs(), g1.abs())
@@ -1381,38 +1468,20 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
       r = r * torch.tensor([1.0, 0.0], device=dev)
     return r.max().reshape(1)
 
-  def mixed(parts):
-    return float(torch.cat(parts).max().item())
-
+  sc = types.SimpleNamespace(g=g, g1=None, K=[None] * (stages + 1), stage=scal_stage, ratio=scal_ratio)
   T0, T1 = float(span[0]), float(span[-1])
-  Ks = [None] * (stages + 1)
-  Ks[0] = feval(Y, A_, 0)
-  # initial step (Hairer, Norsett & Wanner), as misc.py _select_initial_step over the mixed norm
-  d0 = mixed([comp_rms(Y, Y, [Y], [1.0]), comp_rms(A_, A_, [A_], [1.0]), scal_ratio(g, g, g)])
-  d1 = mixed([comp_rms(Y, Y, [KF[0]], [1.0]), comp_rms(A_, A_, [KV[0]], [1.0]), scal_ratio(Ks[0], g, g)])
-  h0 = 1e-6 if (d0 < 1e-5 or d1 < 1e-5) else float(f32(0.01) * f32(d0) / f32(d1))
-  torch.add(Y, KF[0], alpha=-h0, out=UY0)
-  torch.add(A_, KV[0], alpha=h0, out=UA0)
-  Ks[1] = feval(UY0, UA0, 1)
-  d2 = mixed([comp_rms(Y, Y, [KF[1], KF[0]], [1.0, -1.0]), comp_rms(A_, A_, [KV[1], KV[0]], [1.0, -1.0]), scal_ratio(Ks[1] - Ks[0], g, g)]) / h0
-  h1 = max(1e-6, h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) else float(f32(f32(0.01) / f32(max(d1, d2))) ** f32(1.0 / order))
-  dt = float(min(100 * h0, h1))
   if (ia is not None and (ib is not None or not has_src) and not func.opt.get('gnpde_host_controller_adjoint')
       and Y.stride(0) % 4 == 0 and d <= 256):
-    # the rest of the interval with the controller on the device (csrc/adjoint_adaptive.hip: one hipGraph replay per trial step of the
-    # embedded pair; the host reads a record once per batch)
+    # the initial step on the host, the rest of the interval with the controller on the device (csrc/adjoint_adaptive.hip: one
+    # hipGraph replay per trial step of the embedded pair; the host reads a record once per batch)
     from .utils import MaxNFEException
-    if cache.get('w_t') is None or cache['w_t'].numel() != max(graph.e, 1):
-      cache['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=dev)
+    dt = _solve_pair_host(method, [cy, ca], T0, T1, func._check_nfe, scalars=sc, initial_step_only=True)[0]
+    if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
+      ex['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=dev)
     if graph.e > 0:
-      cache['w_t'][:graph.e].copy_(w_t)          # persistent address: the captured trial steps keep the pointer
-    sig = (func._descriptor_signature(desc_f), id(gt), float(rt), float(at))
-    if cache.get('solver') is None or cache.get('solver_sig') != sig:
-      if cache.get('solver') is not None:
-        cache['solver'].close()
-      cache['solver'] = ops.AdjointAdaptiveSolver(desc_f, gt, cache['w_t'], method, rt, at, dev)
-      cache['solver_sig'] = sig
-    sol = cache['solver']
+      ex['w_t'][:graph.e].copy_(w_t)          # persistent address: the captured trial steps keep the pointer
+    sol = _solver_for(ent, (func._descriptor_signature(desc_f), id(gt), rt, at),
+                      lambda: ops.AdjointAdaptiveSolver(desc_f, gt, ex['w_t'], method, rt, at, dev))
     room = func._nfe_room()
     if room <= 0:
       raise MaxNFEException
@@ -1424,90 +1493,27 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
     if ib is not None:
       new[ib] = g[1].reshape(gparams[ib].shape)
     return A_[:, :d].clone(memory_format=torch.contiguous_format), new
-  t_cur = T0
-  a_out = None
-  g_out = g
-  while T1 > t_cur:
-    assert t_cur + dt > t_cur, 'underflow in dt {}'.format(dt)
-    dty = f32(dt)
-    rows = [[float(f32(b) * dty) for b in row] for row in tab['beta']]
-    # first stage input from the derivative carried over (rk_common: f1 = k[..., -1], also for the non-FSAL Heun pair)
-    torch.add(Y, KF[0], alpha=-rows[0][0], out=UY0)
-    torch.add(A_, KV[0], alpha=rows[0][0], out=UA0)
-    uy, ua = [UY0, UY1], [UA0, UA1]
-    src_y, src_a = UY0, UA0
-    for r in range(1, stages + 1):               # K_r at stage input u_r; its epilogue forms u_{r+1}
-      if r < stages:
-        last = r == stages - 1 and tab['fsal']    # (first-same-as-last: the last stage input IS the solution)
-        dst_y = Y1 if last else uy[r % 2]
-        dst_a = A1 if last else ua[r % 2]
-        Ks[r] = feval(src_y, src_a, r, (dst_y, dst_a, rows[r]))
-        src_y, src_a = dst_y, dst_a
-      else:
-        Ks[r] = feval(src_y, src_a, r)
+  end = {'a': None, 'g': g}
 
-    def axpys(base, ks, cs, sign, out):
-      """out = base + sign * sum_j cs_j ks_j (views of padded rows are fine: plain torch ops)"""
-      first = True
-      for kj, c in zip(ks, cs):
-        if c == 0.0:
-          continue
-        if first:
-          torch.add(base, kj, alpha=sign * c, out=out)
-          first = False
-        else:
-          out.add_(kj, alpha=sign * c)
-      if first:
-        out.copy_(base)
-      return out
-    if tab['fsal']:
-      sol = rows[stages - 1]
-    else:
-      sol = [float(f32(c) * dty) for c in tab['c_sol']]
-      axpys(Y, KF, sol, -1.0, Y1)
-      axpys(A_, KV, sol, 1.0, A1)
-    g1 = g + sum(Ks[j] * sol[j] for j in range(len(sol)) if sol[j] != 0.0)
-    cerr = [float(f32(e) * dty) for e in tab['c_err']]
-    err_s = sum(Ks[j] * cerr[j] for j in range(stages + 1) if cerr[j] != 0.0)
-    ratio = mixed([comp_rms(Y, Y1, KF, cerr), comp_rms(A_, A1, KV, cerr), scal_ratio(err_s, g, g1)])
-    if _TRIAL_TRACE is not None:
-      _TRIAL_TRACE.append((t_cur, dt, ratio))
-    if ratio <= 1:
-      t_next = t_cur + dt
-      if t_next >= T1:     # the end time lies in this step: torchdiffeq's quartic interpolation (only a and the scalars are returned)
-        xf = float(f32((T1 - t_cur) / (t_next - t_cur)))
-        cmid = [float(f32(c) * dty) for c in tab['c_mid']]
-        h = float(dty)
-
-        def interp(v0, v1, k0, k1, mid):
-          ca = 2 * h * (k1 - k0) - 8 * (v1 + v0) + 16 * mid
-          cb = h * (5 * k0 - 3 * k1) + 18 * v0 + 14 * v1 - 32 * mid
-          cc = h * (k1 - 4 * k0) - 11 * v0 - 5 * v1 + 16 * mid
-          cd = h * k0
-          return v0 + xf * cd + xf ** 2 * cc + xf ** 3 * cb + xf ** 4 * ca
-        a_mid = axpys(A_, KV, cmid, 1.0, torch.empty_like(A_))
-        a_out = interp(A_, A1, KV[0], KV[stages], a_mid)[:, :d].contiguous()
-        g_mid = g + sum(Ks[j] * cmid[j] for j in range(stages + 1) if cmid[j] != 0.0)
-        g_out = interp(g, g1, Ks[0], Ks[stages], g_mid)
-      Y, Y1 = Y1, Y
-      A_, A1 = A1, A_
-      KF[0], KF[stages] = KF[stages], KF[0]
-      KV[0], KV[stages] = KV[stages], KV[0]
-      Ks[0] = Ks[stages]
-      g = g1
-      t_cur = t_next
-      # (the descriptor of f reads y-independent operands only: alpha, beta, x0, the weights -- its `ld` is every buffer's)
-    if ratio == 0:
-      dt = dt * ifactor
-    else:
-      lo = 1.0 if ratio < 1 else dfactor
-      dt = dt * min(ifactor, max(safety / ratio ** (1.0 / order), lo))
+  def interp(x, h, c_mid):
+    """torchdiffeq's quartic interpolation at the end time (only a and the scalars are returned)"""
+    def quartic(v0, v1, k0, k1, mid):
+      ca_ = 2 * h * (k1 - k0) - 8 * (v1 + v0) + 16 * mid
+      cb = h * (5 * k0 - 3 * k1) + 18 * v0 + 14 * v1 - 32 * mid
+      cc = h * (k1 - 4 * k0) - 11 * v0 - 5 * v1 + 16 * mid
+      cd = h * k0
+      return v0 + x * cd + x ** 2 * cc + x ** 3 * cb + x ** 4 * ca_
+    a_mid = ca.axpys(c_mid, torch.empty_like(ca.y))
+    end['a'] = quartic(ca.y, ca.y1, ca.K[0], ca.K[stages], a_mid)[:, :d].contiguous()
+    g_mid = sc.g + sum(sc.K[j] * c_mid[j] for j in range(stages + 1) if c_mid[j] != 0.0)
+    end['g'] = quartic(sc.g, sc.g1, sc.K[0], sc.K[stages], g_mid)
+  _solve_pair_host(method, [cy, ca], T0, T1, func._check_nfe, scalars=sc, interp=interp)
   new = {}
   if ia is not None:
-    new[ia] = g_out[0].reshape(gparams[ia].shape)
+    new[ia] = end['g'][0].reshape(gparams[ia].shape)
   if ib is not None:
-    new[ib] = g_out[1].reshape(gparams[ib].shape)
-  return a_out, new
+    new[ib] = end['g'][1].reshape(gparams[ib].shape)
+  return end['a'], new
 
 
 class _AdjointSolve(torch.autograd.Function):

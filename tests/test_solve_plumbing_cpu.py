@@ -91,6 +91,28 @@ def test_solver_for_keeps_the_solver_of_the_same_signature():
   assert first.closed == 1 and sweep.closed == 1 and ent['sweep'] is None and second.closed == 0
 
 
+@pytest.mark.parametrize('slot,bufs', [('_dopri5_host', O._component_bufs('y', 6) + ('out',)),
+                                       ('_adjoint_adaptive', O._component_bufs('y', 1) + O._component_bufs('a', 1))])
+def test_host_pair_slots(slot, bufs):
+  """The two host-controlled embedded-pair solves keep their buffers, the scratch of the norm reductions and (the adjoint) the
+  device solver and its transposed weights in an _entry like every other path."""
+  f = StubFunc(add_source=True)
+  ent = O._host_pair_entry(f, slot, 'k0', 5, 6, CPU, bufs)
+  assert len(set(bufs)) == len(bufs) and all(tuple(ent[nm].shape) == (5, 6) and _lib.is_padded(ent[nm]) for nm in bufs + ('x0',))
+  assert ent['extra']['ratio_dev'].tolist() == [0.0] and ent['extra']['err_ws'].numel() == 4096
+  ent['extra']['w_t'] = torch.ones(3)
+  solver = O._solver_for(ent, ('sig', 1), StubSolver)
+  held = [ent[nm] for nm in bufs + ('x0',)] + [ent['extra'][nm] for nm in ('ratio_dev', 'err_ws', 'w_t')]
+  again = O._host_pair_entry(f, slot, 'k0', 5, 6, CPU, bufs)                  # a hit: the same buffers, extras and solver
+  assert again is ent and all(a is b for a, b in zip(held, [ent[nm] for nm in bufs + ('x0',)] + list(ent['extra'].values())))
+  assert O._solver_for(ent, ('sig', 1), StubSolver) is solver and solver.closed == 0
+  other = _filled(f, '_adjoint_state', 'k')
+  new = O._host_pair_entry(f, slot, 'k1', 5, 6, CPU, bufs)                    # a miss: closes the old solver, and only that slot's
+  assert solver.closed == 1 and other['solver'].closed == 0 and f.__dict__[slot] == {'k1': new}
+  assert new['solver'] is None and 'w_t' not in new['extra'] and new['y'] is not ent['y']
+  assert new['extra']['ratio_dev'] is not ent['extra']['ratio_dev']
+
+
 def test_fixed_nfe_charge():
   f = StubFunc(max_nfe=10, nfe=3)
   f._charge_fixed_nfe(8)                 # evaluations 4 .. 11 find nfe = 3 .. 10: none of them raises
