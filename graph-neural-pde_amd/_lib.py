@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 21     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 22     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
@@ -71,6 +71,26 @@ class LinearLaunchStruct(ctypes.Structure):
 
 
 LINEAR_FAMILIES = ('small', 'staged2', 'staged', 'persistent', 'lds', 'tile')     # GNPDE_LINEAR_* of include/gnpde.h
+
+
+class SpmmLaunchStruct(ctypes.Structure):
+  """gnpde_spmm_launch_t: the launch plan of an aggregation (gnpde_spmm_plan)."""
+  _fields_ = [('family', ctypes.c_int32), ('lane_bytes', ctypes.c_int32), ('L', ctypes.c_int32), ('K', ctypes.c_int32), ('U', ctypes.c_int32),
+              ('full', ctypes.c_int32), ('lo', ctypes.c_int32), ('defer', ctypes.c_int32), ('grid', ctypes.c_uint32), ('block', ctypes.c_uint32),
+              ('forked', ctypes.c_int32), ('fold', ctypes.c_int32)]
+
+  @property
+  def kernel(self):
+    return SPMM_FAMILIES[self.family]
+
+  @property
+  def fold_kind(self):
+    return SPMM_FOLDS[self.fold]
+
+
+SPMM_FAMILIES = ('rows', 'wide', 'pair', 'quad_lo')                               # GNPDE_SPMM_*
+SPMM_FOLDS = ('none', 'in_kernel', 'reduce4', 'reduce4_lo', 'scalar')             # GNPDE_SPMM_FOLD_*
+SPMM_PLAN_LO, SPMM_PLAN_TICKETS, SPMM_PLAN_DEFER, SPMM_PLAN_FORK = 1, 2, 4, 8     # GNPDE_SPMM_PLAN_*
 
 
 class EpilogueStruct(ctypes.Structure):
@@ -193,6 +213,9 @@ PROTOTYPES = {
                                        ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(LinearLaunchStruct), ctypes.c_int32]),
   'gnpde_linear_split_plan': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
                                              ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.POINTER(LinearLaunchStruct)]),
+  'gnpde_adjoint_rows_dot_slots': (ctypes.c_int32, [ctypes.POINTER(GraphStruct), ctypes.c_int32]),
+  'gnpde_spmm_plan': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(EpilogueStruct),
+                                     ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(SpmmLaunchStruct)]),
   'gnpde_linear_split': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp,
                                         ctypes.c_int32, c_vp]),
   'gnpde_adjoint_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]),

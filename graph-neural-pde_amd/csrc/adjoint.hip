@@ -964,7 +964,9 @@ int enqueue_stage(gnpde_adjoint* s, const float* uy, const float* ua, float* Fou
     // V = alpha (A^T ua - ua) [+ 1 * P]
     eV.alpha = r.alpha; eV.beta = source_scale; eV.x0 = source; eV.alpha_sigmoid = r.alpha_sigmoid;
     eV.out_k = Vout;
-    rc = launch_spmm_rhs(gt, wt, ua, d, ld, &eV, nullptr, s->ws_spmm_t, s->spmm_t_bytes, st, nullptr, padded);
+    SpmmOptions opt;
+    opt.padded_rows = padded;
+    rc = launch_spmm_rhs(gt, wt, ua, d, ld, &eV, nullptr, s->ws_spmm_t, s->spmm_t_bytes, st, opt);
     if (rc) return rc;
   }
   // parameter gradients

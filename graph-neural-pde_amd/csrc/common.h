@@ -45,6 +45,7 @@ constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kXcds = 8;           // MI355X: 8 XCDs, block b is dispatched to XCD b % 8
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // Grid rounded to a multiple of the XCD count so that the swizzle below is a bijection.
 inline unsigned xcd_grid(long long blocks) {
@@ -119,6 +120,21 @@ enum {
   GNPDE_TUNE_COUNT = 22
 };
 extern int g_tune[GNPDE_TUNE_COUNT];
+
+// Block size of the row -> XCD deal (xcd_row_of): blocks of 16 .. 128 rows, >= 8192 of them where the graph is large enough (the more
+// blocks an XCD draws, the closer the hash brings heavy-tailed row lengths to the mean: 0.2 % at the R-MAT shape with
+// 16 384 blocks of 128, 5 % with 2 048 blocks of 1 024); always even (row pairs stay together).  -1: contiguous eighths.
+inline int choose_row_shift(long long rn, int graph_deal) {
+  const int knob = g_tune[GNPDE_TUNE_XCD_ROWS];           // A/B: 1 = contiguous eighths, 2 = hashed blocks, whatever the graph says
+  const bool hashed = knob == 2 || (knob != 1 && graph_deal == GNPDE_XCD_HASHED);
+  if (!hashed) return -1;
+  int s = 4;
+  while (s < 7 && (rn >> (s + 1)) >= 8192) ++s;
+  return s;
+}
+// Grid of every launch that walks the aggregation's work lists (spmm.hip): each XCD takes every 8th hub chunk, one wave each, and then its
+// share of the rows at rows_per_wave rows a wave, in workgroups of waves_per_block waves
+unsigned agg_grid(long long chunks, long long rows, int row_shift, int rows_per_wave, int waves_per_block);
 // gnpde_agg_fold_launch(1): the hub rows of the row-pair aggregation are folded by spmm_long_reduce4_kernel in a launch of its own where the
 // solver would let the last chunk item of each row fold it inside the aggregation launch (A/B and bit reference of the in-kernel fold)
 extern int g_agg_fold_launch;
@@ -174,13 +190,21 @@ struct HubDefer {
 };
 
 // internal launchers used by the solver (defined in the kernel translation units)
+// What a call of launch_spmm_rhs may add to the plain launch; default-constructed: none of it.
+struct SpmmOptions {
+  const Fork* fork = nullptr;       // hub-chunk work and fold on the second stream
+  bool padded_rows = false;         // columns [d, ld) of every operand are padding (GNPDE_RHS_PADDED_ROWS): d % 4 != 0 keeps 16-byte lanes
+  const LoPair* lo = nullptr;       // bf16 gather operand
+  const HubDefer* defer = nullptr;  // hub-chunk items form the weights of their entries
+  // tickets (gnpde_spmm_ticket_bytes(g) bytes, all zero when the launch starts and again when it ends): lets the launch fold the hub rows
+  // inside the row-pair kernel where the launch plan says it may; every other route ignores them and keeps the fold launch
+  void* tickets = nullptr;
+  size_t ticket_bytes = 0;
+};
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
                     const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes,
-                    hipStream_t stream, const Fork* fork = nullptr, bool padded_rows = false, const LoPair* lo = nullptr,
-                    const HubDefer* defer = nullptr, void* tickets = nullptr, size_t ticket_bytes = 0);
-// tickets (optional, gnpde_spmm_ticket_bytes(g) bytes, all zero when the launch starts and again when it ends): lets the launch fold the hub
-// rows inside the row-pair kernel where launch_spmm_rhs says it may; every other route ignores them and keeps the fold launch
-// true where launch_spmm_rhs (no fork, no bf16 operand) runs kernels whose hub-chunk items can take a HubDefer
+                    hipStream_t stream, const SpmmOptions& opt = SpmmOptions());
+// true where launch_spmm_rhs (no fork, no bf16 operand) plans a kernel whose hub-chunk items can take a HubDefer
 bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int ld, const gnpde_epilogue_t& epi, const void* ws,
                               bool padded_rows);
 int launch_edge_attention_deferred(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,

@@ -86,7 +86,11 @@ static std::atomic<long long> g_one_launch_evals{0};
 int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& epi, char* ws, const RhsLayout& L,
                 hipStream_t s, const Fork* fork, const RhsRecord* record, const LoPair* lo, bool tickets) {
   const gnpde_graph_t* g = r.graph;
-  void* const tk = tickets && L.ticket_bytes > 0 ? ws + L.tickets : nullptr;
+  const bool padded = (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0;
+  SpmmOptions opt;      // of the aggregation that ends the evaluation
+  opt.padded_rows = padded;
+  opt.tickets = tickets && L.ticket_bytes > 0 ? ws + L.tickets : nullptr;
+  opt.ticket_bytes = L.ticket_bytes;
   const float* w = r.w_csr;
   if (record != nullptr && rhs_record_stride(r) == 0) record = nullptr;
   if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
@@ -127,7 +131,6 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
       at.type = GNPDE_ATT_SCALED_DOT;
     }
     at.n_key_rows = r.n_state_rows > g->n ? r.n_state_rows : 0;     // halo rows: the GAT node terms cover them
-    const bool padded = (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0;
     if (lo == nullptr && record == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && fork == nullptr && r.proj_row_end == 0 && r.n_state_rows <= g->n &&
         (r.d % 4 == 0 || padded) && attn_spmm_supported(g, at, r.d, r.ld, u, epi)) {
       // scaled-dot row softmax: the short rows are attended inside the aggregation kernel; only the hub rows' weights are
@@ -146,14 +149,16 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
       rc = launch_edge_attention_deferred(g, &at, wmean, ws + L.att, L.att_bytes, s, &defer);
       if (rc) return rc;
       if (defer.taken) g_one_launch_evals.fetch_add(1, std::memory_order_relaxed);
-      return launch_spmm_rhs(g, wmean, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, nullptr, padded, nullptr, &defer, tk, L.ticket_bytes);
+      opt.defer = &defer;
+      return launch_spmm_rhs(g, wmean, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, opt);
     }
     rc = launch_edge_attention(g, &at, wmean, nullptr, nullptr, ws + L.att, L.att_bytes, s, fork);
     if (rc) return rc;
     w = wmean;
   }
-  return launch_spmm_rhs(g, w, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, fork,
-                         (r.flags & GNPDE_RHS_PADDED_ROWS) != 0 && r.ld % 4 == 0, lo, nullptr, tk, L.ticket_bytes);
+  opt.fork = fork;
+  opt.lo = lo;
+  return launch_spmm_rhs(g, w, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, opt);
 }
 
 bool rhs_gather_lo_supported(const gnpde_rhs_t& r) {

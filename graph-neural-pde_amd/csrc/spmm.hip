@@ -59,8 +59,6 @@ struct SpmmArgs {
 // launch: nontemporal, so that they do not evict the gathered table from L2 (cached form measured slower, profiles/r02_ab_*.log).
 constexpr bool kNT = true;
 
-inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // Work item of wave `lw` (index local to the XCD) of a block that runs on XCD x = blockIdx % 8.  Every XCD gets every
 // 8th long-row chunk FIRST (512 entries each = the longest-running waves: they start at time 0 and overlap with
 // everything else instead of forming the kernel's tail) and then its share of the rows.  (Handing the chunks out
@@ -108,27 +106,6 @@ __device__ __forceinline__ Item item_of(const SpmmArgs& a, int x, int lw) {
   it.e1 = __builtin_amdgcn_readfirstlane(a.rowptr[it.row + 1]);
   it.valid = it.e1 - it.e0 <= GNPDE_LONG_ROW;   // longer rows are processed as chunks
   return it;
-}
-
-// Block size of the row -> XCD deal: blocks of 16 .. 128 rows, >= 8192 of them where the graph is large enough (the more
-// blocks an XCD draws, the closer the hash brings heavy-tailed row lengths to the mean: 0.2 % at the R-MAT shape with
-// 16 384 blocks of 128, 5 % with 2 048 blocks of 1 024); always even (row pairs stay together).
-inline int choose_row_shift(long long rn, int graph_deal) {
-  const int knob = g_tune[GNPDE_TUNE_XCD_ROWS];           // A/B: 1 = contiguous eighths, 2 = hashed blocks, whatever the graph says
-  const bool hashed = knob == 2 || (knob != 1 && graph_deal == GNPDE_XCD_HASHED);
-  if (!hashed) return -1;
-  int s = 4;
-  while (s < 7 && (rn >> (s + 1)) >= 8192) ++s;
-  return s;
-}
-
-// blocks of WPB waves so that every XCD can reach the end of its local list
-inline unsigned balanced_grid(const SpmmArgs& a, int wpb) {
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per_xcd = (cn + kXcds - 1) / kXcds + xcd_rows_per(static_cast<int>(rn), a.row_shift);
-  long long blocks = (per_xcd + wpb - 1) / wpb;
-  if (blocks < 1) blocks = 1;
-  return static_cast<unsigned>(blocks * kXcds);
 }
 
 template <int VEC, int L, int K, int U, bool LO = false>
@@ -273,8 +250,9 @@ struct Pre {   // epilogue operands requested ahead of the gather loop
   float ui[VEC], x0[VEC], y[VEC], k1[VEC];
 };
 
-template <int VEC, bool NT>
-__device__ __forceinline__ bool stage_prefetchable(int stage) {
+// THE list of stages whose operands are requested ahead of the gather loop (epilogue_pre) and that fold_stage states float by float:
+// the kernels, both folds and the launch plan (which lets the row-pair kernel fold a hub row only for these) ask here
+constexpr __host__ __device__ bool stage_prefetchable(int stage) {
   return stage == GNPDE_STAGE_RHS || stage == GNPDE_STAGE_EULER || (stage >= GNPDE_STAGE_RK1C && stage <= GNPDE_STAGE_RK4C);
 }
 
@@ -404,14 +382,14 @@ __device__ __forceinline__ void fold_stage(const gnpde_epilogue_t& ep, float alp
   store_vec<4>((ep.stage == GNPDE_STAGE_RHS ? ep.out_k : ep.out_y) + off, o);
 }
 
-// fp32 table.  HANDOFF (the row-pair kernel's last arriver): prefetchable stages only -- launch_spmm_rhs keeps the fold launch otherwise
+// fp32 table.  HANDOFF (the row-pair kernel's last arriver): prefetchable stages only -- the launch plan keeps the fold launch otherwise
 template <bool HANDOFF>
 __device__ __forceinline__ void fold_long_row(const SpmmArgs& a, int row, int c0, int c1, int lane) {
   constexpr int VEC = 4;
   const bool plain = a.plain_out != nullptr;
   const float alpha = plain ? 0.0f : alpha_of(a.ep);
   const float beta = (!plain && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
-  const bool pre_ok = !plain && stage_prefetchable<VEC, false>(a.ep.stage);
+  const bool pre_ok = !plain && stage_prefetchable(a.ep.stage);
   for (int col = lane * VEC; col < a.d; col += kWave * VEC) {
     const size_t off = static_cast<size_t>(row) * a.ld + col;
     Pre<VEC, false> pre;
@@ -471,7 +449,7 @@ __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs
     const bool plain = a.plain_out != nullptr;
     const float alpha = plain ? 0.0f : alpha_of(a.ep);
     const float beta = (!plain && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
-    const bool pre_ok = !plain && stage_prefetchable<VEC, false>(a.ep.stage);
+    const bool pre_ok = !plain && stage_prefetchable(a.ep.stage);
     for (int col = static_cast<int>(threadIdx.x) * VEC; col < a.d; col += kWave * VEC) {
       const size_t off = static_cast<size_t>(row) * a.ld + col;
       Pre<VEC, false> pre;
@@ -692,11 +670,11 @@ __global__ __launch_bounds__(kWave) void spmm_wide_kernel(const SpmmArgs a) {
   int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) + static_cast<int>(threadIdx.x >> 6));
   const int stride = static_cast<int>(gridDim.x / kXcds);   // waves per XCD of this launch
   const int lw_end = chunks_of_xcd(a, xcd) + rows_per_xcd(a);
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, kNT>(a.ep.stage);
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable(a.ep.stage);
   const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
   const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
 
-  // One item per wave: the grid has a wave for every item (balanced_grid), so stride >= lw_end and the loop body runs once.  It stays
+  // One item per wave: the grid has a wave for every item (agg_grid), so stride >= lw_end and the loop body runs once.  It stays
   // written as the loop it was when a resident grid strode over the items: as straight-line code (and as a call of shared_row_item
   // with L as a parameter) the compiler emits a different instruction stream for all eight instantiations, and this kernel is only
   // changed together with a measurement.
@@ -843,7 +821,7 @@ __global__ __launch_bounds__(kWave) void spmm_pair_kernel(const SpmmArgs a) {
   const bool col_ok = FULL ? true : col < a.d;
   const int xcd = static_cast<int>(blockIdx.x % kXcds);
   const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) + static_cast<int>(threadIdx.x >> 6));
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, kNT>(a.ep.stage);
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable(a.ep.stage);
   const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
   const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
 
@@ -1050,7 +1028,7 @@ __global__ __launch_bounds__(kWave) void attn_spmm_kernel(const AttnSpmmArgs fa)
   if (!it.valid) return;
   const int row = it.row, e0 = it.e0, e1 = it.e1, chunk = it.chunk;
   const size_t off = static_cast<size_t>(row) * a.ld + col;
-  const bool pre_ok = stage_prefetchable<VEC, kNT>(a.ep.stage);
+  const bool pre_ok = stage_prefetchable(a.ep.stage);
 
   Pre<VEC, kNT> pre;
   const bool do_pre = pre_ok && chunk < 0 && sub == 0 && col_ok;
@@ -1158,7 +1136,7 @@ template <int H, int DK4>
 bool launch_attn_spmm_hd(const AttnSpmmArgs& fa, hipStream_t st) {
   const SpmmArgs& a = fa.s;
   const int slots = (a.d + 3) / 4;
-  const unsigned grid = balanced_grid(a, 1);
+  const unsigned grid = agg_grid(a.chunk_end - a.chunk_begin, a.row_end - a.row_begin, a.row_shift, 1, 1);
 #define GNPDE_AS(LL)                                                                                                     \
   if (a.d == LL * 4) hipLaunchKernelGGL((attn_spmm_kernel<4, LL, 8, H, DK4, true>), dim3(grid), dim3(kWave), 0, st, fa); \
   else hipLaunchKernelGGL((attn_spmm_kernel<4, LL, 8, H, DK4, false>), dim3(grid), dim3(kWave), 0, st, fa);
@@ -1167,108 +1145,6 @@ bool launch_attn_spmm_hd(const AttnSpmmArgs& fa, hipStream_t st) {
   if (slots <= 64) { GNPDE_AS(64) return true; }
 #undef GNPDE_AS
   return false;
-}
-
-template <int L>
-void launch_wide(const SpmmArgs& a, hipStream_t s) {   // 8 gathers in flight, one wavefront per workgroup
-  const unsigned grid = balanced_grid(a, 1);
-  if (a.d == L * 4) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, true>), dim3(grid), dim3(kWave), 0, s, a);
-  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, false>), dim3(grid), dim3(kWave), 0, s, a);
-}
-
-// row pairs: one wave per two consecutive rows (hub chunks first, as balanced_grid)
-inline unsigned pair_grid(const SpmmArgs& a) {
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
-  long long blocks = (cn + kXcds - 1) / kXcds + (per + 1) / 2;
-  if (blocks < 1) blocks = 1;
-  return static_cast<unsigned>(blocks * kXcds);
-}
-
-// a launch with hub chunks whose weights are still to be formed (SpmmArgs::hub_part)
-inline bool hub_deferred(const SpmmArgs& a) { return a.hub_part != nullptr && a.chunk_end > a.chunk_begin; }
-
-void launch_pair(const SpmmArgs& a, hipStream_t s) {
-  if (hub_deferred(a)) {    // hub-chunk items that normalise their row's softmax (the row pairs: the same code)
-    if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true, false, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
-    else hipLaunchKernelGGL((spmm_pair_kernel<4, false, false, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
-    return;
-  }
-  if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
-  else hipLaunchKernelGGL((spmm_pair_kernel<4, false>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
-}
-
-template <int VEC, int L, int K, int U>
-void launch_rows(const SpmmArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((spmm_rows_kernel<VEC, L, K, U>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
-}
-
-// THE route test of the row-pair kernel, given 16-byte lanes of the fp32 table (dispatch_rows<4>): rows of 17..32 lanes in a graph of mostly
-// short rows.  The dispatch below, the deferred hub weights and the in-kernel hub fold all ask here -- the last two hand the launch work
-// that only spmm_pair_kernel does (hub weights, the fold), so a second copy of the condition that drifted would leave it undone silently.
-inline bool mostly_short_rows(const gnpde_graph_t* g) { return 2LL * g->n_bin16 >= g->n; }
-inline bool pair_kernel_route(int d, bool short_rows) {
-  const int slots = (d + 3) / 4;
-  return slots > 16 && slots <= 32 && short_rows;
-}
-
-// One line per width class (slots = lanes of VEC floats that cover a row); what every class takes was measured, the alternatives that
-// lost are recorded in DESIGN.md section 3 and profiles/.
-template <int VEC>
-int dispatch_rows(const SpmmArgs& a, hipStream_t s) {
-  const int slots = (a.d + VEC - 1) / VEC;
-  const bool pair = VEC == 4 && pair_kernel_route(a.d, a.short_rows != 0);
-  if ((a.tickets != nullptr || hub_deferred(a)) && !pair) {     // (work of the row-pair kernel alone: never reached while the callers ask the same test)
-    set_error("spmm: hub-row tickets / deferred hub weights handed to a kernel other than the row-pair kernel (d=%d)", a.d);
-    return GNPDE_EINVAL;
-  }
-  if (slots <= 8) launch_rows<VEC, 8, 1, 4>(a, s);
-  else if (slots <= 16) launch_rows<VEC, 16, 1, 4>(a, s);
-  else if (slots <= 64) {
-    if constexpr (VEC == 4) {
-      // 16-byte lanes, rows of 17..64 lanes (d = 68..256): the wide-row kernel, 8 gathers in flight, one wavefront per workgroup --
-      // measured best at the ogbn-arxiv shape (178 vs 221 us) and within 1 % of the best at the R-MAT d = 256 shape (16.6 vs
-      // 16.8 ms), profiles/r02_ab_*.log.
-      // Rows of 17..32 lanes (d = 68..128) in graphs whose rows are mostly short (the ogbn-arxiv shape: median 8 entries): two rows
-      // per wave, 16 gathers in flight per half (spmm_pair_kernel; bit-identical results): 171 vs 184 us at the ogbn-arxiv shape,
-      // 193 vs 230 us on a uniform degree-8 graph, but 2 % slower at degree 24 -- hence the hint (profiles/r02_ab_row_pairs.txt)
-      if (pair) launch_pair(a, s);
-      else if (slots <= 32) launch_wide<32>(a, s);
-      else launch_wide<64>(a, s);
-    } else {
-      if (slots <= 32) launch_rows<VEC, 16, 2, 4>(a, s);
-      else launch_rows<VEC, 32, 2, 4>(a, s);
-    }
-  }
-  else if (slots <= 128) launch_rows<VEC, 64, 2, 2>(a, s);
-  else if (slots <= 192) launch_rows<VEC, 64, 3, 1>(a, s);
-  else if (slots <= 256) launch_rows<VEC, 64, 4, 1>(a, s);
-  else {
-    set_error("spmm: feature width d=%d too large for VEC=%d (max %d)", a.d, VEC, 256 * VEC);
-    return GNPDE_ESHAPE;
-  }
-  return 0;
-}
-
-
-// bf16 gather operand (16-byte lanes of the state only): the default kernel of every width class with the gather element type
-// switched -- same work items, lane mapping and summation order as the fp32 kernels that dispatch_rows<4> picks, so a plain
-// aggregation from a shadow is bit-identical to gnpde_spmm on the widened table.
-template <int L, int K, int U>
-void launch_rows_lo(const SpmmArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((spmm_rows_kernel<4, L, K, U, true>), dim3(balanced_grid(a, kWavesPerBlock)), dim3(kBlock), 0, s, a);
-}
-
-template <int L>
-void launch_wide_lo(const SpmmArgs& a, hipStream_t s) {
-  const unsigned grid = balanced_grid(a, 1);
-  if (a.d == L * 4) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, true, true>), dim3(grid), dim3(kWave), 0, s, a);
-  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, false, true>), dim3(grid), dim3(kWave), 0, s, a);
-}
-
-void launch_pair_lo(const SpmmArgs& a, hipStream_t s) {
-  if (a.d == 32 * 4) hipLaunchKernelGGL((spmm_pair_kernel<4, true, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
-  else hipLaunchKernelGGL((spmm_pair_kernel<4, false, true>), dim3(pair_grid(a)), dim3(kWave), 0, s, a);
 }
 
 // Row-QUAD form of the row-pair kernel for the bf16 gather operand: a bf16 row of d <= 128 columns is 256 bytes, so with the pair
@@ -1287,7 +1163,7 @@ __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
   const bool col_ok = col < a.d;
   const int xcd = static_cast<int>(blockIdx.x % kXcds);
   const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds));
-  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable<VEC, kNT>(a.ep.stage);
+  const bool pre_ok = a.plain_out == nullptr && stage_prefetchable(a.ep.stage);
   const float alpha = a.plain_out == nullptr ? alpha_of(a.ep) : 0.0f;
   const float beta = (a.plain_out == nullptr && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
   // the shared-row mode keeps the 32 x 4 mapping
@@ -1408,149 +1284,240 @@ __global__ __launch_bounds__(kWave) void spmm_quad_lo_kernel(const SpmmArgs a) {
   }
 }
 
-void launch_quad_lo(const SpmmArgs& a, hipStream_t s) {
-  const long long cn = a.chunk_end - a.chunk_begin, rn = a.row_end - a.row_begin;
-  const long long per = xcd_rows_per(static_cast<int>(rn), a.row_shift);
-  long long blocks = (cn + kXcds - 1) / kXcds + (per + 3) / 4;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((spmm_quad_lo_kernel<16>), dim3(static_cast<unsigned>(blocks * kXcds)), dim3(kWave), 0, s, a);
+// ------------------------------------------------------------------------------------------------
+// Host side.  What the three launchers of this file share (the graph part of SpmmArgs, the epilogue rules, the lane test), then the launch
+// plan of launch_spmm_rhs: ONE decision -- lanes, kernel and template line, grid, fork, hub-row fold -- taken in plan_spmm, exported as it
+// is taken by gnpde_spmm_plan (gnpde.h documents the table) and carried out by launch_planned.
+// ------------------------------------------------------------------------------------------------
+
+// The graph, state and work ranges of a launch over rows [g->row_begin, n) and all hub chunks; the chunk partials must fit the workspace.
+int fill_args(SpmmArgs& a, const gnpde_graph_t* g, const float* w, const float* u, int d, int ld, void* ws, size_t ws_bytes, const char* who) {
+  a.n = g->n; a.n_long_chunks = g->n_long_chunks;
+  a.rowptr = g->rowptr; a.colidx = g->colidx;
+  a.lc_row = g->long_chunk_row; a.lc_begin = g->long_chunk_begin; a.lc_end = g->long_chunk_end;
+  a.w = w; a.u = u; a.d = d; a.ld = ld;
+  a.ldp = static_cast<int>(align_up(static_cast<size_t>(d), 4));
+  a.partial = static_cast<float*>(ws);
+  a.chunk_begin = 0; a.chunk_end = g->n_long_chunks; a.row_begin = g->row_begin; a.row_end = g->n;
+  a.row_shift = choose_row_shift(static_cast<long long>(a.row_end) - a.row_begin, g->xcd_deal);
+  a.short_rows = 2LL * g->n_bin16 >= g->n ? 1 : 0;
+  if (g->n_long_chunks > 0) {
+    const size_t need = static_cast<size_t>(g->n_long_chunks) * a.ldp * sizeof(float);
+    GNPDE_CHECK_ARG(ws != nullptr && ws_bytes >= need, GNPDE_EWS, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+  }
+  return 0;
 }
 
-int dispatch_rows_lo(const SpmmArgs& a, hipStream_t s) {
-  const int slots = (a.d + 3) / 4;
-  const bool quad_ok = a.d % 8 == 0 && a.ld % 8 == 0 && aligned(a.u_lo, 16) && aligned(a.out_y_lo, 16);
-  const bool quad = g_tune[GNPDE_TUNE_LO_MAPPING] == 2 && quad_ok;
-  if (slots <= 8) launch_rows_lo<8, 1, 4>(a, s);
-  else if (slots <= 16) launch_rows_lo<16, 1, 4>(a, s);
-  else if (slots <= 32 && a.short_rows && quad) launch_quad_lo(a, s);
-  else if (slots <= 32 && a.short_rows) launch_pair_lo(a, s);
-  else if (slots <= 32) launch_wide_lo<32>(a, s);
-  else if (slots <= 64) launch_wide_lo<64>(a, s);
-  else if (slots <= 128) launch_rows_lo<64, 2, 2>(a, s);
-  else if (slots <= 192) launch_rows_lo<64, 3, 1>(a, s);
-  else if (slots <= 256) launch_rows_lo<64, 4, 1>(a, s);
+// An epilogue against the stages a launcher accepts (bit s: stage s) and the operands each stage reads and writes.
+constexpr unsigned kStagesAll = (2u << GNPDE_STAGE_LINCOMB) - 1;
+constexpr unsigned kStagesAdjoint = 1u << GNPDE_STAGE_LINCOMB | 1u << GNPDE_STAGE_EULER | 0xFu << GNPDE_STAGE_RK1C;
+int check_epilogue(const char* who, const gnpde_epilogue_t& e, const void* u, unsigned accepted) {
+  const int st = e.stage;
+  GNPDE_CHECK_ARG(st >= GNPDE_STAGE_RHS && st <= GNPDE_STAGE_LINCOMB && (accepted >> st & 1u), GNPDE_EINVAL, "%s: bad stage %d", who, st);
+  GNPDE_CHECK_ARG(e.alpha != nullptr, GNPDE_EINVAL, "%s: alpha pointer is null", who);
+  GNPDE_CHECK_ARG(e.x0 == nullptr || e.beta != nullptr, GNPDE_EINVAL, "%s: x0 given without beta", who);
+  if (st == GNPDE_STAGE_LINCOMB) {
+    GNPDE_CHECK_ARG(e.n_prev >= 0 && e.n_prev <= GNPDE_MAX_PREV, GNPDE_EINVAL, "%s: bad n_prev %d", who, e.n_prev);
+    GNPDE_CHECK_ARG(e.out_y == nullptr || e.y != nullptr, GNPDE_EINVAL, "%s: LINCOMB needs y", who);
+    for (int j = 0; j < e.n_prev; ++j) GNPDE_CHECK_ARG(e.prev[j] != nullptr, GNPDE_EINVAL, "%s: LINCOMB prev[%d] is null", who, j);
+  }
+  const bool needs_k = st == GNPDE_STAGE_RHS || (st >= GNPDE_STAGE_RK1 && st <= GNPDE_STAGE_RK3);
+  const bool needs_y = st == GNPDE_STAGE_EULER || (st >= GNPDE_STAGE_RK1 && st <= GNPDE_STAGE_RK4) || st == GNPDE_STAGE_RK2C || st == GNPDE_STAGE_RK4C;
+  const bool needs_k1 = (st >= GNPDE_STAGE_RK2 && st <= GNPDE_STAGE_RK4) || st == GNPDE_STAGE_RK3C || st == GNPDE_STAGE_RK4C;
+  GNPDE_CHECK_ARG(!needs_k || e.out_k != nullptr, GNPDE_EINVAL, "%s: out_k is null", who);
+  GNPDE_CHECK_ARG(st == GNPDE_STAGE_RHS || st == GNPDE_STAGE_LINCOMB || e.out_y != nullptr, GNPDE_EINVAL, "%s: out_y is null", who);
+  GNPDE_CHECK_ARG(!needs_y || e.y != nullptr, GNPDE_EINVAL, "%s: y is null", who);
+  GNPDE_CHECK_ARG(!needs_k1 || e.k1 != nullptr, GNPDE_EINVAL, "%s: k1 is null", who);
+  GNPDE_CHECK_ARG(!(st == GNPDE_STAGE_RK3 || st == GNPDE_STAGE_RK4) || e.k2 != nullptr, GNPDE_EINVAL, "%s: k2 is null", who);
+  GNPDE_CHECK_ARG(st != GNPDE_STAGE_RK4 || e.k3 != nullptr, GNPDE_EINVAL, "%s: k3 is null", who);
+  // every row gathers from u while other rows run their epilogue: outputs must not alias u
+  GNPDE_CHECK_ARG(e.out_k != u && e.out_y != u, GNPDE_EINVAL, "%s: output aliases the gathered operand", who);
+  return 0;
+}
+
+// THE lane test: the row stride and every operand of a launch -- the state, two more tables (plain output, workspace, second state) and
+// whatever the epilogue reads or writes -- on lanes of `bytes` bytes (16 or 8).  The width rule (d against padded rows) is the caller's.
+bool on_lanes(size_t bytes, int ld, const void* u, const void* t1, const void* t2, const gnpde_epilogue_t* e) {
+  bool ok = ld % static_cast<int>(bytes / sizeof(float)) == 0 && aligned(u, bytes) && aligned(t1, bytes) && aligned(t2, bytes);
+  if (e == nullptr) return ok;
+  const void* ptrs[] = {e->x0, e->y, e->k1, e->k2, e->k3, e->out_k, e->out_y};
+  for (const void* p : ptrs) ok = ok && aligned(p, bytes);
+  if (e->stage == GNPDE_STAGE_LINCOMB)
+    for (int j = 0; j < e->n_prev && j < GNPDE_MAX_PREV; ++j) ok = ok && aligned(e->prev[j], bytes);
+  return ok;
+}
+
+struct SpmmPlan {
+  gnpde_spmm_launch_t l;     // what gnpde_spmm_plan reports
+  int chunk_end, row_end;    // work of the launch with grid l.grid: chunks [0, chunk_end), rows [g->row_begin, row_end)
+  bool pair_only;            // the route on which the row-pair kernel may be handed work that it alone does
+};
+
+// rows per wave and waves per workgroup of a planned kernel -> its grid over `chunks` hub chunks and `rows` rows
+unsigned plan_grid(const gnpde_spmm_launch_t& l, long long chunks, long long rows, int row_shift) {
+  const int rows_per_wave = l.family == GNPDE_SPMM_PAIR ? 2 : l.family == GNPDE_SPMM_QUAD_LO ? 4 : 1;
+  return agg_grid(chunks, rows, row_shift, rows_per_wave, static_cast<int>(l.block) / kWave);
+}
+
+// THE table: one line per width class (slots = lanes of `vec` floats that cover a row); what every class takes was measured, the
+// alternatives that lost are recorded in DESIGN.md section 3 and profiles/.  The bf16 gather operand (16-byte lanes only) takes the
+// same line with the gather element type switched -- same work items, lane mapping and summation order, so a plain aggregation from
+// a shadow is bit-identical to gnpde_spmm on the widened table.
+int width_class(int vec, int d, bool short_rows, bool quad_lo, gnpde_spmm_launch_t& l) {
+  const int slots = (d + vec - 1) / vec;
+  auto rows = [&l](int L, int K, int U) { l.family = GNPDE_SPMM_ROWS; l.L = L; l.K = K; l.U = U; l.block = kBlock; };
+  if (slots <= 8) rows(8, 1, 4);
+  else if (slots <= 16) rows(16, 1, 4);
+  else if (slots <= 64 && vec == 4) {
+    // 16-byte lanes, rows of 17..64 lanes (d = 68..256): the wide-row kernel, 8 gathers in flight, one wavefront per workgroup --
+    // measured best at the ogbn-arxiv shape (178 vs 221 us) and within 1 % of the best at the R-MAT d = 256 shape (16.6 vs
+    // 16.8 ms), profiles/r02_ab_*.log.
+    // Rows of 17..32 lanes (d = 68..128) in graphs whose rows are mostly short (the ogbn-arxiv shape: median 8 entries): two rows
+    // per wave, 16 gathers in flight per half (spmm_pair_kernel; bit-identical results): 171 vs 184 us at the ogbn-arxiv shape,
+    // 193 vs 230 us on a uniform degree-8 graph, but 2 % slower at degree 24 -- hence the hint (profiles/r02_ab_row_pairs.txt).
+    // The quad form (four rows per wave from a bf16 table, GNPDE_TUNE_LO_MAPPING 2) has no FULL instantiation.
+    const bool pair = slots <= 32 && short_rows;
+    l.family = !pair ? GNPDE_SPMM_WIDE : quad_lo ? GNPDE_SPMM_QUAD_LO : GNPDE_SPMM_PAIR;
+    l.L = l.family == GNPDE_SPMM_QUAD_LO ? 16 : slots <= 32 ? 32 : 64;
+    l.K = 1;
+    l.U = pair ? 16 : 8;
+    l.full = l.family != GNPDE_SPMM_QUAD_LO && d == l.L * 4;
+    l.block = kWave;
+  }
+  else if (slots <= 32) rows(16, 2, 4);
+  else if (slots <= 64) rows(32, 2, 4);
+  else if (slots <= 128) rows(64, 2, 2);
+  else if (slots <= 192) rows(64, 3, 1);
+  else if (slots <= 256) rows(64, 4, 1);
   else {
-    set_error("spmm: feature width d=%d too large for 16-byte lanes (max %d)", a.d, 256 * 4);
+    set_error("spmm: feature width d=%d too large for %d-byte lanes (max %d)", d, 4 * vec, 256 * vec);
     return GNPDE_ESHAPE;
   }
   return 0;
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// SDDMM: out[p] = scale * a[row_p] . b[col_p] for every stored entry -- the gradient of the aggregation
-// w.r.t. the edge weights (d w_e = alpha' g_row . x_col), needed when attention_weights carry gradients.
-// Same work items as the aggregation (512-entry chunks of the hub rows first, then one wavefront per row, XCD-aware
-// block order), a_row slice kept in registers, L lanes per neighbour, U independent gathers in flight,
-// xor-butterfly dot.  Entries are independent, so the hub chunks need no second pass.
-// ------------------------------------------------------------------------------------------------
-struct SddmmArgs {
-  int n, n_long_chunks;
-  const int* __restrict__ rowptr;
-  const int* __restrict__ colidx;
-  const int* __restrict__ lc_row;
-  const int* __restrict__ lc_begin;
-  const int* __restrict__ lc_end;
-  const float* __restrict__ a;
-  const float* __restrict__ b;
-  int d, lda, ldb;
-  const float* __restrict__ scale_ptr;
-  int scale_sigmoid;
-  float* __restrict__ out;
-  int row_shift;         // rows -> XCDs as in the aggregation (xcd_row_of): < 0 contiguous eighths, else hashed blocks of 2^row_shift rows
-};
-
-template <int VEC, int L, int K, int U>
-__global__ __launch_bounds__(kBlock) void sddmm_kernel(const SddmmArgs s) {
-  constexpr int G = kWave / L;
-  const int lane = threadIdx.x & (kWave - 1);
-  // same XCD-balanced work list as the aggregation (item_of): every 8th chunk first, then this XCD's share of the rows
-  const int x = static_cast<int>(blockIdx.x % kXcds);
-  const int lw = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x / kXcds) * kWavesPerBlock + static_cast<int>(threadIdx.x >> 6));
-  const int cx = (s.n_long_chunks + kXcds - 1 - x) / kXcds;
-  int row, e0, e1;
-  if (lw >= cx) {
-    row = xcd_row_of(0, s.n, s.row_shift, x, lw - cx);
-    if (row < 0) return;
-    e0 = s.rowptr[row];
-    e1 = s.rowptr[row + 1];
-    if (e1 - e0 > GNPDE_LONG_ROW) return;  // processed as chunks
+// The plan of launch_spmm_rhs for these operands.  Operand pointers are read for their alignment and for being null, never through; of the
+// options: whether there is a second stream, tickets, a bf16 operand (and its alignment), hub weights to form.
+int plan_spmm(const gnpde_graph_t* g, const void* u, int d, int ld, const gnpde_epilogue_t* e, const void* plain_out, const void* ws,
+              const SpmmOptions& opt, SpmmPlan* p) {
+  *p = SpmmPlan{};
+  gnpde_spmm_launch_t& l = p->l;
+  const LoPair* lo = opt.lo != nullptr && opt.lo->u_lo != nullptr ? opt.lo : nullptr;
+  // (a plain aggregation from a shadow has no fp32 table at all)
+  GNPDE_CHECK_ARG(g && (u || (lo && plain_out)), GNPDE_EINVAL, "spmm: null pointer");
+  GNPDE_CHECK_ARG(d >= 1 && ld >= d, GNPDE_EINVAL, "spmm: bad d=%d ld=%d", d, ld);
+  GNPDE_CHECK_ARG((e != nullptr) != (plain_out != nullptr), GNPDE_EINVAL, "spmm: need exactly one of epilogue / plain output");
+  if (g->n == 0) return 0;
+  GNPDE_CHECK_ARG(g->n_long_chunks <= 0 || (g->long_rows && g->long_chunk_ptr && g->long_chunk_row && g->long_chunk_begin && g->long_chunk_end),
+                  GNPDE_EINVAL, "spmm: long-row arrays missing");
+  if (e != nullptr) {
+    if (const int rc = check_epilogue("spmm", *e, u, kStagesAll)) return rc;
+    GNPDE_CHECK_ARG(e->stage != GNPDE_STAGE_LINCOMB || e->out_k != nullptr || e->out_y != nullptr, GNPDE_EINVAL, "spmm: LINCOMB without output");
   } else {
-    const int item = lw * kXcds + x;
-    row = s.lc_row[item];
-    e0 = s.lc_begin[item];
-    e1 = s.lc_end[item];
+    GNPDE_CHECK_ARG(plain_out != u, GNPDE_EINVAL, "spmm: output aliases the gathered operand");
   }
-  const int sub = lane / L, cl = lane % L;
-  float scale = 1.0f;
-  if (s.scale_ptr != nullptr) {
-    scale = *s.scale_ptr;
-    if (s.scale_sigmoid) scale = 1.0f / (1.0f + expf(-scale));
+  // padded_rows: the caller guarantees that columns [d, ld) of every operand are padding (GNPDE_RHS_PADDED_ROWS), so a
+  // width that is not a multiple of 4 still takes 16-byte lanes (the last lane reads / writes up to 3 padding columns)
+  const bool a16 = (d % 4 == 0 || opt.padded_rows) && on_lanes(16, ld, u, plain_out, ws, e);
+  const bool a8 = d % 2 == 0 && on_lanes(8, ld, u, plain_out, ws, e);
+  l.lane_bytes = a16 ? 16 : a8 ? 8 : 4;
+  const uint16_t* out_y_lo = lo != nullptr && e != nullptr ? lo->out_y_lo : nullptr;
+  if (lo != nullptr) {
+    l.lo = 1;
+    GNPDE_CHECK_ARG(a16 && aligned(lo->u_lo, 8) && aligned(out_y_lo, 8), GNPDE_ESHAPE,
+                    "spmm: the bf16 gather operand needs 16-byte lanes (d %% 4 == 0, or padded rows with ld %% 4 == 0; 16-byte aligned "
+                    "operands, 8-byte aligned shadows): d=%d ld=%d", d, ld);
+    GNPDE_CHECK_ARG(out_y_lo == nullptr || out_y_lo != lo->u_lo, GNPDE_EINVAL, "spmm: a stage must not write the shadow it gathers from");
   }
-  float av[K][VEC];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int col = (k * L + cl) * VEC;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) av[k][v] = 0.0f;
-    if (col < s.d) load_vec<VEC>(s.a + static_cast<size_t>(row) * s.lda + col, av[k]);
-  }
-  for (int j = e0; j < e1; j += G * U) {
-    float bv[U][K][VEC];
-#pragma unroll
-    for (int t = 0; t < U; ++t) {
-      const int e = j + t * G + sub;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) bv[t][k][v] = 0.0f;
-      if (e < e1) {
-        const float* src = s.b + static_cast<size_t>(s.colidx[e]) * s.ldb;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const int col = (k * L + cl) * VEC;
-          if (col < s.d) load_vec<VEC>(src + col, bv[t][k]);
-        }
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < U; ++t) {
-      float p = 0.0f;
-#pragma unroll
-      for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) p = fmaf(av[k][v], bv[t][k][v], p);
-#pragma unroll
-      for (int off = 1; off < L; off <<= 1) p += __shfl_xor(p, off, kWave);
-      const int e = j + t * G + sub;
-      if (cl == 0 && e < e1) s.out[e] = scale * p;
-    }
-  }
+  // Rows and long-row chunks in one launch, then the per-row reduction of the chunk partials; with a fork the chunks + reduction
+  // run as a parallel branch.  The boundary pass of a partitioned graph covers rows [row_begin, n) only (its chunks belong to those rows).
+  GNPDE_CHECK_ARG(g->row_begin >= 0 && g->row_begin <= g->n, GNPDE_EINVAL, "spmm: bad row_begin %d", g->row_begin);
+  const bool forked = opt.fork != nullptr && opt.fork->aux != nullptr && g->n_long_rows > 0;
+  GNPDE_CHECK_ARG(!(forked && g->row_begin > 0), GNPDE_EINVAL, "spmm: fork with row_begin");
+  l.forked = forked;
+  const int part = g_tune[GNPDE_TUNE_SPMM_PART];           // (timing the two kinds of work items separately)
+  p->chunk_end = forked || part == 2 ? 0 : g->n_long_chunks;
+  p->row_end = part == 1 ? g->row_begin : g->n;
+  const bool quad_lo = lo != nullptr && g_tune[GNPDE_TUNE_LO_MAPPING] == 2 && d % 8 == 0 && ld % 8 == 0 && aligned(lo->u_lo, 16) && aligned(out_y_lo, 16);
+  if (const int rc = width_class(l.lane_bytes / 4, d, 2LL * g->n_bin16 >= g->n, quad_lo, l)) return rc;
+  l.grid = plan_grid(l, p->chunk_end, p->row_end - g->row_begin, choose_row_shift(static_cast<long long>(g->n) - g->row_begin, g->xcd_deal));
+  // THE condition for work that spmm_pair_kernel<.., LO = false> alone does -- the weights of the hub entries (HubDefer) and the hub-row
+  // fold by the last chunk item to arrive (tickets): its instantiations over the whole graph, on one stream, with every work item.  The
+  // wide-row kernel is left as it is: with the deferred path its instantiations need 92 - 101 VGPRs instead of 80 - 86 (a wave per SIMD
+  // less for EVERY row of the launch) and spill SGPRs, for the sake of the hub chunks alone.
+  p->pair_only = l.family == GNPDE_SPMM_PAIR && l.lane_bytes == 16 && !l.lo && !forked && g->row_begin == 0 && part == 0;
+  const bool defer = opt.defer != nullptr && opt.defer->taken != 0 && g->n_long_rows > 0;     // (without hub rows there is no weight left to form)
+  GNPDE_CHECK_ARG(!defer || p->pair_only, GNPDE_EINVAL,
+                  "spmm: deferred hub weights need the row-pair kernel (16-byte lanes, d = 68..128, mostly short rows, the whole graph; d=%d ld=%d)", d, ld);
+  l.defer = defer;
+  // Where the row-pair kernel runs an epilogue launch and the caller gave tickets, the last chunk item of a hub row to arrive folds the
+  // row inside that launch (fold_ticket: write-through partials, a drained store queue and one counter add per chunk wave; a first form
+  // with an agent-scope release fence in every chunk wave was measured 1.7x slower on the whole launch, every fence writing back the
+  // XCD's dirty L2 lines) and the reduction launch is not enqueued.  gnpde_agg_fold_launch(1) keeps the launch (A/B and bit reference),
+  // as does every other route and every stage that fold_stage does not state.
+  if (g->n_long_rows <= 0) l.fold = GNPDE_SPMM_FOLD_NONE;
+  else if (opt.tickets != nullptr && e != nullptr && p->pair_only && stage_prefetchable(e->stage) && g_agg_fold_launch == 0) l.fold = GNPDE_SPMM_FOLD_IN_KERNEL;
+  else l.fold = l.lo ? GNPDE_SPMM_FOLD_REDUCE4_LO : a16 ? GNPDE_SPMM_FOLD_REDUCE4 : GNPDE_SPMM_FOLD_SCALAR;
+  return 0;
 }
 
-template <int VEC>
-int dispatch_sddmm(const gnpde_graph_t* g, const float* a, const float* b, int d, int lda, int ldb, const float* scale,
-                   int scale_sigmoid, float* out, hipStream_t st) {
-  SddmmArgs s;
-  s.n = g->n; s.n_long_chunks = g->n_long_chunks;
-  s.rowptr = g->rowptr; s.colidx = g->colidx;
-  s.lc_row = g->long_chunk_row; s.lc_begin = g->long_chunk_begin; s.lc_end = g->long_chunk_end;
-  s.a = a; s.b = b; s.d = d; s.lda = lda; s.ldb = ldb; s.scale_ptr = scale; s.scale_sigmoid = scale_sigmoid; s.out = out;
-  s.row_shift = choose_row_shift(g->n, g->xcd_deal);
-  const long long per_xcd = (static_cast<long long>(g->n_long_chunks) + kXcds - 1) / kXcds + xcd_rows_per(g->n, s.row_shift);
-  const unsigned grid = static_cast<unsigned>(((per_xcd + kWavesPerBlock - 1) / kWavesPerBlock) * kXcds);
-  const int slots = (d + VEC - 1) / VEC;
-#define GNPDE_SDDMM(LL, KK, UU) hipLaunchKernelGGL((sddmm_kernel<VEC, LL, KK, UU>), dim3(grid), dim3(kBlock), 0, st, s)
-  if (slots <= 16) GNPDE_SDDMM(16, 1, 4);
-  else if (slots <= 32) GNPDE_SDDMM(16, 2, 4);
-  else if (slots <= 64) GNPDE_SDDMM(32, 2, 2);
-  else if (slots <= 128) GNPDE_SDDMM(64, 2, 2);
-  else if (slots <= 256) GNPDE_SDDMM(64, 4, 1);
-  else {
-    set_error("sddmm: feature width d=%d too large for VEC=%d", d, VEC);
-    return GNPDE_ESHAPE;
+// The launch of a planned kernel: one template per family, LO = the bf16 gather operand.  Only the lines of width_class are instantiated.
+template <int VEC, bool LO>
+bool launch_rows(const SpmmArgs& a, const gnpde_spmm_launch_t& l, unsigned grid, hipStream_t s) {
+#define GNPDE_ROWS(LL, KK, UU)                                                                                              \
+  if (l.L == LL && l.K == KK && l.U == UU) {                                                                                \
+    hipLaunchKernelGGL((spmm_rows_kernel<VEC, LL, KK, UU, LO>), dim3(grid), dim3(kBlock), 0, s, a);                         \
+    return true;                                                                                                            \
   }
-#undef GNPDE_SDDMM
+  GNPDE_ROWS(8, 1, 4) GNPDE_ROWS(16, 1, 4)
+  if constexpr (VEC != 4) { GNPDE_ROWS(16, 2, 4) GNPDE_ROWS(32, 2, 4) }
+  GNPDE_ROWS(64, 2, 2) GNPDE_ROWS(64, 3, 1) GNPDE_ROWS(64, 4, 1)
+#undef GNPDE_ROWS
+  return false;
+}
+
+template <int L, bool LO>
+void launch_wide(const SpmmArgs& a, bool full, unsigned grid, hipStream_t s) {   // 8 gathers in flight, one wavefront per workgroup
+  if (full) hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, true, LO>), dim3(grid), dim3(kWave), 0, s, a);
+  else hipLaunchKernelGGL((spmm_wide_kernel<4, L, 8, false, LO>), dim3(grid), dim3(kWave), 0, s, a);
+}
+
+template <bool LO>
+void launch_pair(const SpmmArgs& a, const gnpde_spmm_launch_t& l, unsigned grid, hipStream_t s) {
+  if constexpr (!LO) {
+    if (l.defer) {    // hub-chunk items that normalise their row's softmax (the row pairs: the same code)
+      if (l.full) hipLaunchKernelGGL((spmm_pair_kernel<4, true, false, true>), dim3(grid), dim3(kWave), 0, s, a);
+      else hipLaunchKernelGGL((spmm_pair_kernel<4, false, false, true>), dim3(grid), dim3(kWave), 0, s, a);
+      return;
+    }
+  }
+  if (l.full) hipLaunchKernelGGL((spmm_pair_kernel<4, true, LO>), dim3(grid), dim3(kWave), 0, s, a);
+  else hipLaunchKernelGGL((spmm_pair_kernel<4, false, LO>), dim3(grid), dim3(kWave), 0, s, a);
+}
+
+int launch_planned(const SpmmArgs& a, const gnpde_spmm_launch_t& l, unsigned grid, hipStream_t s) {
+  if (a.chunk_end <= a.chunk_begin && a.row_end <= a.row_begin) return 0;
+  bool ok = true;
+  switch (l.family) {
+    case GNPDE_SPMM_ROWS:
+      ok = l.lo ? launch_rows<4, true>(a, l, grid, s) : l.lane_bytes == 16 ? launch_rows<4, false>(a, l, grid, s) :
+           l.lane_bytes == 8 ? launch_rows<2, false>(a, l, grid, s) : launch_rows<1, false>(a, l, grid, s);
+      break;
+    case GNPDE_SPMM_WIDE:
+      if (l.L == 32) l.lo ? launch_wide<32, true>(a, l.full, grid, s) : launch_wide<32, false>(a, l.full, grid, s);
+      else l.lo ? launch_wide<64, true>(a, l.full, grid, s) : launch_wide<64, false>(a, l.full, grid, s);
+      break;
+    case GNPDE_SPMM_PAIR:
+      l.lo ? launch_pair<true>(a, l, grid, s) : launch_pair<false>(a, l, grid, s);
+      break;
+    case GNPDE_SPMM_QUAD_LO:
+      hipLaunchKernelGGL((spmm_quad_lo_kernel<16>), dim3(grid), dim3(kWave), 0, s, a);
+      break;
+    default:
+      ok = false;
+  }
+  GNPDE_CHECK_ARG(ok, GNPDE_ESTATE, "spmm: a launch plan names no kernel (family %d, L %d K %d U %d)", l.family, l.L, l.K, l.U);
+  GNPDE_LAUNCH_CHECK();
   return 0;
 }
 
@@ -1776,61 +1743,39 @@ __global__ __launch_bounds__(kWave) void adjoint_long_reduce4_kernel(const AdjRo
 
 }  // namespace
 
-namespace {
-// grid of the adjoint row kernel: one wavefront per work item.  (A row-PAIR form as spmm_pair_kernel -- two rows of <= 32 entries per
+// THE grid formula (common.h): blocks of waves_per_block waves so that every XCD can reach the end of its local list
+unsigned agg_grid(long long chunks, long long rows, int row_shift, int rows_per_wave, int waves_per_block) {
+  const long long per = xcd_rows_per(static_cast<int>(rows), row_shift);
+  const long long waves = (chunks + kXcds - 1) / kXcds + (per + rows_per_wave - 1) / rows_per_wave;
+  long long blocks = (waves + waves_per_block - 1) / waves_per_block;
+  if (blocks < 1) blocks = 1;
+  return static_cast<unsigned>(blocks * kXcds);
+}
+
+// Grid of the adjoint row kernel: one wavefront per work item.  (A row-PAIR form as spmm_pair_kernel -- two rows of <= 32 entries per
 // wave, 16 gathers in flight per half -- was built and measured SLOWER at the ogbn-arxiv shape, 263 vs 248 us: with the 16 partial
 // dots and g_i next to the 16 gathered float4s it needs 140 VGPRs, three waves per SIMD against five here; profiles/r04_train_*.)
-inline unsigned adjoint_rows_grid(const gnpde_graph_t* g) {
-  SpmmArgs a{};
-  a.chunk_begin = 0; a.chunk_end = g->n_long_chunks; a.row_begin = 0; a.row_end = g->n;
-  a.row_shift = choose_row_shift(g->n, g->xcd_deal);
-  return balanced_grid(a, 1);
-}
-}  // namespace
-
-// number of per-wave dot slots launch_adjoint_rows writes (its grid + one per long row)
+// Number of per-wave dot slots launch_adjoint_rows writes: that grid + one per long row.
 int adjoint_rows_dot_slots(const gnpde_graph_t* g, int d) {
   (void)d;
-  return static_cast<int>(adjoint_rows_grid(g)) + g->n_long_rows;
+  return static_cast<int>(agg_grid(g->n_long_chunks, g->n, choose_row_shift(g->n, g->xcd_deal), 1, 1)) + g->n_long_rows;
 }
 
 int launch_adjoint_rows(const gnpde_graph_t* g, const float* w_csr, const float* u, const float* gvec, int d, int ld,
                         const gnpde_epilogue_t* epi, float* r_out, float* dots, void* ws, size_t ws_bytes, hipStream_t stream,
                         bool padded_rows, bool accumulate_r, float r_scale, const int* wpos) {
   GNPDE_CHECK_ARG(g && u && gvec && epi && r_out && dots && (w_csr || g->e == 0), GNPDE_EINVAL, "adjoint_rows: null pointer");
-  const int stg = epi->stage;
-  GNPDE_CHECK_ARG((stg == GNPDE_STAGE_LINCOMB || stg == GNPDE_STAGE_EULER || (stg >= GNPDE_STAGE_RK1C && stg <= GNPDE_STAGE_RK4C)) &&
-                  epi->alpha != nullptr && (epi->x0 == nullptr || epi->beta != nullptr), GNPDE_EINVAL,
-                  "adjoint_rows: needs a LINCOMB, euler or compact rk4 epilogue");
-  GNPDE_CHECK_ARG(stg != GNPDE_STAGE_LINCOMB || (epi->n_prev >= 0 && epi->n_prev <= GNPDE_MAX_PREV && (epi->out_y == nullptr || epi->y != nullptr)),
-                  GNPDE_EINVAL, "adjoint_rows: bad LINCOMB epilogue");
-  GNPDE_CHECK_ARG(stg == GNPDE_STAGE_LINCOMB || epi->out_y != nullptr, GNPDE_EINVAL, "adjoint_rows: out_y is null");
-  GNPDE_CHECK_ARG(!(stg == GNPDE_STAGE_EULER || stg == GNPDE_STAGE_RK2C || stg == GNPDE_STAGE_RK4C) || epi->y != nullptr, GNPDE_EINVAL, "adjoint_rows: y is null");
-  GNPDE_CHECK_ARG(!(stg == GNPDE_STAGE_RK3C || stg == GNPDE_STAGE_RK4C) || epi->k1 != nullptr, GNPDE_EINVAL, "adjoint_rows: k1 is null");
-  GNPDE_CHECK_ARG(epi->out_k != u && epi->out_y != u, GNPDE_EINVAL, "adjoint_rows: output aliases the gathered operand");
+  if (const int rc = check_epilogue("adjoint_rows", *epi, u, kStagesAdjoint)) return rc;      // LINCOMB, euler or compact rk4
   GNPDE_CHECK_ARG(g->row_begin == 0 && d >= 1 && d <= 256 && ld >= d && ld % 4 == 0 && (d % 4 == 0 || padded_rows), GNPDE_ESHAPE,
                   "adjoint_rows: whole graphs, rows of up to 256 floats in 16-byte lanes");
   if (g->n == 0) return 0;
   AdjRowsArgs fa{};
   SpmmArgs& a = fa.s;
-  a.n = g->n; a.n_long_chunks = g->n_long_chunks;
-  a.rowptr = g->rowptr; a.colidx = g->colidx;
-  a.lc_row = g->long_chunk_row; a.lc_begin = g->long_chunk_begin; a.lc_end = g->long_chunk_end;
-  a.w = w_csr; a.u = u; a.d = d; a.ld = ld; a.plain_out = nullptr;
-  a.ldp = static_cast<int>(align_up(static_cast<size_t>(d), 4));
-  a.partial = static_cast<float*>(ws);
+  if (const int rc = fill_args(a, g, w_csr, u, d, ld, ws, ws_bytes, "adjoint_rows")) return rc;
   a.ep = *epi;
-  a.chunk_begin = 0; a.chunk_end = g->n_long_chunks; a.row_begin = 0; a.row_end = g->n;
-  a.row_shift = choose_row_shift(g->n, g->xcd_deal);
-  if (g->n_long_chunks > 0) {
-    const size_t need = static_cast<size_t>(g->n_long_chunks) * a.ldp * sizeof(float);
-    GNPDE_CHECK_ARG(ws != nullptr && ws_bytes >= need, GNPDE_EWS, "adjoint_rows: workspace %zu < %zu bytes", ws_bytes, need);
-  }
-  const void* ptrs[] = {u, gvec, ws, epi->x0, epi->y, epi->k1, epi->out_k, epi->out_y, stg == GNPDE_STAGE_LINCOMB ? epi->prev[0] : nullptr,
-                        stg == GNPDE_STAGE_LINCOMB ? epi->prev[1] : nullptr, stg == GNPDE_STAGE_LINCOMB ? epi->prev[2] : nullptr};
-  for (const void* p : ptrs) GNPDE_CHECK_ARG(aligned(p, 16), GNPDE_EINVAL, "adjoint_rows: operands must be 16-byte aligned");
+  GNPDE_CHECK_ARG(on_lanes(16, ld, u, gvec, ws, epi), GNPDE_EINVAL, "adjoint_rows: operands must be 16-byte aligned");
   fa.g = gvec; fa.r = r_out; fa.dots = dots; fa.r_accumulate = accumulate_r ? 1 : 0; fa.r_scale = r_scale; fa.wpos = wpos;
-  const unsigned grid = adjoint_rows_grid(g);
+  const unsigned grid = agg_grid(a.chunk_end, a.row_end, a.row_shift, 1, 1);
   const int slots = (d + 3) / 4;
   if (slots <= 16) hipLaunchKernelGGL((adjoint_rows_kernel<16, 8>), dim3(grid), dim3(kWave), 0, stream, fa);
   else if (slots <= 32) hipLaunchKernelGGL((adjoint_rows_kernel<32, 8>), dim3(grid), dim3(kWave), 0, stream, fa);
@@ -1848,181 +1793,68 @@ int launch_adjoint_rows(const gnpde_graph_t* g, const float* w_csr, const float*
 static std::atomic<long long> g_in_kernel_folds{0};
 
 int launch_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int d, int ld,
-                    const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes, hipStream_t stream,
-                    const Fork* fork, bool padded_rows, const LoPair* lo, const HubDefer* defer, void* tickets, size_t ticket_bytes) {
-  if (lo != nullptr && lo->u_lo == nullptr) lo = nullptr;
-  if (defer != nullptr && (defer->taken == 0 || g == nullptr || g->n_long_rows == 0)) defer = nullptr;
-  // (a plain aggregation from a shadow has no fp32 table at all)
-  GNPDE_CHECK_ARG(g && (u || (lo && plain_out)) && (w_csr || g->e == 0), GNPDE_EINVAL, "spmm: null pointer");
-  GNPDE_CHECK_ARG(d >= 1 && ld >= d, GNPDE_EINVAL, "spmm: bad d=%d ld=%d", d, ld);
-  GNPDE_CHECK_ARG((epi != nullptr) != (plain_out != nullptr), GNPDE_EINVAL, "spmm: need exactly one of epilogue / plain output");
-  GNPDE_CHECK_ARG(tickets == nullptr || (ticket_bytes >= gnpde_spmm_ticket_bytes(g) && aligned(tickets, 4)), GNPDE_EWS,
-                  "spmm: tickets %zu < %zu bytes (one 32-bit word per long row)", ticket_bytes, gnpde_spmm_ticket_bytes(g));
+                    const gnpde_epilogue_t* epi, float* plain_out, void* ws, size_t ws_bytes, hipStream_t stream, const SpmmOptions& opt) {
+  GNPDE_CHECK_ARG(g && (w_csr || g->e == 0), GNPDE_EINVAL, "spmm: null pointer");
+  GNPDE_CHECK_ARG(opt.tickets == nullptr || (opt.ticket_bytes >= gnpde_spmm_ticket_bytes(g) && aligned(opt.tickets, 4)), GNPDE_EWS,
+                  "spmm: tickets %zu < %zu bytes (one 32-bit word per long row)", opt.ticket_bytes, gnpde_spmm_ticket_bytes(g));
+  SpmmPlan plan;
+  if (const int rc = plan_spmm(g, u, d, ld, epi, plain_out, ws, opt, &plan)) return rc;
   if (g->n == 0) return 0;
+  const gnpde_spmm_launch_t& l = plan.l;
   SpmmArgs a{};
-  a.n = g->n;
-  a.n_long_chunks = g->n_long_chunks;
-  a.rowptr = g->rowptr;
-  a.colidx = g->colidx;
-  a.lc_row = g->long_chunk_row;
-  a.lc_begin = g->long_chunk_begin;
-  a.lc_end = g->long_chunk_end;
-  a.w = w_csr;
-  a.u = u;
-  a.d = d;
-  a.ld = ld;
+  if (const int rc = fill_args(a, g, w_csr, u, d, ld, ws, ws_bytes, "spmm")) return rc;
   a.plain_out = plain_out;
-  a.ldp = static_cast<int>(align_up(static_cast<size_t>(d), 4));
-  a.partial = static_cast<float*>(ws);
-  if (g->n_long_chunks > 0) {
-    const size_t need = static_cast<size_t>(g->n_long_chunks) * a.ldp * sizeof(float);
-    GNPDE_CHECK_ARG(ws != nullptr && ws_bytes >= need, GNPDE_EWS, "spmm: workspace %zu < %zu bytes", ws_bytes, need);
-    GNPDE_CHECK_ARG(g->long_rows && g->long_chunk_ptr && g->long_chunk_row && g->long_chunk_begin && g->long_chunk_end,
-                    GNPDE_EINVAL, "spmm: long-row arrays missing");
+  if (epi) a.ep = *epi;
+  if (l.lo) {
+    a.u_lo = opt.lo->u_lo;
+    a.out_y_lo = epi ? opt.lo->out_y_lo : nullptr;
   }
-  // padded_rows: the caller guarantees that columns [d, ld) of every operand are padding (GNPDE_RHS_PADDED_ROWS), so a
-  // width that is not a multiple of 4 still takes 16-byte lanes (the last lane reads / writes up to 3 padding columns)
-  bool a16 = (d % 4 == 0 || padded_rows) && (ld % 4 == 0) && aligned(u, 16) && aligned(plain_out, 16) && aligned(ws, 16);
-  bool a8 = (d % 2 == 0) && (ld % 2 == 0) && aligned(u, 8) && aligned(plain_out, 8) && aligned(ws, 8);
-  if (epi) {
-    a.ep = *epi;
-    const gnpde_epilogue_t& e = a.ep;
-    GNPDE_CHECK_ARG(e.alpha != nullptr, GNPDE_EINVAL, "spmm: alpha pointer is null");
-    GNPDE_CHECK_ARG(e.x0 == nullptr || e.beta != nullptr, GNPDE_EINVAL, "spmm: x0 given without beta");
-    GNPDE_CHECK_ARG(e.stage >= GNPDE_STAGE_RHS && e.stage <= GNPDE_STAGE_LINCOMB, GNPDE_EINVAL, "spmm: bad stage %d", e.stage);
-    const int st = e.stage;
-    if (st == GNPDE_STAGE_LINCOMB) {
-      GNPDE_CHECK_ARG(e.n_prev >= 0 && e.n_prev <= GNPDE_MAX_PREV, GNPDE_EINVAL, "spmm: bad n_prev %d", e.n_prev);
-      GNPDE_CHECK_ARG(e.out_k != nullptr || e.out_y != nullptr, GNPDE_EINVAL, "spmm: LINCOMB without output");
-      GNPDE_CHECK_ARG(e.out_y == nullptr || e.y != nullptr, GNPDE_EINVAL, "spmm: LINCOMB needs y");
-      for (int j = 0; j < e.n_prev; ++j) {
-        GNPDE_CHECK_ARG(e.prev[j] != nullptr, GNPDE_EINVAL, "spmm: LINCOMB prev[%d] is null", j);
-        a16 = a16 && aligned(e.prev[j], 16);
-        a8 = a8 && aligned(e.prev[j], 8);
-      }
-    }
-    const bool needs_k = st == GNPDE_STAGE_RHS || (st >= GNPDE_STAGE_RK1 && st <= GNPDE_STAGE_RK3);
-    const bool needs_y = st == GNPDE_STAGE_EULER || (st >= GNPDE_STAGE_RK1 && st <= GNPDE_STAGE_RK4) ||
-                         st == GNPDE_STAGE_RK2C || st == GNPDE_STAGE_RK4C;
-    const bool needs_k1 = (st >= GNPDE_STAGE_RK2 && st <= GNPDE_STAGE_RK4) || st == GNPDE_STAGE_RK3C || st == GNPDE_STAGE_RK4C;
-    GNPDE_CHECK_ARG(!needs_k || e.out_k != nullptr, GNPDE_EINVAL, "spmm: out_k is null");
-    GNPDE_CHECK_ARG(st == GNPDE_STAGE_RHS || st == GNPDE_STAGE_LINCOMB || e.out_y != nullptr, GNPDE_EINVAL, "spmm: out_y is null");
-    GNPDE_CHECK_ARG(!needs_y || e.y != nullptr, GNPDE_EINVAL, "spmm: y is null");
-    GNPDE_CHECK_ARG(!needs_k1 || e.k1 != nullptr, GNPDE_EINVAL, "spmm: k1 is null");
-    GNPDE_CHECK_ARG(!(st == GNPDE_STAGE_RK3 || st == GNPDE_STAGE_RK4) || e.k2 != nullptr, GNPDE_EINVAL, "spmm: k2 is null");
-    GNPDE_CHECK_ARG(st != GNPDE_STAGE_RK4 || e.k3 != nullptr, GNPDE_EINVAL, "spmm: k3 is null");
-    // every row gathers from u while other rows run their epilogue: outputs must not alias u
-    GNPDE_CHECK_ARG(e.out_k != u && e.out_y != u, GNPDE_EINVAL, "spmm: output aliases the gathered operand");
-    const void* ptrs[] = {e.x0, e.y, e.k1, e.k2, e.k3, e.out_k, e.out_y};
-    for (const void* p : ptrs) {
-      a16 = a16 && aligned(p, 16);
-      a8 = a8 && aligned(p, 8);
-    }
-  } else {
-    GNPDE_CHECK_ARG(plain_out != u, GNPDE_EINVAL, "spmm: output aliases the gathered operand");
-  }
-  if (lo != nullptr) {
-    a.u_lo = lo->u_lo;
-    a.out_y_lo = epi ? lo->out_y_lo : nullptr;
-    GNPDE_CHECK_ARG(a16 && aligned(a.u_lo, 8) && aligned(a.out_y_lo, 8), GNPDE_ESHAPE,
-                    "spmm: the bf16 gather operand needs 16-byte lanes (d %% 4 == 0, or padded rows with ld %% 4 == 0; 16-byte aligned "
-                    "operands, 8-byte aligned shadows): d=%d ld=%d", d, ld);
-    GNPDE_CHECK_ARG(a.out_y_lo == nullptr || a.out_y_lo != a.u_lo, GNPDE_EINVAL, "spmm: a stage must not write the shadow it gathers from");
-  }
-  auto run = [&](const SpmmArgs& arg, hipStream_t st) -> int {
-    if (arg.chunk_end <= arg.chunk_begin && arg.row_end <= arg.row_begin) return 0;
-    if (lo != nullptr) return dispatch_rows_lo(arg, st);
-    if (a16) return dispatch_rows<4>(arg, st);
-    if (a8) return dispatch_rows<2>(arg, st);
-    return dispatch_rows<1>(arg, st);
-  };
-  const bool forked = fork != nullptr && fork->aux != nullptr && g->n_long_rows > 0;
-  if (defer != nullptr) {
-    // the hub entries' weights do not exist yet: only the kernels whose chunk items form them may run (spmm_hub_defer_supported)
-    GNPDE_CHECK_ARG(a16 && lo == nullptr && !forked && pair_kernel_route(d, mostly_short_rows(g)) && g->row_begin == 0 &&
-                    g_tune[GNPDE_TUNE_SPMM_PART] == 0 &&
-                    defer->part && defer->scores && defer->chunk_first && defer->w_out == w_csr && defer->h >= 1 && defer->h <= 8 &&
-                    aligned(defer->scores, 16),
-                    GNPDE_EINVAL, "spmm: deferred hub weights need the row-pair kernel (16-byte lanes, d = 68..128, mostly short rows, the whole graph; d=%d ld=%d)", d, ld);
+  if (l.defer) {     // the hub entries' weights do not exist yet: the planned kernel's chunk items form them
+    const HubDefer* defer = opt.defer;
+    GNPDE_CHECK_ARG(defer->part && defer->scores && defer->chunk_first && defer->w_out == w_csr && defer->h >= 1 && defer->h <= 8 &&
+                    aligned(defer->scores, 16), GNPDE_EINVAL, "spmm: incomplete deferred hub weights (h=%d)", defer->h);
     a.hub_part = defer->part;
     a.hub_scores = defer->scores;
     a.hub_chunk_first = defer->chunk_first;
     a.w_out = defer->w_out;
     a.hub_h = defer->h;
   }
-  // rows and long-row chunks in one launch, then the per-row reduction of the chunk partials; with a fork the chunks + reduction
-  // run as a parallel branch.  The boundary pass of a partitioned graph covers rows [row_begin, n) only (its chunks belong to those rows).
-  // Where the row-pair kernel runs an epilogue launch over the whole graph on one stream from the fp32 table and the caller gave
-  // tickets, the last chunk item of a hub row to arrive folds the row inside that launch (fold_ticket: write-through partials, a
-  // drained store queue and one counter add per chunk wave; a first form with an agent-scope release fence in every chunk wave was
-  // measured 1.7x slower on the whole launch, every fence writing back the XCD's dirty L2 lines) and the reduction launch is not
-  // enqueued.  gnpde_agg_fold_launch(1) keeps the launch (A/B and bit reference), as does every other route.
-  GNPDE_CHECK_ARG(g->row_begin >= 0 && g->row_begin <= g->n, GNPDE_EINVAL, "spmm: bad row_begin %d", g->row_begin);
-  GNPDE_CHECK_ARG(!(forked && g->row_begin > 0), GNPDE_EINVAL, "spmm: fork with row_begin");
-  a.chunk_begin = 0;
-  a.chunk_end = forked ? 0 : g->n_long_chunks;
-  a.short_rows = mostly_short_rows(g) ? 1 : 0;
-  a.row_begin = g->row_begin;
-  a.row_end = g->n;
-  a.row_shift = choose_row_shift(static_cast<long long>(a.row_end) - a.row_begin, g->xcd_deal);
-  if (g_tune[GNPDE_TUNE_SPMM_PART] == 1) a.row_end = a.row_begin;       // (timing the two kinds of work items separately)
-  if (g_tune[GNPDE_TUNE_SPMM_PART] == 2) a.chunk_end = 0;
-  const bool fold_in_kernel = tickets != nullptr && epi != nullptr && g->n_long_rows > 0 && !forked && lo == nullptr && g->row_begin == 0 &&
-                              a16 && pair_kernel_route(d, a.short_rows != 0) &&
-                              (epi->stage == GNPDE_STAGE_RHS || epi->stage == GNPDE_STAGE_EULER || (epi->stage >= GNPDE_STAGE_RK1C && epi->stage <= GNPDE_STAGE_RK4C)) &&   // (the stages fold_stage states)
-                              g_tune[GNPDE_TUNE_SPMM_PART] == 0 && g_agg_fold_launch == 0;
-  if (fold_in_kernel) {
-    a.tickets = static_cast<unsigned*>(tickets);
+  a.chunk_end = plan.chunk_end;
+  a.row_end = plan.row_end;
+  if (l.fold == GNPDE_SPMM_FOLD_IN_KERNEL) {
+    a.tickets = static_cast<unsigned*>(opt.tickets);
     a.long_chunk_ptr = g->long_chunk_ptr;
     a.n_long_rows = g->n_long_rows;
   }
-  int rc = run(a, stream);
-  if (rc != 0) return rc;
+  if (const int rc = launch_planned(a, l, l.grid, stream)) return rc;
+  if (l.fold == GNPDE_SPMM_FOLD_IN_KERNEL) g_in_kernel_folds.fetch_add(1, std::memory_order_relaxed);
+  if (l.fold == GNPDE_SPMM_FOLD_NONE || l.fold == GNPDE_SPMM_FOLD_IN_KERNEL) return 0;
+  hipStream_t br = stream;
+  if (l.forked) {
+    if (const int rc = fork_begin(opt.fork, stream, &br)) return rc;
+    SpmmArgs c = a;
+    c.chunk_end = g->n_long_chunks;
+    c.row_begin = c.row_end = 0;
+    if (const int rc = launch_planned(c, l, plan_grid(l, c.chunk_end, 0, c.row_shift), br)) return rc;
+  }
+  if (l.fold == GNPDE_SPMM_FOLD_REDUCE4_LO)
+    hipLaunchKernelGGL(spmm_long_reduce4_kernel<true>, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
+  else if (l.fold == GNPDE_SPMM_FOLD_REDUCE4)
+    hipLaunchKernelGGL(spmm_long_reduce4_kernel<false>, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
+  else
+    hipLaunchKernelGGL(spmm_long_reduce_kernel, dim3(g->n_long_rows), dim3(kBlock), 0, br, a, g->long_rows, g->long_chunk_ptr);
   GNPDE_LAUNCH_CHECK();
-  if (fold_in_kernel) {
-    g_in_kernel_folds.fetch_add(1, std::memory_order_relaxed);
-    return 0;
-  }
-  if (g->n_long_rows > 0) {
-    hipStream_t br = stream;
-    if (forked) { const int frc = fork_begin(fork, stream, &br); if (frc) return frc; }
-    if (forked) {
-      SpmmArgs c = a;
-      c.chunk_end = g->n_long_chunks;
-      c.row_begin = c.row_end = 0;
-      rc = run(c, br);
-      if (rc != 0) return rc;
-      GNPDE_LAUNCH_CHECK();
-    }
-    if (lo != nullptr)
-      hipLaunchKernelGGL(spmm_long_reduce4_kernel<true>, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
-    else if (a16)
-      hipLaunchKernelGGL(spmm_long_reduce4_kernel<false>, dim3(g->n_long_rows), dim3(kWave), 0, br, a, g->long_rows, g->long_chunk_ptr);
-    else
-      hipLaunchKernelGGL(spmm_long_reduce_kernel, dim3(g->n_long_rows), dim3(kBlock), 0, br, a, g->long_rows,
-                         g->long_chunk_ptr);
-    GNPDE_LAUNCH_CHECK();
-    if (forked) { const int frc = fork_end(fork, stream, br); if (frc) return frc; }
-  }
-  return 0;
+  return l.forked ? fork_end(opt.fork, stream, br) : 0;
 }
-
 
 // the route test of launch_spmm_rhs for an epilogue launch, ahead of the attention that decides on the one-launch form
 bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int ld, const gnpde_epilogue_t& e, const void* ws,
                               bool padded_rows) {
-  // the row-pair kernel (dispatch_rows<4>: 17..32 lanes of 16 bytes, at least half of the rows with <= 16 entries).  The wide-row kernel is
-  // left as it is: with the deferred path its instantiations need 92 - 101 VGPRs instead of 80 - 86 (a wave per SIMD less for EVERY row of
-  // the launch) and spill SGPRs, for the sake of the hub chunks alone.
-  if (g == nullptr || u == nullptr || !pair_kernel_route(d, mostly_short_rows(g)) || g->row_begin != 0 ||
-      g_tune[GNPDE_TUNE_SPMM_PART] != 0)
-    return false;
-  bool a16 = (d % 4 == 0 || padded_rows) && (ld % 4 == 0) && aligned(u, 16) && aligned(ws, 16);
-  if (e.stage == GNPDE_STAGE_LINCOMB)
-    for (int j = 0; j < e.n_prev && j < GNPDE_MAX_PREV; ++j) a16 = a16 && aligned(e.prev[j], 16);
-  const void* ptrs[] = {e.x0, e.y, e.k1, e.k2, e.k3, e.out_k, e.out_y};
-  for (const void* p : ptrs) a16 = a16 && aligned(p, 16);
-  return a16;
+  if (g == nullptr || u == nullptr) return false;
+  SpmmOptions opt;
+  opt.padded_rows = padded_rows;
+  SpmmPlan plan;
+  return plan_spmm(g, u, d, ld, &e, nullptr, ws, opt, &plan) == 0 && plan.pair_only;
 }
 
 bool attn_spmm_supported(const gnpde_graph_t* g, const gnpde_attention_t& at, int d, int ld, const float* u,
@@ -2038,13 +1870,7 @@ bool attn_spmm_supported(const gnpde_graph_t* g, const gnpde_attention_t& at, in
   if (!((at.heads == 4 && dk == 4) || (at.heads == 8 && dk == 16) || (at.heads == 4 && dk == 16) || (at.heads == 2 && dk == 16)))
     return false;
   const int slots = (d + 3) / 4;
-  if (ld % 4 != 0 || slots <= 16 || slots > 64 || g->row_begin != 0) return false;
-  if (e.stage == GNPDE_STAGE_LINCOMB) {
-    for (int j = 0; j < e.n_prev; ++j) if (!aligned(e.prev[j], 16)) return false;
-  }
-  const void* ptrs[] = {u, e.x0, e.y, e.k1, e.k2, e.k3, e.out_k, e.out_y};
-  for (const void* p : ptrs) if (!aligned(p, 16)) return false;
-  return true;
+  return slots > 16 && slots <= 64 && g->row_begin == 0 && on_lanes(16, ld, u, nullptr, nullptr, &e);
 }
 
 // rows: attention + aggregation in one kernel; hub chunks aggregate with the weights in w_hub_csr (written before by
@@ -2053,24 +1879,13 @@ int launch_attn_spmm(const gnpde_graph_t* g, const gnpde_attention_t* at, const 
                      const gnpde_epilogue_t* epi, void* ws, size_t ws_bytes, hipStream_t stream, bool padded_rows) {
   GNPDE_CHECK_ARG(g && at && u && epi && at->q && at->k, GNPDE_EINVAL, "attn_spmm: null argument");
   GNPDE_CHECK_ARG(d % 4 == 0 || padded_rows, GNPDE_ESHAPE, "attn_spmm: width %d needs padded rows", d);
-  GNPDE_CHECK_ARG(epi->alpha != nullptr && (epi->x0 == nullptr || epi->beta != nullptr), GNPDE_EINVAL, "attn_spmm: bad epilogue");
-  GNPDE_CHECK_ARG(epi->out_k != u && epi->out_y != u, GNPDE_EINVAL, "attn_spmm: output aliases the gathered operand");
+  if (const int rc = check_epilogue("attn_spmm", *epi, u, kStagesAll)) return rc;
   if (g->n == 0) return 0;
   AttnSpmmArgs fa{};
   SpmmArgs& a = fa.s;
-  a.n = g->n; a.n_long_chunks = g->n_long_chunks;
-  a.rowptr = g->rowptr; a.colidx = g->colidx;
-  a.lc_row = g->long_chunk_row; a.lc_begin = g->long_chunk_begin; a.lc_end = g->long_chunk_end;
-  a.w = w_hub_csr; a.u = u; a.d = d; a.ld = ld; a.plain_out = nullptr;
-  a.ldp = static_cast<int>(align_up(static_cast<size_t>(d), 4));
-  a.partial = static_cast<float*>(ws);
+  GNPDE_CHECK_ARG(g->row_begin == 0 && (g->n_long_chunks == 0 || w_hub_csr != nullptr), GNPDE_EINVAL, "attn_spmm: whole graphs, hub weights given");
+  if (const int rc = fill_args(a, g, w_hub_csr, u, d, ld, ws, ws_bytes, "attn_spmm")) return rc;
   a.ep = *epi;
-  a.chunk_begin = 0; a.chunk_end = g->n_long_chunks; a.row_begin = 0; a.row_end = g->n;
-  a.row_shift = choose_row_shift(g->n, g->xcd_deal);
-  if (g->n_long_chunks > 0) {
-    const size_t need = static_cast<size_t>(g->n_long_chunks) * a.ldp * sizeof(float);
-    GNPDE_CHECK_ARG(ws != nullptr && ws_bytes >= need && w_hub_csr != nullptr, GNPDE_EWS, "attn_spmm: workspace %zu < %zu bytes", ws_bytes, need);
-  }
   fa.q = at->q; fa.k = at->k; fa.ldqk = at->ldqk;
   const int dk = at->att_dim / at->heads;
   fa.inv_sqrt_dk = 1.0f / sqrtf(static_cast<float>(dk));
@@ -2091,6 +1906,32 @@ int launch_attn_spmm(const gnpde_graph_t* g, const gnpde_attention_t* at, const 
 }
 
 }  // namespace gnpde
+
+extern "C" int gnpde_spmm_plan(const gnpde_graph_t* g, uint64_t u_addr, int32_t d, int32_t ld, const gnpde_epilogue_t* epi, uint64_t plain_out_addr,
+                               uint64_t workspace_addr, int32_t padded_rows, uint32_t flags, gnpde_spmm_launch_t* plan) {
+  GNPDE_CHECK_ARG(plan != nullptr, GNPDE_EINVAL, "spmm_plan: plan is null");
+  auto ptr = [](uint64_t v) { return reinterpret_cast<const void*>(static_cast<uintptr_t>(v)); };
+  // stand-ins for what the flags say is given: the planner reads that they are there, and the alignment of the two shadows (16 bytes)
+  gnpde::LoPair lo;
+  lo.u_lo = reinterpret_cast<const uint16_t*>(uintptr_t{16});
+  lo.out_y_lo = reinterpret_cast<uint16_t*>(uintptr_t{32});
+  gnpde::Fork fork;
+  fork.aux = reinterpret_cast<hipStream_t>(uintptr_t{16});
+  gnpde::HubDefer defer;
+  defer.taken = 1;
+  gnpde::SpmmOptions opt;
+  opt.padded_rows = padded_rows != 0;
+  if (flags & GNPDE_SPMM_PLAN_LO) opt.lo = &lo;
+  if (flags & GNPDE_SPMM_PLAN_FORK) opt.fork = &fork;
+  if (flags & GNPDE_SPMM_PLAN_DEFER) opt.defer = &defer;
+  if (flags & GNPDE_SPMM_PLAN_TICKETS) opt.tickets = &lo;
+  gnpde::SpmmPlan p;
+  const int rc = gnpde::plan_spmm(g, ptr(u_addr), d, ld, epi, ptr(plain_out_addr), ptr(workspace_addr), opt, &p);
+  *plan = p.l;
+  return rc;
+}
+
+extern "C" int32_t gnpde_adjoint_rows_dot_slots(const gnpde_graph_t* g, int32_t d) { return g ? gnpde::adjoint_rows_dot_slots(g, d) : 0; }
 
 extern "C" int gnpde_xcd_row_map(int32_t row_begin, int32_t row_end, int32_t deal, int32_t* row_shift, int32_t* rows_per_xcd,
                                  int32_t* map) {
@@ -2123,8 +1964,10 @@ extern "C" int gnpde_spmm_rhs_tickets(const gnpde_graph_t* g, const float* w_csr
                                       size_t ticket_bytes, void* stream) {
   GNPDE_CHECK_ARG(epi != nullptr, GNPDE_EINVAL, "spmm_rhs: epilogue is null");
   GNPDE_CHECK_ARG(tickets != nullptr || ticket_bytes == 0, GNPDE_EINVAL, "spmm_rhs: ticket bytes without tickets");
-  return gnpde::launch_spmm_rhs(g, w_csr, u, d, ld, epi, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream),
-                                nullptr, false, nullptr, nullptr, tickets, ticket_bytes);
+  gnpde::SpmmOptions opt;
+  opt.tickets = tickets;
+  opt.ticket_bytes = ticket_bytes;
+  return gnpde::launch_spmm_rhs(g, w_csr, u, d, ld, epi, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), opt);
 }
 
 extern "C" int gnpde_spmm_rhs(const gnpde_graph_t* g, const float* w_csr, const float* u, int32_t d, int32_t ld,
@@ -2141,28 +1984,15 @@ extern "C" int gnpde_spmm(const gnpde_graph_t* g, const float* w_csr, const floa
                                 static_cast<hipStream_t>(stream));
 }
 
-extern "C" int gnpde_sddmm(const gnpde_graph_t* g, const float* a, int32_t lda, const float* b, int32_t ldb, int32_t d,
-                           const float* scale, int32_t scale_sigmoid, float* out_csr, void* stream) {
-  using namespace gnpde;
-  GNPDE_CHECK_ARG(g && a && b && out_csr && d >= 1 && lda >= d && ldb >= d, GNPDE_EINVAL, "sddmm: bad arguments");
-  if (g->n == 0 || g->e == 0) return 0;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc;
-  if (d % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && aligned(a, 16) && aligned(b, 16)) rc = dispatch_sddmm<4>(g, a, b, d, lda, ldb, scale, scale_sigmoid, out_csr, s);
-  else if (d % 2 == 0 && lda % 2 == 0 && ldb % 2 == 0 && aligned(a, 8) && aligned(b, 8)) rc = dispatch_sddmm<2>(g, a, b, d, lda, ldb, scale, scale_sigmoid, out_csr, s);
-  else rc = dispatch_sddmm<1>(g, a, b, d, lda, ldb, scale, scale_sigmoid, out_csr, s);
-  if (rc) return rc;
-  GNPDE_LAUNCH_CHECK();
-  return 0;
-}
-
 extern "C" int gnpde_spmm_lo(const gnpde_graph_t* g, const float* w_csr, const void* u_lo, int32_t d, int32_t ld,
                              float* out, void* workspace, size_t workspace_bytes, void* stream) {
   GNPDE_CHECK_ARG(out != nullptr && u_lo != nullptr, GNPDE_EINVAL, "spmm_lo: out / u_lo is null");
   gnpde::LoPair lo;
   lo.u_lo = static_cast<const uint16_t*>(u_lo);
-  return gnpde::launch_spmm_rhs(g, w_csr, nullptr, d, ld, nullptr, out, workspace, workspace_bytes,
-                                static_cast<hipStream_t>(stream), nullptr, /*padded_rows=*/ld % 4 == 0, &lo);
+  gnpde::SpmmOptions opt;
+  opt.padded_rows = ld % 4 == 0;
+  opt.lo = &lo;
+  return gnpde::launch_spmm_rhs(g, w_csr, nullptr, d, ld, nullptr, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), opt);
 }
 
 extern "C" int gnpde_spmm_rhs_lo(const gnpde_graph_t* g, const float* w_csr, const float* u, const void* u_lo, int32_t d, int32_t ld,
@@ -2171,6 +2001,8 @@ extern "C" int gnpde_spmm_rhs_lo(const gnpde_graph_t* g, const float* w_csr, con
   gnpde::LoPair lo;
   lo.u_lo = static_cast<const uint16_t*>(u_lo);
   lo.out_y_lo = static_cast<uint16_t*>(out_y_lo);
-  return gnpde::launch_spmm_rhs(g, w_csr, u, d, ld, epi, nullptr, workspace, workspace_bytes,
-                                static_cast<hipStream_t>(stream), nullptr, /*padded_rows=*/ld % 4 == 0, &lo);
+  gnpde::SpmmOptions opt;
+  opt.padded_rows = ld % 4 == 0;
+  opt.lo = &lo;
+  return gnpde::launch_spmm_rhs(g, w_csr, u, d, ld, epi, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), opt);
 }

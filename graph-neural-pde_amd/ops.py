@@ -255,6 +255,19 @@ def spmm_rhs(graph, w_csr, u, alpha, beta=None, x0=None, alpha_sigmoid=True, out
   return out
 
 
+def spmm_plan(graph, u_addr, d, ld, epi=None, plain_out_addr=0, ws_addr=0, padded_rows=False, lo=False, tickets=False, defer=False,
+              fork=False):
+  """The launch an aggregation with these operands takes (gnpde_spmm_plan -> _lib.SpmmLaunchStruct): kernel family and template line,
+  lanes, grid, fork and hub-row fold.  Addresses are integers read for their alignment only; epi is an epilogue (make_epilogue) or None
+  for the plain aggregation to plain_out_addr.  Nothing is launched and no device is needed; a call the launch would refuse raises."""
+  plan = _lib.SpmmLaunchStruct()
+  flags = (_lib.SPMM_PLAN_LO * bool(lo) | _lib.SPMM_PLAN_TICKETS * bool(tickets) | _lib.SPMM_PLAN_DEFER * bool(defer) |
+           _lib.SPMM_PLAN_FORK * bool(fork))
+  check(_lib.lib().gnpde_spmm_plan(graph.ref(), int(u_addr), d, ld, None if epi is None else ctypes.byref(epi), int(plain_out_addr),
+                                   int(ws_addr), int(bool(padded_rows)), flags, ctypes.byref(plan)))
+  return plan
+
+
 def spmm(graph, w_csr, u, out=None):
   """Plain aggregation out = A u."""
   require_hip(u, w_csr)

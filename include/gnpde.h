@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 21  /* 21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 22  /* 22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -563,6 +563,57 @@ int gnpde_linear_plan(uint64_t x_addr, int32_t n, int32_t d, int32_t ldx, uint64
 int gnpde_linear_split_plan(uint64_t x_addr, int32_t n, int32_t d, int32_t ldx, uint64_t w_addr, int32_t m, int32_t ldw,
                             uint64_t out_q_addr, uint64_t out_k_addr, int32_t split, gnpde_linear_launch_t* plan);
 
+/* The launch decision of gnpde_spmm_rhs / gnpde_spmm and their _lo and _tickets forms, as gnpde_linear_plan gives the projection's: the
+ * kernel a call with these operands takes, its grid, and how its hub rows (more than GNPDE_LONG_ROW entries) are folded.  Nothing is
+ * launched, no device is needed and no address is dereferenced: u_addr, plain_out_addr, workspace_addr and the pointer fields of *epi are
+ * read for their alignment (and for being null) only.  Exactly one of epi / plain_out_addr is given.  The launchers of the library
+ * switch on the very same result, so a plan is what runs.  flags: GNPDE_SPMM_PLAN_LO a bf16 gather operand is given (shadows taken as
+ * 16-byte aligned), _TICKETS a ticket buffer is given, _DEFER the hub-chunk items are to form their entries' weights (the one-launch row
+ * attention), _FORK the hub-row work is to run on a second stream.  Returns what the launch would return for these operands:
+ * 0, or GNPDE_EINVAL / GNPDE_ESHAPE with gnpde_last_error set (workspace and ticket SIZES are not part of the question).
+ *   lane_bytes  16 where d % 4 == 0 (or padded_rows), ld % 4 == 0 and u, plain_out, the workspace and every epilogue operand are 16-byte
+ *               aligned; 8 by the same rule with 2 and 8 bytes; else 4.  A bf16 operand needs 16 (GNPDE_ESHAPE otherwise).
+ *   the kernel  by slots = lanes that cover a row = ceil(d / (lane_bytes / 4)):
+ *     slots <= 8          GNPDE_SPMM_ROWS (L, K, U) = (8, 1, 4)             <= 16          ROWS (16, 1, 4)
+ *     17 .. 64, 16-byte   GNPDE_SPMM_PAIR (L 32, U 16) where slots <= 32 and at least half of the rows have <= 16 entries (with a bf16
+ *                         operand and gnpde_tune(18, 2), d % 8 == 0: GNPDE_SPMM_QUAD_LO, L 16, U 16); else GNPDE_SPMM_WIDE, L = 32 or 64,
+ *                         U 8; full = 1 where d == 4 L (no column predicate; never for QUAD_LO)
+ *     17 .. 64, narrower  ROWS (16, 2, 4) for slots <= 32, else ROWS (32, 2, 4)
+ *     <= 128 / 192 / 256  ROWS (64, 2, 2) / (64, 3, 1) / (64, 4, 1)            more: GNPDE_ESHAPE
+ *     L lanes cover one neighbour row (K column tiles of them), U gathers are in flight; ROWS runs workgroups of 256 (four waves, a row
+ *     each), the others of 64; PAIR takes two and QUAD_LO four rows per wave.  lo = 1: the instantiation that gathers bf16.
+ *   grid        8 * max(1, ceil((ceil(chunks / 8) + ceil(rows_per_xcd / rows per wave)) / waves per workgroup)), rows_per_xcd as
+ *               gnpde_xcd_row_map gives it for [row_begin, n); forked = 1: the hub chunks run in a second launch of the same kernel on the
+ *               other stream (chunks = 0 here)
+ *   the pair kernel alone (whole graph, one stream, fp32 table, gnpde_tune(9, 0)) can take _DEFER (defer = 1 where the graph has hub
+ *   rows; GNPDE_EINVAL on any other route) and fold the hub rows itself
+ *   fold        GNPDE_SPMM_FOLD_NONE no hub rows; _IN_KERNEL tickets given, the pair kernel alone, stage RHS, EULER or RK1C..RK4C,
+ *               gnpde_agg_fold_launch(0); else a launch of its own: _REDUCE4_LO with a bf16 operand, _REDUCE4 on 16-byte lanes, _SCALAR */
+#define GNPDE_SPMM_ROWS    0
+#define GNPDE_SPMM_WIDE    1
+#define GNPDE_SPMM_PAIR    2
+#define GNPDE_SPMM_QUAD_LO 3
+#define GNPDE_SPMM_FOLD_NONE       0
+#define GNPDE_SPMM_FOLD_IN_KERNEL  1
+#define GNPDE_SPMM_FOLD_REDUCE4    2
+#define GNPDE_SPMM_FOLD_REDUCE4_LO 3
+#define GNPDE_SPMM_FOLD_SCALAR     4
+#define GNPDE_SPMM_PLAN_LO      1u
+#define GNPDE_SPMM_PLAN_TICKETS 2u
+#define GNPDE_SPMM_PLAN_DEFER   4u
+#define GNPDE_SPMM_PLAN_FORK    8u
+typedef struct gnpde_spmm_launch_t {
+  int32_t  family;      /* GNPDE_SPMM_* */
+  int32_t  lane_bytes;  /* 16, 8 or 4 */
+  int32_t  L, K, U;     /* template line of the kernel (above) */
+  int32_t  full, lo, defer;
+  uint32_t grid, block;
+  int32_t  forked;
+  int32_t  fold;        /* GNPDE_SPMM_FOLD_* */
+} gnpde_spmm_launch_t;
+int gnpde_spmm_plan(const gnpde_graph_t* g, uint64_t u_addr, int32_t d, int32_t ld, const gnpde_epilogue_t* epi, uint64_t plain_out_addr,
+                    uint64_t workspace_addr, int32_t padded_rows, uint32_t flags, gnpde_spmm_launch_t* plan);
+
 /* One un-fused evaluation out = f(u) of the same descriptor (what ODEFunc.forward returns). */
 int gnpde_rhs_eval(const gnpde_rhs_t* rhs, const float* u, float* out, void* workspace,
                    size_t workspace_bytes, void* stream);
@@ -589,6 +640,9 @@ size_t gnpde_rhs_workspace_bytes(const gnpde_rhs_t* rhs);
 typedef struct gnpde_adjoint gnpde_adjoint_t;
 int    gnpde_adjoint_grad_floats(const gnpde_rhs_t* rhs);
 size_t gnpde_adjoint_workspace_bytes(const gnpde_rhs_t* rhs, const gnpde_graph_t* graph_t, int32_t method);
+/* Per-wave dot-product slots the adjoint stage's row kernel writes over g (part of the workspace above): its grid -- one wave per work
+ * item, the aggregation's grid formula (gnpde_spmm_plan) with one row per wave and one wave per workgroup -- plus one per hub row. */
+int32_t gnpde_adjoint_rows_dot_slots(const gnpde_graph_t* g, int32_t d);
 int    gnpde_adjoint_create(gnpde_adjoint_t** out, const gnpde_rhs_t* rhs, const gnpde_graph_t* graph_t, const int32_t* t_from_csr,
                             const float* proj_wt, const float* w_t_csr, int32_t method, const float* dts, int32_t n_steps,
                             void* workspace, size_t workspace_bytes);

@@ -1,4 +1,4 @@
-"""Every line of the aggregation's dispatch table (dispatch_rows in csrc/spmm.hip) once, against the CPU oracle.
+"""Every line of the aggregation's dispatch table (width_class in csrc/spmm.hip) once, against the CPU oracle.
 
 The table is keyed by the lane type (16-, 8- or 4-byte lanes: contiguous rows, so ld = d decides it), the number of lanes that cover a
 row, and -- for rows of 17..32 16-byte lanes -- by whether at least half of the graph's rows have <= 16 entries (two rows per wave) or
