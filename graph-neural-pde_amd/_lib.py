@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 22     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 23     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
@@ -30,6 +30,7 @@ TUNE_KNN_SPLITS = 19     # column splits of the k-nearest-neighbour search: 0 = 
 METRIC_SQEUCLIDEAN = 0   # GNPDE_METRIC_* of include/gnpde.h (the key of a pair in gnpde_knn_metric / gnpde_radius_*)
 METRIC_POINCARE = 1
 TUNE_KNN_VARIANT = 20    # tile kernel of the search (A/B): 2 = the k > 32 kernel (256-key row buffers) for every k; 1 is removed and refused
+TUNE_GMAX_SMALL, TUNE_ATT_ROWS16 = 16, 17     # squareplus' maximum on a small grid: 1 = slots + fold launch; rows of <= 16 entries at 4 heads: 9 = a whole wave a row (A/B)
 TUNE_ATT_ONE_LAUNCH = 21  # 1: the row attention of a GRAND-nl evaluation keeps its two launches (A/B against the one-launch form)
 TUNE_LO_MAPPING = 18      # bf16 gather operand at d = 68..128, short rows: 1 = 32 lanes x 4 elements, 2 = 16 lanes x 8 elements (A/B)
 SAMPLING_EMPTY_COLUMN, SAMPLING_NONFINITE, SAMPLING_ZERO_MASS, SAMPLING_INDEX_RANGE = 1, 2, 4, 8   # GNPDE_SAMPLING_* flag bits
@@ -91,6 +92,36 @@ class SpmmLaunchStruct(ctypes.Structure):
 SPMM_FAMILIES = ('rows', 'wide', 'pair', 'quad_lo')                               # GNPDE_SPMM_*
 SPMM_FOLDS = ('none', 'in_kernel', 'reduce4', 'reduce4_lo', 'scalar')             # GNPDE_SPMM_FOLD_*
 SPMM_PLAN_LO, SPMM_PLAN_TICKETS, SPMM_PLAN_DEFER, SPMM_PLAN_FORK = 1, 2, 4, 8     # GNPDE_SPMM_PLAN_*
+
+
+class AttentionLaunchStruct(ctypes.Structure):
+  """gnpde_attention_launch_t: the launch plan of a row attention (gnpde_attention_plan)."""
+  _fields_ = [('route', ctypes.c_int32), ('vec4', ctypes.c_int32), ('h', ctypes.c_int32), ('dk4', ctypes.c_int32), ('n_sweeps', ctypes.c_int32),
+              ('mode', ctypes.c_int32 * 2), ('scatter', ctypes.c_int32), ('swapped', ctypes.c_int32), ('rows16', ctypes.c_int32),
+              ('gmax', ctypes.c_int32), ('gmax_count', ctypes.c_int32), ('hubs', ctypes.c_int32), ('n_hub', ctypes.c_int32),
+              ('hub_fold', ctypes.c_int32), ('gat_terms', ctypes.c_int32), ('passes', ctypes.c_int32), ('seg_stats_heads', ctypes.c_int32),
+              ('n_long', ctypes.c_int32), ('max_chunks', ctypes.c_int32), ('launches', ctypes.c_int32), ('grid', (ctypes.c_uint32 * 2) * 2)]
+
+  @property
+  def route_name(self):
+    return ATT_ROUTES[self.route]
+
+  @property
+  def modes(self):
+    return tuple(self.mode[:self.n_sweeps])
+
+  @property
+  def grids(self):
+    """((<= 16 entries, 17..512 entries) per sweep)"""
+    return tuple((self.grid[s][0], self.grid[s][1]) for s in range(self.n_sweeps))
+
+
+ATT_ROUTES = ('none', 'hubs_only', 'sd_one', 'sd_rows', 'rows', 'general')                               # GNPDE_ATT_ROUTE_*
+ATT_ROWS16_NONE, ATT_ROWS16_QUARTER, ATT_ROWS16_LANES, ATT_ROWS16_WHOLE_WAVE = range(4)                  # GNPDE_ATT_ROWS16_*
+ATT_GMAX_NONE, ATT_GMAX_PER_WAVE, ATT_GMAX_SLOTS_FOLD, ATT_GMAX_ATOMIC = range(4)                        # GNPDE_ATT_GMAX_*
+ATT_HUBS_NONE, ATT_HUBS_IN_ROWS, ATT_HUBS_DEFERRED, ATT_HUBS_OWN, ATT_HUBS_OWN_FORKED, ATT_HUBS_LONG_STATS = range(6)   # GNPDE_ATT_HUBS_*
+ATT_PLAN_W_MEAN, ATT_PLAN_ATT_EDGE, ATT_PLAN_PRODS_EDGE, ATT_PLAN_FORK, ATT_PLAN_DEFER, ATT_PLAN_HUBS_ONLY, ATT_PLAN_STATS_ONLY = (
+  1, 2, 4, 8, 16, 32, 64)                                                                                # GNPDE_ATT_PLAN_*
 
 
 class EpilogueStruct(ctypes.Structure):
@@ -216,6 +247,8 @@ PROTOTYPES = {
   'gnpde_adjoint_rows_dot_slots': (ctypes.c_int32, [ctypes.POINTER(GraphStruct), ctypes.c_int32]),
   'gnpde_spmm_plan': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(EpilogueStruct),
                                      ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(SpmmLaunchStruct)]),
+  'gnpde_attention_plan': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.POINTER(AttentionStruct), ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64,
+                                          ctypes.POINTER(AttentionLaunchStruct)]),
   'gnpde_linear_split': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp,
                                         ctypes.c_int32, c_vp]),
   'gnpde_adjoint_set_tape': (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]),

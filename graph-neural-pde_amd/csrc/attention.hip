@@ -20,6 +20,7 @@
 //   registers, max / sum are DPP-style xor reductions inside the group, w is written once.  Long
 //   rows run the general passes restricted to their chunks.
 #include <cmath>
+#include <type_traits>
 #include "common.h"
 #include "rhs.h"
 
@@ -999,251 +1000,102 @@ AttLayout att_layout(int n, int e, int h, bool gat, size_t long_slots, int key_r
   return L;
 }
 
-template <int TYPE>
-void launch_scores(const AttArgs& a, bool vec4, unsigned grid, hipStream_t s) {
-  if (vec4) hipLaunchKernelGGL((scores_kernel<TYPE, true>), dim3(grid), dim3(kBlock), 0, s, a);
-  else hipLaunchKernelGGL((scores_kernel<TYPE, false>), dim3(grid), dim3(kBlock), 0, s, a);
-}
-
-void launch_scores_any(const AttArgs& a, bool vec4, unsigned grid, hipStream_t s) {
-  switch (a.type) {
-    case GNPDE_ATT_SCALED_DOT: launch_scores<GNPDE_ATT_SCALED_DOT>(a, vec4, grid, s); break;
-    case GNPDE_ATT_COSINE: launch_scores<GNPDE_ATT_COSINE>(a, vec4, grid, s); break;
-    case GNPDE_ATT_PEARSON: launch_scores<GNPDE_ATT_PEARSON>(a, vec4, grid, s); break;
-    case GNPDE_ATT_EXP_KERNEL: launch_scores<GNPDE_ATT_EXP_KERNEL>(a, vec4, grid, s); break;
-    default: launch_scores<GNPDE_ATT_GAT>(a, false, grid, s); break;
-  }
-}
-
-// rows per workgroup of the <= 16-entry class of row_attention_sd_kernel (launch_rows_sd_mode's first launch)
-// (4 heads, d_k 4 or 16: a QUARTER of a wave per row, see launch_rows_sd_mode)
-constexpr bool sd_quarter_rows(int h, int dk4) { return h == 4 && (dk4 == 1 || dk4 == 4); }
-constexpr int sd_rows_per_block16(int h, int dk4) {
-  const int gl16 = sd_quarter_rows(h, dk4) ? 16 : ((16 * h < kWave) ? 16 * h : kWave);
-  const int p16 = (16 * h + gl16 - 1) / gl16;
-  const int ri16 = sd_quarter_rows(h, dk4) ? 2 : ((dk4 == 1 && p16 == 1) ? 4 : (p16 == 1 ? 2 : 1));
-  return (kWave / gl16) * ri16 * kWavesPerBlock;
-}
-// waves of the two launches of a sweep without hub blocks: [0] the <= 16-entry class, [1] the others (AttArgs::gmax_part)
-inline void sd_sweep_waves(int h, int dk4, int n16, int n64, long long (&w)[2]) {
-  const long long rpb = sd_rows_per_block16(h, dk4);
-  w[0] = n16 > 0 ? (n16 + rpb - 1) / rpb * kWavesPerBlock : 0;
-  w[1] = n64 > 0 ? static_cast<long long>(n64 + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock : 0;
-}
-
-// lane mapping of the two row classes of the scaled-dot row kernels (launch_rows_sd_mode explains the choices)
-template <int H, int DK4>
-struct SdShape {
-  static constexpr bool QUARTER = sd_quarter_rows(H, DK4);
-  static constexpr int GL16 = QUARTER ? 16 : ((16 * H < kWave) ? 16 * H : kWave);   // lanes per row for rows with <= 16 entries
-  static constexpr int P16 = (16 * H + GL16 - 1) / GL16;           // passes to cover 16 entries
-  static constexpr int RPW16 = kWave / GL16;
-  static constexpr int RI16 = QUARTER ? 2 : ((DK4 == 1 && P16 == 1) ? 4 : (P16 == 1 ? 2 : 1));  // rows interleaved per group
-  static constexpr int P64 = GNPDE_LONG_ROW / (kWave / H);         // passes to cover GNPDE_LONG_ROW entries
-  static constexpr int PB64 = (DK4 == 1) ? 4 : 2;
-};
-
-template <int H, int DK4, int MODE, bool SCATTER>
-void launch_rows_sd_mode(const AttArgs& a_in, int n16, int n64, hipStream_t s, int n_hub, float* part, const int* chunk_first) {
-  AttArgs a = a_in;
-  // Rows of <= 16 entries.  4 heads (round 6): a QUARTER of a wave per row -- 16 lanes = 4 entries x 4 heads per pass, four passes, two
-  // rows interleaved per group: 8 rows per wave instead of 4 on whole waves, where a median row of 8 entries left half of the lanes without
-  // an entry.  Measured at the ogbn-arxiv shape: row attention 41.2 -> 37.3 us per evaluation (1074 -> 1089 steps/s at T = 100), R-MAT
-  // (d_k = 16) 4.48 -> 3.98 ms; the other packings tried on the row softmax (half a wave x 2 passes with 8 / 4 rows per wave: 38.2; a quarter
-  // with 16 rows per wave: 40.4, with 4: 37.3; half with 16 rows: 43.0; an eighth x 8 passes with 16 / 8 rows: 40.4 / 37.2) are in DESIGN.md,
-  // the whole-wave form stays behind gnpde_tune(17, 9) for the row softmax (A/B).  Other head counts: 16 H lanes (at most a wave) per row.
-  using S = SdShape<H, DK4>;
-  constexpr bool QUARTER = S::QUARTER;
-  constexpr int GL16 = S::GL16, P16 = S::P16, RPW16 = S::RPW16, RI16 = S::RI16, P64 = S::P64, PB64 = S::PB64;
-  // launch 1: hub phase 0 + rows with <= 16 entries; launch 2: hub phase 1 + rows with 17..512 entries (the maximum sweep of
-  // squareplus, MODE 2, has no hub phase 1)
-  bool first_done = false;
-  if constexpr (QUARTER && MODE == 0 && !SCATTER) {
-    if (g_tune[GNPDE_TUNE_ATT_ROWS16] == 9 && (n16 > 0 || n_hub > 0)) {      // A/B: a whole wave per row, four rows interleaved (until round 6)
-      constexpr int RIW = DK4 == 1 ? 4 : 2;
-      const long long rpb = static_cast<long long>(RIW) * kWavesPerBlock;
-      const unsigned grid = static_cast<unsigned>((n16 + rpb - 1) / rpb) + n_hub;
-      hipLaunchKernelGGL((row_attention_sd_kernel<H, DK4, kWave, RIW, 1, 1, MODE, SCATTER>), dim3(grid), dim3(kBlock), 0, s, a, 0, n16, n_hub, 0, part,
-                         chunk_first);
-      first_done = true;
-    }
-  }
-  if (!first_done && (n16 > 0 || n_hub > 0)) {
-    const long long rows_per_block = static_cast<long long>(RPW16) * RI16 * kWavesPerBlock;
-    static_assert(RPW16 * RI16 * kWavesPerBlock == sd_rows_per_block16(H, DK4), "sd_sweep_waves counts this launch's waves");
-    const unsigned grid = static_cast<unsigned>((n16 + rows_per_block - 1) / rows_per_block) + n_hub;
-    hipLaunchKernelGGL((row_attention_sd_kernel<H, DK4, GL16, RI16, P16, 1, MODE, SCATTER>), dim3(grid), dim3(kBlock), 0, s, a, 0, n16, n_hub,
-                       0, part, chunk_first);
-    if (MODE == 2 && a.gmax_part != nullptr) a.gmax_base += static_cast<int>(grid - n_hub) * kWavesPerBlock;   // the second launch's waves follow
-  }
-  const int n_hub2 = MODE == 2 ? 0 : n_hub;
-  if (n64 > 0 || n_hub2 > 0) {
-    const unsigned grid = static_cast<unsigned>((n64 + kWavesPerBlock - 1) / kWavesPerBlock) + n_hub2;
-    hipLaunchKernelGGL((row_attention_sd_kernel<H, DK4, kWave, 1, PB64, P64 / PB64, MODE, SCATTER>), dim3(grid), dim3(kBlock), 0, s, a, n16,
-                       n64, n_hub2, 1, part, chunk_first);
-  }
-}
-
-template <int H, int DK4>
-void launch_rows_sd(const AttArgs& a, int n16, int n64, hipStream_t s, int n_hub = 0, float* part = nullptr,
-                    const int* chunk_first = nullptr) {
-  const bool sc = a.out_pos != nullptr;
-  if (a.sp_mode == 4) { launch_rows_sd_mode<H, DK4, 4, false>(a, n16, n64, s, n_hub, part, chunk_first); return; }   // exp kernel scores
-  if (a.sp_mode == 3) {              // GAT scores through the scaled-dot kernels (4-wide vectors only)
-    if constexpr (DK4 == 1) launch_rows_sd_mode<H, DK4, 3, false>(a, n16, n64, s, n_hub, part, chunk_first);
-    return;
-  }
-  if (a.sp_mode == 2) launch_rows_sd_mode<H, DK4, 2, false>(a, n16, n64, s, n_hub, part, chunk_first);      // (writes no weights)
-  else if (a.sp_mode == 1) {
-    if (sc) launch_rows_sd_mode<H, DK4, 1, true>(a, n16, n64, s, n_hub, part, chunk_first);
-    else launch_rows_sd_mode<H, DK4, 1, false>(a, n16, n64, s, n_hub, part, chunk_first);
-  } else {
-    if (sc) launch_rows_sd_mode<H, DK4, 0, true>(a, n16, n64, s, n_hub, part, chunk_first);
-    else launch_rows_sd_mode<H, DK4, 0, false>(a, n16, n64, s, n_hub, part, chunk_first);
-  }
-}
-
-// scaled-dot rows + hub chunks in two launches; false if this (heads, d_k) has no specialised kernel
-bool launch_sd_with_hubs(const AttArgs& c, int n16, int n64, int n_hub, float* part, const int* chunk_first, hipStream_t s) {
-  if (g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] != 0) return false;
-#define GNPDE_SD(HH)                                                                              \
-  case HH:                                                                                        \
-    if (c.dk == 4) { launch_rows_sd<HH, 1>(c, n16, n64, s, n_hub, part, chunk_first); return true; }  \
-    if (c.dk == 8) { launch_rows_sd<HH, 2>(c, n16, n64, s, n_hub, part, chunk_first); return true; }  \
-    if (c.dk == 16) { launch_rows_sd<HH, 4>(c, n16, n64, s, n_hub, part, chunk_first); return true; } \
-    return false;
-  switch (c.h) {
-    GNPDE_SD(1) GNPDE_SD(2) GNPDE_SD(4) GNPDE_SD(8)
-    default: return false;
-  }
-#undef GNPDE_SD
-}
-
-// The plain row softmax in ONE launch (row_attention_sd_one_kernel): hub phase 0, the rows of 17..512 entries, the rows of <= 16
-// entries.  The hub entries' weights are NOT written: the caller hands the chunk statistics to the aggregation (HubDefer).
-template <int H, int DK4>
-void launch_rows_sd_one(const AttArgs& a, int n16, int n64, int n_hub, float* part, hipStream_t s) {
-  using S = SdShape<H, DK4>;
-  const long long rpb16 = static_cast<long long>(S::RPW16) * S::RI16 * kWavesPerBlock;
-  const int blocks64 = (n64 + kWavesPerBlock - 1) / kWavesPerBlock;
-  const long long grid = static_cast<long long>(n_hub) + blocks64 + (n16 + rpb16 - 1) / rpb16;
-  if (grid == 0) return;
-  hipLaunchKernelGGL((row_attention_sd_one_kernel<H, DK4, S::GL16, S::RI16, S::P16, S::PB64, S::P64 / S::PB64>), dim3(static_cast<unsigned>(grid)),
-                     dim3(kBlock), 0, s, a, n16, n64, n_hub, part);
-}
-
-bool launch_sd_one(const AttArgs& c, int n16, int n64, int n_hub, float* part, hipStream_t s) {
-#define GNPDE_SD1(HH)                                                                  \
-  case HH:                                                                             \
-    if (c.dk == 4) { launch_rows_sd_one<HH, 1>(c, n16, n64, n_hub, part, s); return true; }  \
-    if (c.dk == 8) { launch_rows_sd_one<HH, 2>(c, n16, n64, n_hub, part, s); return true; }  \
-    if (c.dk == 16) { launch_rows_sd_one<HH, 4>(c, n16, n64, n_hub, part, s); return true; } \
-    return false;
-  // (8 heads keep the two launches: their long-row body needs 96 - 123 VGPRs, and one kernel would run the <= 16-entry rows -- 54 - 56
-  //  VGPRs, 8 waves per SIMD in a launch of their own -- at 4 - 5)
-  switch (c.h) {
-    GNPDE_SD1(1) GNPDE_SD1(2) GNPDE_SD1(4)
-    default: return false;
-  }
-#undef GNPDE_SD1
-}
-
-template <int TYPE, int H, bool VEC4>
-void launch_rows_th(const AttArgs& a, int n16, int n64, hipStream_t s) {
-  if constexpr (TYPE == GNPDE_ATT_SCALED_DOT && VEC4) {
-    if (g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] == 0) {
-      if (a.dk == 4) return launch_rows_sd<H, 1>(a, n16, n64, s);
-      if (a.dk == 8) return launch_rows_sd<H, 2>(a, n16, n64, s);
-      if (a.dk == 16) return launch_rows_sd<H, 4>(a, n16, n64, s);
-    }
-  }
-  // rows with <= 16 entries: 16*H lanes cover them in one pass when H <= 4, else a whole wave in H/4 passes
-  constexpr int GL16 = (16 * H < kWave) ? 16 * H : kWave;
-  constexpr int P16 = (16 * H + GL16 - 1) / GL16;
-  constexpr int RPW16 = kWave / GL16;
-  constexpr int P64 = GNPDE_LONG_ROW / (kWave / H);
-  if (n16 > 0) {
-    const unsigned grid = static_cast<unsigned>((n16 + RPW16 * kWavesPerBlock - 1) / (RPW16 * kWavesPerBlock));
-    hipLaunchKernelGGL((row_attention_kernel<TYPE, H, GL16, P16, VEC4>), dim3(grid), dim3(kBlock), 0, s, a, 0, n16);
-  }
-  if (n64 > 0) {
-    const unsigned grid = static_cast<unsigned>((n64 + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL((row_attention_kernel<TYPE, H, kWave, P64, VEC4>), dim3(grid), dim3(kBlock), 0, s, a, n16, n64);
-  }
-}
-
-template <int TYPE, bool VEC4>
-bool launch_rows_t(const AttArgs& a, int n16, int n64, hipStream_t s) {
-  switch (a.h) {
-    case 1: launch_rows_th<TYPE, 1, VEC4>(a, n16, n64, s); return true;
-    case 2: launch_rows_th<TYPE, 2, VEC4>(a, n16, n64, s); return true;
-    case 4: launch_rows_th<TYPE, 4, VEC4>(a, n16, n64, s); return true;
-    case 8: launch_rows_th<TYPE, 8, VEC4>(a, n16, n64, s); return true;
-    default: return false;
-  }
-}
-
 template <int H>
 __global__ __launch_bounds__(kBlock) void hub_scores_partial_sd_kernel(const AttArgs a, float* __restrict__ part) {
   hub_scores_partial_heads<GNPDE_ATT_SCALED_DOT, true, H>(a, part, blockIdx.x);
 }
 
-template <int TYPE>
-void launch_hub_a(const AttArgs& c, bool vec4, float* part, int n_chunks, hipStream_t s) {
-  if constexpr (TYPE == GNPDE_ATT_SCALED_DOT) {
-    if (vec4) {
-      switch (c.h) {
-        case 1: hipLaunchKernelGGL(hub_scores_partial_sd_kernel<1>, dim3(n_chunks), dim3(kBlock), 0, s, c, part); return;
-        case 2: hipLaunchKernelGGL(hub_scores_partial_sd_kernel<2>, dim3(n_chunks), dim3(kBlock), 0, s, c, part); return;
-        case 4: hipLaunchKernelGGL(hub_scores_partial_sd_kernel<4>, dim3(n_chunks), dim3(kBlock), 0, s, c, part); return;
-        case 8: hipLaunchKernelGGL(hub_scores_partial_sd_kernel<8>, dim3(n_chunks), dim3(kBlock), 0, s, c, part); return;
-        default: break;
-      }
-    }
-  }
-  if (vec4) hipLaunchKernelGGL((hub_scores_partial_kernel<TYPE, true>), dim3(n_chunks), dim3(kBlock), 0, s, c, part);
-  else hipLaunchKernelGGL((hub_scores_partial_kernel<TYPE, false>), dim3(n_chunks), dim3(kBlock), 0, s, c, part);
+// ------------------------------------------------------------------------------------------------
+// Host side.  ONE decision per call -- validation, route, template line of the row kernels, sweeps, grids, hub handling -- taken in
+// plan_attention, exported as it is taken by gnpde_attention_plan (gnpde.h documents the table) and carried out by launch_planned.
+// ------------------------------------------------------------------------------------------------
+
+// What a call asks of the attention; default-constructed: nothing.
+struct AttRequest {
+  float* w_mean = nullptr;       // outputs wanted: [e] head-mean weights in CSR order,
+  float* att_edge = nullptr;     //   [E,h] attention and
+  float* prods_edge = nullptr;   //   [E,h] scores in the caller's edge order
+  const Fork* fork = nullptr;    // the hub rows' own launches as a branch on the second stream
+  HubDefer* defer = nullptr;     // the caller's aggregation follows on this stream and can normalise the hub rows
+  bool hubs_only = false;        // the weights of the hub rows' entries only (the short rows are attended elsewhere)
+  bool stats_only = false;       // the general passes 1-2 only (scores + segment statistics stay in the workspace) ...
+  AttArgs* args_out = nullptr;   // ... and the kernel arguments handed back: the backward pass continues from there
+  int pass = 0;                  // 1..3: that pass of the general path alone; 0: all
+};
+
+// THE (heads, d_k) dispatcher and THE score-type dispatcher: every template line of this file's launches is reached through them.
+// visit_value calls f(Int<v>) for the v of its list that equals x (false: none does), so a call site instantiates its kernel for the
+// values it lists and for no other.
+template <int V> using Int = std::integral_constant<int, V>;
+template <int... V, class F>
+bool visit_value(int x, F&& f) { return ((x == V && (f(Int<V>{}), true)) || ...); }
+// heads 1, 2, 4 and, unless MAXH says 4, 8 ...
+template <int MAXH = 8, class F>
+bool visit_heads(int h, F&& f) {
+  if constexpr (MAXH >= 8) return visit_value<1, 2, 4, 8>(h, f);
+  else return visit_value<1, 2, 4>(h, f);
+}
+// ... x d_k / 4 in {1, 2, 4}
+template <int MAXH = 8, class F>
+bool visit_line(int h, int dk4, F&& f) {
+  return visit_heads<MAXH>(h, [&](auto H) { visit_value<1, 2, 4>(dk4, [&](auto D) { f(H, D); }); });
+}
+// (a type outside the list is GAT's: plan_attention has refused every other)
+template <class F>
+void visit_type(int type, F&& f) {
+  if (!visit_value<GNPDE_ATT_SCALED_DOT, GNPDE_ATT_COSINE, GNPDE_ATT_PEARSON, GNPDE_ATT_EXP_KERNEL>(type, f)) f(Int<GNPDE_ATT_GAT>{});
 }
 
-void launch_hub_a_any(const AttArgs& c, bool vec4, float* part, int n_chunks, hipStream_t s) {
-  switch (c.type) {
-    case GNPDE_ATT_SCALED_DOT: launch_hub_a<GNPDE_ATT_SCALED_DOT>(c, vec4, part, n_chunks, s); break;
-    case GNPDE_ATT_COSINE: launch_hub_a<GNPDE_ATT_COSINE>(c, vec4, part, n_chunks, s); break;
-    case GNPDE_ATT_PEARSON: launch_hub_a<GNPDE_ATT_PEARSON>(c, vec4, part, n_chunks, s); break;
-    case GNPDE_ATT_EXP_KERNEL: launch_hub_a<GNPDE_ATT_EXP_KERNEL>(c, vec4, part, n_chunks, s); break;
-    default: launch_hub_a<GNPDE_ATT_GAT>(c, false, part, n_chunks, s); break;
-  }
+// THE lane mapping of the two row classes.  dk4 = d_k / 4 for the scaled-dot row kernels (row_attention_sd_kernel and its one-launch
+// form), 0 for row_attention_kernel, which interleaves no rows.
+// Rows of <= 16 entries.  4 heads, d_k 4 or 16 (round 6): a QUARTER of a wave per row -- 16 lanes = 4 entries x 4 heads per pass, four
+// passes, two rows interleaved per group: 8 rows per wave instead of 4 on whole waves, where a median row of 8 entries left half of the
+// lanes without an entry.  Measured at the ogbn-arxiv shape: row attention 41.2 -> 37.3 us per evaluation (1074 -> 1089 steps/s at
+// T = 100), R-MAT (d_k = 16) 4.48 -> 3.98 ms; the other packings tried on the row softmax (half a wave x 2 passes with 8 / 4 rows per
+// wave: 38.2; a quarter with 16 rows per wave: 40.4, with 4: 37.3; half with 16 rows: 43.0; an eighth x 8 passes with 16 / 8 rows:
+// 40.4 / 37.2) are in DESIGN.md, the whole-wave form (quarter_rows = false: four or two rows interleaved) stays behind
+// gnpde_tune(17, 9) for the row softmax (A/B).  Other head counts: 16 H lanes (at most a wave) per row.
+struct RowShape {
+  bool quarter;
+  int gl16, p16, ri16;   // <= 16 entries: lanes per row, passes to cover 16 entries x H heads, rows interleaved per group,
+  int rows16;            //   rows per workgroup
+  int p64, pb64;         // 17..GNPDE_LONG_ROW entries, a wave per row: passes to cover GNPDE_LONG_ROW entries, passes per batch
+};
+constexpr RowShape row_shape(int h, int dk4, bool quarter_rows = true) {
+  RowShape s{};
+  s.quarter = quarter_rows && h == 4 && (dk4 == 1 || dk4 == 4);
+  s.gl16 = s.quarter ? 16 : ((16 * h < kWave) ? 16 * h : kWave);
+  s.p16 = (16 * h + s.gl16 - 1) / s.gl16;
+  s.ri16 = dk4 == 0 ? 1 : s.quarter ? 2 : ((dk4 == 1 && s.p16 == 1) ? 4 : (s.p16 == 1 ? 2 : 1));
+  s.rows16 = (kWave / s.gl16) * s.ri16 * kWavesPerBlock;
+  s.p64 = GNPDE_LONG_ROW / (kWave / h);
+  s.pb64 = (dk4 == 1) ? 4 : 2;
+  return s;
 }
 
-// fused row kernels exist for these (type, heads, alignment) combinations
-bool fused_supported(const AttArgs& a, bool vec4) {
-  if (!(a.h == 1 || a.h == 2 || a.h == 4 || a.h == 8)) return false;
-  if (a.type == GNPDE_ATT_GAT) return true;
-  return vec4 && (a.type == GNPDE_ATT_SCALED_DOT || a.type == GNPDE_ATT_COSINE || a.type == GNPDE_ATT_PEARSON ||
-                  a.type == GNPDE_ATT_EXP_KERNEL);
-}
+struct AttPlan {
+  gnpde_attention_launch_t l;     // what gnpde_attention_plan reports
+  const gnpde_graph_t* g;         // the call
+  const gnpde_attention_t* at;
+  AttRequest rq;
+  const gnpde_graph_t* rows;      // the graph whose rows the row and hub kernels walk: g, or its transpose (normalisation over columns)
+  char* ws;                       // the workspace and its regions
+  AttLayout L;
+  int row_hubs;                   // hub blocks in front of the row launches (l.n_hub or 0)
+  const int* long_list;           // general path: the long segments that have passes of their own (nullptr: none)
+  unsigned scores_grid, stats_grid, norm_grid;
+};
 
-void launch_rows_any(const AttArgs& a, int n16, int n64, hipStream_t s) {
-  switch (a.type) {
-    case GNPDE_ATT_SCALED_DOT: launch_rows_t<GNPDE_ATT_SCALED_DOT, true>(a, n16, n64, s); break;
-    case GNPDE_ATT_COSINE: launch_rows_t<GNPDE_ATT_COSINE, true>(a, n16, n64, s); break;
-    case GNPDE_ATT_PEARSON: launch_rows_t<GNPDE_ATT_PEARSON, true>(a, n16, n64, s); break;
-    case GNPDE_ATT_EXP_KERNEL: launch_rows_t<GNPDE_ATT_EXP_KERNEL, true>(a, n16, n64, s); break;
-    default: launch_rows_t<GNPDE_ATT_GAT, false>(a, n16, n64, s); break;
-  }
-}
+inline unsigned ceil_blocks(long long items, long long per_block) { return static_cast<unsigned>((items + per_block - 1) / per_block); }
 
-}  // namespace
-
-size_t attention_workspace_bytes(const gnpde_graph_t* g, int h, bool gat);
-
-// stats_only: run the general passes 1-2 only (scores + segment statistics stay in the workspace) and hand back the
-// kernel arguments -- the backward pass continues from there
-static int edge_attention_impl(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, float* att_edge,
-                               float* prods_edge, void* ws, size_t ws_bytes, hipStream_t stream, const Fork* fork,
-                               bool stats_only, AttArgs* args_out, bool hubs_only = false, int pass_only = 0, HubDefer* defer = nullptr) {
+// The plan of a call.  Operand pointers are read for their alignment and for being null, never through; ws_bytes is compared and nothing
+// else.  g_tune is read here and nowhere else on the attention's host side.
+int plan_attention(const gnpde_graph_t* g, const gnpde_attention_t* at, const AttRequest& rq, void* ws, size_t ws_bytes, AttPlan* p) {
+  *p = AttPlan{};
+  gnpde_attention_launch_t& l = p->l;
   GNPDE_CHECK_ARG(g && at, GNPDE_EINVAL, "edge_attention: null descriptor");
-  GNPDE_CHECK_ARG(stats_only || w_mean_csr || att_edge || prods_edge, GNPDE_EINVAL, "edge_attention: no output requested");
+  GNPDE_CHECK_ARG(rq.stats_only || rq.pass == 1 || rq.pass == 2 || rq.w_mean || rq.att_edge || rq.prods_edge, GNPDE_EINVAL,
+                  "edge_attention: no output requested");
   GNPDE_CHECK_ARG(at->heads >= 1 && at->att_dim >= at->heads && at->att_dim % at->heads == 0, GNPDE_EINVAL,
                   "edge_attention: heads (%d) must be a factor of the attention dimension (%d)", at->heads, at->att_dim);
   GNPDE_CHECK_ARG(at->type >= GNPDE_ATT_SCALED_DOT && at->type <= GNPDE_ATT_GAT, GNPDE_EINVAL, "edge_attention: bad type %d", at->type);
@@ -1254,17 +1106,133 @@ static int edge_attention_impl(const gnpde_graph_t* g, const gnpde_attention_t* 
                   "edge_attention: exp_kernel needs output_var and lengthscale");
   GNPDE_CHECK_ARG(at->norm_idx == 0 || (g->cscptr && g->cscpos), GNPDE_EINVAL, "edge_attention: norm_idx=1 needs the CSC view");
   GNPDE_CHECK_ARG(g->rowidx && g->perm, GNPDE_EINVAL, "edge_attention: graph lacks rowidx/perm");
-  if (g->e == 0 || g->n == 0) return 0;
+  if (g->e == 0 || g->n == 0) return 0;     // (GNPDE_ATT_ROUTE_NONE: nothing to launch)
   const bool gat = at->type == GNPDE_ATT_GAT;
-  const int n_long = at->norm_idx == 0 ? g->n_long_rows : g->n_long_cols;
-  const int* long_list = at->norm_idx == 0 ? g->long_rows : g->long_cols;
-  const int max_len = at->norm_idx == 0 ? g->max_row_len : g->max_col_len;
-  const int max_chunks = (max_len + GNPDE_LONG_ROW - 1) / GNPDE_LONG_ROW;
-  const AttLayout L = att_layout(g->n, g->e, at->heads, gat, long_slots_of(g), at->n_key_rows);
-  GNPDE_CHECK_ARG(ws && ws_bytes >= L.total, GNPDE_EWS, "edge_attention: workspace %zu < %zu bytes", ws_bytes, L.total);
+  p->L = att_layout(g->n, g->e, at->heads, gat, long_slots_of(g), at->n_key_rows);
+  GNPDE_CHECK_ARG(ws && ws_bytes >= p->L.total, GNPDE_EWS, "edge_attention: workspace %zu < %zu bytes", ws_bytes, p->L.total);
   GNPDE_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % 16 == 0, GNPDE_EINVAL, "edge_attention: workspace must be 16-byte aligned");
-  char* base = static_cast<char*>(ws);
+  p->g = g; p->at = at; p->rq = rq; p->ws = static_cast<char*>(ws);
 
+  const int h = at->heads, dk = at->att_dim / h;
+  const bool heads_ok = h == 1 || h == 2 || h == 4 || h == 8;       // the row kernels' head counts
+  const bool dk_ok = dk == 4 || dk == 8 || dk == 16;                // the scaled-dot row kernels' head widths
+  const bool generic = g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] != 0;    // A/B: no scaled-dot row kernels
+  const bool one_stream = rq.fork == nullptr || rq.fork->aux == nullptr;
+  const bool sq = at->square_plus != 0;
+  // the scaled-dot row kernels carry a graph's hub chunks in their first blocks, given its chunk -> first-chunk table
+  auto hubs_ride = [&](const gnpde_graph_t* x) { return one_stream && (x->n_long_rows == 0 || x->long_chunk_first != nullptr); };
+  const bool w_alone = !rq.stats_only && rq.pass == 0 && rq.att_edge == nullptr && rq.prods_edge == nullptr;
+  l.h = h;
+  l.hub_fold = g_tune[GNPDE_TUNE_HUB_FOLD] == 2 ? 2 : 0;   // (0, staged through LDS: default since round 3, bit-identical; -3.4 % on the R-MAT launch)
+  l.vec4 = (dk % 4 == 0) && (at->ldqk % 4 == 0) && (reinterpret_cast<uintptr_t>(at->q) % 16 == 0) && (reinterpret_cast<uintptr_t>(at->k) % 16 == 0);
+  if (gat) l.gat_terms = 1;
+
+  // the row softmax with the head-mean weights alone: fused row kernels exist for these (type, heads, alignment) combinations
+  const bool fused = w_alone && at->norm_idx == 0 && !sq && g->bin_rows != nullptr && heads_ok && (gat || l.vec4);
+  GNPDE_CHECK_ARG(g->row_begin == 0 || fused, GNPDE_EINVAL, "edge_attention: a row sub-range needs the fused row path");
+  // ... and the scaled-dot scores with the OTHER normalisers in fused segment passes (the three general passes round-trip an [E,h]
+  // score array and walk the segments twice: 2 - 2.5 x the time of the row softmax at the ogbn-arxiv shape).  squareplus: one sweep for
+  // the global maximum (MODE 2), then the fused kernel with it (MODE 1); normalisation over the columns: the same kernels over the rows
+  // of the transposed graph with q and k exchanged, the weights scattered to their CSR positions.
+  const gnpde_graph_t* sg = at->norm_idx == 0 ? g : at->graph_t;
+  const bool sd_fast = !fused && w_alone && !rq.hubs_only && at->type == GNPDE_ATT_SCALED_DOT && l.vec4 && rq.w_mean != nullptr && heads_ok &&
+                       dk_ok && !generic && g->row_begin == 0 && sg != nullptr && sg->bin_rows != nullptr && sg->rowidx != nullptr &&
+                       sg->n == g->n && sg->e == g->e && sg->row_begin == 0 && one_stream &&
+                       (sg->n_long_rows == 0 || (sg->long_chunk_first != nullptr && sg->long_chunk_begin != nullptr)) &&
+                       (at->norm_idx == 0 || (at->t_from_csr != nullptr && at->edge_w_csr == nullptr));
+  p->rows = sd_fast ? sg : g;
+  l.n_hub = p->rows->n_long_rows > 0 ? p->rows->n_long_chunks : 0;
+  const int n16 = p->rows->n_bin16, n64 = p->rows->n_bin64;
+
+  // a route whose row launches are row_attention_sd_kernel's (or its one-launch form): template line (l.h, dk4, MODE per sweep, l.scatter)
+  auto sd = [&l](int route, int dk4, int mode0, int mode1 = -1) {
+    l.route = route; l.dk4 = dk4; l.n_sweeps = mode1 < 0 ? 1 : 2; l.mode[0] = mode0; l.mode[1] = mode1 < 0 ? 0 : mode1;
+  };
+  if (fused && rq.hubs_only) {
+    l.route = GNPDE_ATT_ROUTE_HUBS_ONLY;
+    l.hubs = l.n_hub > 0 ? GNPDE_ATT_HUBS_OWN : GNPDE_ATT_HUBS_NONE;
+  } else if (fused && gat && rq.w_mean != nullptr && at->edge_w_csr == nullptr && hubs_ride(g) && !generic) {
+    // GAT's row softmax on the scaled-dot row kernels (gat_terms_kernel's table, MODE 3: leaky ReLU on the score)
+    sd(GNPDE_ATT_ROUTE_SD_ROWS, 1, 3);
+    l.gat_terms = 2;
+  } else if (fused && rq.defer != nullptr && at->type == GNPDE_ATT_SCALED_DOT && rq.fork == nullptr && at->edge_w_csr == nullptr &&
+             rq.w_mean != nullptr && g->row_begin == 0 && at->n_key_rows == 0 && dk_ok && h <= 4 &&
+             (g->n_long_rows == 0 || (g->long_chunk_first != nullptr && g->long_chunk_begin != nullptr && g->long_chunk_end != nullptr)) &&
+             g_tune[GNPDE_TUNE_ATT_ONE_LAUNCH] == 0 && !generic && g_tune[GNPDE_TUNE_ATT_ROWS16] == 0) {
+    // THE one-launch condition: the caller's aggregation takes the hub rows' normalisation (HubDefer).  8 heads keep the two launches:
+    // their long-row body needs 96 - 123 VGPRs, and one kernel would run the <= 16-entry rows -- 54 - 56 VGPRs, 8 waves per SIMD in a
+    // launch of their own -- at 4 - 5.
+    sd(GNPDE_ATT_ROUTE_SD_ONE, dk / 4, 0);
+  } else if (fused && (at->type == GNPDE_ATT_SCALED_DOT || at->type == GNPDE_ATT_EXP_KERNEL) && dk_ok && hubs_ride(g) && !generic) {
+    // (the exp kernel through the same row kernels, MODE 4: squared distance instead of the dot product, per-entry formula as
+    //  edge_score<GNPDE_ATT_EXP_KERNEL>: 815 -> ~1000 steps/s at the ogbn-arxiv shape)
+    sd(GNPDE_ATT_ROUTE_SD_ROWS, dk / 4, at->type == GNPDE_ATT_EXP_KERNEL ? 4 : 0);
+  } else if (fused) {
+    // a row kernel per class; the hub rows in two launches of their own, as a parallel branch when a second stream is given.  The
+    // scaled-dot scores keep their specialised row kernels here (a forked stream, or a graph without the chunk table)
+    sd(GNPDE_ATT_ROUTE_ROWS, at->type == GNPDE_ATT_SCALED_DOT && dk_ok && !generic ? dk / 4 : 0, 0);
+    l.hubs = l.n_hub == 0 ? GNPDE_ATT_HUBS_NONE : one_stream ? GNPDE_ATT_HUBS_OWN : GNPDE_ATT_HUBS_OWN_FORKED;
+  } else if (sd_fast) {
+    sd(GNPDE_ATT_ROUTE_SD_ROWS, dk / 4, sq ? 2 : 0, sq ? 1 : -1);
+    l.swapped = l.scatter = at->norm_idx == 1;
+  } else {
+    l.route = GNPDE_ATT_ROUTE_GENERAL;
+    l.passes = (rq.pass == 0 ? 7 : 1 << (rq.pass - 1)) & (rq.stats_only ? 3 : 7);
+    if (sq && rq.pass <= 1) l.gmax = GNPDE_ATT_GMAX_ATOMIC;      // (scores_kernel: atomic maxima, behind a memset)
+    l.seg_stats_heads = heads_ok;
+    l.n_long = at->norm_idx == 0 ? g->n_long_rows : g->n_long_cols;
+    p->long_list = l.n_long > 0 ? (at->norm_idx == 0 ? g->long_rows : g->long_cols) : nullptr;
+    l.max_chunks = ((at->norm_idx == 0 ? g->max_row_len : g->max_col_len) + GNPDE_LONG_ROW - 1) / GNPDE_LONG_ROW;
+    const bool long_passes = p->long_list != nullptr && (l.passes & 2);
+    if (long_passes) l.hubs = GNPDE_ATT_HUBS_LONG_STATS;
+    p->scores_grid = stream_grid(static_cast<long long>(g->e) * h);
+    p->stats_grid = ceil_blocks(g->n, kWavesPerBlock);
+    p->norm_grid = stream_grid(g->e);
+    l.launches = (l.passes & 1) + ((l.passes >> 1) & 1) * (long_passes ? 3 : 1) + ((l.passes >> 2) & 1);
+  }
+
+  if (l.route == GNPDE_ATT_ROUTE_SD_ROWS) p->row_hubs = l.n_hub;
+  if (p->row_hubs > 0) l.hubs = GNPDE_ATT_HUBS_IN_ROWS;
+  // the grids of the row launches: [sweep][0] rows of <= 16 entries, [sweep][1] rows of 17..GNPDE_LONG_ROW entries (0: no launch)
+  if (l.route == GNPDE_ATT_ROUTE_SD_ONE) {
+    // ONE launch: hub phase 0, the rows of 17..512 entries, the rows of <= 16 entries.  The hub entries' weights are NOT written.
+    const RowShape s = row_shape(h, l.dk4);
+    l.hubs = l.n_hub > 0 ? GNPDE_ATT_HUBS_DEFERRED : GNPDE_ATT_HUBS_NONE;
+    l.rows16 = s.quarter ? GNPDE_ATT_ROWS16_QUARTER : GNPDE_ATT_ROWS16_LANES;
+    l.grid[0][0] = static_cast<unsigned>(l.n_hub) + ceil_blocks(n64, kWavesPerBlock) + ceil_blocks(n16, s.rows16);
+  } else {
+    for (int sw = 0; sw < l.n_sweeps; ++sw) {
+      // first launch: hub phase 0 + rows of <= 16 entries; second: hub phase 1 + rows of 17..512 entries (the maximum sweep of
+      // squareplus, MODE 2, has no hub phase 1)
+      const bool whole_wave = l.dk4 != 0 && l.mode[sw] == 0 && !l.scatter && g_tune[GNPDE_TUNE_ATT_ROWS16] == 9 && row_shape(h, l.dk4).quarter;
+      const RowShape s = row_shape(h, l.dk4, !whole_wave);
+      if (sw == 0) l.rows16 = whole_wave ? GNPDE_ATT_ROWS16_WHOLE_WAVE : s.quarter ? GNPDE_ATT_ROWS16_QUARTER : GNPDE_ATT_ROWS16_LANES;
+      const int hubs2 = l.mode[sw] == 2 ? 0 : p->row_hubs;
+      if (n16 > 0 || p->row_hubs > 0) l.grid[sw][0] = ceil_blocks(n16, s.rows16) + p->row_hubs;
+      if (n64 > 0 || hubs2 > 0) l.grid[sw][1] = ceil_blocks(n64, kWavesPerBlock) + hubs2;
+    }
+    if (l.n_sweeps == 2) {
+      // the maximum sweep of a small grid without hub blocks: per-wave maxima, folded by the blocks of the second sweep
+      // (AttArgs::gmax_part) -- nothing to clear, no fold launch; else slot atomics behind a memset, folded by gmax_fold_kernel
+      const long long waves = (static_cast<long long>(l.grid[0][0]) + l.grid[0][1]) * kWavesPerBlock;
+      const bool per_wave = l.n_hub == 0 && waves <= kGmaxPartCap && g_tune[GNPDE_TUNE_GMAX_SMALL] == 0;
+      l.gmax = per_wave ? GNPDE_ATT_GMAX_PER_WAVE : GNPDE_ATT_GMAX_SLOTS_FOLD;
+      if (per_wave) l.gmax_count = static_cast<int>(waves);
+    }
+  }
+  if (l.route != GNPDE_ATT_ROUTE_GENERAL) {
+    for (int sw = 0; sw < 2; ++sw) l.launches += (l.grid[sw][0] > 0) + (l.grid[sw][1] > 0);
+    l.launches += (l.gmax == GNPDE_ATT_GMAX_SLOTS_FOLD) + (l.hubs == GNPDE_ATT_HUBS_OWN || l.hubs == GNPDE_ATT_HUBS_OWN_FORKED ? 2 : 0);
+  }
+  l.launches += l.gat_terms != 0;
+  return 0;
+}
+
+// AttArgs of a plan: filled once, here.
+AttArgs fill_args(const AttPlan& p) {
+  const gnpde_graph_t* g = p.g;
+  const gnpde_attention_t* at = p.at;
+  const gnpde_attention_launch_t& l = p.l;
   AttArgs a{};
   a.n = g->n; a.e = g->e; a.h = at->heads; a.dk = at->att_dim / at->heads;
   a.type = at->type; a.norm_idx = at->norm_idx; a.square_plus = at->square_plus ? 1 : 0;
@@ -1277,192 +1245,223 @@ static int edge_attention_impl(const gnpde_graph_t* g, const gnpde_attention_t* 
   a.segpos = at->norm_idx == 0 ? nullptr : g->cscpos;
   a.q = at->q; a.k = at->k; a.ldqk = at->ldqk;
   a.output_var = at->output_var; a.lengthscale = at->lengthscale; a.edge_w = at->edge_w_csr;
-  a.scores = reinterpret_cast<float*>(base + L.scores);
-  a.seg_m = reinterpret_cast<float*>(base + L.seg_m);
-  a.seg_den = reinterpret_cast<float*>(base + L.seg_den);
-  a.gmax = reinterpret_cast<unsigned*>(base + L.gmax);
-  a.gat_terms = reinterpret_cast<float*>(base + L.gat);
-  a.w_mean = w_mean_csr; a.att_edge = att_edge; a.prods_edge = prods_edge;
-  a.hub_fold_lds = g_tune[GNPDE_TUNE_HUB_FOLD] == 2 ? 0 : 1;   // default since round 3 (bit-identical; -3.4 % on the R-MAT launch)
-  float* part = reinterpret_cast<float*>(base + L.part);
+  a.scores = reinterpret_cast<float*>(p.ws + p.L.scores);
+  a.seg_m = reinterpret_cast<float*>(p.ws + p.L.seg_m);
+  a.seg_den = reinterpret_cast<float*>(p.ws + p.L.seg_den);
+  a.gmax = reinterpret_cast<unsigned*>(p.ws + p.L.gmax);
+  a.gat_terms = reinterpret_cast<float*>(p.ws + p.L.gat);
+  a.w_mean = p.rq.w_mean; a.att_edge = p.rq.att_edge; a.prods_edge = p.rq.prods_edge;
+  a.hub_fold_lds = l.hub_fold == 2 ? 0 : 1;
+  if (l.route == GNPDE_ATT_ROUTE_GENERAL) {
+    a.long_segs = p.long_list;
+    return a;
+  }
+  // the row and hub kernels: the walked graph and its hub chunks
+  const gnpde_graph_t* r = p.rows;
+  a.rowidx = r->rowidx; a.colidx = r->colidx; a.rowptr = r->rowptr; a.bin_rows = r->bin_rows;
+  a.chunk_begin = r->long_chunk_begin; a.chunk_end = r->long_chunk_end; a.long_segs = r->long_rows;
+  if (l.swapped) {
+    a.q = at->k; a.k = at->q;            // the segment's own vector is k_j, the gathered one q_i
+    a.out_pos = at->t_from_csr;
+  }
+  if (l.gat_terms == 2) {                // gat_terms_kernel's table, read as 4-wide scaled-dot vectors
+    a.type = GNPDE_ATT_SCALED_DOT;
+    a.q = reinterpret_cast<const float*>(p.ws + p.L.gat_table);
+    a.k = a.q + 4 * a.h;
+    a.ldqk = 8 * a.h;
+    a.dk = 4;
+    a.scale_mul = 0.5f;
+    a.inv_sqrt_dk_den = 2.0f;
+  }
+  a.sp_mode = l.mode[0];
+  if (l.gmax == GNPDE_ATT_GMAX_PER_WAVE) {
+    a.gmax_part = a.gmax + 64;           // (256 bytes behind the maximum itself, as the slots)
+    a.gmax_count = l.gmax_count;
+  }
+  return a;
+}
 
-  // GAT's row softmax on the scaled-dot row kernels (gat_terms_kernel's table): the fused row path without edge weights
-  const bool gat_sd = gat && !stats_only && pass_only == 0 && !hubs_only && a.norm_idx == 0 && !a.square_plus && att_edge == nullptr &&
-                      prods_edge == nullptr && w_mean_csr != nullptr && g->bin_rows != nullptr && a.edge_w == nullptr &&
-                      (a.h == 1 || a.h == 2 || a.h == 4 || a.h == 8) && (fork == nullptr || fork->aux == nullptr) &&
-                      (g->n_long_rows == 0 || g->long_chunk_first != nullptr) && g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] == 0;
-  if (gat) {
-    const int term_rows = at->n_key_rows > g->n ? at->n_key_rows : g->n;      // every row a column may address
-    const long long items = static_cast<long long>(term_rows) * a.h;
-    hipLaunchKernelGGL(gat_terms_kernel, dim3(static_cast<unsigned>((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
-                       at->q, at->ldqk, at->gat_a, term_rows, a.h, a.dk, reinterpret_cast<float*>(base + L.gat),
-                       gat_sd ? reinterpret_cast<float*>(base + L.gat_table) : nullptr);
-    GNPDE_LAUNCH_CHECK();
-  }
-  const bool vec4 = (a.dk % 4 == 0) && (a.ldqk % 4 == 0) && (reinterpret_cast<uintptr_t>(a.q) % 16 == 0) &&
-                    (reinterpret_cast<uintptr_t>(a.k) % 16 == 0);
+// ---- launch_planned and its parts: they carry a plan out and decide nothing
+float* hub_part(const AttPlan& p) { return reinterpret_cast<float*>(p.ws + p.L.part); }
 
-  const bool fused = !stats_only && pass_only == 0 && a.norm_idx == 0 && !a.square_plus && att_edge == nullptr &&
-                     prods_edge == nullptr && g->bin_rows != nullptr && fused_supported(a, vec4);
-  GNPDE_CHECK_ARG(g->row_begin == 0 || fused, GNPDE_EINVAL, "edge_attention: a row sub-range needs the fused row path");
-  if (fused) {
-    AttArgs c = a;
-    c.chunk_begin = g->long_chunk_begin;
-    c.chunk_end = g->long_chunk_end;
-    c.long_segs = g->long_rows;
-    if (hubs_only) {   // head-mean weights of the entries of the long rows only (the short rows are attended elsewhere)
-      if (g->n_long_rows > 0) {
-        launch_hub_a_any(c, vec4, part, g->n_long_chunks, stream);
-        GNPDE_LAUNCH_CHECK();
-        hipLaunchKernelGGL(hub_normalise_kernel, dim3(g->n_long_chunks), dim3(kBlock), 0, stream, c, part, g->long_chunk_first);
-        GNPDE_LAUNCH_CHECK();
-      }
-      return 0;
-    }
-    if (gat_sd) {
-      AttArgs c2 = c;
-      c2.type = GNPDE_ATT_SCALED_DOT;
-      c2.q = reinterpret_cast<const float*>(base + L.gat_table);
-      c2.k = c2.q + 4 * a.h;
-      c2.ldqk = 8 * a.h;
-      c2.dk = 4;
-      c2.scale_mul = 0.5f;
-      c2.inv_sqrt_dk_den = 2.0f;
-      c2.sp_mode = 3;
-      if (launch_sd_with_hubs(c2, g->n_bin16, g->n_bin64, g->n_long_rows > 0 ? g->n_long_chunks : 0, part, g->long_chunk_first, stream)) {
-        GNPDE_LAUNCH_CHECK();
-        return 0;
+// one sweep of the scaled-dot row kernels over both row classes, the plan's hub blocks in front of each launch
+template <int H, int DK4, int MODE, bool SCATTER>
+void launch_sd_sweep(const AttPlan& p, AttArgs a, int sw, hipStream_t s) {
+  const gnpde_attention_launch_t& l = p.l;
+  const int n16 = p.rows->n_bin16, n64 = p.rows->n_bin64;
+  float* part = p.row_hubs > 0 ? hub_part(p) : nullptr;
+  const int* chunk_first = p.row_hubs > 0 ? p.rows->long_chunk_first : nullptr;
+  constexpr RowShape S = row_shape(H, DK4);
+  a.sp_mode = MODE;
+  if (l.grid[sw][0] > 0) {
+    bool whole_wave = false;
+    if constexpr (S.quarter && MODE == 0 && !SCATTER) {
+      if (l.rows16 == GNPDE_ATT_ROWS16_WHOLE_WAVE) {      // A/B: a whole wave per row, four (d_k 4) or two rows interleaved (until round 6)
+        constexpr RowShape W = row_shape(H, DK4, false);
+        hipLaunchKernelGGL((row_attention_sd_kernel<H, DK4, W.gl16, W.ri16, W.p16, 1, MODE, SCATTER>), dim3(l.grid[sw][0]), dim3(kBlock), 0, s,
+                           a, 0, n16, p.row_hubs, 0, part, chunk_first);
+        whole_wave = true;
       }
     }
-    // the caller's aggregation follows on this stream and takes the hub rows' normalisation (launch_edge_attention_deferred): one launch
-    if (defer != nullptr && a.type == GNPDE_ATT_SCALED_DOT && vec4 && fork == nullptr && a.edge_w == nullptr && w_mean_csr != nullptr &&
-        g->row_begin == 0 && at->n_key_rows == 0 && (a.dk == 4 || a.dk == 8 || a.dk == 16) &&
-        (g->n_long_rows == 0 || (g->long_chunk_first != nullptr && g->long_chunk_begin != nullptr && g->long_chunk_end != nullptr)) &&
-        g_tune[GNPDE_TUNE_ATT_ONE_LAUNCH] == 0 && g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] == 0 && g_tune[GNPDE_TUNE_ATT_ROWS16] == 0) {
-      const int n_hub = g->n_long_rows > 0 ? g->n_long_chunks : 0;
-      if (launch_sd_one(c, g->n_bin16, g->n_bin64, n_hub, part, stream)) {
-        GNPDE_LAUNCH_CHECK();
-        defer->part = part;
-        defer->scores = a.scores;
-        defer->chunk_first = g->long_chunk_first;
-        defer->w_out = w_mean_csr;
-        defer->h = a.h;
-        defer->taken = 1;
-        return 0;
-      }
-    }
-    if (a.type == GNPDE_ATT_SCALED_DOT && vec4 && (fork == nullptr || fork->aux == nullptr) &&
-        (g->n_long_rows == 0 || g->long_chunk_first != nullptr) &&
-        launch_sd_with_hubs(c, g->n_bin16, g->n_bin64, g->n_long_rows > 0 ? g->n_long_chunks : 0, part, g->long_chunk_first,
-                            stream)) {
-      GNPDE_LAUNCH_CHECK();
-      return 0;
-    }
-    if (a.type == GNPDE_ATT_EXP_KERNEL && vec4 && (fork == nullptr || fork->aux == nullptr) &&
-        (g->n_long_rows == 0 || g->long_chunk_first != nullptr)) {
-      // the exp kernel through the same row kernels (MODE 4: squared distance instead of the dot product, per-entry formula as
-      // edge_score<GNPDE_ATT_EXP_KERNEL>): 815 -> ~1000 steps/s at the ogbn-arxiv shape
-      AttArgs c4 = c;
-      c4.sp_mode = 4;
-      if (launch_sd_with_hubs(c4, g->n_bin16, g->n_bin64, g->n_long_rows > 0 ? g->n_long_chunks : 0, part, g->long_chunk_first, stream)) {
-        GNPDE_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    hipStream_t br = stream;
-    if (g->n_long_rows > 0) {  // hubs: chunk passes, as a parallel branch when a fork stream is given
-      { const int frc = fork_begin(fork, stream, &br); if (frc) return frc; }
-      launch_hub_a_any(c, vec4, part, g->n_long_chunks, br);
-      GNPDE_LAUNCH_CHECK();
-      hipLaunchKernelGGL(hub_normalise_kernel, dim3(g->n_long_chunks), dim3(kBlock), 0, br, c, part, g->long_chunk_first);
-      GNPDE_LAUNCH_CHECK();
-    }
-    launch_rows_any(a, g->n_bin16, g->n_bin64, stream);
-    GNPDE_LAUNCH_CHECK();
-    if (g->n_long_rows > 0) { const int frc = fork_end(fork, stream, br); if (frc) return frc; }
-    return 0;
+    if (!whole_wave)
+      hipLaunchKernelGGL((row_attention_sd_kernel<H, DK4, S.gl16, S.ri16, S.p16, 1, MODE, SCATTER>), dim3(l.grid[sw][0]), dim3(kBlock), 0, s,
+                         a, 0, n16, p.row_hubs, 0, part, chunk_first);
+    if (MODE == 2 && l.gmax == GNPDE_ATT_GMAX_PER_WAVE) a.gmax_base = static_cast<int>(l.grid[sw][0]) * kWavesPerBlock;   // the second launch's waves follow
   }
+  if (l.grid[sw][1] > 0)
+    hipLaunchKernelGGL((row_attention_sd_kernel<H, DK4, kWave, 1, S.pb64, S.p64 / S.pb64, MODE, SCATTER>), dim3(l.grid[sw][1]), dim3(kBlock), 0, s,
+                       a, n16, n64, MODE == 2 ? 0 : p.row_hubs, 1, part, chunk_first);
+}
 
-  // scaled-dot scores with the OTHER normalisers in fused segment passes (the three passes below round-trip an [E,h] score array
-  // and walk the segments twice: 2 - 2.5 x the time of the row softmax at the ogbn-arxiv shape).  squareplus: one sweep for the
-  // global maximum, then the fused kernel with it; normalisation over the columns: the same kernels over the rows of the
-  // transposed graph with q and k exchanged, the weights scattered to their CSR positions.
-  {
-    const gnpde_graph_t* sg = a.norm_idx == 0 ? g : at->graph_t;
-    const bool sd_fast = !stats_only && pass_only == 0 && !hubs_only && a.type == GNPDE_ATT_SCALED_DOT && vec4 && att_edge == nullptr &&
-                         prods_edge == nullptr && w_mean_csr != nullptr && (fork == nullptr || fork->aux == nullptr) &&
-                         (a.h == 1 || a.h == 2 || a.h == 4 || a.h == 8) && (a.dk == 4 || a.dk == 8 || a.dk == 16) &&
-                         g_tune[GNPDE_TUNE_ATT_GENERIC_ROWS] == 0 && g->row_begin == 0 && sg != nullptr && sg->bin_rows != nullptr &&
-                         sg->rowidx != nullptr && sg->n == g->n && sg->e == g->e && sg->row_begin == 0 &&
-                         (sg->n_long_rows == 0 || (sg->long_chunk_first != nullptr && sg->long_chunk_begin != nullptr)) &&
-                         (a.norm_idx == 0 || (at->t_from_csr != nullptr && a.edge_w == nullptr));
-    if (sd_fast) {
-      AttArgs c = a;
-      c.rowidx = sg->rowidx; c.colidx = sg->colidx; c.rowptr = sg->rowptr; c.bin_rows = sg->bin_rows;
-      c.chunk_begin = sg->long_chunk_begin; c.chunk_end = sg->long_chunk_end; c.long_segs = sg->long_rows;
-      if (a.norm_idx == 1) {
-        c.q = a.k; c.k = a.q;            // the segment's own vector is k_j, the gathered one q_i
-        c.out_pos = at->t_from_csr;
-      }
-      const int n_hub = sg->n_long_rows > 0 ? sg->n_long_chunks : 0;
-      if (a.square_plus) {
-        c.sp_mode = 2;
-        long long sw[2];
-        sd_sweep_waves(a.h, a.dk / 4, sg->n_bin16, sg->n_bin64, sw);
-        if (n_hub == 0 && sw[0] + sw[1] <= kGmaxPartCap && g_tune[GNPDE_TUNE_GMAX_SMALL] == 0) {
-          // small grid: per-wave maxima, folded by the blocks of the second sweep (AttArgs::gmax_part) -- nothing to clear, no fold launch
-          c.gmax_part = a.gmax + 64;
-          c.gmax_base = 0;
-          c.gmax_count = static_cast<int>(sw[0] + sw[1]);
-          if (!launch_sd_with_hubs(c, sg->n_bin16, sg->n_bin64, n_hub, part, sg->long_chunk_first, stream)) return GNPDE_ESHAPE;
-          GNPDE_LAUNCH_CHECK();
-        } else {
-          GNPDE_HIP(hipMemsetAsync(a.gmax, 0, 256 + kGmaxSlots * 128, stream));
-          c.gmax_slots = a.gmax + 64;          // (256 bytes behind the maximum itself)
-          if (!launch_sd_with_hubs(c, sg->n_bin16, sg->n_bin64, n_hub, part, sg->long_chunk_first, stream)) return GNPDE_ESHAPE;
-          GNPDE_LAUNCH_CHECK();
-          hipLaunchKernelGGL(gmax_fold_kernel, dim3(1), dim3(kWave), 0, stream, c.gmax_slots, a.gmax);
-          GNPDE_LAUNCH_CHECK();
-          c.gmax_slots = nullptr;
-        }
-        c.sp_mode = 1;
-      }
-      if (!launch_sd_with_hubs(c, sg->n_bin16, sg->n_bin64, n_hub, part, sg->long_chunk_first, stream)) return GNPDE_ESHAPE;
-      GNPDE_LAUNCH_CHECK();
-      return 0;
+// THE (MODE, SCATTER) switch of the scaled-dot row kernels: MODE 3 at d_k = 4 only, SCATTER at MODE 0 and 1
+void launch_sd_rows(const AttPlan& p, const AttArgs& a, int sw, hipStream_t s) {
+  const int mode = p.l.mode[sw];
+  const bool sc = p.l.scatter != 0;
+  visit_line(p.l.h, p.l.dk4, [&](auto H_, auto D_) {
+    constexpr int H = decltype(H_)::value, DK4 = decltype(D_)::value;
+    if (mode == 4) launch_sd_sweep<H, DK4, 4, false>(p, a, sw, s);             // exp kernel scores
+    else if (mode == 3) {                                                       // GAT scores (4-wide vectors only)
+      if constexpr (DK4 == 1) launch_sd_sweep<H, DK4, 3, false>(p, a, sw, s);
     }
-  }
-  if (a.square_plus && pass_only <= 1) GNPDE_HIP(hipMemsetAsync(a.gmax, 0, 256 + kGmaxSlots * 128, stream));    // (scores_kernel: atomic maxima)
-  if (pass_only == 0 || pass_only == 1) {
-    launch_scores_any(a, vec4, stream_grid(static_cast<long long>(a.e) * a.h), stream);
-    GNPDE_LAUNCH_CHECK();
-  }
-  a.long_segs = (n_long > 0 && long_list != nullptr) ? long_list : nullptr;
-  if (pass_only == 0 || pass_only == 2) {
-    const dim3 sgrid((g->n + kWavesPerBlock - 1) / kWavesPerBlock);
-    switch (a.h) {
-      case 1: hipLaunchKernelGGL(seg_stats_heads_kernel<1>, sgrid, dim3(kBlock), 0, stream, a); break;
-      case 2: hipLaunchKernelGGL(seg_stats_heads_kernel<2>, sgrid, dim3(kBlock), 0, stream, a); break;
-      case 4: hipLaunchKernelGGL(seg_stats_heads_kernel<4>, sgrid, dim3(kBlock), 0, stream, a); break;
-      case 8: hipLaunchKernelGGL(seg_stats_heads_kernel<8>, sgrid, dim3(kBlock), 0, stream, a); break;
-      default: hipLaunchKernelGGL(seg_stats_kernel, sgrid, dim3(kBlock), 0, stream, a); break;
+    else if (mode == 2) launch_sd_sweep<H, DK4, 2, false>(p, a, sw, s);        // (the maximum sweep: writes no weights)
+    else if (mode == 1 && sc) launch_sd_sweep<H, DK4, 1, true>(p, a, sw, s);
+    else if (mode == 1) launch_sd_sweep<H, DK4, 1, false>(p, a, sw, s);
+    else if (sc) launch_sd_sweep<H, DK4, 0, true>(p, a, sw, s);
+    else launch_sd_sweep<H, DK4, 0, false>(p, a, sw, s);
+  });
+}
+
+// the row launches of GNPDE_ATT_ROUTE_ROWS: row_attention_kernel per class, or the scaled-dot row kernels without hub blocks
+void launch_rows(const AttPlan& p, const AttArgs& a, hipStream_t s) {
+  if (p.l.dk4 != 0) return launch_sd_rows(p, a, 0, s);
+  const int n16 = p.rows->n_bin16, n64 = p.rows->n_bin64;
+  visit_type(a.type, [&](auto T_) {
+    visit_heads(p.l.h, [&](auto H_) {
+      constexpr int TYPE = decltype(T_)::value, H = decltype(H_)::value;
+      constexpr bool VEC4 = TYPE != GNPDE_ATT_GAT;
+      constexpr RowShape S = row_shape(H, 0);
+      if (p.l.grid[0][0] > 0)
+        hipLaunchKernelGGL((row_attention_kernel<TYPE, H, S.gl16, S.p16, VEC4>), dim3(p.l.grid[0][0]), dim3(kBlock), 0, s, a, 0, n16);
+      if (p.l.grid[0][1] > 0)
+        hipLaunchKernelGGL((row_attention_kernel<TYPE, H, kWave, S.p64, VEC4>), dim3(p.l.grid[0][1]), dim3(kBlock), 0, s, a, n16, n64);
+    });
+  });
+}
+
+// the hub rows in two launches of their own: chunk statistics, then the weights of the chunks' entries
+int launch_hubs(const AttPlan& p, const AttArgs& a, hipStream_t s) {
+  float* part = hub_part(p);
+  const dim3 grid(p.l.n_hub);
+  visit_type(a.type, [&](auto T_) {
+    constexpr int TYPE = decltype(T_)::value;
+    const bool v = p.l.vec4 && TYPE != GNPDE_ATT_GAT;
+    if constexpr (TYPE == GNPDE_ATT_SCALED_DOT) {
+      if (v && visit_heads(p.l.h, [&](auto H_) {
+            hipLaunchKernelGGL(hub_scores_partial_sd_kernel<decltype(H_)::value>, grid, dim3(kBlock), 0, s, a, part);
+          })) return;
     }
-  }
+    if (v) hipLaunchKernelGGL((hub_scores_partial_kernel<TYPE, true>), grid, dim3(kBlock), 0, s, a, part);
+    else hipLaunchKernelGGL((hub_scores_partial_kernel<TYPE, false>), grid, dim3(kBlock), 0, s, a, part);
+  });
   GNPDE_LAUNCH_CHECK();
-  if (a.long_segs != nullptr && (pass_only == 0 || pass_only == 2)) {
-    hipLaunchKernelGGL(seg_stats_long_partial_kernel, dim3(n_long, max_chunks), dim3(kBlock), 0, stream, a, part, max_chunks);
-    GNPDE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(seg_stats_long_combine_kernel, dim3(n_long), dim3(kWave), 0, stream, a, part, max_chunks);
+  hipLaunchKernelGGL(hub_normalise_kernel, grid, dim3(kBlock), 0, s, a, part, p.rows->long_chunk_first);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_planned(const AttPlan& p, hipStream_t stream) {
+  const gnpde_attention_launch_t& l = p.l;
+  if (l.route == GNPDE_ATT_ROUTE_NONE) return 0;
+  AttArgs a = fill_args(p);
+  if (l.gat_terms != 0) {
+    const int term_rows = p.at->n_key_rows > p.g->n ? p.at->n_key_rows : p.g->n;      // every row a column may address
+    hipLaunchKernelGGL(gat_terms_kernel, dim3(ceil_blocks(static_cast<long long>(term_rows) * l.h, kBlock)), dim3(kBlock), 0, stream,
+                       p.at->q, p.at->ldqk, p.at->gat_a, term_rows, l.h, p.at->att_dim / l.h, reinterpret_cast<float*>(p.ws + p.L.gat),
+                       l.gat_terms == 2 ? reinterpret_cast<float*>(p.ws + p.L.gat_table) : nullptr);
     GNPDE_LAUNCH_CHECK();
   }
-  if (args_out != nullptr) *args_out = a;
-  if (stats_only) return 0;
-  if (pass_only == 0 || pass_only == 3) {
-    hipLaunchKernelGGL(normalise_kernel, dim3(stream_grid(a.e)), dim3(kBlock), 0, stream, a);
+  switch (l.route) {
+    case GNPDE_ATT_ROUTE_HUBS_ONLY:
+      return l.hubs == GNPDE_ATT_HUBS_OWN ? launch_hubs(p, a, stream) : 0;
+    case GNPDE_ATT_ROUTE_SD_ONE: {
+      if (l.grid[0][0] > 0)
+        visit_line<4>(l.h, l.dk4, [&](auto H_, auto D_) {
+          constexpr RowShape S = row_shape(decltype(H_)::value, decltype(D_)::value);
+          hipLaunchKernelGGL((row_attention_sd_one_kernel<decltype(H_)::value, decltype(D_)::value, S.gl16, S.ri16, S.p16, S.pb64, S.p64 / S.pb64>),
+                             dim3(l.grid[0][0]), dim3(kBlock), 0, stream, a, p.g->n_bin16, p.g->n_bin64, l.n_hub, hub_part(p));
+        });
+      GNPDE_LAUNCH_CHECK();
+      *p.rq.defer = HubDefer{hub_part(p), a.scores, p.g->long_chunk_first, p.rq.w_mean, l.h, 1};     // (taken)
+      return 0;
+    }
+    case GNPDE_ATT_ROUTE_SD_ROWS:
+      for (int sw = 0; sw < l.n_sweeps; ++sw) {
+        const bool slots = sw == 0 && l.gmax == GNPDE_ATT_GMAX_SLOTS_FOLD;
+        if (slots) {
+          GNPDE_HIP(hipMemsetAsync(a.gmax, 0, 256 + kGmaxSlots * 128, stream));
+          a.gmax_slots = a.gmax + 64;          // (256 bytes behind the maximum itself)
+        }
+        launch_sd_rows(p, a, sw, stream);
+        GNPDE_LAUNCH_CHECK();
+        if (slots) {
+          hipLaunchKernelGGL(gmax_fold_kernel, dim3(1), dim3(kWave), 0, stream, a.gmax_slots, a.gmax);
+          GNPDE_LAUNCH_CHECK();
+          a.gmax_slots = nullptr;
+        }
+      }
+      return 0;
+    case GNPDE_ATT_ROUTE_ROWS: {
+      hipStream_t br = stream;
+      if (l.hubs != GNPDE_ATT_HUBS_NONE) {  // hubs: chunk passes, as a parallel branch when a fork stream is given
+        if (const int rc = fork_begin(p.rq.fork, stream, &br)) return rc;
+        if (const int rc = launch_hubs(p, a, br)) return rc;
+      }
+      launch_rows(p, a, stream);      // (a carries the hub chunk tables too: the row kernels read them in hub blocks only, and here they have none)
+      GNPDE_LAUNCH_CHECK();
+      return l.hubs != GNPDE_ATT_HUBS_NONE ? fork_end(p.rq.fork, stream, br) : 0;
+    }
+    default: break;
+  }
+  // the three general passes
+  if (l.gmax == GNPDE_ATT_GMAX_ATOMIC) GNPDE_HIP(hipMemsetAsync(a.gmax, 0, 256 + kGmaxSlots * 128, stream));
+  if (l.passes & 1) {
+    visit_type(a.type, [&](auto T_) {
+      constexpr int TYPE = decltype(T_)::value;
+      if (l.vec4 && TYPE != GNPDE_ATT_GAT) hipLaunchKernelGGL((scores_kernel<TYPE, true>), dim3(p.scores_grid), dim3(kBlock), 0, stream, a);
+      else hipLaunchKernelGGL((scores_kernel<TYPE, false>), dim3(p.scores_grid), dim3(kBlock), 0, stream, a);
+    });
+    GNPDE_LAUNCH_CHECK();
+  }
+  if (l.passes & 2) {
+    if (l.seg_stats_heads)
+      visit_heads(l.h, [&](auto H_) { hipLaunchKernelGGL(seg_stats_heads_kernel<decltype(H_)::value>, dim3(p.stats_grid), dim3(kBlock), 0, stream, a); });
+    else
+      hipLaunchKernelGGL(seg_stats_kernel, dim3(p.stats_grid), dim3(kBlock), 0, stream, a);
+    GNPDE_LAUNCH_CHECK();
+  }
+  if (l.hubs == GNPDE_ATT_HUBS_LONG_STATS) {
+    hipLaunchKernelGGL(seg_stats_long_partial_kernel, dim3(l.n_long, l.max_chunks), dim3(kBlock), 0, stream, a, hub_part(p), l.max_chunks);
+    GNPDE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(seg_stats_long_combine_kernel, dim3(l.n_long), dim3(kWave), 0, stream, a, hub_part(p), l.max_chunks);
+    GNPDE_LAUNCH_CHECK();
+  }
+  if (p.rq.args_out != nullptr) *p.rq.args_out = a;
+  if (l.passes & 4) {
+    hipLaunchKernelGGL(normalise_kernel, dim3(p.norm_grid), dim3(kBlock), 0, stream, a);
     GNPDE_LAUNCH_CHECK();
   }
   return 0;
 }
+
+int edge_attention_impl(const gnpde_graph_t* g, const gnpde_attention_t* at, const AttRequest& rq, void* ws, size_t ws_bytes, hipStream_t stream) {
+  AttPlan plan;
+  if (const int rc = plan_attention(g, at, rq, ws, ws_bytes, &plan)) return rc;
+  return launch_planned(plan, stream);
+}
+
+}  // namespace
+
+size_t attention_workspace_bytes(const gnpde_graph_t* g, int h, bool gat);
 
 // One pass of the general path at a time (the row-partitioned solver exchanges between them: the global maximum of squareplus
 // after pass 1, the per-column partial statistics of attention_norm_idx = 1 after pass 2)
@@ -1470,9 +1469,41 @@ int launch_edge_attention_pass(const gnpde_graph_t* g, const gnpde_attention_t* 
                                size_t ws_bytes, hipStream_t stream) {
   GNPDE_CHECK_ARG(pass >= 1 && pass <= 3, GNPDE_EINVAL, "edge_attention_pass: pass must be 1 (scores), 2 (segment statistics) or 3 (normalise)");
   GNPDE_CHECK_ARG(pass != 3 || w_mean_csr != nullptr, GNPDE_EINVAL, "edge_attention_pass: pass 3 writes w_mean_csr");
-  float dummy_out = 0.f;   // (the impl wants an output to be named; passes 1 and 2 write none)
-  return edge_attention_impl(g, at, pass == 3 ? w_mean_csr : &dummy_out, nullptr, nullptr, ws, ws_bytes, stream, nullptr, false, nullptr,
-                             false, pass);
+  AttRequest rq;
+  rq.pass = pass;
+  rq.w_mean = pass == 3 ? w_mean_csr : nullptr;      // (passes 1 and 2 write no output)
+  return edge_attention_impl(g, at, rq, ws, ws_bytes, stream);
+}
+
+int launch_edge_attention(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, float* att_edge,
+                          float* prods_edge, void* ws, size_t ws_bytes, hipStream_t stream, const Fork* fork) {
+  AttRequest rq;
+  rq.w_mean = w_mean_csr; rq.att_edge = att_edge; rq.prods_edge = prods_edge;
+  rq.fork = fork;
+  return edge_attention_impl(g, at, rq, ws, ws_bytes, stream);
+}
+
+// The attention of an evaluation whose aggregation (launch_spmm_rhs with `defer`, same stream) follows.  Where the plain scaled-dot
+// row softmax runs (whole graph, no re-weighting, a specialised (heads, d_k)) it takes ONE launch, leaves the weights of the hub
+// rows' entries unwritten and sets defer->taken: the aggregation's hub-chunk items form and store them.  Everything else runs
+// launch_edge_attention's launches and leaves defer->taken == 0 (the weights are complete): one plan either way.
+int launch_edge_attention_deferred(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
+                                   hipStream_t stream, HubDefer* defer) {
+  *defer = HubDefer{};
+  AttRequest rq;
+  rq.w_mean = w_mean_csr;
+  rq.defer = defer;
+  return edge_attention_impl(g, at, rq, ws, ws_bytes, stream);
+}
+
+// w_mean_csr[p] for the entries of the rows longer than GNPDE_LONG_ROW only (row softmax path); the caller attends the
+// other rows itself (attn_spmm_kernel)
+int launch_hub_attention(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
+                         hipStream_t stream) {
+  AttRequest rq;
+  rq.w_mean = w_mean_csr;
+  rq.hubs_only = true;
+  return edge_attention_impl(g, at, rq, ws, ws_bytes, stream);
 }
 
 // merge of segment statistics (m, den) <- (m, den) (+) (m_in, den_in) for the rows listed: the online-softmax combination,
@@ -1495,27 +1526,6 @@ __global__ __launch_bounds__(kBlock) void stats_merge_kernel(float* __restrict__
   m[o] = mm;
 }
 
-int launch_edge_attention(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, float* att_edge,
-                          float* prods_edge, void* ws, size_t ws_bytes, hipStream_t stream, const Fork* fork) {
-  return edge_attention_impl(g, at, w_mean_csr, att_edge, prods_edge, ws, ws_bytes, stream, fork, false, nullptr);
-}
-
-// The attention of an evaluation whose aggregation (launch_spmm_rhs with `defer`, same stream) follows.  Where the plain scaled-dot
-// row softmax runs (whole graph, no re-weighting, a specialised (heads, d_k)) it takes ONE launch, leaves the weights of the hub
-// rows' entries unwritten and sets defer->taken: the aggregation's hub-chunk items form and store them.  Everything else runs
-// launch_edge_attention's launches and leaves defer->taken == 0 (the weights are complete).
-int launch_edge_attention_deferred(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
-                                   hipStream_t stream, HubDefer* defer) {
-  *defer = HubDefer{};
-  return edge_attention_impl(g, at, w_mean_csr, nullptr, nullptr, ws, ws_bytes, stream, nullptr, false, nullptr, false, 0, defer);
-}
-
-// w_mean_csr[p] for the entries of the rows longer than GNPDE_LONG_ROW only (row softmax path); the caller attends the
-// other rows itself (attn_spmm_kernel)
-int launch_hub_attention(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
-                         hipStream_t stream) {
-  return edge_attention_impl(g, at, w_mean_csr, nullptr, nullptr, ws, ws_bytes, stream, nullptr, false, nullptr, true);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Backward of the normalisation + head mean for EVERY normaliser (softmax or squareplus, over rows or columns):
@@ -1681,7 +1691,10 @@ int launch_edge_attention_bwd(const gnpde_graph_t* g, const gnpde_attention_t* a
   const size_t need = attention_bwd_workspace_bytes(g, at->heads, gat);
   GNPDE_CHECK_ARG(ws && ws_bytes >= need, GNPDE_EWS, "edge_attention_bwd: workspace %zu < %zu bytes", ws_bytes, need);
   AttArgs a{};
-  int rc = edge_attention_impl(g, at, nullptr, nullptr, nullptr, ws, fwd, stream, nullptr, true, &a);
+  AttRequest rq;     // the forward's general passes 1-2, recomputed, and their arguments
+  rq.stats_only = true;
+  rq.args_out = &a;
+  int rc = edge_attention_impl(g, at, rq, ws, fwd, stream);
   if (rc) return rc;
   BwdArgs b{};
   b.dw = dw_csr;
@@ -1763,6 +1776,29 @@ extern "C" int gnpde_edge_attention(const gnpde_graph_t* g, const gnpde_attentio
                                     float* prods_edge, void* workspace, size_t workspace_bytes, void* stream) {
   return gnpde::launch_edge_attention(g, a, w_mean_csr, att_edge, prods_edge, workspace, workspace_bytes,
                                       static_cast<hipStream_t>(stream), nullptr);
+}
+
+extern "C" int gnpde_attention_plan(const gnpde_graph_t* g, const gnpde_attention_t* a, uint32_t request_flags, int32_t pass,
+                                    uint64_t workspace_addr, gnpde_attention_launch_t* plan) {
+  GNPDE_CHECK_ARG(plan != nullptr && pass >= 0 && pass <= 3, GNPDE_EINVAL, "attention_plan: plan is null or pass outside 0..3");
+  // stand-ins for what the flags say is given: the planner reads that they are there
+  float* const given = reinterpret_cast<float*>(uintptr_t{16});
+  gnpde::Fork fork;
+  fork.aux = reinterpret_cast<hipStream_t>(uintptr_t{16});
+  gnpde::HubDefer defer;
+  gnpde::AttRequest rq;
+  if (request_flags & GNPDE_ATT_PLAN_W_MEAN) rq.w_mean = given;
+  if (request_flags & GNPDE_ATT_PLAN_ATT_EDGE) rq.att_edge = given;
+  if (request_flags & GNPDE_ATT_PLAN_PRODS_EDGE) rq.prods_edge = given;
+  if (request_flags & GNPDE_ATT_PLAN_FORK) rq.fork = &fork;
+  if (request_flags & GNPDE_ATT_PLAN_DEFER) rq.defer = &defer;
+  rq.hubs_only = (request_flags & GNPDE_ATT_PLAN_HUBS_ONLY) != 0;
+  rq.stats_only = (request_flags & GNPDE_ATT_PLAN_STATS_ONLY) != 0;
+  rq.pass = pass;
+  gnpde::AttPlan p;
+  const int rc = gnpde::plan_attention(g, a, rq, reinterpret_cast<void*>(static_cast<uintptr_t>(workspace_addr)), SIZE_MAX, &p);
+  *plan = p.l;
+  return rc;
 }
 
 extern "C" size_t gnpde_attention_bwd_workspace_bytes(const gnpde_graph_t* g, const gnpde_attention_t* a) {

@@ -141,10 +141,12 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
     }
     // Whole-graph GRAND-nl with the plain scaled-dot row softmax, fp32 gather, aggregation next on this stream: the row attention is
     // ONE launch, and the hub-chunk items of the aggregation normalise the hub rows (HubDefer) -- the weight buffer is complete after the
-    // aggregation, so a recorded solve takes this form too.  Whatever the attention launcher does not cover keeps its own launches.
-    if (lo == nullptr && fork == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && r.att.type == GNPDE_ATT_SCALED_DOT && r.att.norm_idx == 0 &&
-        !r.att.square_plus && r.att.edge_w_csr == nullptr && r.proj_row_end == 0 && r.n_state_rows <= g->n && g->row_begin == 0 &&
-        g_tune[GNPDE_TUNE_ATT_ONE_LAUNCH] == 0 && spmm_hub_defer_supported(g, u, r.d, r.ld, epi, ws + L.spmm, padded)) {
+    // aggregation, so a recorded solve takes this form too.  Here stand the conditions that are the evaluation's -- among them the
+    // score type the CALLER named: cosine_sim / pearson reach the attention as scaled_dot (above) and keep their two launches.  The
+    // attention's own conditions are its plan's: the deferred launcher plans once, runs what the plan says (the plain launcher's launches
+    // where that is not the one launch) and reports in defer.taken which it was.
+    if (lo == nullptr && fork == nullptr && r.kind == GNPDE_RHS_TRANSFORMER && r.att.type == GNPDE_ATT_SCALED_DOT && r.proj_row_end == 0 &&
+        r.n_state_rows <= g->n && spmm_hub_defer_supported(g, u, r.d, r.ld, epi, ws + L.spmm, padded)) {
       HubDefer defer;
       rc = launch_edge_attention_deferred(g, &at, wmean, ws + L.att, L.att_bytes, s, &defer);
       if (rc) return rc;

@@ -1574,6 +1574,20 @@ def attention_struct(att_type, heads, att_dim, norm_idx, square_plus, q=None, k=
   return a
 
 
+def attention_plan(graph, att, want_w_mean=True, want_att=False, want_prods=False, ws_addr=256, fork=False, defer=False, hubs_only=False,
+                   stats_only=False, pass_=0):
+  """The launches a row attention with these operands takes (gnpde_attention_plan -> _lib.AttentionLaunchStruct): route, template line
+  of the row kernels, sweeps, grids, hub handling.  att is an attention_struct whose addresses are read for their alignment (and for
+  being null) only; graph (and the struct's graph_t) may live on the host.  Nothing is launched and no device is needed; a call the
+  launch would refuse raises."""
+  plan = _lib.AttentionLaunchStruct()
+  flags = (_lib.ATT_PLAN_W_MEAN * bool(want_w_mean) | _lib.ATT_PLAN_ATT_EDGE * bool(want_att) | _lib.ATT_PLAN_PRODS_EDGE * bool(want_prods) |
+           _lib.ATT_PLAN_FORK * bool(fork) | _lib.ATT_PLAN_DEFER * bool(defer) | _lib.ATT_PLAN_HUBS_ONLY * bool(hubs_only) |
+           _lib.ATT_PLAN_STATS_ONLY * bool(stats_only))
+  check(_lib.lib().gnpde_attention_plan(graph.ref(), ctypes.byref(att), flags, int(pass_), int(ws_addr), ctypes.byref(plan)))
+  return plan
+
+
 def edge_attention(graph, att, want_w_mean=True, want_att=False, want_prods=False, like=None):
   """Run the three attention passes.  Returns (w_mean_csr [e] | None, att [E,h] | None, prods [E,h] | None),
   the [E,h] tensors in the caller's edge order."""

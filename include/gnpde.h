@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 22  /* 22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 23  /* 23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -387,6 +387,92 @@ int gnpde_edge_attention_pass(const gnpde_graph_t* g, const gnpde_attention_t* a
 int gnpde_attention_workspace_regions(const gnpde_graph_t* g, const gnpde_attention_t* a, size_t* offsets);
 int gnpde_segment_stats_merge(float* seg_m, float* seg_den, const int32_t* rows, int32_t n_rows, int32_t heads,
                               const float* m_in, const float* den_in, int32_t square_plus, void* stream);
+
+/* The launch decision of gnpde_edge_attention, gnpde_edge_attention_pass, the backward's forward passes and the attention inside
+ * gnpde_rhs_eval / the solvers, as gnpde_spmm_plan gives the aggregation's: route, template line of the row kernels, sweeps, grids and how
+ * the hub rows (more than GNPDE_LONG_ROW entries) are handled.  Nothing is launched, no device is needed and no address is dereferenced:
+ * workspace_addr and the pointer fields of *a (q, k, gat_a, output_var, lengthscale, edge_w_csr, t_from_csr) are read for their alignment
+ * and for being null only; *g and a->graph_t are host structs whose counts and non-null arrays are read.  The launchers of the library
+ * switch on the very same result, so a plan is what runs.  request_flags: GNPDE_ATT_PLAN_W_MEAN / _ATT_EDGE / _PRODS_EDGE the outputs
+ * wanted, _FORK a second stream is given for the hub rows, _DEFER an aggregation follows that can normalise the hub rows (the solver's
+ * evaluation), _HUBS_ONLY the hub rows' weights alone, _STATS_ONLY general passes 1-2 alone (the backward); pass: 0, or 1..3 as
+ * gnpde_edge_attention_pass.  Returns what the launch would return for these operands: 0, or GNPDE_EINVAL / GNPDE_EWS (workspace
+ * null) with gnpde_last_error set; the workspace SIZE is not part of the question.
+ *   vec4     d_k % 4 == 0, ldqk % 4 == 0, q and k 16-byte aligned
+ *   route    by the first line that holds (h in {1,2,4,8} for every line but the last; "rows alone" = head-mean weights alone,
+ *            attention_norm_idx 0, no squareplus, the graph has bin_rows, GAT or vec4):
+ *     GNPDE_ATT_ROUTE_NONE       no node or no edge
+ *     GNPDE_ATT_ROUTE_HUBS_ONLY  rows alone, _HUBS_ONLY: hub chunk statistics + hub_normalise_kernel (hubs = OWN), nothing without hub rows
+ *     GNPDE_ATT_ROUTE_SD_ROWS    row_attention_sd_kernel<h, dk4, .., MODE, SCATTER>, one launch per row class and sweep, the hub chunks in
+ *                                their first blocks (hubs = IN_ROWS); needs one stream, the graph's long_chunk_first, gnpde_tune(4, 0):
+ *                                  rows alone, GAT without edge weights: gat_terms = 2 (node terms + their 4-wide table), dk4 1, MODE 3
+ *                                  rows alone, scaled_dot / exp_kernel, d_k in {4,8,16}: MODE 0 / MODE 4
+ *                                  weights alone, scaled_dot, vec4, d_k in {4,8,16}, squareplus and / or attention_norm_idx 1 (graph_t and
+ *                                  t_from_csr given, no edge weights: swapped = scatter = 1, the rows of graph_t with q and k exchanged):
+ *                                  MODE 0, or the sweeps MODE 2 (global maximum) then MODE 1 for squareplus
+ *     GNPDE_ATT_ROUTE_SD_ONE     _DEFER, rows alone, scaled_dot, d_k in {4,8,16}, h <= 4, whole graph, no halo rows, no edge weights, no
+ *                                fork, gnpde_tune(21, 0), (4, 0), (17, 0): row_attention_sd_one_kernel, ONE launch (grid[0][0]); hubs =
+ *                                DEFERRED: the aggregation forms the hub entries' weights.  Tested before the scaled_dot line of SD_ROWS.
+ *     GNPDE_ATT_ROUTE_ROWS       rows alone, whatever is left: one launch per row class -- row_attention_sd_kernel without hub blocks
+ *                                (dk4 != 0: scaled_dot, d_k in {4,8,16}, gnpde_tune(4, 0); reached with _FORK or without long_chunk_first)
+ *                                or row_attention_kernel<type, h> (dk4 = 0) -- and the hub rows in two launches of their own (hubs = OWN,
+ *                                or OWN_FORKED on the second stream)
+ *     GNPDE_ATT_ROUTE_GENERAL    everything else: the passes of the bit mask `passes` (1 scores_kernel, 2 segment statistics --
+ *                                seg_stats_heads = 1: seg_stats_heads_kernel<h> -- plus, hubs = LONG_STATS, two launches over the n_long
+ *                                long segments x max_chunks chunks, 4 normalise_kernel); a row sub-range (row_begin > 0): GNPDE_EINVAL
+ *   rows16   lane mapping of the rows of <= 16 entries: QUARTER 16 lanes a row, two rows interleaved (h = 4, d_k 4 or 16 on the SD
+ *            kernels), LANES 16 h lanes (at most a wave), WHOLE_WAVE the A/B form of gnpde_tune(17, 9) (QUARTER's cases, MODE 0, no SCATTER)
+ *   gmax     squareplus' global maximum: PER_WAVE one word per wave of the MODE 2 sweep (gmax_count of them), folded by the second sweep
+ *            (no hub rows, at most 8192 waves, gnpde_tune(16, 0)); SLOTS_FOLD memset + slot atomics + gmax_fold_kernel; ATOMIC memset +
+ *            atomics in scores_kernel (GENERAL, pass 0 or 1)
+ *   grid     [sweep][0] rows of <= 16 entries: ceil(n_bin16 / rows per workgroup) + hub blocks, rows per workgroup = 4 x (64 / lanes a row)
+ *            x rows interleaved (SD kernels: 4 at d_k 4, else 2, where one pass covers 16 entries x h; 1 where not; row_attention_kernel: 1);
+ *            [sweep][1] rows of 17..GNPDE_LONG_ROW entries: ceil(n_bin64 / 4) + hub blocks (none in a MODE 2 sweep); 0: no launch
+ *   hub_fold 2 under gnpde_tune(11, 2), else 0;  launches: kernel launches in all (memsets not counted) */
+#define GNPDE_ATT_ROUTE_NONE      0
+#define GNPDE_ATT_ROUTE_HUBS_ONLY 1
+#define GNPDE_ATT_ROUTE_SD_ONE    2
+#define GNPDE_ATT_ROUTE_SD_ROWS   3
+#define GNPDE_ATT_ROUTE_ROWS      4
+#define GNPDE_ATT_ROUTE_GENERAL   5
+#define GNPDE_ATT_ROWS16_NONE       0
+#define GNPDE_ATT_ROWS16_QUARTER    1
+#define GNPDE_ATT_ROWS16_LANES      2
+#define GNPDE_ATT_ROWS16_WHOLE_WAVE 3
+#define GNPDE_ATT_GMAX_NONE       0
+#define GNPDE_ATT_GMAX_PER_WAVE   1
+#define GNPDE_ATT_GMAX_SLOTS_FOLD 2
+#define GNPDE_ATT_GMAX_ATOMIC     3
+#define GNPDE_ATT_HUBS_NONE       0
+#define GNPDE_ATT_HUBS_IN_ROWS    1
+#define GNPDE_ATT_HUBS_DEFERRED   2
+#define GNPDE_ATT_HUBS_OWN        3
+#define GNPDE_ATT_HUBS_OWN_FORKED 4
+#define GNPDE_ATT_HUBS_LONG_STATS 5
+#define GNPDE_ATT_PLAN_W_MEAN     1u
+#define GNPDE_ATT_PLAN_ATT_EDGE   2u
+#define GNPDE_ATT_PLAN_PRODS_EDGE 4u
+#define GNPDE_ATT_PLAN_FORK       8u
+#define GNPDE_ATT_PLAN_DEFER      16u
+#define GNPDE_ATT_PLAN_HUBS_ONLY  32u
+#define GNPDE_ATT_PLAN_STATS_ONLY 64u
+typedef struct gnpde_attention_launch_t {
+  int32_t  route;            /* GNPDE_ATT_ROUTE_* */
+  int32_t  vec4;
+  int32_t  h, dk4;           /* heads; d_k / 4 of the SD row kernels' template line (1 for GAT's table), 0 where none runs */
+  int32_t  n_sweeps, mode[2];/* sweeps over the rows and the MODE of each */
+  int32_t  scatter, swapped; /* SCATTER (weights stored through t_from_csr); q and k exchanged */
+  int32_t  rows16;           /* GNPDE_ATT_ROWS16_* */
+  int32_t  gmax, gmax_count; /* GNPDE_ATT_GMAX_* */
+  int32_t  hubs, n_hub;      /* GNPDE_ATT_HUBS_*; hub chunks of the walked graph */
+  int32_t  hub_fold;
+  int32_t  gat_terms;        /* 0, 1 gat_terms_kernel, 2 with its table */
+  int32_t  passes, seg_stats_heads, n_long, max_chunks;   /* GENERAL */
+  int32_t  launches;
+  uint32_t grid[2][2];
+} gnpde_attention_launch_t;
+int gnpde_attention_plan(const gnpde_graph_t* g, const gnpde_attention_t* a, uint32_t request_flags, int32_t pass, uint64_t workspace_addr,
+                         gnpde_attention_launch_t* plan);
 
 /* Backward of the normalisation + head mean of gnpde_edge_attention for EVERY normaliser the reference has (softmax or
  * squareplus, opt['attention_norm_idx'] 0 or 1; reference src/function_transformer_attention.py:210-213, src/utils.py:179-208,

@@ -209,6 +209,26 @@ def _cases():
 CASES = _cases()
 OUTPUT_VAR = 1.2
 
+# the routes of gnpde_attention_plan (_lib.ATT_ROUTES) that gnpde_edge_attention reaches: the scaled-dot row kernels with the hub chunks in
+# their first blocks, a row kernel per class + hub launches, the three general passes
+SD, ROWS, GENERAL = 'sd_rows', 'rows', 'general'
+
+
+def intended(c, generic):
+  """The route a case is there to run (the table of tests/test_attention_dispatch_gpu.py's docstring), generic =
+  gnpde_tune(TUNE_ATT_GENERIC_ROWS, .)."""
+  if c.part in (1, 4):
+    return ROWS if (generic or c.dk == 12) else SD
+  if c.part in (2, 3):
+    return GENERAL if (generic or c.reweight) else SD
+  if c.part == 5:
+    return GENERAL if c.h == 3 else (ROWS if (generic or c.reweight) else SD)
+  if c.part == 6:
+    return ROWS
+  if c.part == 7:
+    return GENERAL
+  return SD if not generic else (GENERAL if c.sqp else ROWS)
+
 
 def lengthscale(dk):
   """|q - k|^2 of standard-normal head vectors is about 2 d_k: a lengthscale of 0.8 sqrt(d_k) keeps the exp kernel's scores O(1) apart,

@@ -1,12 +1,14 @@
-"""Every line of the row attention's dispatch (edge_attention_impl in csrc/attention.hip) against a float64 oracle, judged segment by
+"""Every line of the row attention's dispatch (plan_attention / launch_planned in csrc/attention.hip) against a float64 oracle, judged segment by
 segment (tests/row_cases.py: the metric, the staircase graphs, the cases).  Every case draws a standard-normal fp32 table directly (no
 projection), asks ops.edge_attention for the head-mean weights and compares them in CSR order with the float64 head mean of
 oracle/restate.py on the same table; helpers.TOL applies to every ROW (column for attention_norm_idx = 1), hub rows included.  Each case
-runs twice, gnpde_tune(TUNE_ATT_GENERIC_ROWS, .) 0 and 1, and both runs are compared with float64, never with each other.
+runs twice, gnpde_tune(TUNE_ATT_GENERIC_ROWS, .) 0 and 1, and both runs are compared with float64, never with each other.  Which line a
+run takes is asked of the library (ops.attention_plan with the call's own operands: the plan the launchers switch on) and must be the
+one the case is listed under (row_cases.intended); tests/test_attention_plan_cpu.py pins template lines, grids and the other routes.
 
 dispatch line                                                                        case (part-graph ... of row_cases.CASES)     knob
 ---------------------------------------------------------------------------------------------------------------------------------------
-launch_sd_with_hubs -> launch_rows_sd<H, DK4>, H in {1,2,4,8} x d_k in {4,8,16}: row_attention_sd_kernel<H, DK4, .., MODE, SCATTER>,
+route sd_rows (launch_sd_rows), H in {1,2,4,8} x d_k in {4,8,16}: row_attention_sd_kernel<H, DK4, .., MODE, SCATTER> per sweep,
 two lane mappings (rows <= 16 entries / 17..512), hub chunks in the first blocks (hub_scores_partial_heads, hub_normalise_body)
   MODE 0 (row softmax), with and without edge_w                                     1-hubs, the 12 pairs, plain and -rw             0
   MODE 2 -> 1 (squareplus), per-wave maxima (gmax_part, no hub rows)                 2-nohubs, the 12 pairs                          0
@@ -16,24 +18,25 @@ two lane mappings (rows <= 16 entries / 17..512), hub chunks in the first blocks
   MODE 4 (exp kernel)                                                                4-hubs exp_kernel, the 12 pairs                 0
   MODE 3 (GAT through the 4-wide table of gat_terms_kernel, DK4 = 1)                 5-hubs gat h in {1,2,4,8}, d_k 4 and 16         0
   a launch of hub blocks only (n_rows == 0 clamp): no row <= 16 / none of 17..512    8-no16, 8-no64 at (4,4), (8,16), plain / -sqp   0
-  other d_k: returns false -> launch_rows_any                                        6 scaled_dot d_k 12, 32; 4 exp_kernel d_k 12    0, 1
-launch_rows_any -> launch_rows_t<TYPE, VEC4> -> launch_rows_th<TYPE, H, VEC4>: row_attention_kernel<TYPE, H, GL, P, VEC4> per row class,
-hub rows by launch_hub_a_any (hub_scores_partial_sd_kernel<H> / hub_scores_partial_kernel<TYPE, VEC4>) + hub_normalise_kernel
+  other d_k: no such line -> route rows                                              6 scaled_dot d_k 12, 32; 4 exp_kernel d_k 12    0, 1
+route rows (launch_rows): row_attention_kernel<TYPE, H, GL, P, VEC4> per row class,
+hub rows by launch_hubs (hub_scores_partial_sd_kernel<H> / hub_scores_partial_kernel<TYPE, VEC4>) + hub_normalise_kernel
   SCALED_DOT, H in {1,2,4,8}                                                         1-hubs (12 pairs); 6 d_k 12, 32                 1; 0, 1
   COSINE, PEARSON, H in {1,2,4,8}                                                    6-hubs cosine_sim / pearson, d_k 4, 8           0, 1
   EXP_KERNEL, H in {1,2,4,8}                                                         4-hubs (12 pairs); d_k 12                       1; 0, 1
   GAT (VEC4 false), H in {1,2,4,8}                                                   5-hubs gat; with edge_w (-rw leaves gat_sd)     1; 0, 1
-  (launch_rows_th's own call of launch_rows_sd serves a forked solver stream only: not reachable from gnpde_edge_attention)
-general three passes: scores_kernel<TYPE, VEC4>, seg_stats_heads_kernel<H> / seg_stats_kernel, seg_stats_long_partial_kernel +
+  (the row_attention_sd_kernel form of this route serves a forked solver stream: tests/test_attention_plan_cpu.py pins it)
+route general, the three passes: scores_kernel<TYPE, VEC4>, seg_stats_heads_kernel<H> / seg_stats_kernel, seg_stats_long_partial_kernel +
 seg_stats_long_combine_kernel (hub rows; long COLUMNS with max_chunks = 3 for norm_idx 1), normalise_kernel
   d_k = 2 / h = 3 / ldqk = 2A + 1 (VEC4 false)                                       7-hubs, 7-hubs_t: dk2, h3, -ld+1                0, 1
   att [E,h] and prods [E,h] requested, H in {1,2,4,8} and 3, softmax and squareplus  7 -all                                          0, 1
   squareplus / norm_idx 1 with the specialised rows switched off                     2, 3, 8 -sqp                                    1
   norm_idx 1 with edge_w (leaves the SCATTER fast path)                              3-hubs_t-h4-dk4-n1-rw                           0, 1
   GAT, h = 3                                                                         5-hubs-gat-h3                                   0, 1
-launch_sd_one (one launch, hub weights deferred to the aggregation), launch_attn_spmm (attention inside the aggregation): reached through
+route sd_one (one launch, hub weights deferred to the aggregation), launch_attn_spmm (attention inside the aggregation): reached through
 gnpde_rhs_eval only -- tests/test_attention_routes_gpu.py
 """
+import ctypes
 import functools
 
 import pytest
@@ -45,8 +48,6 @@ import row_cases as RC
 from helpers import TOL, assert_parity
 
 pytestmark = pytest.mark.gpu
-
-SD, ROWS, GENERAL = 'launch_sd_with_hubs', 'launch_rows_any', 'general passes'
 
 
 @functools.lru_cache(maxsize=None)
@@ -61,36 +62,9 @@ def _graph(name, dev):
   return graph
 
 
-def _line(c, generic, vec4):
-  """The line edge_attention_impl takes for head-mean weights alone (the conditions of csrc/attention.hip, restated)."""
-  heads_ok = c.h in (1, 2, 4, 8)
-  if c.outputs == 'all':
-    return GENERAL
-  if c.att_type == 'gat':
-    if c.norm_idx == 0 and not c.sqp and heads_ok:
-      return SD if (not c.reweight and not generic) else ROWS
-    return GENERAL
-  if c.norm_idx == 0 and not c.sqp and heads_ok and vec4:       # fused rows
-    if c.att_type in ('scaled_dot', 'exp_kernel') and not generic and c.dk in (4, 8, 16):
-      return SD
-    return ROWS
-  if c.att_type == 'scaled_dot' and vec4 and heads_ok and c.dk in (4, 8, 16) and not generic and (c.norm_idx == 0 or not c.reweight):
-    return SD
-  return GENERAL
-
-
-def _intended(c, generic):
-  if c.part in (1, 4):
-    return ROWS if (generic or c.dk == 12) else SD
-  if c.part in (2, 3):
-    return GENERAL if (generic or c.reweight) else SD
-  if c.part == 5:
-    return GENERAL if c.h == 3 else (ROWS if (generic or c.reweight) else SD)
-  if c.part == 6:
-    return ROWS
-  if c.part == 7:
-    return GENERAL
-  return SD if not generic else (GENERAL if c.sqp else ROWS)
+def _ws_addr(graph, st):
+  """The workspace gnpde_edge_attention will be handed (graph.workspace caches it by tag and size)."""
+  return graph.workspace('att', _lib.lib().gnpde_attention_workspace_bytes(graph.ref(), ctypes.byref(st))).data_ptr()
 
 
 @pytest.mark.parametrize('generic', [0, 1], ids=['specialised', 'generic'])
@@ -109,12 +83,11 @@ def test_dispatch_line(dev, c, generic):
   assert ld == (A if gat else 2 * A) + c.ld_pad and A // c.h == c.dk
   vec4 = c.dk % 4 == 0 and ld % 4 == 0 and q.data_ptr() % 16 == 0 and k.data_ptr() % 16 == 0
   assert vec4 == (c.dk % 4 == 0 and c.ld_pad == 0), 'alignment of q / k'
-  assert _line(c, generic, vec4) == _intended(c, generic), RC.case_id(c)
   view = graph.transposed_positions()[0] if side else graph
   if c.graph in ('hubs', 'hubs_t'):
     assert view.n_long_rows == len(RC.HUBS) and view.n_bin16 > 0 and view.n_bin64 > 0
   elif c.graph == 'nohubs':
-    assert view.n_long_rows == 0 and RC.sd_sweep_waves(c.h, c.dk // 4, view.n_bin16, view.n_bin64) <= RC.GMAX_PART_CAP
+    assert view.n_long_rows == 0
   elif c.graph == 'no16':
     assert view.n_bin16 == 0 and view.n_bin64 > 0 and view.n_long_rows == 2
   elif c.graph == 'no64':
@@ -128,6 +101,11 @@ def test_dispatch_line(dev, c, generic):
   want_all = c.outputs == 'all'
   try:
     ops.tune(_lib.TUNE_ATT_GENERIC_ROWS, generic)
+    # the library's own answer for the very operands of the call below: the case runs the line it is there for
+    plan = ops.attention_plan(graph, st, True, want_all, want_all, ws_addr=_ws_addr(graph, st))
+    assert plan.route_name == RC.intended(c, generic) and plan.vec4 == vec4, (RC.case_id(c), plan.route_name)
+    if c.sqp and plan.route_name == RC.SD:      # squareplus' maximum sweep: per-wave maxima without hub rows, slots + fold with them
+      assert plan.gmax == (_lib.ATT_GMAX_PER_WAVE if c.graph == 'nohubs' else _lib.ATT_GMAX_SLOTS_FOLD)
     w, att, prods = ops.edge_attention(graph, st, True, want_all, want_all, like=tab)
     torch.cuda.synchronize()
   finally:
@@ -136,7 +114,7 @@ def test_dispatch_line(dev, c, generic):
   att64, prods64 = RC.reference64(c)            # computed once per case, shared by both knob values
   perm = graph.perm_long.cpu()
   seg = ei[c.norm_idx]
-  what = '%s [%s, %s]' % (RC.case_id(c), 'generic' if generic else 'specialised', _intended(c, generic))
+  what = '%s [%s, %s]' % (RC.case_id(c), 'generic' if generic else 'specialised', RC.intended(c, generic))
   w_ref = att64.mean(dim=1)[perm]
   print('ROWERR %s head-mean %s' % (what, RC.class_errors(RC.per_segment_error(w[:graph.e], w_ref, seg[perm]), lens)))
   RC.assert_rows(w[:graph.e], w_ref, seg[perm], lens, TOL, what + ' head-mean weights (CSR order)')

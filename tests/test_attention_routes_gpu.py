@@ -10,6 +10,8 @@ ROW (largest error in the row over the row's largest |reference|, helpers.TOL fo
     weights formed by the aggregation's chunk items (HubDefer)                 A = 16 (d_k 16, 8, 4); the counter advances
   two launches: launch_sd_with_hubs, hub rows normalised by the second         the same with gnpde_tune(TUNE_ATT_ONE_LAUNCH, 1), and
                                                                                H = 8 (never one launch); the counter stands still
+    cosine_sim / pearson: scaled_dot over rows the evaluation normalised,      the same staircase, H in {2, 4} at A = 16, d = 128: the
+    and NOT the one launch (the condition names the caller's score type)       counter stands still, same bits with the key at 1
 
 The float64 reference (oracle/restate.py, dtype-generic) takes the DEVICE's own fp32 projection output, read back from the evaluation's
 workspace and upcast, as its q||k: the projection's rounding is not part of the comparison.  The fp32 oracle's own per-row error on the
@@ -44,7 +46,7 @@ def _count():
   return int(_lib.lib().gnpde_one_launch_evaluations())
 
 
-def _evaluate(name, d, h, A, dev, tunes=()):
+def _evaluate(name, d, h, A, dev, tunes=(), att_type=_lib.ATT_SCALED_DOT):
   """(f [n, d], q||k [n, 2A] as the evaluation's projection wrote it, one-launch evaluations counted, inputs on the CPU)."""
   graph = _graph(name, str(dev))
   n = graph.n
@@ -54,7 +56,7 @@ def _evaluate(name, d, h, A, dev, tunes=()):
   b = torch.randn(2 * A, generator=g) * 0.1
   xd, x0d, Wd, bd = x.to(dev), x0.to(dev), W.to(dev), b.to(dev)
   alpha, beta = torch.tensor(ALPHA, device=dev), torch.tensor(BETA, device=dev)
-  st = ops.attention_struct(_lib.ATT_SCALED_DOT, h, A, 0, False)
+  st = ops.attention_struct(att_type, h, A, 0, False)
   desc = ops.RhsDescriptor(_lib.RHS_TRANSFORMER, graph, d, xd.stride(0), alpha, beta, x0d, True, proj_w=Wd, proj_b=bd, att=st)
   desc.keep += [st]
   L = _lib.lib()
@@ -77,6 +79,8 @@ def _evaluate(name, d, h, A, dev, tunes=()):
     qk = flat.view(n, 2 * A)
   # it IS the projection (a wrong guess of the layout would hand the oracle another table)
   lin = torch.nn.functional.linear(x.double(), W.double(), b.double())
+  if att_type != _lib.ATT_SCALED_DOT:        # (cosine_sim / pearson: the evaluation normalised the projected rows in place)
+    return f, qk.cpu(), taken, (x, x0)
   assert float((qk.cpu().double() - lin).abs().max()) <= 1e-5 * float(lin.abs().max()), 'projection read back from the workspace'
   return f, qk.cpu(), taken, (x, x0)
 
@@ -132,3 +136,18 @@ def test_one_launch_and_two_launches(dev, d, h):
     assert taken == 0
     runs.append(('two launches', f, qk, inputs))
   _check('hubs', runs, h, A, 'rhs_eval d=%d h=%d d_k=%d' % (d, h, A // h))
+
+
+@pytest.mark.parametrize('h', [2, 4])
+@pytest.mark.parametrize('att_type', ['cosine_sim', 'pearson'])
+def test_cosine_and_pearson_keep_their_two_launches(dev, att_type, h):
+  """enqueue_rhs hands these to the attention as scaled_dot over normalised head vectors, a shape the one-launch form would accept; its
+  condition names the score type the caller asked for, so the counter stands still and gnpde_tune(TUNE_ATT_ONE_LAUNCH, 1) changes
+  nothing.  (Their numbers: tests/test_golden_gpu.py and the dispatch cases of part 6.)"""
+  d, A = 128, 16
+  graph = _graph('hubs', str(dev))
+  assert graph.n_long_rows == len(RC.HUBS)
+  f, qk, taken, _ = _evaluate('hubs', d, h, A, dev, att_type=_lib.ATT_TYPES[att_type])
+  assert taken == 0, '%s h=%d: %d evaluations in the one-launch form' % (att_type, h, taken)
+  f1, qk1, taken1, _ = _evaluate('hubs', d, h, A, dev, tunes=[(_lib.TUNE_ATT_ONE_LAUNCH, 1)], att_type=_lib.ATT_TYPES[att_type])
+  assert taken1 == 0 and bool(torch.isfinite(f).all()) and torch.equal(f, f1) and torch.equal(qk, qk1)
