@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 23     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 24     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
@@ -204,6 +204,13 @@ PROTOTYPES = {
   'gnpde_softmax_rows_bwd': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, ctypes.c_int32, c_vp, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp]),
   'gnpde_attention_rows_bwd': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.POINTER(AttentionStruct), c_vp, c_vp,
                                               ctypes.c_int32, c_vp, c_vp]),
+  'gnpde_attention_rows_bwd_dq': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.POINTER(AttentionStruct), c_vp, c_vp, c_vp,
+                                                 ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, c_vp, c_vp]),
+  'gnpde_head_rowsum': (ctypes.c_int, [ctypes.POINTER(GraphStruct), c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32,
+                                       ctypes.c_float, c_vp, ctypes.c_int32, c_vp, c_vp]),
+  'gnpde_hub_bwd_workspace_floats': (ctypes.c_size_t, [ctypes.POINTER(GraphStruct), ctypes.c_int32, ctypes.c_int32]),
+  'gnpde_head_rowsum_supported': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
+  'gnpde_attention_rows_bwd_dq_supported': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32]),
   'gnpde_head_spmm': (ctypes.c_int, [ctypes.POINTER(GraphStruct), ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp,
                                      ctypes.c_int32, ctypes.c_float, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_linear': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32,

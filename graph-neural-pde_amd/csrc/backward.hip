@@ -1321,3 +1321,25 @@ extern "C" int gnpde_attention_rows_bwd(const gnpde_graph_t* g, const gnpde_atte
                                         int32_t scale_sigmoid, float* ds_csr, void* stream) {
   return gnpde::launch_attention_rows_bwd_dq(g, att, r_csr, scale, scale_sigmoid, ds_csr, nullptr, 0, nullptr, static_cast<hipStream_t>(stream), nullptr);
 }
+
+// the adjoint stage's row kernels as entry points of their own (plain forwards: every optional operand of the launchers)
+extern "C" int gnpde_attention_rows_bwd_dq(const gnpde_graph_t* g, const gnpde_attention_t* att, const float* r, const int32_t* rpos,
+                                           const float* scale, int32_t scale_sigmoid, float* ds_csr, float* dq, int32_t lddq,
+                                           float* hub_ws, void* stream) {
+  return gnpde::launch_attention_rows_bwd_dq(g, att, r, scale, scale_sigmoid, ds_csr, dq, lddq, hub_ws, static_cast<hipStream_t>(stream), rpos);
+}
+
+extern "C" int gnpde_head_rowsum(const gnpde_graph_t* g, const int32_t* pos, const float* ds, int32_t heads, int32_t dk, const float* feat,
+                                 int32_t ldf, float scale, float* out, int32_t ldo, float* hub_ws, void* stream) {
+  return gnpde::launch_head_rowsum(g, pos, ds, heads, dk, feat, ldf, scale, out, ldo, hub_ws, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t gnpde_hub_bwd_workspace_floats(const gnpde_graph_t* g, int32_t heads, int32_t att_dim) {
+  return g != nullptr ? gnpde::hub_bwd_workspace_floats(g, heads, att_dim) : 0;
+}
+
+extern "C" int gnpde_head_rowsum_supported(int32_t heads, int32_t dk) { return gnpde::head_rowsum_supported(heads, dk) ? 1 : 0; }
+
+extern "C" int gnpde_attention_rows_bwd_dq_supported(int32_t heads, int32_t dk) {
+  return gnpde::attention_rows_bwd_dq_supported(heads, dk) ? 1 : 0;
+}

@@ -318,6 +318,46 @@ def attention_rows_bwd(graph, att, r_csr, heads, scale=None, scale_sigmoid=False
   return ds
 
 
+def hub_bwd_workspace(graph, heads, att_dim, like):
+  """Scratch for the chunked hub rows of attention_rows_bwd_dq / head_rowsum (gnpde_hub_bwd_workspace_floats), or None for a graph
+  without hub rows."""
+  floats = _lib.lib().gnpde_hub_bwd_workspace_floats(graph.ref(), int(heads), int(att_dim))
+  return torch.empty(floats, dtype=torch.float32, device=like.device) if floats else None
+
+
+def attention_rows_bwd_dq(graph, att, r, rpos=None, scale=None, scale_sigmoid=False, dq=None, hub_ws=None):
+  """ds [E,h] (CSR order) of gnpde_attention_rows_bwd_dq.  r [E]: in CSR order, or in the order rpos (int32 [E]) maps CSR positions
+  into.  dq: None, or a [n, heads*d_k] view with unit column stride that receives d q (rows without entries are left alone).
+  hub_ws: None (a block per hub row) or hub_bwd_workspace (chunked hub rows).  A shape without a kernel raises."""
+  require_hip(r)
+  ds = torch.empty(max(graph.e, 1), att.heads, dtype=torch.float32, device=r.device)
+  sc = _scalar_dev(scale, r) if scale is not None else None
+  if dq is not None and (dq.stride(1) != 1 or dq.shape != (graph.n, att.att_dim) or dq.dtype != torch.float32):
+    raise _lib.GnpdeError('attention_rows_bwd_dq: dq must be fp32 [n, heads*d_k] with unit column stride')
+  if rpos is not None and (rpos.dtype != torch.int32 or rpos.numel() < graph.e):
+    raise _lib.GnpdeError('attention_rows_bwd_dq: rpos must be int32 [E]')
+  if hub_ws is not None and hub_ws.numel() < _lib.lib().gnpde_hub_bwd_workspace_floats(graph.ref(), att.heads, att.att_dim):
+    raise _lib.GnpdeError('attention_rows_bwd_dq: hub_ws is too small')
+  check(_lib.lib().gnpde_attention_rows_bwd_dq(graph.ref(), ctypes.byref(att), ptr(r), ptr(rpos), ptr(sc), int(bool(scale_sigmoid)), ptr(ds),
+                                               ptr(dq), dq.stride(0) if dq is not None else 0, ptr(hub_ws), stream_of(r)))
+  return ds
+
+
+def head_rowsum(graph, ds, feat, heads, dk, scale, out, pos=None, hub_ws=None):
+  """out[seg, :] = scale * sum over the rows of `graph` of ds[pos[t] or t, head] * feat[colidx[t], :] (gnpde_head_rowsum) into the
+  [n, heads*dk] view `out`; rows without entries are left alone.  A shape without a kernel raises."""
+  require_hip(ds, feat)
+  if feat.stride(1) != 1 or out.stride(1) != 1 or out.shape != (graph.n, heads * dk) or ds.shape[1] != heads or not ds.is_contiguous():
+    raise _lib.GnpdeError('head_rowsum: feat / out need unit column stride, out [n, heads*dk], ds contiguous [E, heads]')
+  if pos is not None and (pos.dtype != torch.int32 or pos.numel() < graph.e):
+    raise _lib.GnpdeError('head_rowsum: pos must be int32 [E]')
+  if hub_ws is not None and hub_ws.numel() < graph.n_long_chunks * heads * dk:
+    raise _lib.GnpdeError('head_rowsum: hub_ws is too small')
+  check(_lib.lib().gnpde_head_rowsum(graph.ref(), ptr(pos), ptr(ds), int(heads), int(dk), ptr(feat), feat.stride(0), float(scale), ptr(out),
+                                     out.stride(0), ptr(hub_ws), stream_of(feat)))
+  return out
+
+
 def edge_attention_bwd(graph, att, r_csr, scale=None, scale_sigmoid=False):
   """ds [E,h] (CSR order) for any normaliser (softmax / squareplus over rows / columns), see gnpde_edge_attention_bwd."""
   require_hip(r_csr)

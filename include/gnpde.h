@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 23  /* 23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 24  /* 24: gnpde_attention_rows_bwd_dq, gnpde_head_rowsum, gnpde_hub_bwd_workspace_floats, gnpde_head_rowsum_supported, gnpde_attention_rows_bwd_dq_supported (the adjoint stage's row kernels as entry points of their own);  23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -500,6 +500,25 @@ int gnpde_edge_attention_bwd_heads(const gnpde_graph_t* g, const gnpde_attention
  * r_csr[p] = g_row . x_col (gnpde_sddmm without scale); att->edge_w_csr is honoured. */
 int gnpde_attention_rows_bwd(const gnpde_graph_t* g, const gnpde_attention_t* att, const float* r_csr, const float* scale,
                              int32_t scale_sigmoid, float* ds_csr, void* stream);
+
+/* The row kernels of the adjoint stage (csrc/adjoint.hip) as entry points of their own; plain forwards.
+ * gnpde_attention_rows_bwd_dq: gnpde_attention_rows_bwd with its three optional operands --
+ *   rpos    (NULL or [E] int32) r is stored in another order: the kernel reads r[rpos[p]] for CSR position p;
+ *   dq      (NULL or [n, lddq]) also d q[row, 0:A] = (1 / sqrt d_k) sum_{p in row} ds[p, head] k[col_p, :], for the head shapes of
+ *           gnpde_attention_rows_bwd_dq_supported (heads * d_k <= 32; GNPDE_ESHAPE otherwise).  Rows without entries are not written;
+ *   hub_ws  (NULL or gnpde_hub_bwd_workspace_floats(g, heads, att_dim) floats) rows longer than GNPDE_LONG_ROW as 512-entry chunks
+ *           over the whole chip (three kernels) instead of one 1024-thread block per row.
+ * gnpde_head_rowsum: out[seg, 0:A] = scale * sum over the rows of g (entry t: ds[pos ? pos[t] : t, head], feat[colidx[t], :]) with a
+ *   lane per entry, for the head shapes of gnpde_head_rowsum_supported (GNPDE_ESHAPE otherwise); feat and ds 16-byte aligned,
+ *   ldf % 4 == 0; rows without entries are not written; hub_ws as above (heads * dk floats per chunk are used). */
+size_t gnpde_hub_bwd_workspace_floats(const gnpde_graph_t* g, int32_t heads, int32_t att_dim);
+int gnpde_head_rowsum_supported(int32_t heads, int32_t dk);
+int gnpde_attention_rows_bwd_dq_supported(int32_t heads, int32_t dk);
+int gnpde_attention_rows_bwd_dq(const gnpde_graph_t* g, const gnpde_attention_t* att, const float* r, const int32_t* rpos,
+                                const float* scale, int32_t scale_sigmoid, float* ds_csr, float* dq, int32_t lddq, float* hub_ws,
+                                void* stream);
+int gnpde_head_rowsum(const gnpde_graph_t* g, const int32_t* pos, const float* ds, int32_t heads, int32_t dk, const float* feat,
+                      int32_t ldf, float scale, float* out, int32_t ldo, float* hub_ws, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------
