@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 24     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 25     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
@@ -147,7 +147,8 @@ class RhsStruct(ctypes.Structure):
               ('alpha', c_vp), ('beta', c_vp), ('x0', c_vp), ('alpha_sigmoid', ctypes.c_int32),
               ('w_csr', c_vp),
               ('proj_w', c_vp), ('proj_b', c_vp), ('proj_m', ctypes.c_int32),
-              ('att', AttentionStruct)]
+              ('att', AttentionStruct),
+              ('out_w', c_vp), ('out_ld', ctypes.c_int32)]      # GNPDE_RHS_MIX_FEATURES (ABI 25, appended)
 
 
 class DecoderStruct(ctypes.Structure):
@@ -215,6 +216,8 @@ PROTOTYPES = {
                                      ctypes.c_int32, ctypes.c_float, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_linear': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32,
                                   ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, c_vp]),
+  'gnpde_linear_epilogue': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32, ctypes.c_int32,
+                                           c_vp, ctypes.c_int32, ctypes.POINTER(EpilogueStruct), c_vp]),
   'gnpde_relu_linear': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32,
                                        ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, c_vp]),
   'gnpde_attention_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(GraphStruct), ctypes.POINTER(AttentionStruct)]),
@@ -485,6 +488,7 @@ def f32c(t, name='tensor'):
 
 
 RHS_PADDED_ROWS = 1
+RHS_MIX_FEATURES = 2
 GATHER_FP32, GATHER_BF16 = 0, 1
 GATHER_DTYPES = {'fp32': GATHER_FP32, 'bf16': GATHER_BF16}
 

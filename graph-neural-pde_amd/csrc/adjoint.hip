@@ -650,6 +650,9 @@ bool rows_bwd_shape(const gnpde_attention_t& at) {
 int check_adjoint(const gnpde_rhs_t* rhs, const gnpde_graph_t* gt, int method) {
   int rc = check_rhs(rhs);
   if (rc) return rc;
+  // (the stage kernels below take kind GAT for A(x) x and would compute the gradients of the wrong function)
+  GNPDE_CHECK_ARG((rhs->flags & GNPDE_RHS_MIX_FEATURES) == 0, GNPDE_ESHAPE,
+                  "adjoint: the mix_features form of the GAT function has no native VJP stage (train it on the differentiable host loop)");
   GNPDE_CHECK_ARG(gt != nullptr && gt->n == rhs->graph->n && gt->e == rhs->graph->e, GNPDE_EINVAL,
                   "adjoint: the transposed graph does not match the descriptor's graph");
   GNPDE_CHECK_ARG(method == GNPDE_METHOD_EULER || method == GNPDE_METHOD_RK4 || method == GNPDE_METHOD_MIDPOINT ||

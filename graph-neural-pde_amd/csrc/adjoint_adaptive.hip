@@ -542,6 +542,8 @@ extern "C" int gnpde_adjoint_adaptive_create(gnpde_adjoint_adaptive_t** out, con
   GNPDE_CHECK_ARG(out != nullptr, GNPDE_EINVAL, "adjoint_adaptive_create: out is null");
   *out = nullptr;
   if (int rc = check_rhs(rhs)) return rc;
+  GNPDE_CHECK_ARG((rhs->flags & GNPDE_RHS_MIX_FEATURES) == 0, GNPDE_ESHAPE,
+                  "adjoint_adaptive_create: the mix_features form of the GAT function has no adjoint solve");
   const Tableau* tab = tableau_of(method);
   GNPDE_CHECK_ARG(tab != nullptr, GNPDE_EINVAL, "adjoint_adaptive_create: method must be GNPDE_ADAPTIVE_HEUN or GNPDE_ADAPTIVE_DOPRI5");
   GNPDE_CHECK_ARG(rhs->kind == GNPDE_RHS_LAPLACIAN, GNPDE_EINVAL, "adjoint_adaptive_create: the Laplacian function only (f linear in the state)");

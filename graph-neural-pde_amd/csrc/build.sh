@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I${ROOT}/include -I. -Wall -W
 mkdir -p build
 objs=""
 pids=""
-for f in error.cpp graph_prep.cpp spmm.hip sddmm.hip linear.hip attention.hip fused_attn.hip backward.hip adjoint.hip solver.hip misc.hip early_stop.hip sharded.hip rewire.hip twohop.hip dopri5.hip adjoint_adaptive.hip graph_device.hip knn.hip gdc.hip gdc_push.hip posdist.hip edge_sampling.hip deepwalk.hip hyperbolic.hip nmf.hip; do
+for f in error.cpp graph_prep.cpp spmm.hip sddmm.hip linear.hip out_proj.hip attention.hip fused_attn.hip backward.hip adjoint.hip solver.hip misc.hip early_stop.hip sharded.hip rewire.hip twohop.hip dopri5.hip adjoint_adaptive.hip graph_device.hip knn.hip gdc.hip gdc_push.hip posdist.hip edge_sampling.hip deepwalk.hip hyperbolic.hip nmf.hip; do
   o="build/${f%.*}.o"
   stale=""
   for h in "$f" *.h "${ROOT}/include/gnpde.h"; do if [ "$h" -nt "$o" ]; then stale=1; fi; done

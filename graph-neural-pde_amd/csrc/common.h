@@ -210,6 +210,18 @@ bool spmm_hub_defer_supported(const gnpde_graph_t* g, const float* u, int d, int
 int launch_edge_attention_deferred(const gnpde_graph_t* g, const gnpde_attention_t* at, float* w_mean_csr, void* ws, size_t ws_bytes,
                                    hipStream_t stream, HubDefer* defer);
 
+// An epilogue against the stages a launcher accepts (bit s: stage s) and the operands each stage reads and writes; `u`: the operand
+// other rows gather from while a row's epilogue runs, which no output may alias.  on_lanes: the row stride and every operand of a
+// launch on lanes of `bytes` bytes.  (spmm.hip)
+constexpr unsigned kEpilogueStagesAll = (2u << GNPDE_STAGE_LINCOMB) - 1;
+int check_epilogue(const char* who, const gnpde_epilogue_t& e, const void* u, unsigned accepted);
+bool on_lanes(size_t bytes, int ld, const void* u, const void* t1, const void* t2, const gnpde_epilogue_t* e);
+
+// Out-projection with the diffusion epilogue and the stage algebra (out_proj.hip): stage(alpha' (z Wout - u) + beta x0)
+bool linear_epilogue_supported(int A, int d);
+int launch_linear_epilogue(const float* z, int n, int A, int ldz, const float* W, int d, int ldw, const float* u, int ld,
+                           const gnpde_epilogue_t& e, bool padded_rows, hipStream_t s);
+
 // fp32 [n, d] (row stride ld) -> bf16 shadow [n, ld] (misc.hip)
 int launch_to_bf16(const float* src, long long n, int d, int ld, uint16_t* dst, hipStream_t s);
 

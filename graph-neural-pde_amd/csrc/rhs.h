@@ -12,7 +12,9 @@ namespace gnpde {
 struct RhsLayout {
   size_t proj, wmean, att, spmm, tickets, fused, total;
   size_t att_bytes, spmm_bytes, ticket_bytes, fused_bytes;     // tickets: gnpde_spmm_ticket_bytes, the last region
+  size_t z;                                                    // GNPDE_RHS_MIX_FEATURES only: the aggregate A(x) (x W), [n, A]
 };
+inline bool rhs_mix_features(const gnpde_rhs_t& r) { return (r.flags & GNPDE_RHS_MIX_FEATURES) != 0; }
 
 // Recorded solve (gnpde_solver_set_tape) of GRAND-nl: the evaluation writes its q||k projection and its head-mean weights into buffers
 // of their own (the record of that evaluation) instead of the shared scratch regions, and keeps to the separate kernels (no attention

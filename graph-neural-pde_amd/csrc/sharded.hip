@@ -670,6 +670,9 @@ int check_sharded_args(const gnpde_halo_t* h, const gnpde_rhs_t* ri, const gnpde
   if (rc) return rc;
   rc = check_rhs(rb);
   if (rc) return rc;
+  // (a world of one rank hands whole-graph descriptors that check_rhs lets pass: the passes here would run them on row ranges)
+  GNPDE_CHECK_ARG(((ri->flags | rb->flags) & GNPDE_RHS_MIX_FEATURES) == 0, GNPDE_ESHAPE,
+                  "sharded solver: the mix_features form of the GAT function is not partitioned (solve it on one GPU)");
   GNPDE_CHECK_ARG(h->world >= 1 && h->world <= kMaxWorld && h->n_own >= 0 && h->n_halo >= 0 && h->send_counts && h->recv_counts,
                   GNPDE_EINVAL, "sharded solver: bad halo description");
   GNPDE_CHECK_ARG(ri->d == rb->d && ri->ld == rb->ld && ri->kind == rb->kind, GNPDE_EINVAL,

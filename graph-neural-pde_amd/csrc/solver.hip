@@ -41,8 +41,11 @@ RhsLayout rhs_layout(const gnpde_rhs_t& r) {
     const size_t prow = r.n_state_rows > g.n ? r.n_state_rows : g.n;
     L.proj = off;  off += align_up(prow * r.proj_m * 4, 256);
   }
+  // mix_features: the aggregation gathers rows of the projection table (A wide) instead of state rows (d wide); the workspace is
+  // sized for the wider of the two
+  const bool mix = rhs_mix_features(r);
   L.spmm = off;
-  L.spmm_bytes = gnpde_spmm_workspace_bytes(&g, r.d);
+  L.spmm_bytes = gnpde_spmm_workspace_bytes(&g, mix && r.att.att_dim > r.d ? r.att.att_dim : r.d);
   off += align_up(L.spmm_bytes, 256);
   if (r.kind != GNPDE_RHS_LAPLACIAN) {
     L.wmean = off; off += align_up(static_cast<size_t>(g.e) * 4, 256);
@@ -54,6 +57,9 @@ RhsLayout rhs_layout(const gnpde_rhs_t& r) {
       L.fused_bytes = fused_attn_workspace_bytes(&g, r.d, r.att.heads);
       off += align_up(L.fused_bytes, 256);
     }
+  }
+  if (mix) {   // the aggregate z = A(x) (x W) that gnpde_linear_epilogue reads (without the flag no offset above or below moves)
+    L.z = off; off += align_up(static_cast<size_t>(g.n) * r.att.att_dim * 4, 256);
   }
   // the aggregation's hub-row tickets (they belong to the partials; LAST, so that every other region keeps its offset)
   L.tickets = off;
@@ -75,6 +81,14 @@ int check_rhs(const gnpde_rhs_t* r) {
     GNPDE_CHECK_ARG(r->proj_w != nullptr && r->proj_m >= 1, GNPDE_EINVAL, "rhs: projection weights missing");
     const int need = r->kind == GNPDE_RHS_TRANSFORMER ? 2 * r->att.att_dim : r->att.att_dim;
     GNPDE_CHECK_ARG(r->proj_m == need, GNPDE_EINVAL, "rhs: proj_m=%d but attention needs %d", r->proj_m, need);
+  }
+  if (rhs_mix_features(*r)) {
+    GNPDE_CHECK_ARG(r->kind == GNPDE_RHS_GAT, GNPDE_EINVAL, "rhs: GNPDE_RHS_MIX_FEATURES is the GAT function's (kind %d)", r->kind);
+    GNPDE_CHECK_ARG(r->out_w != nullptr && r->out_ld >= r->att.att_dim, GNPDE_EINVAL, "rhs: mix_features needs out_w [d, A] with out_ld >= A");
+    GNPDE_CHECK_ARG(r->proj_row_end == 0 && r->n_state_rows <= r->graph->n, GNPDE_ESHAPE,
+                    "rhs: mix_features on a partitioned descriptor (whole-graph descriptors only)");
+    GNPDE_CHECK_ARG(linear_epilogue_supported(r->att.att_dim, r->d), GNPDE_ESHAPE,
+                    "rhs: mix_features with attention_dim = %d, d = %d (attention_dim a multiple of 4 up to 256, d up to 256)", r->att.att_dim, r->d);
   }
   return 0;
 }
@@ -154,6 +168,16 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
       opt.defer = &defer;
       return launch_spmm_rhs(g, wmean, u, r.d, r.ld, &epi, nullptr, ws + L.spmm, L.spmm_bytes, s, opt);
     }
+    if (rhs_mix_features(r)) {
+      // f = alpha' (A(x) (x W) Wout - x) + beta x0: the plain aggregation gathers rows of the projection table (its normal hub-row
+      // handling, one stream, fp32), and the out-projection carries the caller's epilogue
+      rc = launch_edge_attention(g, &at, wmean, nullptr, nullptr, ws + L.att, L.att_bytes, s, nullptr);
+      if (rc) return rc;
+      float* z = reinterpret_cast<float*>(ws + L.z);
+      rc = launch_spmm_rhs(g, wmean, proj, r.att.att_dim, r.proj_m, nullptr, z, ws + L.spmm, L.spmm_bytes, s);
+      if (rc) return rc;
+      return launch_linear_epilogue(z, g->n, r.att.att_dim, r.att.att_dim, r.out_w, r.d, r.out_ld, u, r.ld, epi, padded, s);
+    }
     rc = launch_edge_attention(g, &at, wmean, nullptr, nullptr, ws + L.att, L.att_bytes, s, fork);
     if (rc) return rc;
     w = wmean;
@@ -165,7 +189,7 @@ int enqueue_rhs(const gnpde_rhs_t& r, const float* u, const gnpde_epilogue_t& ep
 
 bool rhs_gather_lo_supported(const gnpde_rhs_t& r) {
   const bool padded = (r.flags & GNPDE_RHS_PADDED_ROWS) != 0;
-  return r.ld % 4 == 0 && (r.d % 4 == 0 || padded) && r.d <= 1024 && r.n_state_rows <= r.graph->n && r.proj_row_end == 0 &&
+  return !rhs_mix_features(r) && r.ld % 4 == 0 && (r.d % 4 == 0 || padded) && r.d <= 1024 && r.n_state_rows <= r.graph->n && r.proj_row_end == 0 &&
          r.graph->row_begin == 0;
 }
 
@@ -458,6 +482,8 @@ extern "C" int gnpde_solver_set_tape(gnpde_solver_t* s, void* tape, size_t tape_
   s->tape = nullptr;
   s->tape_rec = nullptr;
   if (tape == nullptr) return 0;
+  GNPDE_CHECK_ARG(!rhs_mix_features(s->rhs), GNPDE_ESHAPE,
+                  "solver_set_tape: no reverse sweep differentiates the mix_features form of the GAT function; it is not recorded");
   const size_t need = gnpde_solver_tape_bytes(&s->rhs, s->method, static_cast<int32_t>(s->dts.size()));
   GNPDE_CHECK_ARG(reinterpret_cast<uintptr_t>(tape) % 256 == 0 && tape_bytes >= need, GNPDE_EWS,
                   "solver_set_tape: %zu bytes (need %zu, 256-byte aligned, zero-filled)", tape_bytes, need);

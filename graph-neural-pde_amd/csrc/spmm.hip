@@ -1309,8 +1309,10 @@ int fill_args(SpmmArgs& a, const gnpde_graph_t* g, const float* w, const float* 
 }
 
 // An epilogue against the stages a launcher accepts (bit s: stage s) and the operands each stage reads and writes.
-constexpr unsigned kStagesAll = (2u << GNPDE_STAGE_LINCOMB) - 1;
+constexpr unsigned kStagesAll = kEpilogueStagesAll;
 constexpr unsigned kStagesAdjoint = 1u << GNPDE_STAGE_LINCOMB | 1u << GNPDE_STAGE_EULER | 0xFu << GNPDE_STAGE_RK1C;
+}  // namespace
+// (check_epilogue and on_lanes are shared with out_proj.hip: common.h)
 int check_epilogue(const char* who, const gnpde_epilogue_t& e, const void* u, unsigned accepted) {
   const int st = e.stage;
   GNPDE_CHECK_ARG(st >= GNPDE_STAGE_RHS && st <= GNPDE_STAGE_LINCOMB && (accepted >> st & 1u), GNPDE_EINVAL, "%s: bad stage %d", who, st);
@@ -1346,6 +1348,7 @@ bool on_lanes(size_t bytes, int ld, const void* u, const void* t1, const void* t
     for (int j = 0; j < e->n_prev && j < GNPDE_MAX_PREV; ++j) ok = ok && aligned(e->prev[j], bytes);
   return ok;
 }
+namespace {
 
 struct SpmmPlan {
   gnpde_spmm_launch_t l;     // what gnpde_spmm_plan reports

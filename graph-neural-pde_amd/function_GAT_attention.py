@@ -105,15 +105,24 @@ class ODEFuncAtt(ODEFunc):
         return ops.linear(ops.spmm(graph, w, _lib.f32c(wx)), self.multihead_att_layer.out_weight())
       return ops.spmm(graph, w, _lib.f32c(x))
 
-  def forward(self, t, x):
+  def _has_native_rhs(self, x):
+    """mix_features: A(x) (xW) Wout replaces A(x) x, so the aggregation cannot carry the epilogue; the out-projection kernel
+    (csrc/out_proj.hip, GNPDE_RHS_MIX_FEATURES) carries it for attention_dim % 4 == 0, attention_dim <= 256 and a state of up to
+    256 columns.  Outside that rule there is no descriptor: solves take the host loops over the eager chain in `forward`."""
     if not self.opt['mix_features']:
+      return True
+    A = self.multihead_att_layer.attention_dim
+    return x.dim() == 2 and A % 4 == 0 and A <= 256 and x.shape[1] <= 256
+
+  def forward(self, t, x):
+    if self._needs_grad(x) or self._has_native_rhs(x):
       return super(ODEFuncAtt, self).forward(t, x)
-    # mix_features: A(x) (xW) Wout replaces A(x) x, so the aggregation cannot carry the epilogue;
-    # the elementwise tail is three tiny torch ops on [N,d] (this option is off in every best_params)
     self._check_nfe()
-    if self._needs_grad(x):
-      from .autograd import rhs_with_grad
-      return rhs_with_grad(self, x)
+    return self._eager_chain(x)
+
+  def _eager_chain(self, x):
+    """mix_features outside the out-projection kernel's shapes (and the A/B reference of tools/gat_mix_ab.py): projection, attention,
+    aggregation and out-projection launches and an elementwise tail of three torch ops on [N,d]."""
     with torch.no_grad():
       attention, wx = self.multihead_att_layer(x, self.edge_index)
       ax = self.multiply_attention(x, attention, wx)
@@ -124,17 +133,20 @@ class ODEFuncAtt(ODEFunc):
     return f
 
   def _descriptor(self, x, x0_override=None, graph=None):
-    if self.opt['mix_features']:
-      raise NotImplementedError('mix_features has no fused descriptor')
+    if not self._has_native_rhs(x):
+      raise NotImplementedError('mix_features with attention_dim = %d, d = %d has no fused descriptor (attention_dim a multiple of 4 '
+                                'up to 256, d up to 256)' % (self.multihead_att_layer.attention_dim, x.shape[-1]))
     graph = self._graph(x) if graph is None else graph
     layer = self.multihead_att_layer
+    # mix_features: Wout transposed [d, A]; refreshed in place at a stable address, so a captured graph sees an optimiser step
+    out_w = layer.out_weight() if self.opt['mix_features'] else None
     x0 = x0_override if x0_override is not None else self._source(x)
     alpha = ops._scalar_dev(self.alpha_train, x)
     beta = ops._scalar_dev(self.beta_train, x) if x0 is not None else None
     st, keep = layer.attention_struct(graph)
     desc = ops.RhsDescriptor(_lib.RHS_GAT, graph, x.shape[1], x.stride(0), alpha, beta,
                              None if x0 is None else self._match_rows(x0, x), not self.opt['no_alpha_sigmoid'],
-                             proj_w=layer.proj_weight(), proj_b=None, att=st, padded_rows=_lib.is_padded(x))
+                             proj_w=layer.proj_weight(), proj_b=None, att=st, padded_rows=_lib.is_padded(x), out_w=out_w)
     desc.keep += keep
     return desc
 
@@ -142,7 +154,7 @@ class ODEFuncAtt(ODEFunc):
     s = desc.struct
     a = s.att
     return (id(desc.graph), s.alpha, s.beta, s.x0, s.alpha_sigmoid, s.proj_w, s.proj_m, s.d, s.ld,
-            a.heads, a.att_dim, a.norm_idx, a.gat_a, a.leaky_slope)
+            a.heads, a.att_dim, a.norm_idx, a.gat_a, a.leaky_slope, s.out_w, s.out_ld, s.flags & _lib.RHS_MIX_FEATURES)
 
   def __repr__(self):
     return self.__class__.__name__ + ' (' + str(self.in_features) + ' -> ' + str(self.out_features) + ')'

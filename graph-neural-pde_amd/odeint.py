@@ -152,7 +152,7 @@ def _weights_t(func, graph, out=None):
 # --------------------------------------------------------------------------------------------------
 def _native_ok(func, y0, t):
   return (hasattr(func, '_descriptor') and y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32
-          and len(t) == 2 and not func._needs_grad(y0))
+          and len(t) == 2 and not func._needs_grad(y0) and func._has_native_rhs(y0))
 
 
 def gather_dtype_requested(func):

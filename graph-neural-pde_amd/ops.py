@@ -172,6 +172,18 @@ def make_epilogue(alpha, beta, x0, alpha_sigmoid, stage=_lib.STAGE_RHS, dt=0.0, 
   return e
 
 
+def linear_epilogue(z, wout_t, u, epi):
+  """stage(alpha' (z Wout - u) + beta x0) in one launch (gnpde_linear_epilogue; the out-projection of the GAT function's
+  mix_features form): z [n, A], wout_t [d, A] (Wout transposed), u [n, d]; epi: an EpilogueStruct (make_epilogue) whose operands
+  and outputs are [n, d] with u's row stride."""
+  require_hip(z, wout_t, u)
+  z, wout_t, u = _lib.f32rows(z, 'z'), _lib.f32rows(wout_t, 'wout_t'), _lib.f32rows(u, 'u')
+  if z.shape[0] != u.shape[0] or wout_t.shape != (u.shape[1], z.shape[1]):
+    raise _lib.GnpdeError('linear_epilogue: z %s, wout_t %s and u %s do not fit' % (tuple(z.shape), tuple(wout_t.shape), tuple(u.shape)))
+  check(_lib.lib().gnpde_linear_epilogue(ptr(z), z.shape[0], z.shape[1], z.stride(0), ptr(wout_t), u.shape[1], wout_t.stride(0),
+                                         ptr(u), u.stride(0), ctypes.byref(epi), stream_of(u)))
+
+
 def _check_shadow(t, like, name):
   """A bf16 shadow [n, d] of the fp32 state `like`: same shape, same row stride (elements), unit column stride."""
   require_hip(t)
@@ -1677,9 +1689,9 @@ class RhsDescriptor(object):
   """Python owner of a gnpde_rhs_t: keeps every tensor the descriptor points to alive."""
 
   def __init__(self, kind, graph, d, ld, alpha, beta, x0, alpha_sigmoid, w_csr=None, proj_w=None, proj_b=None,
-               att=None, n_state_rows=0, proj_rows=None, padded_rows=False):
+               att=None, n_state_rows=0, proj_rows=None, padded_rows=False, out_w=None):
     self.graph = graph
-    self.keep = [alpha, beta, x0, w_csr, proj_w, proj_b]
+    self.keep = [alpha, beta, x0, w_csr, proj_w, proj_b, out_w]
     r = _lib.RhsStruct()
     r.kind = int(kind)
     r.graph = ctypes.pointer(graph.struct)
@@ -1698,6 +1710,10 @@ class RhsDescriptor(object):
     r.proj_m = int(proj_w.shape[0]) if proj_w is not None else 0
     if att is not None:
       r.att = att
+    if out_w is not None:      # the GAT function's mix_features form: Wout transposed, [d, A] (GNPDE_RHS_MIX_FEATURES)
+      r.flags |= _lib.RHS_MIX_FEATURES
+      r.out_w = out_w.data_ptr()
+      r.out_ld = int(out_w.stride(0))
     self.struct = r
 
   def ref(self):

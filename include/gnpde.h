@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 24  /* 24: gnpde_attention_rows_bwd_dq, gnpde_head_rowsum, gnpde_hub_bwd_workspace_floats, gnpde_head_rowsum_supported, gnpde_attention_rows_bwd_dq_supported (the adjoint stage's row kernels as entry points of their own);  23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 25  /* 25: GNPDE_RHS_MIX_FEATURES, gnpde_rhs_t.out_w / out_ld appended, gnpde_linear_epilogue (no-grad solves of the GAT function's mix_features form);  24: gnpde_attention_rows_bwd_dq, gnpde_head_rowsum, gnpde_hub_bwd_workspace_floats, gnpde_head_rowsum_supported, gnpde_attention_rows_bwd_dq_supported (the adjoint stage's row kernels as entry points of their own);  23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -318,6 +318,19 @@ int gnpde_head_spmm(const gnpde_graph_t* g, int32_t by_column, const float* ds_c
 int gnpde_linear(const float* x, int32_t n, int32_t d, int32_t ldx, const float* W, int32_t m,
                  int32_t ldw, const float* b, float* out, int32_t ldo, void* stream);
 
+/* Out-projection with the diffusion epilogue and the stage algebra behind it (the GAT function's mix_features form,
+ * src/function_GAT_attention.py:32-38; GNPDE_RHS_MIX_FEATURES):
+ *   ax[i, c] = sum_k z[i, k] * Wout_t[c, k]        z [n, A] (ldz >= A), Wout_t [d, A] row-major (ldw >= A)
+ *   k        = alpha' * (ax - u_i) + beta * x0_i   and then epi->stage, every GNPDE_STAGE_* (see gnpde_epilogue_t above)
+ * u and every operand of the epilogue are [n, ldu] with ldu >= d.  Same matrix-core product as gnpde_linear (one wavefront owns 16
+ * rows and all d columns, fixed K order: bit-identical from run to run); the accumulator tile is brought to row-contiguous lanes
+ * through LDS before the epilogue streams its operands.  Shapes: A % 4 == 0, A <= 256, d <= 256, n >= 0; GNPDE_ESHAPE otherwise,
+ * before any launch.  d % 4 == 0 with ldu % 4 == 0 and 16-byte aligned state operands takes 16-byte lanes, anything else scalar
+ * lanes; columns [d, ldu) of the outputs are never written.  (A descriptor with GNPDE_RHS_PADDED_ROWS also takes 16-byte lanes for
+ * d % 4 != 0, over its padding columns.)  An output may be u itself (the stage runs element by element) but not z. */
+int gnpde_linear_epilogue(const float* z, int32_t n, int32_t A, int32_t ldz, const float* Wout_t, int32_t d, int32_t ldw,
+                          const float* u, int32_t ldu, const gnpde_epilogue_t* epi, void* stream);
+
 /* out = relu(x) W^T + b: the decoder of the reference's GNN.forward (F.relu -> [dropout, identity at test time] -> m2,
  * src/GNN.py:61-71) in one pass; same kernels as gnpde_linear with the activation applied to the A operand. */
 int gnpde_relu_linear(const float* x, int32_t n, int32_t d, int32_t ldx, const float* W, int32_t m, int32_t ldw,
@@ -553,6 +566,17 @@ enum { GNPDE_RHS_LAPLACIAN = 0, GNPDE_RHS_TRANSFORMER = 1, GNPDE_RHS_GAT = 2 };
  * input, x0, y, k*, outputs) are padding that may be read and overwritten -- lets a state width that is not a multiple of
  * 4 (BLEND ogbn-arxiv: d = 162, reference best_params feat_hidden_dim 64 + pos_enc_hidden_dim 98) use 16-byte lanes. */
 #define GNPDE_RHS_PADDED_ROWS 1
+/* MIX_FEATURES (kind GNPDE_RHS_GAT only; GNPDE_EINVAL on another kind): the second form of the reference's GAT function
+ * (src/function_GAT_attention.py:32-38, opt['mix_features']):  f = alpha' (A(x) (x W) Wout - x) + beta x0.  out_w is Wout TRANSPOSED,
+ * [d, A] row-major with row stride out_ld >= A (A = att.att_dim).  An evaluation is the projection and the attention of the plain GAT
+ * form, the plain aggregation z = A(x) (x W) of rows of the projection table into a workspace region [n, A], and
+ * gnpde_linear_epilogue over z, which carries the diffusion epilogue and the stage algebra (Wout sits between the aggregate and
+ * "- x", so the aggregation cannot).  Shapes: A % 4 == 0, A <= 256, d <= 256, whole-graph descriptors (proj_row_end == 0,
+ * n_state_rows <= graph->n); GNPDE_ESHAPE otherwise.  Covered by gnpde_rhs_eval / gnpde_rhs_stage, gnpde_solver_* (early stopping
+ * included) and gnpde_dopri5_* on one GPU.  NOT covered, and refused with GNPDE_ESHAPE: the adjoint objects (gnpde_adjoint_create,
+ * every method; gnpde_adjoint_adaptive_create), the recorded solve (gnpde_solver_set_tape), the bf16 gather operand
+ * (gnpde_solver_gather_bytes returns 0) and the row-partitioned solver -- none of them differentiates or shards this function. */
+#define GNPDE_RHS_MIX_FEATURES 2
 /* MIDPOINT (torchdiffeq fixed_grid.py Midpoint, advertised by the reference at src/run_GNN.py:330): y + dt f(y + (dt / 2) f(y)),
  * two evaluations per step, both as GNPDE_STAGE_LINCOMB stages; gnpde_solver_* only.
  * DOPRI5_TAPE: no method of a solve -- gnpde_adjoint_create only: the object sweeps a recorded Dormand-Prince solve
@@ -568,7 +592,7 @@ typedef struct gnpde_rhs {
   int32_t proj_row_begin;     /* with proj_row_end > 0: project only rows [proj_row_begin, proj_row_end)
                                  (interior / boundary passes overlapping the halo exchange) */
   int32_t proj_row_end;
-  int32_t flags;              /* GNPDE_RHS_PADDED_ROWS or 0 */
+  int32_t flags;              /* GNPDE_RHS_PADDED_ROWS | GNPDE_RHS_MIX_FEATURES, or 0 */
   /* epilogue scalars */
   const float* alpha; const float* beta; const float* x0; int32_t alpha_sigmoid;
   /* LAPLACIAN: fixed weights, CSR order */
@@ -577,6 +601,9 @@ typedef struct gnpde_rhs {
    * descriptor (its q/k/ldqk fields are filled by the solver from its workspace)               */
   const float* proj_w; const float* proj_b; int32_t proj_m;
   gnpde_attention_t att;
+  /* GNPDE_RHS_MIX_FEATURES: Wout transposed, [d, att.att_dim] row-major, row stride out_ld (appended in ABI 25: every field above
+   * keeps its offset) */
+  const float* out_w; int32_t out_ld;
 } gnpde_rhs_t;
 
 typedef struct gnpde_solver gnpde_solver_t;
