@@ -212,6 +212,7 @@ __global__ __launch_bounds__(kBlock) void spmm_long_reduce_kernel(const SpmmArgs
   const int lr = blockIdx.x;
   const int row = long_rows[lr];
   const int c0 = long_chunk_ptr[lr], c1 = long_chunk_ptr[lr + 1];
+  if (row < a.row_begin) return;   // a launch over rows [row_begin, n) writes no other row
   const bool plain = a.plain_out != nullptr;
   const float alpha = plain ? 0.0f : alpha_of(a.ep);
   const float beta = (!plain && a.ep.x0 != nullptr) ? *a.ep.beta : 0.0f;
@@ -443,6 +444,7 @@ __global__ __launch_bounds__(kWave) void spmm_long_reduce4_kernel(const SpmmArgs
   const int lr = blockIdx.x;
   const int row = long_rows[lr];
   const int c0 = long_chunk_ptr[lr], c1 = long_chunk_ptr[lr + 1];
+  if (row < a.row_begin) return;   // a launch over rows [row_begin, n) writes no other row
   if constexpr (!LO) {
     fold_long_row<false>(a, row, c0, c1, static_cast<int>(threadIdx.x));
   } else {

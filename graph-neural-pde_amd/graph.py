@@ -235,7 +235,8 @@ class CSRGraph(object):
 
   def set_row_range(self, row_begin, n_rows, rowptr=None):
     """The aggregation launches of this view cover the rows [row_begin, n_rows) (everything for an ordinary graph; the
-    interior / boundary passes of a row-partitioned graph narrow it, distributed.py).  Also decides how those launches deal
+    interior / boundary passes of a row-partitioned graph narrow it, distributed.py) and write no other row: a hub row below
+    row_begin is not folded (the views of distributed.py hold only their own rows' edges and have none).  Also decides how those launches deal
     the rows to the 8 XCDs (gnpde_graph_t.xcd_deal): contiguous eighths while that is balanced -- neighbouring rows then
     share an XCD's L2, and it measured 1.8 % faster than hashed blocks at the ogbn-arxiv shape, where both are balanced --
     hashed blocks as soon as the row length depends on the row id (R-MAT: 1.46 by this measure)."""
