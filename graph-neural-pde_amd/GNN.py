@@ -130,3 +130,11 @@ class GNN(BaseGNN):
     else:
       z = self.odeblock(x)
     return self.decode(z, x.shape[1])
+
+  def forward_at(self, x, times, pos_encoding=None):
+    """Logits at every entry of `times` (strictly increasing, times[0] the start of the diffusion), [len(times), n, classes], from ONE
+    solve (ODEblock.trajectory): accuracy as a function of depth, the path of the diffusion."""
+    x = self.encode(x, pos_encoding)
+    self.odeblock.set_x0(x)
+    states = self.odeblock.trajectory(x, times)
+    return torch.stack([self.decode(z, x.shape[1]) for z in states])

@@ -18,7 +18,7 @@ LONG_ROW = 512
 STAGE_RHS, STAGE_EULER, STAGE_RK1, STAGE_RK2, STAGE_RK3, STAGE_RK4 = range(6)
 STAGE_RK1C, STAGE_RK2C, STAGE_RK3C, STAGE_RK4C = range(6, 10)
 STAGE_LINCOMB = 10
-ABI_VERSION = 25     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
+ABI_VERSION = 26     # GNPDE_ABI_VERSION of include/gnpde.h this package's struct layouts and prototypes were written for
 ATT_SCALED_DOT, ATT_COSINE, ATT_PEARSON, ATT_EXP_KERNEL, ATT_GAT = range(5)
 RHS_LAPLACIAN, RHS_TRANSFORMER, RHS_GAT = range(3)
 METHOD_EULER, METHOD_RK4, METHOD_MIDPOINT, METHOD_DOPRI5_TAPE = range(4)
@@ -285,6 +285,12 @@ PROTOTYPES = {
   'gnpde_early_stop_reset': (ctypes.c_int, [c_vp, c_vp]),
   'gnpde_early_stop_eval': (ctypes.c_int, [ctypes.POINTER(DecoderStruct), c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_int32, c_vp, c_vp, ctypes.c_int32, c_vp]),
+  'gnpde_solver_set_outputs': (ctypes.c_int, [c_vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), c_vp,
+                                              ctypes.c_int32, c_vp]),
+  'gnpde_solver_set_output_order': (ctypes.c_int, [c_vp, c_vp]),
+  'gnpde_snapshot_rows': (ctypes.c_int, [c_vp, c_vp, ctypes.c_float, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_vp, ctypes.c_int32,
+                                         c_vp, c_vp]),
+  'gnpde_dopri5_set_outputs': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int32, c_vp, ctypes.c_int32]),
   'gnpde_solver_set_early_stop': (ctypes.c_int, [c_vp, ctypes.POINTER(DecoderStruct), c_vp, c_vp, ctypes.c_int32]),
   'gnpde_lincomb': (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), c_float_p, ctypes.c_int32, ctypes.c_int64, c_vp, c_vp]),
   'gnpde_solver_num_rhs_evals': (ctypes.c_int, [c_vp]),

@@ -302,9 +302,39 @@ class ODEblock(nn.Module):
     self.test_integrator = odeint
     self.set_tol()
 
+  def trajectory(self, x, times):
+    """The state at every entry of `times` (strictly increasing, times[0] the start), [len(times), n, d], from ONE solve: the block's own
+    `forward` runs -- attention weights, edge selection and rewiring are prepared as usual -- with `times` in place of `self.t` (the
+    reference stitches separate integrations together, GNN_image.forward_plot_path, each restarting the step-size controller).
+    No-grad solves of the package's functions run natively (odeint: 'native fixed grid' / 'native device controller')."""
+    if self.training and self.nreg > 0:
+      raise _lib.GnpdeError('ODEblock.trajectory: not while training with regularisers (their integrals belong to the end time)')
+    times = torch.as_tensor(times, dtype=torch.float32) if not torch.is_tensor(times) else times
+    if times.dim() != 1 or times.numel() < 2:
+      raise ValueError('ODEblock.trajectory: times must be a vector of at least two times')
+    # one device tensor per set of values, kept on the block like `self.t`: odeint caches its host reads of the times (grid, plan,
+    # end points) per tensor object, so repeated calls with the same times read nothing back
+    key = (str(times.dtype), tuple(times.detach().cpu().tolist()))
+    kept = self.__dict__.get('_trajectory_kept')
+    if kept is None or kept[0] != key:
+      kept = self.__dict__['_trajectory_kept'] = (key, times.detach().to(self.device))
+    self._trajectory_times = kept[1]
+    try:
+      return self.forward(x)
+    finally:
+      self._trajectory_times = None
+
   def _integrate(self, x, options):
-    """Common tail of the block forwards (reference src/block_constant.py:35-70)."""
-    t = self.t.type_as(x)
+    """Common tail of the block forwards (reference src/block_constant.py:35-70).  Inside `trajectory` the output times are the
+    caller's and every output is returned."""
+    times = getattr(self, '_trajectory_times', None)
+    t = self.t.type_as(x) if times is None else times
+    if times is not None and t.dtype != x.dtype:      # (kept per state dtype as well: type_as of another dtype makes a new tensor)
+      cast = self.__dict__.setdefault('_trajectory_cast', {})
+      hit = cast.get(x.dtype)
+      if hit is None or hit[0] is not times:
+        hit = cast[x.dtype] = (times, times.type_as(x))
+      t = hit[1]
     integrator = self.train_integrator if self.training else self.test_integrator
     regularised = self.training and self.nreg > 0
     kw = dict(method=self.opt['method'], options=options, atol=self.atol, rtol=self.rtol)
@@ -317,7 +347,7 @@ class ODEblock(nn.Module):
       state_dt = integrator(self.reg_odefunc, state, t, **kw)
       return state_dt[0][1], tuple(st[1] for st in state_dt[1:])
     state_dt = integrator(self.odefunc, x, t, **kw)
-    return state_dt[1]
+    return state_dt[1] if times is None else state_dt
 
   def __repr__(self):
     return self.__class__.__name__ + '( Time Interval ' + str(self.t[0].item()) + ' -> ' + str(self.t[1].item()) + ")"

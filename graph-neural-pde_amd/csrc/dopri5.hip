@@ -22,6 +22,7 @@
 #include <vector>
 #include "common.h"
 #include "embedded_pair.h"
+#include "epilogue.h"
 #include "graph_capture.h"
 #include "rhs.h"
 
@@ -246,6 +247,93 @@ __global__ __launch_bounds__(kBlock) void tape_store_kernel(const TapeArgs a) {
   }
 }
 
+// Outputs at several times (gnpde_dopri5_set_outputs).  The stepping never looks at them: an ACCEPTED trial step [t_prev, t] writes out[j]
+// = its quartic interpolant at x = fl32((t_out[j] - t_prev) / (t - t_prev)) for every pending j < n_out - 1 with t_out[j] <= t (the last
+// output is the end point: the finish kernel's).  Runs between the control kernel (the record already holds the new time) and the finish
+// kernel (which overwrites what a rejected step hands on).  The pending index and the start time of the step are carried in a record of
+// their own, in two slots like Ctl::h: a trial step reads slot `parity` and its one-thread tail writes slot 1 - parity for the next
+// one, so no thread of the grid reads what the tail writes.
+struct OutRec {
+  double t_prev[2];
+  int next_out[2];
+  int n_out, pad_;
+};
+static_assert(sizeof(OutRec) == 32, "output record");
+
+__global__ void emit_init_kernel(OutRec* q, double t0, int n_out) {
+  q->t_prev[0] = q->t_prev[1] = t0;
+  q->next_out[0] = q->next_out[1] = 0;
+  q->n_out = n_out;
+}
+
+struct EmitArgs {
+  const float* y; const float* y1;
+  const float* k[7];
+  float mid[7];                   // fl32(c_mid_j)
+  int n_k, last;
+  long long n;
+  int d, ld;
+  float* out; int ld_out;         // [n_out][n, ld_out]
+  const int* order;               // solver row r -> the caller's row order[r] (null: r)
+  const double* t_out;            // [n_out], ascending, t_out[n_out - 1] = t1
+  OutRec* rec;
+  const Ctl* c;
+  int parity;
+};
+
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void emit_outputs_kernel(const EmitArgs a) {
+  constexpr int W = VEC4 ? 4 : 1;
+  const int accept = a.c->accept;
+  const double t = a.c->t, t_prev = a.rec->t_prev[a.parity];
+  const int j0 = a.rec->next_out[a.parity], n_out = a.rec->n_out;
+  // (everything the bound depends on is read from device memory written by earlier kernels: the same for every thread of the grid)
+  int j1 = j0;
+  if (accept)
+    while (j1 < n_out - 1 && a.t_out[j1] <= t) ++j1;
+  if (j1 > j0) {
+    const float h = a.c->h[a.parity];
+    const int groups = a.d / W;
+    const long long total = a.n * groups;
+    const size_t slab = static_cast<size_t>(a.n) * a.ld_out;
+    for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<long long>(gridDim.x) * kBlock) {
+      const long long row = i / groups;
+      const int col = static_cast<int>(i - row * groups) * W;
+      const size_t off = static_cast<size_t>(row) * a.ld + col;
+      const long long orow = a.order != nullptr ? static_cast<long long>(a.order[row]) : row;
+      float ya[W], yb[W], fa[W], fb[W], ym[W];
+      load_vec<W>(a.y + off, ya);
+      load_vec<W>(a.y1 + off, yb);
+      load_vec<W>(a.k[0] + off, fa);
+      load_vec<W>(a.k[a.last] + off, fb);
+#pragma unroll
+      for (int c = 0; c < W; ++c) ym[c] = ya[c];
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        const float m = j < a.n_k ? a.mid[j] * h : 0.0f;
+        if (m != 0.0f) {
+          float kj[W];
+          load_vec<W>(a.k[j] + off, kj);
+#pragma unroll
+          for (int c = 0; c < W; ++c) ym[c] += kj[c] * m;
+        }
+      }
+      float* o = a.out + static_cast<size_t>(orow) * a.ld_out + col;
+      for (int j = j0; j < j1; ++j) {
+        const float x = static_cast<float>((a.t_out[j] - t_prev) / (t - t_prev));
+        float v[W];
+#pragma unroll
+        for (int c = 0; c < W; ++c) v[c] = quartic(ya[c], yb[c], fa[c], fb[c], ym[c], h, x);
+        store_vec<W>(o + j * slab, v);
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {      // the tail: what the next trial step (the other parity) starts from
+    a.rec->next_out[1 - a.parity] = j1;
+    a.rec->t_prev[1 - a.parity] = accept ? t : t_prev;
+  }
+}
+
 // sum over the per-wave dots of every launch of the reverse sweep: sum d1 - sum d2 in double, fixed order -- kTapeFoldBlocks blocks over
 // contiguous ranges, then one wave over their partial sums
 constexpr int kTapeFoldBlocks = 128;
@@ -317,6 +405,13 @@ struct gnpde_dopri5 {
   float* host_h = nullptr;      // pinned copy of the accepted steps' sizes, read once behind a recorded solve
   int host_h_capacity = 0;
   const int* row_order = nullptr;   // gnpde_dopri5_set_row_order: solver row r <-> caller's row row_order[r]
+  // outputs at several times (gnpde_dopri5_set_outputs)
+  const double* t_out = nullptr;    // device, [n_out]
+  int n_out = 0;
+  double t_out_last = 0.0;          // host copy of t_out[n_out - 1]: the t1 of the runs
+  float* out = nullptr;
+  int ld_out = 0;
+  OutRec* out_rec = nullptr;
   // Row-partitioned solve (gnpde_dopri5_create_sharded): the evaluations go through the exchange engine (its stage buffers hold the four
   // states that are ever an evaluation's input: Y[0], Y[1], u[0], u[1]), the error norms are summed over the ranks inside the stream
   int pair = GNPDE_ADAPTIVE_DOPRI5;   // gnpde_dopri5_set_pair: the embedded pair (Dormand-Prince 5(4) / torchdiffeq's adaptive_heun 2(1))
@@ -413,6 +508,26 @@ int enqueue_trial(gnpde_dopri5* s, int parity, hipStream_t st) {
   hipLaunchKernelGGL(control_kernel, dim3(1), dim3(kBlock), 0, st, reinterpret_cast<const double*>(s->err_ws), nblocks, s->count, s->ctl, parity,
                      s->early ? s->times : nullptr, s->early ? s->times_capacity : 0, tab.order);
   GNPDE_LAUNCH_CHECK();
+  if (s->t_out != nullptr) {
+    EmitArgs ea{};
+    ea.y = y; ea.y1 = y1;
+    for (int j = 0; j < 7; ++j) {
+      ea.k[j] = k[j];
+      ea.mid[j] = cmid[j];
+    }
+    ea.n_k = n_k; ea.last = S;
+    ea.n = n; ea.d = r.d; ea.ld = r.ld;
+    ea.out = s->out; ea.ld_out = s->ld_out; ea.order = s->row_order; ea.t_out = s->t_out; ea.rec = s->out_rec; ea.c = s->ctl; ea.parity = parity;
+    // (the state side always allows 16-byte lanes: ld % 4 == 0 is checked at creation and every buffer is a 256-byte aligned slice of the
+    //  workspace, as the finish kernel relies on; what varies is the width and the caller's output)
+    const bool v4 = r.d % 4 == 0 && s->ld_out % 4 == 0 && reinterpret_cast<uintptr_t>(s->out) % 16 == 0;
+    long long eb = (n * (v4 ? r.d / 4 : r.d) + kBlock - 1) / kBlock;
+    if (eb > 4096) eb = 4096;
+    if (eb < 1) eb = 1;
+    if (v4) hipLaunchKernelGGL((emit_outputs_kernel<true>), dim3(static_cast<unsigned>(eb)), dim3(kBlock), 0, st, ea);
+    else hipLaunchKernelGGL((emit_outputs_kernel<false>), dim3(static_cast<unsigned>(eb)), dim3(kBlock), 0, st, ea);
+    GNPDE_LAUNCH_CHECK();
+  }
   if (s->tape != nullptr) {
     TapeArgs ta{};
     ta.src[0] = y;
@@ -503,6 +618,7 @@ extern "C" int gnpde_dopri5_create(gnpde_dopri5_t** out, const gnpde_rhs_t* rhs,
   s->ws_bytes = workspace_bytes;
   s->ctl = reinterpret_cast<Ctl*>(s->ws + s->off_ctl);
   s->init = reinterpret_cast<Init*>(s->ws + s->off_ctl + 128);
+  s->out_rec = reinterpret_cast<OutRec*>(s->ws + s->off_ctl + 160);
   s->err_ws = reinterpret_cast<float*>(s->ws + s->off_err);
   float* base = reinterpret_cast<float*>(s->ws + s->off_state);
   const size_t stride = s->state_bytes / 4;
@@ -574,6 +690,7 @@ extern "C" int gnpde_dopri5_create_sharded(gnpde_dopri5_t** out, gnpde_sharded_s
   s->ws_bytes = workspace_bytes;
   s->ctl = reinterpret_cast<Ctl*>(s->ws + s->off_ctl);
   s->init = reinterpret_cast<Init*>(s->ws + s->off_ctl + 128);
+  s->out_rec = reinterpret_cast<OutRec*>(s->ws + s->off_ctl + 160);
   s->err_ws = reinterpret_cast<float*>(s->ws + s->off_err);
   // every state that is ever an evaluation's input lives in a shared stage buffer: the peers push their boundary rows into its halo rows
   s->Y[0] = sharded_stage_buffer(engine, 0); s->Y[1] = sharded_stage_buffer(engine, 1);
@@ -597,6 +714,8 @@ extern "C" int gnpde_dopri5_run(gnpde_dopri5_t* s, const float* y0, int32_t ld_y
   GNPDE_CHECK_ARG(s && y0 && y_out, GNPDE_EINVAL, "dopri5_run: null argument");
   const gnpde_rhs_t& r = s->rhs;
   GNPDE_CHECK_ARG(ld_y0 >= r.d && ld_out >= r.d && t1 > t0, GNPDE_EINVAL, "dopri5_run: bad strides or time span");
+  GNPDE_CHECK_ARG(s->t_out == nullptr || t1 == s->t_out_last, GNPDE_EINVAL, "dopri5_run: t1 = %.17g but the last output time is %.17g", t1,
+                  s->t_out_last);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (trials_per_sync < 1) trials_per_sync = 1;
   const int n = static_cast<int>(s->n_rows);
@@ -645,6 +764,10 @@ extern "C" int gnpde_dopri5_run(gnpde_dopri5_t* s, const float* y0, int32_t ld_y
     hipLaunchKernelGGL(init_dt_kernel, dim3(1), dim3(1), 0, st, s->init, s->ctl, t0, t1, s->early ? s->max_trials : 0,
                        s->early ? s->times : nullptr, s->early ? s->times_capacity : 0, tab.order);
     GNPDE_LAUNCH_CHECK();
+    if (s->t_out != nullptr) {
+      hipLaunchKernelGGL(emit_init_kernel, dim3(1), dim3(1), 0, st, s->out_rec, t0, s->n_out);
+      GNPDE_LAUNCH_CHECK();
+    }
     // first stage input of the first trial step (later ones come out of the finish kernel)
     const float c[1] = {static_cast<float>(tab.a[0][0])};
     if (int rc = launch_lincomb(s->Y[0], w, c, 1, flat, s->u[0], st, &s->ctl->h[0])) return rc;
@@ -706,6 +829,8 @@ extern "C" int gnpde_dopri5_set_early_stop(gnpde_dopri5_t* s, const gnpde_decode
     s->early = false;
     return 0;
   }
+  GNPDE_CHECK_ARG(s->t_out == nullptr, GNPDE_EINVAL,
+                  "dopri5_set_early_stop: not together with outputs at several times (detach them first: gnpde_dopri5_set_outputs(s, NULL, 0, NULL, 0))");
   GNPDE_CHECK_ARG(s->shard == nullptr, GNPDE_ESTATE, "dopri5_set_early_stop: not on a row-partitioned solve (the split counts are over all rows)");
   if (int rc = check_decoder(dec, s->rhs.d)) return rc;
   GNPDE_CHECK_ARG(state != nullptr && max_trial_steps >= 1, GNPDE_EINVAL, "dopri5_set_early_stop: state is null or no trial steps allowed");
@@ -736,7 +861,38 @@ extern "C" int gnpde_dopri5_set_pair(gnpde_dopri5_t* s, int32_t pair) {
 extern "C" int gnpde_dopri5_set_row_order(gnpde_dopri5_t* s, const int32_t* order) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "dopri5_set_row_order: solver is null");
   GNPDE_CHECK_ARG(order == nullptr || s->shard == nullptr, GNPDE_ESTATE, "dopri5_set_row_order: not on a row-partitioned solve");
-  s->row_order = order;      // (read by the copy kernels of gnpde_dopri5_run only: the captured trial steps are untouched)
+  if (s->t_out != nullptr && order != s->row_order) {      // (with outputs attached the captured emit kernel writes through the map)
+    for (int p = 0; p < 2; ++p) drop_capture(&s->graph_obj[p], &s->exec[p]);
+  }
+  s->row_order = order;      // (otherwise read by the copy kernels of gnpde_dopri5_run only: the captured trial steps are untouched)
+  return 0;
+}
+
+extern "C" int gnpde_dopri5_set_outputs(gnpde_dopri5_t* s, const double* t_out, int32_t n_out, float* out, int32_t ld_out) {
+  GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "dopri5_set_outputs: solver is null");
+  GNPDE_CHECK_ARG(n_out >= 0, GNPDE_EINVAL, "dopri5_set_outputs: n_out = %d", n_out);
+  auto drop = [&]() {      // the emit kernel and its pointers are part of the captured trial step
+    for (int p = 0; p < 2; ++p) drop_capture(&s->graph_obj[p], &s->exec[p]);
+  };
+  if (n_out == 0 || t_out == nullptr) {
+    if (s->t_out != nullptr) drop();
+    s->t_out = nullptr;
+    s->out = nullptr;
+    s->n_out = 0;
+    return 0;
+  }
+  GNPDE_CHECK_ARG(s->shard == nullptr, GNPDE_EINVAL, "dopri5_set_outputs: not on a row-partitioned solve (it has two output times)");
+  GNPDE_CHECK_ARG(s->tape == nullptr, GNPDE_EINVAL, "dopri5_set_outputs: a recorded solve has two output times (detach the tape first)");
+  GNPDE_CHECK_ARG(!s->early, GNPDE_EINVAL, "dopri5_set_outputs: not together with the early-stopping evaluator (detach it first)");
+  GNPDE_CHECK_ARG(out != nullptr && ld_out >= s->rhs.d, GNPDE_EINVAL, "dopri5_set_outputs: out is null or ld_out %d < d %d", ld_out, s->rhs.d);
+  double last = 0.0;
+  GNPDE_HIP(hipMemcpy(&last, t_out + (n_out - 1), sizeof(double), hipMemcpyDeviceToHost));
+  if (t_out != s->t_out || out != s->out || ld_out != s->ld_out) drop();      // (n_out and the times themselves are read from device memory)
+  s->t_out = t_out;
+  s->n_out = n_out;
+  s->t_out_last = last;
+  s->out = out;
+  s->ld_out = ld_out;
   return 0;
 }
 
@@ -785,6 +941,8 @@ extern "C" int gnpde_dopri5_set_tape(gnpde_dopri5_t* s, void* tape, size_t tape_
   s->tape = nullptr;
   s->tape_steps = 0;
   if (tape == nullptr) return 0;
+  GNPDE_CHECK_ARG(s->t_out == nullptr, GNPDE_EINVAL,
+                  "dopri5_set_tape: a recorded solve has two output times (detach the outputs first: gnpde_dopri5_set_outputs(s, NULL, 0, NULL, 0))");
   GNPDE_CHECK_ARG(s->shard == nullptr, GNPDE_ESTATE, "dopri5_set_tape: not on a row-partitioned solve");
   GNPDE_CHECK_ARG(s->pair == GNPDE_ADAPTIVE_DOPRI5, GNPDE_ESTATE, "dopri5_set_tape: the recorded solve is Dormand-Prince's");
   // (the store kernel copies stage inputs whatever f is; GRAND-nl / GAT records are swept by gnpde_adjoint_set_dopri5_tape, which

@@ -634,3 +634,61 @@ int launch_to_bf16(const float* src, long long n, int d, int ld, uint16_t* dst, 
 extern "C" int gnpde_to_bf16(const float* src, int64_t n, int32_t d, int32_t ld, void* dst, void* stream) {
   return gnpde::launch_to_bf16(src, n, d, ld, static_cast<uint16_t*>(dst), static_cast<hipStream_t>(stream));
 }
+
+// Output of a fixed-grid solve at a time inside (or at the end of) a step: out[m(r), 0:d] = ya[r] + frac (yb[r] - ya[r]), m the optional
+// row map (solver row r -> the caller's row order[r]); frac == 1 is the plain copy of yb through the same map (ya is not read).  The
+// state rows have stride ld, the output rows ld_out.  One lane per group of four columns where every stride and address allows 16-byte
+// accesses and d % 4 == 0, element by element otherwise.
+namespace gnpde {
+namespace {
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void snapshot_rows_kernel(const float* __restrict__ ya, const float* __restrict__ yb, float frac, int copy,
+                                                               long long n, int d, int ld, float* __restrict__ out, int ld_out,
+                                                               const int* __restrict__ order) {
+  constexpr int W = VEC4 ? 4 : 1;
+  const int groups = d / W;
+  const long long total = n * groups;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < total; i += static_cast<long long>(gridDim.x) * kBlock) {
+    const long long row = i / groups;
+    const int col = static_cast<int>(i - row * groups) * W;
+    const size_t off = static_cast<size_t>(row) * ld + col;
+    const long long orow = order != nullptr ? static_cast<long long>(order[row]) : row;
+    float b[W], v[W];
+    load_vec<W>(yb + off, b);
+    if (copy) {
+#pragma unroll
+      for (int c = 0; c < W; ++c) v[c] = b[c];
+    } else {
+      float a[W];
+      load_vec<W>(ya + off, a);
+#pragma unroll
+      for (int c = 0; c < W; ++c) v[c] = fmaf(frac, b[c] - a[c], a[c]);
+    }
+    store_vec<W>(out + static_cast<size_t>(orow) * ld_out + col, v);
+  }
+}
+}  // namespace
+
+int launch_snapshot_rows(const float* ya, const float* yb, float frac, long long n, int d, int ld, float* out, int ld_out, const int* order,
+                         hipStream_t s) {
+  const bool copy = frac == 1.0f;
+  GNPDE_CHECK_ARG(yb && out && (ya || copy) && n >= 0 && d >= 1 && ld >= d && ld_out >= d, GNPDE_EINVAL,
+                  "snapshot_rows: bad arguments (n=%lld d=%d ld=%d ld_out=%d)", n, d, ld, ld_out);
+  if (n == 0) return 0;
+  auto lanes16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  const bool v4 = d % 4 == 0 && ld % 4 == 0 && ld_out % 4 == 0 && lanes16(yb) && lanes16(out) && (copy || lanes16(ya));
+  long long blocks = (n * (v4 ? d / 4 : d) + kBlock - 1) / kBlock;
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  if (v4) hipLaunchKernelGGL((snapshot_rows_kernel<true>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, ya, yb, frac, copy ? 1 : 0, n, d, ld,
+                             out, ld_out, order);
+  else hipLaunchKernelGGL((snapshot_rows_kernel<false>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, ya, yb, frac, copy ? 1 : 0, n, d, ld,
+                          out, ld_out, order);
+  GNPDE_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace gnpde
+
+extern "C" int gnpde_snapshot_rows(const float* ya, const float* yb, float frac, int64_t n, int32_t d, int32_t ld, float* out, int32_t ld_out,
+                                   const int32_t* order, void* stream) {
+  return gnpde::launch_snapshot_rows(ya, yb, frac, n, d, ld, out, ld_out, order, static_cast<hipStream_t>(stream));
+}

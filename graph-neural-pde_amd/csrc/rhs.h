@@ -62,6 +62,11 @@ bool rhs_gather_lo_supported(const gnpde_rhs_t& r);
 // epilogue with the descriptor's alpha / beta / x0 filled in
 gnpde_epilogue_t base_epilogue(const gnpde_rhs_t& r);
 
+// out[m(r), 0:d] = ya[r] + frac (yb[r] - ya[r]) between two row strides, m = the optional row map `order` (misc.hip; gnpde_snapshot_rows):
+// the outputs of a fixed-grid solve at times inside its grid (gnpde_solver_set_outputs).  frac == 1: the copy of yb, ya may be null.
+int launch_snapshot_rows(const float* ya, const float* yb, float frac, long long n, int d, int ld, float* out, int ld_out, const int* order,
+                         hipStream_t s);
+
 // The exchange engine of the row-partitioned solvers (a gnpde_sharded_solver_t with the P2P transport, sharded.hip) as the adaptive
 // solver drives it (dopri5.hip, gnpde_dopri5_create_sharded): one evaluation = push of the boundary rows of `u` + interior pass +
 // wait + boundary pass; one sum = the all-reduce of a double over the ranks, inside the stream (no host, no library call).

@@ -230,6 +230,14 @@ struct gnpde_solver {
   float* tape = nullptr;     // recorded solve (gnpde_solver_set_tape): n_evals + 1 state-sized slots, the stage inputs in evaluation order
   float* tape_rec = nullptr; // ... followed by one RhsRecord per evaluation (GRAND-nl with scaled-dot scores: q||k and the weights)
   uint16_t* lo = nullptr;    // bf16 gather operand (gnpde_solver_set_gather): one shadow per stage-input buffer, caller's memory
+  // outputs at several times (gnpde_solver_set_outputs): output j is taken after step out_step[j] (1-based, non-decreasing) at the
+  // fraction out_frac[j] of that step; a step with an output strictly inside it keeps its start state in out_scratch
+  std::vector<int> out_step;
+  std::vector<float> out_frac;
+  float* out = nullptr;
+  int ld_out = 0;
+  float* out_scratch = nullptr;
+  const int* out_order = nullptr;
 };
 
 namespace {
@@ -280,6 +288,27 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
     return enqueue_early_stop_eval(s->dec, state, r.ld, r.graph->n, step, s->early_state,
                                    s->early_trace, s->early_trace_capacity, st);
   };
+  // outputs at several times: before a step with an output strictly inside it the start state goes to the scratch buffer (the stage
+  // buffers are recycled inside the step), after a step every output that falls into it is one snapshot launch
+  size_t next_out = 0;
+  auto interior = [](float f) { return f != 1.0f; };
+  auto before_step = [&](int i, const float* state) -> int {      // i: the 1-based number of the step about to run
+    for (size_t j = next_out; j < s->out_step.size() && s->out_step[j] == i; ++j)
+      if (interior(s->out_frac[j])) {
+        GNPDE_HIP(hipMemcpyAsync(s->out_scratch, state, static_cast<size_t>(r.graph->n) * r.ld * 4, hipMemcpyDeviceToDevice, st));
+        break;
+      }
+    return 0;
+  };
+  auto after_step = [&](int i, const float* state) -> int {
+    for (; next_out < s->out_step.size() && s->out_step[next_out] == i; ++next_out) {
+      const float f = s->out_frac[next_out];
+      float* dst = s->out + next_out * static_cast<size_t>(r.graph->n) * s->ld_out;
+      if (int rc = launch_snapshot_rows(interior(f) ? s->out_scratch : nullptr, state, f, r.graph->n, r.d, r.ld, dst, s->ld_out, s->out_order, st))
+        return rc;
+    }
+    return 0;
+  };
   if (s->early) GNPDE_HIP(hipMemsetAsync(s->early_state, 0, 8 * sizeof(int32_t), st));
   // hub-row tickets of the aggregation launches: zero at the head of the solve (a memset node of a captured one); every launch that uses
   // them leaves them zero
@@ -312,7 +341,9 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       gnpde_epilogue_t e = base;
       e.dt = dt; e.y = y;
       e.stage = GNPDE_STAGE_RK1; e.out_k = k1; e.out_y = ua;
-      int rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1), true);
+      int rc = before_step(step + 1, y);
+      if (rc) return rc;
+      rc = enqueue_rhs(r, y, e, rws, s->L, st, fk, nullptr, pair(0, 1), true);
       if (rc) return rc;
       e.stage = GNPDE_STAGE_RK2; e.k1 = k1; e.out_k = k2; e.out_y = ub;
       rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 2), true);
@@ -324,6 +355,8 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       rc = enqueue_rhs(r, ua, e, rws, s->L, st, fk, nullptr, pair(1, 0), true);
       if (rc) return rc;
       rc = evaluate(y);
+      if (rc) return rc;
+      rc = after_step(step, y);
       if (rc) return rc;
     }
     return 0;
@@ -356,7 +389,9 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
       idx[i] = (first + i) % B;
       u[i] = s->tape != nullptr ? slot(at + i) : bufs[idx[i]];
     }
-    int rc = enqueue_step(base, s->method, dt, u, [&](int j, const float* in, const gnpde_epilogue_t& e) {
+    int rc = before_step(step + 1, u[0]);
+    if (rc) return rc;
+    rc = enqueue_step(base, s->method, dt, u, [&](int j, const float* in, const gnpde_epilogue_t& e) {
       return enqueue_rhs(r, in, e, rws, s->L, st, fk, rec(at + j), pair(idx[j], idx[j + 1]), true);
     });
     if (rc) return rc;
@@ -364,6 +399,8 @@ int enqueue_solve(gnpde_solver* s, float* y, hipStream_t st) {
     first = idx[S];
     result = u[S];
     rc = evaluate(result);
+    if (rc) return rc;
+    rc = after_step(step, result);
     if (rc) return rc;
   }
   if (result != y) GNPDE_HIP(hipMemcpyAsync(y, result, nbytes, hipMemcpyDeviceToDevice, st));
@@ -478,6 +515,8 @@ extern "C" int gnpde_solver_set_tape(gnpde_solver_t* s, void* tape, size_t tape_
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "solver_set_tape: solver is null");
   GNPDE_CHECK_ARG(tape == nullptr || s->lo == nullptr, GNPDE_EINVAL,
                   "solver_set_tape: a recorded solve keeps the fp32 gather operand (detach the bf16 one first: gnpde_solver_set_gather(s, 0, NULL, 0))");
+  GNPDE_CHECK_ARG(tape == nullptr || s->out_step.empty(), GNPDE_EINVAL,
+                  "solver_set_tape: a recorded solve has two output times (detach the outputs first: gnpde_solver_set_outputs(s, 0, ...))");
   drop_graph(s);
   s->tape = nullptr;
   s->tape_rec = nullptr;
@@ -529,6 +568,8 @@ extern "C" int gnpde_solver_set_gather(gnpde_solver_t* s, int32_t dtype, void* m
 extern "C" int gnpde_solver_set_early_stop(gnpde_solver_t* s, const gnpde_decoder_t* dec, int32_t* state, int32_t* trace,
                                            int32_t trace_capacity) {
   GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "solver_set_early_stop: solver is null");
+  GNPDE_CHECK_ARG(dec == nullptr || s->out_step.empty(), GNPDE_EINVAL,
+                  "solver_set_early_stop: not together with outputs at several times (detach them first: gnpde_solver_set_outputs(s, 0, ...))");
   drop_graph(s);
   if (dec == nullptr) {
     s->early = false;
@@ -543,6 +584,47 @@ extern "C" int gnpde_solver_set_early_stop(gnpde_solver_t* s, const gnpde_decode
   s->early_trace = trace;
   s->early_trace_capacity = trace_capacity;
   s->early = true;
+  return 0;
+}
+
+extern "C" int gnpde_solver_set_outputs(gnpde_solver_t* s, int32_t n_out, const int32_t* step, const float* frac, float* out, int32_t ld_out,
+                                        float* scratch) {
+  GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "solver_set_outputs: solver is null");
+  GNPDE_CHECK_ARG(n_out >= 0, GNPDE_EINVAL, "solver_set_outputs: n_out = %d", n_out);
+  if (n_out == 0) {
+    drop_graph(s);
+    s->out_step.clear();
+    s->out_frac.clear();
+    s->out = s->out_scratch = nullptr;
+    return 0;
+  }
+  GNPDE_CHECK_ARG(s->tape == nullptr, GNPDE_EINVAL, "solver_set_outputs: a recorded solve has two output times (detach the tape first)");
+  GNPDE_CHECK_ARG(!s->early, GNPDE_EINVAL, "solver_set_outputs: not together with the early-stopping evaluator (detach it first)");
+  const gnpde_rhs_t& r = s->rhs;
+  GNPDE_CHECK_ARG(r.n_state_rows <= r.graph->n && r.proj_row_end == 0 && r.graph->row_begin == 0, GNPDE_EINVAL,
+                  "solver_set_outputs: not on a partitioned descriptor (the row-partitioned engine has two output times)");
+  GNPDE_CHECK_ARG(step && frac && out && ld_out >= r.d, GNPDE_EINVAL, "solver_set_outputs: null array or ld_out %d < d %d", ld_out, r.d);
+  bool any_interior = false;
+  for (int j = 0; j < n_out; ++j) {
+    GNPDE_CHECK_ARG(step[j] >= 1 && step[j] <= static_cast<int>(s->dts.size()) && (j == 0 || step[j] >= step[j - 1]), GNPDE_EINVAL,
+                    "solver_set_outputs: step[%d] = %d (1..%d, non-decreasing)", j, step[j], static_cast<int>(s->dts.size()));
+    GNPDE_CHECK_ARG(frac[j] >= 0.0f && frac[j] <= 1.0f, GNPDE_EINVAL, "solver_set_outputs: frac[%d] = %g (0..1)", j, static_cast<double>(frac[j]));
+    any_interior = any_interior || frac[j] != 1.0f;
+  }
+  GNPDE_CHECK_ARG(!any_interior || scratch != nullptr, GNPDE_EINVAL, "solver_set_outputs: an output inside a step needs the scratch state buffer");
+  drop_graph(s);
+  s->out_step.assign(step, step + n_out);
+  s->out_frac.assign(frac, frac + n_out);
+  s->out = out;
+  s->ld_out = ld_out;
+  s->out_scratch = scratch;
+  return 0;
+}
+
+extern "C" int gnpde_solver_set_output_order(gnpde_solver_t* s, const int32_t* order) {
+  GNPDE_CHECK_ARG(s != nullptr, GNPDE_EINVAL, "solver_set_output_order: solver is null");
+  if (order != s->out_order) drop_graph(s);
+  s->out_order = order;
   return 0;
 }
 

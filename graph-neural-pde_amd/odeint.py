@@ -4,8 +4,9 @@ the reference's blocks (src/block_constant.py:57-62, src/block_transformer_atten
 
 Fixed-grid methods (`euler`, `rk4` == torchdiffeq 0.2.1's 3/8-rule rk4_alt_step_func) on one of this
 package's ODEFunc objects run as ONE native solver object whose whole time loop is a captured
-hipGraph (csrc/solver.hip).  Everything else (dopri5, foreign callables, several output times) runs
-the host loops below, which still evaluate f through the native kernels."""
+hipGraph (csrc/solver.hip); dopri5 / adaptive_heun run with the step-size controller on the device (csrc/dopri5.hip).  Both serve
+any number of strictly increasing output times (output_plan / output_times below).  Everything else (foreign callables, non-monotone
+times, differentiated solves without a record) runs the host loops below, which still evaluate f through the native kernels."""
 import contextlib
 import math
 import os
@@ -64,6 +65,39 @@ def end_points(t):
   return _cached_host_read(t, 'ends', lambda t: (float(t[0]), float(t[-1])))
 
 
+def output_plan(t, step_size):
+  """Where the outputs t[1:] of a fixed-grid solve come from, as torchdiffeq's FixedGridODESolver.integrate (and `_solve_fixed_host`)
+  decides it: ((step, frac), ...) -- output j + 1 is produced by the first step [ta, tb] of `time_grid` with tb >= t[j + 1] (`step`, 1-based),
+  as y_next (frac 1.0), y (frac 0.0) or y + frac (y_next - y) with frac = (t[j + 1] - ta) / (tb - ta) computed in t's dtype.  Host floats,
+  cached like step_sizes."""
+  def read(t):
+    tc = t.detach().to('cpu')
+    grid = time_grid(tc, step_size)
+    plan, j = [], 1
+    for i in range(len(grid) - 1):
+      ta, tb = grid[i], grid[i + 1]
+      while j < len(tc) and tb >= tc[j]:
+        if tc[j] == tb:
+          frac = 1.0
+        elif tc[j] == ta:
+          frac = 0.0
+        else:
+          frac = float((tc[j] - ta) / (tb - ta))
+        plan.append((i + 1, frac))
+        j += 1
+    return tuple(plan)
+  return _cached_host_read(t, ('plan', float(step_size)), read)
+
+
+def output_times(t):
+  """t[1:] as host floats (the output times of an adaptive device solve; float64 of t's values, as the host loop's t.to(float64))."""
+  return _cached_host_read(t, 'outs', lambda t: tuple(t.detach().to('cpu', torch.float64)[1:].tolist()))
+
+
+def _strictly_increasing(t):
+  return _cached_host_read(t, 'increasing', lambda t: bool((t[1:] > t[:-1]).all().item()))
+
+
 def default_trials_per_sync(numel):
   """Trial steps of a device-controlled adaptive solve between two host reads of its record, by the size of the WHOLE state.  Launch-bound
   sizes: keep the queue full between reads; large states: a read per trial step costs nothing next to the evaluations and nothing is
@@ -117,6 +151,16 @@ def _solver_for(ent, sig, build):
   return ent['solver']
 
 
+def _order32(view):
+  """view.order as an int32 device tensor, kept on the view (the row map the solvers' own copies take); None without a view."""
+  if view is None:
+    return None
+  order32 = view.__dict__.get('order32')
+  if order32 is None:
+    order32 = view.__dict__['order32'] = view.order.to(torch.int32).contiguous()
+  return order32
+
+
 def _rows_in(view, src, dst):
   """dst = the rows of src in the order the solver runs in (relabelled graph, graph.LocalityView: src[order])."""
   return dst.copy_(src) if view is None else view.enter(src, out=dst)
@@ -153,6 +197,45 @@ def _weights_t(func, graph, out=None):
 def _native_ok(func, y0, t):
   return (hasattr(func, '_descriptor') and y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32
           and len(t) == 2 and not func._needs_grad(y0) and func._has_native_rhs(y0))
+
+
+def host_outputs_requested(func):
+  """opt['gnpde_host_outputs'] (or GNPDE_HOST_OUTPUTS=1): solves with more than two output times keep the host loops (A/B runs, tests)."""
+  opt = getattr(func, 'opt', None)
+  v = os.environ.get('GNPDE_HOST_OUTPUTS', '0') == '1'
+  if hasattr(opt, 'get'):
+    v = opt.get('gnpde_host_outputs', v)
+  return bool(v)
+
+
+def _host_outputs_reason(func, y0, t):
+  """Why a solve with more than two output times cannot take a native route (None: it can).  `_native_ok`'s rule with len(t) > 2 and
+  strictly increasing times; the row-partitioned solver keeps two output times."""
+  if not hasattr(func, '_descriptor'):
+    return 'foreign callable'
+  if not (y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32):
+    return 'state is not a float32 [n, d] tensor on a HIP device'
+  if func._needs_grad(y0):
+    return 'differentiated solve'
+  if not func._has_native_rhs(y0):
+    return 'no native right-hand side for this configuration'
+  if host_outputs_requested(func):
+    return 'gnpde_host_outputs'
+  from . import distributed as D
+  if D.shard_requested(func):
+    return 'gnpde_shard: the row-partitioned solver has two output times'
+  if not _strictly_increasing(t):
+    return 'output times are not strictly increasing'
+  return None
+
+
+def _native_outputs_ok(func, y0, t):
+  return len(t) > 2 and _host_outputs_reason(func, y0, t) is None
+
+
+def _note_output_solve(func, route):
+  if hasattr(func, '_descriptor'):
+    func._last_output_solve = route      # the route the last solve with more than two output times took
 
 
 def gather_dtype_requested(func):
@@ -201,7 +284,11 @@ def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None
   view = func._locality_view(y0) if hasattr(func, '_locality_view') else None
   if evaluator is not None and view is not None:
     evaluator = evaluator.relabelled(view)
-  key = (method, tuple(dts), tuple(y0.shape), str(y0.device), id(view), gather)
+  # more than two output times: the plan rides in the solver (snapshot nodes behind the steps that produce an output)
+  plan = output_plan(t, step_size) if len(t) > 2 else None
+  if plan is not None and evaluator is not None:
+    raise _lib.GnpdeError('early stopping inside a fixed-grid solve has two output times')
+  key = (method, tuple(dts), tuple(y0.shape), str(y0.device), id(view), gather, plan)
   y0c = y0.detach()
   ent = _entry(func, '_solver_state', key, y0c.shape[0], y0c.shape[1], y0c.device, siblings=('_dopri5_device',), view=view)
   _rows_in(view, y0c, ent['y'])
@@ -224,12 +311,20 @@ def _solve_native(func, y0, t, method, step_size, use_graph=True, evaluator=None
     ent['solver'].set_early_stop(evaluator)     # per-step early-stopping evaluation inside the same hipGraph
   if getattr(ent['solver'], 'gather_dtype', 'fp32') != gather:
     ent['solver'].set_gather(gather)            # raises for a shape the bf16 kernels do not cover: never a silent fp32 run
+  if plan is not None:
+    order32 = _order32(view)
+    if getattr(ent['solver'], 'output_plan', None) != plan or getattr(ent['solver'], '_out_order', None) is not order32:
+      # (a buffer with a persistent address: the captured graph holds it; rows land in the caller's order)
+      ent['solver'].set_outputs(plan, torch.empty((len(plan),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device), order32)
   ent['solver'].run(ent['y'], use_graph=use_graph)
   _note_gather(func, gather)
   func.nfe += n_evals
-  out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+  out = torch.empty((len(t),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
   out[0].copy_(y0c)
-  _rows_out(view, ent['y'], out[1])
+  if plan is not None:
+    out[1:].copy_(ent['solver']._outs)
+  else:
+    _rows_out(view, ent['y'], out[1])
   return out
 
 
@@ -629,6 +724,11 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
   sol = _solver_for(ent, func._descriptor_signature(desc), lambda: ops.Dopri5Solver(desc, rtol, atol, y0.device))
   if getattr(sol, 'pair', 'dopri5') != pair:      # (`pair`: 'dopri5' or torchdiffeq's 'adaptive_heun' -- the same controller, another trial step)
     sol.set_pair(pair)
+  times = output_times(t) if len(t) > 2 else None
+  if times is not None and evaluator is not None:
+    raise _lib.GnpdeError('early stopping on the device controller has two output times')
+  if times is None and getattr(sol, 'out_times', None) is not None:
+    sol.set_outputs(None)
   if evaluator is not None:
     if getattr(sol, 'evaluator', None) is not evaluator or getattr(sol, 'max_trial_steps', None) != int(stop_after):
       sol.set_early_stop(evaluator, int(stop_after))
@@ -638,22 +738,27 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
     trials_per_sync = default_trials_per_sync(y0c.numel())
     if os.environ.get('GNPDE_DOPRI5_TRIALS_PER_SYNC'):          # A/B runs
       trials_per_sync = max(1, int(os.environ['GNPDE_DOPRI5_TRIALS_PER_SYNC']))
-  out = torch.empty((2,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+  out = torch.empty((len(t),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
   out[0].copy_(y0c)
   # relabelled graph: the permutation rides in the solver's own first and last copy (gnpde_dopri5_set_row_order) instead of two
   # index_select launches around it
-  order32 = None
-  if view is not None:
-    order32 = view.__dict__.get('order32')
-    if order32 is None:
-      order32 = view.__dict__['order32'] = view.order.to(torch.int32).contiguous()
+  order32 = _order32(view)
   if getattr(sol, '_row_order', None) is not order32:
     sol.set_row_order(order32)
+  if times is not None and getattr(sol, 'out_times', None) != times:
+    # more than two output times: the accepted trial steps write the interior outputs (emit kernel of the captured trial step) into a
+    # buffer with a persistent address, kept while the count stays; the last output is the run's own
+    buf = getattr(sol, '_outs', None)
+    if buf is None or buf.shape[0] != len(times):
+      buf = torch.empty((len(times),) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+    sol.set_outputs(times, buf)
   t0_, t1_ = end_points(t)
-  finished = ent['solver'].run(y0c, t0_, t1_, out[1], trials_per_sync=trials_per_sync, max_evals=room)
+  finished = ent['solver'].run(y0c, t0_, t1_, out[-1], trials_per_sync=trials_per_sync, max_evals=room)
   spent = ent['solver'].stats()['evals']
   func._dopri5_stats = ent['solver'].stats()
   func._settle_adaptive_nfe(room, finished, spent)
+  if times is not None:
+    out[1:-1].copy_(sol._outs[:-1])
   if evaluator is not None:
     n_acc = ent['solver'].stats()['accepted']
     return out, ent['solver'].times[:n_acc + 1].tolist()
@@ -1218,6 +1323,12 @@ def odeint(func, y0, t, *, rtol=1e-7, atol=1e-9, method=None, options=None, use_
     step_size = options.get('step_size', None)
     if step_size is None:
       raise ValueError('fixed-grid methods need options["step_size"]')
+    if len(t) > 2:      # several output times: the same native solver with snapshot nodes, or the host loop -- and the reason
+      reason = _host_outputs_reason(func, y0, t)
+      if reason is None:
+        _note_output_solve(func, 'native fixed grid')
+        return _solve_native(func, y0, t, method, step_size, use_graph=use_graph)
+      _note_output_solve(func, 'host loop (%s)' % reason)
     if _native_ok(func, y0, t):
       from . import distributed as D
       if D.shard_requested(func):     # one process per GPU, rows partitioned over the ranks (distributed.solve_sharded)
@@ -1237,6 +1348,21 @@ def odeint(func, y0, t, *, rtol=1e-7, atol=1e-9, method=None, options=None, use_
       # (a replicated single-GPU solve on every rank would be a silent waste of N - 1 GPUs)
       raise _lib.GnpdeError('gnpde_shard is set but this %s solve cannot run row-partitioned (float32 [n, d] state on a HIP device, two '
                             'output times, no autograd) -- unset gnpde_shard for it' % method)
+  if method in ('dopri5', 'adaptive_heun') and len(t) > 2:
+    # several output times: the device controller with the emit kernel in its trial step, under the conditions of the two-time route
+    reason = _host_outputs_reason(func, y0, t)
+    if reason is None and t.dtype != torch.float32:
+      reason = 'times are not float32'
+    if reason is None and options.get('host_controller', False):
+      reason = 'host_controller'
+    if reason is None and method == 'dopri5' and options.get('eager_stages', False):
+      reason = 'eager_stages'
+    if reason is None and method == 'adaptive_heun' and options.get('norm') is not None:
+      reason = 'a norm of the caller'
+    if reason is None:
+      _note_output_solve(func, 'native device controller')
+      return _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=options.get('trials_per_sync'), pair=method)
+    _note_output_solve(func, 'host loop (%s)' % reason)
   if method == 'dopri5':
     if _recorded_ok(func, y0, t, options):      # training without the adjoint method: recorded solve + native reverse sweep
       return _solve_dopri5_recorded(func, y0, t, rtol, atol)

@@ -1813,6 +1813,30 @@ class Dopri5Solver(_NativeSolver):
     check(_lib.lib().gnpde_dopri5_set_row_order(self.handle, ptr(order32)))
     self._row_order = order32          # (kept alive: the solver holds the address)
 
+  def set_outputs(self, times, out=None):
+    """Outputs at several times (gnpde_dopri5_set_outputs).  times: the output times behind t0, strictly ascending, the last one the t1
+    of the following runs; out: float32 [len(times), n, d], unit column stride, dense slabs -- the accepted trial steps write
+    out[j] for j < len(times) - 1 (through the row order if one is set), the last output is `run`'s.  times None / empty detaches.
+    The same `out` with other times of the same count keeps the captured trial steps."""
+    L = _lib.lib()
+    if times is None or len(times) == 0:
+      check(L.gnpde_dopri5_set_outputs(self.handle, None, 0, None, 0))
+      self.out_times, self._t_out, self._outs = None, None, None
+      return
+    times = tuple(float(v) for v in times)
+    require_hip(out)
+    if (out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != len(times) or out.stride(2) != 1
+        or out.stride(0) != out.shape[1] * out.stride(1)):
+      raise _lib.GnpdeError('dopri5 outputs must be float32 [len(times), n, d] with unit column stride and dense slabs')
+    t_dev = getattr(self, '_t_out', None)
+    host = torch.tensor(times, dtype=torch.float64)
+    if t_dev is None or t_dev.numel() != len(times):
+      t_dev = host.to(out.device)
+    else:
+      t_dev.copy_(host)
+    check(L.gnpde_dopri5_set_outputs(self.handle, ptr(t_dev), len(times), ptr(out), out.stride(1)))
+    self.out_times, self._t_out, self._outs = times, t_dev, out      # (kept alive: the captured trial steps hold the addresses)
+
   # ---- recorded solve (training without the adjoint method): gnpde_dopri5_set_tape / _tape_backward ---------------------------
   def set_tape(self, capacity_steps):
     """Record the accepted steps of the following runs (None / 0 detaches).  The tape is zero-filled device memory owned here."""
@@ -2074,6 +2098,31 @@ class FixedStepSolver(_NativeSolver):
       check(L.gnpde_solver_set_gather(self.handle, _lib.GATHER_BF16, ptr(mem), mem.numel()))
       self.gather_mem = mem
     self.gather_dtype = dtype
+
+  def set_outputs(self, plan, out=None, order32=None):
+    """Outputs at several times (gnpde_solver_set_outputs).  plan: [(step, frac), ...] -- output j is taken after step `step`
+    (1-based) at the fraction `frac` of it (odeint.output_plan); out: float32 [len(plan), n, d], unit column stride, dense slabs;
+    order32: solver row r is written to row order32[r] of every output (int32 device tensor or None).  The scratch state buffer of
+    the interior outputs is device memory owned here.  plan None / empty detaches."""
+    L = _lib.lib()
+    if not plan:
+      check(L.gnpde_solver_set_outputs(self.handle, 0, None, None, None, 0, None))
+      self.output_plan, self._outs, self._out_scratch = None, None, None
+      return
+    plan = tuple((int(i), float(f)) for i, f in plan)
+    require_hip(out)
+    if (out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != len(plan) or out.stride(2) != 1
+        or out.stride(0) != out.shape[1] * out.stride(1)):
+      raise _lib.GnpdeError('solver outputs must be float32 [len(plan), n, d] with unit column stride and dense slabs')
+    scratch = None
+    if any(f != 1.0 for _, f in plan):
+      n = self.desc.graph.n
+      scratch = torch.zeros(n * self.desc.struct.ld + 64, dtype=torch.float32, device=out.device)
+    steps = (ctypes.c_int32 * len(plan))(*[i for i, _ in plan])
+    fracs = (ctypes.c_float * len(plan))(*[f for _, f in plan])
+    check(L.gnpde_solver_set_output_order(self.handle, ptr(order32)))
+    check(L.gnpde_solver_set_outputs(self.handle, len(plan), steps, fracs, ptr(out), out.stride(1), ptr(scratch)))
+    self.output_plan, self._outs, self._out_scratch, self._out_order = plan, out, scratch, order32      # (kept alive: the graph holds the addresses)
 
   def set_tape(self, on=True):
     """Record the stage inputs of the following runs (gnpde_solver_set_tape): the tape is zero-filled device memory owned here."""

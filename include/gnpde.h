@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNPDE_ABI_VERSION 25  /* 25: GNPDE_RHS_MIX_FEATURES, gnpde_rhs_t.out_w / out_ld appended, gnpde_linear_epilogue (no-grad solves of the GAT function's mix_features form);  24: gnpde_attention_rows_bwd_dq, gnpde_head_rowsum, gnpde_hub_bwd_workspace_floats, gnpde_head_rowsum_supported, gnpde_attention_rows_bwd_dq_supported (the adjoint stage's row kernels as entry points of their own);  23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
+#define GNPDE_ABI_VERSION 26  /* 26: gnpde_solver_set_outputs, gnpde_solver_set_output_order, gnpde_dopri5_set_outputs, gnpde_snapshot_rows (native solves with several output times);  25: GNPDE_RHS_MIX_FEATURES, gnpde_rhs_t.out_w / out_ld appended, gnpde_linear_epilogue (no-grad solves of the GAT function's mix_features form);  24: gnpde_attention_rows_bwd_dq, gnpde_head_rowsum, gnpde_hub_bwd_workspace_floats, gnpde_head_rowsum_supported, gnpde_attention_rows_bwd_dq_supported (the adjoint stage's row kernels as entry points of their own);  23: gnpde_attention_plan, gnpde_attention_launch_t, GNPDE_ATT_ROUTE_* / _ROWS16_* / _GMAX_* / _HUBS_* / _PLAN_* (the row attention's launch decision);  22: gnpde_spmm_plan, gnpde_spmm_launch_t, GNPDE_SPMM_* (the aggregation's launch decision), gnpde_adjoint_rows_dot_slots;  21: gnpde_spmm_ticket_bytes, gnpde_spmm_rhs_tickets, gnpde_in_kernel_fold_launches, gnpde_agg_fold_launch (hub rows folded inside the row-pair aggregation launch);  20: gnpde_adjoint_set_dopri5_tape, gnpde_dopri5_tape_slots, GNPDE_METHOD_DOPRI5_TAPE (GRAND-nl / GAT dopri5 training: sweep over a recorded solve), gnpde_dopri5_set_tape takes transformer and GAT descriptors;  19: gnpde_poincare_step(_workspace_bytes) (hyperbolic positional encodings: row-normalised Riemannian SGD on the Poincare ball);  18: gnpde_linear_plan, gnpde_linear_split_plan, gnpde_linear_launch_t, GNPDE_LINEAR_* (the projection's launch decision);  17: gnpde_nmf_cd_sweep(_workspace_bytes) (NMF compression of positional encodings);  16: gnpde_one_launch_evaluations (gnpde_tune(21, .): row attention of an evaluation in one launch);  15: gnpde_random_walks, gnpde_negative_walks, gnpde_random_permutation(_workspace_bytes), gnpde_deepwalk_step(_workspace_bytes), GNPDE_DEEPWALK_* (DeepWalk positional encodings);  14: gnpde_gdc_push_workspace_bytes, gnpde_gdc_push_count, gnpde_gdc_push_fill, gnpde_gdc_push_residuals (approximate PPR by forward push), gnpde_rank_select_begin, gnpde_rank_select_hist, gnpde_rank_select_pick, gnpde_rank_select_values (threshold by avg_degree);  13: gnpde_philox_words, gnpde_random_nodes, gnpde_node_importance, gnpde_sample_nodes(_workspace_bytes), gnpde_edge_union(_workspace_bytes), gnpde_select_edges(_workspace_bytes), gnpde_full_adjacency, GNPDE_SAMPLING_* (edge-sampling rewiring of the fully-adjacent layer);  12: gnpde_knn_metric, gnpde_radius_workspace_bytes, gnpde_radius_quantile, gnpde_radius_count, gnpde_radius_fill, GNPDE_METRIC_* (positional-distance rewiring: Poincare k-NN and radius graphs);  11: gnpde_gdc_workspace_bytes, gnpde_gdc_block, gnpde_gdc_topk, gnpde_gdc_emit, gnpde_gdc_threshold_count, gnpde_gdc_threshold_fill, gnpde_gdc_segment_sums, gnpde_gdc_dense (graph diffusion rewiring);  10: gnpde_split_kernel_grads, gnpde_split_kernel_grad_floats (BLEND split kernel on the native VJP stage), exp-kernel stage to attention_dim 256;  9: gnpde_knn, gnpde_knn_workspace_bytes (k-nearest-neighbour rewiring);  8: optional bf16 gather operand (gnpde_to_bf16, gnpde_spmm_lo, gnpde_spmm_rhs_lo, gnpde_solver_gather_bytes, gnpde_solver_set_gather);  7: gnpde_dopri5_create_sharded (device controller over the row partition), gnpde_dopri5_set_pair, gnpde_sharded_solver_set_general, gnpde_graph_build_device;  6: gnpde_adjoint_set_tape takes csr_from_t, gnpde_adjoint_tape_swapped, gnpde_linear_split;  5: gnpde_solver_set_tape / gnpde_adjoint_set_tape (recorded fixed-grid solve);  4: gnpde_dopri5_set_tape / _tape_backward, gnpde_adjoint_adaptive_*, GNPDE_METHOD_MIDPOINT;  2: gnpde_graph_t.xcd_deal appended, gnpde_xcd_row_map; 3: gnpde_attention_t.graph_t / t_from_csr appended,
                                  gnpde_adjoint_*, gnpde_stream_read; gnpde_graph_t.n_bin_le64 and gnpde_attention_t.n_key_rows in what was
                                  padding (struct sizes unchanged) */
 
@@ -646,6 +646,26 @@ int    gnpde_solver_set_tape(gnpde_solver_t* s, void* tape, size_t tape_bytes);
 size_t gnpde_solver_gather_bytes(const gnpde_rhs_t* rhs, int32_t method);
 int    gnpde_solver_set_gather(gnpde_solver_t* s, int32_t dtype, void* mem, size_t bytes);
 
+/* Outputs at several times of a fixed-grid solve  [torchdiffeq 0.2.1 FixedGridODESolver.integrate: output j comes from the first step
+ * [ta, tb] with tb >= t[j], as y_next (t[j] == tb), y (t[j] == ta) or the linear interpolation y + frac (y_next - y)].  The caller plans
+ * on the host: output j is taken after step step[j] (1-based, non-decreasing) at the fraction frac[j] in [0, 1] of that step (1: the
+ * state after the step) and lands in out + j * n * ld_out, rows of stride ld_out >= d.  Before a step with an output strictly inside it the
+ * solver copies its start state to `scratch` (one [n, ld] state buffer; may be NULL when every frac is 1); after the step one
+ * gnpde_snapshot_rows launch per output.  Copies and snapshots are nodes of the captured hipGraph and of the eager path alike; without
+ * outputs the solver enqueues exactly what it did before.  n_out == 0 detaches.  Drops a captured hipGraph.  GNPDE_EINVAL with a
+ * message together with a tape, the early-stopping evaluator (either order of the calls) or a partitioned descriptor.  The bf16 gather
+ * operand composes: outputs read the fp32 state only.
+ * gnpde_solver_set_output_order: solver row r is written to row order[r] of every output (device int32 [n], must outlive the runs; the
+ * relabelled graph of graph.LocalityView); NULL: row r. */
+int gnpde_solver_set_outputs(gnpde_solver_t* s, int32_t n_out, const int32_t* step, const float* frac, float* out, int32_t ld_out,
+                             float* scratch);
+int gnpde_solver_set_output_order(gnpde_solver_t* s, const int32_t* order);
+/* out[m(r), 0:d] = ya[r, 0:d] + frac (yb[r, 0:d] - ya[r, 0:d]), one fused multiply-add per element; state rows of stride ld, output rows
+ * of stride ld_out; m(r) = order[r] (device int32 [n]) or r when order is NULL.  frac == 1 is the copy of yb through the same map (ya may
+ * be NULL).  16-byte lanes where d, both strides and every address allow them, element by element otherwise. */
+int gnpde_snapshot_rows(const float* ya, const float* yb, float frac, int64_t n, int32_t d, int32_t ld, float* out, int32_t ld_out,
+                        const int32_t* order, void* stream);
+
 /* The q||k projection of SpGraphTransAttentionLayer (nn.Linear Q and K, reference src/function_transformer_attention.py:174-175) as TWO
  * tables q [n, A], k [n, A] instead of interleaved rows [n, 2A]: when a key row is shorter than a 128-byte cache line (A <= 16) the
  * attention's gathers of k rows otherwise fetch the q half of every line.  Offered (gnpde_linear_split_supported != 0) for tall x,
@@ -948,6 +968,18 @@ int gnpde_dopri5_set_early_stop(gnpde_dopri5_t* s, const gnpde_decoder_t* dec, i
  * runs).  gnpde_dopri5_run then reads y0[order[r]] into its row r and writes its row r to y_out[order[r]] (y_out must not alias y0
  * then).  NULL restores the plain copies. */
 int gnpde_dopri5_set_row_order(gnpde_dopri5_t* s, const int32_t* order);
+/* Outputs at several times  [torchdiffeq 0.2.1 RKAdaptiveStepsizeODESolver: the steps are those of the solve from t0 to t1 -- they
+ * never look at the output times -- and output j is the quartic interpolant (interp.py) of the first accepted step [t_prev, t_next] with
+ * t_next >= t_out[j], at x = fl32((t_out[j] - t_prev) / (t_next - t_prev)), the quotient in float64].  t_out: device doubles [n_out],
+ * strictly ascending, all behind the t0 of the runs, t_out[n_out - 1] == the t1 of the runs (gnpde_dopri5_run checks: GNPDE_EINVAL); out:
+ * n_out slabs [n, ld_out].  An emit kernel between the control and the finish kernel of the captured trial step, predicated on the
+ * controller record (a rejected step writes nothing), writes out[j] of every pending j < n_out - 1 with t_out[j] <= the new time -- any
+ * number per step, through the row order if one is set; the pending index and the step's start time live in a 32-byte device record of
+ * their own (the 96-byte controller record is unchanged).  The last output is y_out of gnpde_dopri5_run, as without outputs (slab
+ * n_out - 1 is not written).  Both pairs.  t_out == NULL or n_out == 0 detaches.  Attaching, detaching or other pointers drop the captured
+ * trial steps (other times behind the same pointers do not); reads t_out[n_out - 1] back (synchronises).  GNPDE_EINVAL with a message
+ * together with a tape, the early-stopping evaluator (either order of the calls) or a row-partitioned solver. */
+int gnpde_dopri5_set_outputs(gnpde_dopri5_t* s, const double* t_out, int32_t n_out, float* out, int32_t ld_out);
 /* of the last run: evaluations of f, accepted and rejected steps, graph launches, host synchronisations */
 int gnpde_dopri5_stats(const gnpde_dopri5_t* s, int32_t* n_evals, int32_t* n_accepted, int32_t* n_rejected, int32_t* n_launches,
                        int32_t* n_syncs);
