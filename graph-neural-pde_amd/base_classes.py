@@ -198,7 +198,7 @@ class ODEFunc(nn.Module):
     return x.requires_grad or any(p.requires_grad for p in self.parameters())
 
   def _has_native_rhs(self, x):
-    """Whether `_descriptor(x)` exists for this configuration and state shape: asked by every no-grad native solve (odeint._native_ok)
+    """Whether `_descriptor(x)` exists for this configuration and state shape: asked by every no-grad native solve (routes.py)
     and by `forward`.  Functions with a configuration outside their kernels' shapes override it (ODEFuncAtt with mix_features)."""
     return True
 

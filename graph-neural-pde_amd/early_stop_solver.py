@@ -19,9 +19,10 @@ t0, as the reference does).
 import torch
 
 from . import _lib
-from .odeint import (time_grid, _native_ok, _solve_native, _solve_fixed_host, _solve_dopri5, _solve_dopri5_native,
+from .odeint import (time_grid, _solve_native, _solve_fixed_host, _solve_dopri5, _solve_dopri5_native,
                      _solve_dopri5_device, gather_dtype_requested, _note_gather)
 from . import ops
+from . import routes
 
 
 class _EarlyStopSolver(object):
@@ -79,7 +80,7 @@ class EarlyStopRK4(_EarlyStopSolver):
 
   def integrate(self, t):
     grid = time_grid(t.detach().to('cpu'), self.step_size)
-    if _native_ok(self.func, self.y0, t):
+    if routes.early(self.func, self.y0, t, 'rk4')[0] == 'native_fixed':
       sol = _solve_native(self.func, self.y0, t, 'rk4', self.step_size, evaluator=self.evaluator)
     else:
       self.evaluator.reset()
@@ -103,7 +104,8 @@ class EarlyStopDopri5(_EarlyStopSolver):
     self.trials_per_sync = trials_per_sync
 
   def integrate(self, t):
-    if (not self.host_loop and _native_ok(self.func, self.y0, t) and t.dtype == torch.float32 and int(self.max_test_steps) >= 1):
+    route = routes.early(self.func, self.y0, t, 'dopri5', self.host_loop, self.max_test_steps)[0]
+    if route == 'device_controller':
       # the reference's default evaluation path (dopri5 + early stopping) without a host read per trial step: accept /
       # reject, the trial budget, which state is evaluated and under which tag are all decided on the device
       sol, times = _solve_dopri5_device(self.func, self.y0, t, self.rtol, self.atol, trials_per_sync=self.trials_per_sync,
@@ -128,7 +130,7 @@ class EarlyStopDopri5(_EarlyStopSolver):
         self.evaluator.evaluate(y if y.is_contiguous() else y.contiguous(), 0)
 
     self.evaluator.reset()
-    if _native_ok(self.func, self.y0, t) and t.dtype == torch.float32:
+    if route == 'host_stages':
       sol = _solve_dopri5_native(self.func, self.y0, t, self.rtol, self.atol, on_accept=on_accept,
                                          stop_after=self.max_test_steps, on_reject=on_reject)
     else:

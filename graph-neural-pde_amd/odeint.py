@@ -5,8 +5,9 @@ the reference's blocks (src/block_constant.py:57-62, src/block_transformer_atten
 Fixed-grid methods (`euler`, `rk4` == torchdiffeq 0.2.1's 3/8-rule rk4_alt_step_func) on one of this
 package's ODEFunc objects run as ONE native solver object whose whole time loop is a captured
 hipGraph (csrc/solver.hip); dopri5 / adaptive_heun run with the step-size controller on the device (csrc/dopri5.hip).  Both serve
-any number of strictly increasing output times (output_plan / output_times below).  Everything else (foreign callables, non-monotone
-times, differentiated solves without a record) runs the host loops below, which still evaluate f through the native kernels."""
+any number of strictly increasing output times (output_plan / output_times below).  Everything else runs the host loops below, which
+still evaluate f through the native kernels.  Which runner takes a solve, and why not a faster one, is decided in routes.py (its
+docstring lists the routes): `odeint`, the early-stopping integrators and `_AdjointSolve.backward` ask it and dispatch on the name."""
 import contextlib
 import math
 import os
@@ -14,6 +15,7 @@ import os
 import torch
 
 from . import _lib
+from . import routes
 
 _THIRD = 1 / 3
 _TRIAL_TRACE = None       # tests / diagnostics: a list that receives (t, dt, error ratio) of every trial step of the host-controlled adaptive solves
@@ -139,16 +141,18 @@ def _entry(func, slot, key, n, d, device, bufs=('y',), siblings=(), view=None):
   return ent
 
 
-def _solver_for(ent, sig, build):
-  """ent['solver'], rebuilt by build() when the descriptor signature is another one; a sweep over the old solver goes with it."""
-  if ent['solver'] is None or ent['sig'] != sig:
-    for name in ('solver', 'sweep'):
-      if ent[name] is not None:
-        ent[name].close()
-        ent[name] = None
-    ent['solver'] = build()
-    ent['sig'] = sig
-  return ent['solver']
+def _solver_for(ent, sig, build, name='solver'):
+  """ent[name] ('solver', or the 'sweep' over it), rebuilt by build() when the signature is another one; a sweep over an old solver goes
+  with it."""
+  sig_name = 'sig' if name == 'solver' else 'sweep_sig'
+  if ent[name] is None or ent[sig_name] != sig:
+    for old in ('solver', 'sweep') if name == 'solver' else ('sweep',):
+      if ent[old] is not None:
+        ent[old].close()
+        ent[old] = None
+    ent[name] = build()
+    ent[sig_name] = sig
+  return ent[name]
 
 
 def _order32(view):
@@ -194,48 +198,12 @@ def _weights_t(func, graph, out=None):
 # --------------------------------------------------------------------------------------------------
 # native fixed-step path
 # --------------------------------------------------------------------------------------------------
-def _native_ok(func, y0, t):
-  return (hasattr(func, '_descriptor') and y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32
-          and len(t) == 2 and not func._needs_grad(y0) and func._has_native_rhs(y0))
+_OUTPUT_REPORTS = {'native_fixed': 'native fixed grid', 'device_controller': 'native device controller'}
 
 
-def host_outputs_requested(func):
-  """opt['gnpde_host_outputs'] (or GNPDE_HOST_OUTPUTS=1): solves with more than two output times keep the host loops (A/B runs, tests)."""
-  opt = getattr(func, 'opt', None)
-  v = os.environ.get('GNPDE_HOST_OUTPUTS', '0') == '1'
-  if hasattr(opt, 'get'):
-    v = opt.get('gnpde_host_outputs', v)
-  return bool(v)
-
-
-def _host_outputs_reason(func, y0, t):
-  """Why a solve with more than two output times cannot take a native route (None: it can).  `_native_ok`'s rule with len(t) > 2 and
-  strictly increasing times; the row-partitioned solver keeps two output times."""
-  if not hasattr(func, '_descriptor'):
-    return 'foreign callable'
-  if not (y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32):
-    return 'state is not a float32 [n, d] tensor on a HIP device'
-  if func._needs_grad(y0):
-    return 'differentiated solve'
-  if not func._has_native_rhs(y0):
-    return 'no native right-hand side for this configuration'
-  if host_outputs_requested(func):
-    return 'gnpde_host_outputs'
-  from . import distributed as D
-  if D.shard_requested(func):
-    return 'gnpde_shard: the row-partitioned solver has two output times'
-  if not _strictly_increasing(t):
-    return 'output times are not strictly increasing'
-  return None
-
-
-def _native_outputs_ok(func, y0, t):
-  return len(t) > 2 and _host_outputs_reason(func, y0, t) is None
-
-
-def _note_output_solve(func, route):
-  if hasattr(func, '_descriptor'):
-    func._last_output_solve = route      # the route the last solve with more than two output times took
+def _note_output_solve(func, route, reason):
+  if hasattr(func, '_descriptor'):       # the route the last solve with more than two output times took, or why it was the host loop
+    func._last_output_solve = _OUTPUT_REPORTS[route] if reason is None else 'host loop (%s)' % reason
 
 
 def gather_dtype_requested(func):
@@ -768,15 +736,6 @@ def _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=None, evaluato
 # --------------------------------------------------------------------------------------------------
 # recorded dopri5: training WITHOUT the adjoint method (reference default opt['adjoint'] = False; best_params Cora / Citeseer)
 # --------------------------------------------------------------------------------------------------
-def _tape_busy(func, name):
-  """True while the record of an earlier forward pass of this function is still waiting for its backward (the autograd node of that pass
-  is alive and has not run): the next differentiated solve then takes the host loop instead of overwriting it -- two forwards before
-  one backward (siamese losses, gradient accumulation over two graphs) stay differentiable, as in the reference."""
-  ref = func.__dict__.get(name)
-  ctx = ref() if ref is not None else None
-  return ctx is not None and not getattr(ctx, 'gnpde_consumed', False)
-
-
 def _tape_claim(func, name, ctx):
   import weakref
   func.__dict__[name] = weakref.ref(ctx)
@@ -790,33 +749,6 @@ class _TapeTooLong(_lib.GnpdeError):
 
 
 _TAPE_BUDGET_BYTES = 8 << 30     # first tape allocation (it grows when a solve accepts more steps than it holds)
-
-
-def _recorded_ok(func, y0, t, options):
-  """The differentiated dopri5 solve runs as ONE recorded device solve + ONE native reverse sweep.  The Laplacian function -- f linear
-  in the state, its weights constants of the solve that may carry gradients (attention block), alpha' = sigmoid(alpha_train) -- is
-  swept by csrc/dopri5.hip (gnpde_dopri5_set_tape / _tape_backward); GRAND-nl and GAT within the limits of the native VJP stage
-  (_transformer_stage_native / _gat_stage_native; raw alpha too: the stage sums that form itself) by csrc/adjoint.hip
-  (gnpde_adjoint_set_dopri5_tape: one stage per recorded evaluation, q||k and the weights recomputed at the recorded stage input).
-  Everything else keeps the host loop `_solve_dopri5` over the kernel-backed autograd Functions of autograd.py."""
-  kind = func.__class__.__name__
-  if kind not in ('LaplacianODEFunc', 'ODEFuncTransformerAtt', 'ODEFuncAtt') or not hasattr(func, '_descriptor'):
-    return False
-  if not (y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32 and y0.shape[1] <= 256 and len(t) == 2 and t.dtype == torch.float32):
-    return False
-  opt = func.opt
-  if opt.get('gnpde_host_dopri5_training') or opt.get('gnpde_composite_backward'):
-    return False
-  if kind == 'LaplacianODEFunc':
-    if opt.get('no_alpha_sigmoid'):
-      return False
-  elif opt.get('gnpde_shard') or not (_transformer_stage_native(func) if kind == 'ODEFuncTransformerAtt' else _gat_stage_native(func)):
-    return False
-  if os.environ.get('GNPDE_HOST_DOPRI5_TRAINING', '0') == '1':      # A/B runs (bench.py --config cora-epoch)
-    return False
-  if options.get('norm') is not None or options.get('host_controller') or options.get('eager_stages'):
-    return False
-  return torch.is_grad_enabled() and func._needs_grad(y0)
 
 
 def _run_recorded_dopri5(func, sol, desc, y0c, t0, t1, out1, room):
@@ -960,7 +892,6 @@ class _RecordedDopri5NL(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, grad_out):
-    from . import ops
     func, ent, sol, graph, desc = ctx.func, ctx.ent, ctx.sol, ctx.graph, ctx.desc
     ctx.gnpde_consumed = True
     _check_tape(sol, ctx.gen, 'recorded dopri5', 'opt["gnpde_host_dopri5_training"] = True keeps a tape per forward')
@@ -970,30 +901,18 @@ class _RecordedDopri5NL(torch.autograd.Function):
     with torch.no_grad():
       n, d = grad_out.shape[1], grad_out.shape[2]
       dev = grad_out.device
-      gt, t_from_csr = graph.transposed_positions()
-      ex = ent['extra']
       _check_split_operands(func, ctx.split_sig, 'recorded dopri5')
-      proj_wt = _stage_projection_t(func, ex, dev, forward_values=True)
-      sweep_sig = (ent['sig'], id(gt))
-      if ent['sweep'] is None or ent['sweep_sig'] != sweep_sig:
-        if ent['sweep'] is not None:
-          ent['sweep'].close()
-        ent['sweep'] = ops.AdjointSolver(desc, gt, t_from_csr, proj_wt, None, 'dopri5_tape', (), dev)
-        ent['grads'] = torch.zeros(ent['sweep'].n_grad, dtype=torch.float32, device=dev)
-        ent['sweep_sig'] = sweep_sig
+      _vjp_sweep(func, ent, 'sweep', (ent['sig'],), desc, graph, 'dopri5_tape', (), dev, forward_values=True)
       ent['sweep'].set_dopri5_tape(sol, graph.csr_positions())      # (the accepted steps differ from one iteration to the next)
       ab = ent['a']
       ab.copy_(grad_out[1])
       ent['sweep'].run(ent['y'], ab, ent['grads'], use_graph=False)      # (y is not read: the state comes from the tape)
       dy0 = ab + grad_out[0] if need[0] else None
-      gparams = _param_grads(_grad_vector_by_param(func, ent['grads'], d, ex), ctx.params, need[6:])
+      gparams = _param_grads(_grad_vector_by_param(func, ent['grads'], d, ent['extra']), ctx.params, need[6:])
     return (dy0, None, None, None, None, None) + gparams
 
 
 def _solve_dopri5_recorded(func, y0, t, rtol, atol):
-  if _tape_busy(func, '_tape_live_dopri5'):
-    func._last_train_solve = 'differentiable host loop (the record of an earlier forward pass still awaits its backward)'
-    return _solve_dopri5(func, y0, t, rtol, atol)
   t0_, t1_ = end_points(t)
   nfe0 = func.nfe
   try:
@@ -1062,31 +981,36 @@ def _stage_projection_t(func, ex, dev, forward_values=False):
   return ex['proj_wt']
 
 
-def _recorded_fixed_ok(func, y0, t, method):
-  """The differentiated fixed-grid solve runs as ONE recorded native solve (csrc/solver.hip, gnpde_solver_set_tape: the captured
-  hipGraph of the inference solve with every stage input written to a slot of its own) + ONE native reverse sweep over the record
-  (csrc/adjoint.hip, gnpde_adjoint_set_tape: the VJP stage kernels of the adjoint solve, one hipGraph) for GRAND-l (weights may carry
-  gradients: attention block) and GRAND-nl with scaled-dot scores, alpha' = sigmoid(alpha_train).  Everything else keeps the host
-  loop `_solve_fixed_host` over the kernel-backed autograd Functions of autograd.py."""
-  if method not in ('euler', 'rk4', 'midpoint') or not hasattr(func, '_descriptor'):
-    return False
-  if not (y0.is_cuda and y0.dim() == 2 and y0.dtype == torch.float32 and y0.shape[1] <= 256 and len(t) == 2):
-    return False
-  opt = func.opt
-  if opt.get('gnpde_composite_backward') or opt.get('gnpde_host_fixed_training') or opt.get('gnpde_shard'):
-    return False
-  if os.environ.get('GNPDE_HOST_FIXED_TRAINING', '0') == '1':      # A/B runs (bench.py --train --no-adjoint)
-    return False
-  if not (torch.is_grad_enabled() and func._needs_grad(y0)):
-    return False
-  kind = func.__class__.__name__
-  if kind == 'LaplacianODEFunc':
-    return True
-  if kind == 'ODEFuncTransformerAtt':
-    return _transformer_stage_native(func)
-  if kind == 'ODEFuncAtt':
-    return _gat_stage_native(func)
-  return False
+def _nl_stage(func):
+  """Whether the VJP stage recomputes the attention at every evaluation (GRAND-nl, GAT) instead of reading constant weights (GRAND-l)."""
+  return func.__class__.__name__ in ('ODEFuncTransformerAtt', 'ODEFuncAtt')
+
+
+def _vjp_sweep(func, ent, name, sig, desc, graph, method, dts, dev, forward_values=False):
+  """The VJP-stage sweep (ops.AdjointSolver) of the entry -- ent['solver'] of the fixed-grid adjoint, ent['sweep'] of a recorded solve --
+  over the transposed graph, with its operand refreshed in a buffer of ent['extra'] whose address persists (captured graphs keep the
+  pointer): the transposed projection of GRAND-nl / GAT (_stage_projection_t), or the Laplacian weights in the transposed graph's entry
+  order.  A miss of the caller's signature `sig` rebuilds the sweep and the gradient vector ent['grads'].
+  Returns (the sweep, whether it was just built)."""
+  from . import ops
+  gt, t_from_csr = graph.transposed_positions()
+  nl = _nl_stage(func)
+  ex = ent['extra']
+  proj_wt = w_t = None
+  if nl:
+    proj_wt = _stage_projection_t(func, ex, dev, forward_values=forward_values)
+  else:
+    if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
+      ex['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=dev)
+    w_t = _weights_t(func, graph, out=ex['w_t'])
+  built = []
+
+  def build():
+    sweep = ops.AdjointSolver(desc, gt, t_from_csr if nl else None, proj_wt, w_t, method, dts, dev)
+    ent['grads'] = torch.zeros(sweep.n_grad, dtype=torch.float32, device=dev)
+    built.append(True)
+    return sweep
+  return _solver_for(ent, sig + (id(gt),), build, name), bool(built)
 
 
 def _split_kernel_grads(func, g, d, ex):
@@ -1191,40 +1115,27 @@ class _RecordedFixedGrid(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, grad_out):
-    from . import ops
     func, ent, graph, view, desc = ctx.func, ctx.ent, ctx.graph, ctx.view, ctx.desc
     ctx.gnpde_consumed = True
     sol = ent['solver']
     _check_tape(sol, ctx.gen, 'recorded fixed-grid solve', 'opt["gnpde_host_fixed_training"] = True keeps a graph per forward')
     need = ctx.needs_input_grad
-    nl = func.__class__.__name__ in ('ODEFuncTransformerAtt', 'ODEFuncAtt')
+    nl = _nl_stage(func)
     with torch.no_grad():
       n, d = grad_out.shape[1], grad_out.shape[2]
       dev = grad_out.device
-      gt, t_from_csr = graph.transposed_positions()
       ex = ent['extra']
-      proj_wt = w_t = None
-      if nl:
-        _check_split_operands(func, ctx.split_sig, 'recorded fixed-grid solve')
-        proj_wt = _stage_projection_t(func, ex, dev, forward_values=True)
-      else:
-        if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
-          ex['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=dev)
-          ex['r_acc'] = torch.zeros(max(graph.e, 1), dtype=torch.float32, device=dev)
-        w_t = _weights_t(func, graph, out=ex['w_t'])
+      _check_split_operands(func, ctx.split_sig, 'recorded fixed-grid solve')
       want_dw = (not nl) and ctx.has_edge_values and need[1] and graph.e > 0
-      sweep_sig = (ent['sig'], id(gt), bool(want_dw), id(sol))
-      if ent['sweep'] is None or ent['sweep_sig'] != sweep_sig:
-        if ent['sweep'] is not None:
-          ent['sweep'].close()
-        ent['sweep'] = ops.AdjointSolver(desc, gt, t_from_csr if nl else None, proj_wt, w_t, ctx.method, ctx.dts, dev)
-        ent['sweep'].set_tape(sol.tape, ex['r_acc'] if want_dw else None, graph.csr_positions() if nl else None)
-        ent['grads'] = torch.zeros(ent['sweep'].n_grad, dtype=torch.float32, device=dev)
-        ent['sweep_sig'] = sweep_sig
+      if not nl and (ex.get('r_acc') is None or ex['r_acc'].numel() != max(graph.e, 1)):
+        ex['r_acc'] = torch.zeros(max(graph.e, 1), dtype=torch.float32, device=dev)
+      sweep, built = _vjp_sweep(func, ent, 'sweep', (ent['sig'], bool(want_dw), id(sol)), desc, graph, ctx.method, ctx.dts, dev, forward_values=True)
+      if built:
+        sweep.set_tape(sol.tape, ex['r_acc'] if want_dw else None, graph.csr_positions() if nl else None)
       ab = ent['a']
       g1 = grad_out[1]
       _rows_in(view, g1 if view is None else g1.contiguous(), ab)
-      ent['sweep'].run(ent['y'], ab, ent['grads'])      # (y is not read in the taped mode: the state comes from the tape)
+      sweep.run(ent['y'], ab, ent['grads'])      # (y is not read in the taped mode: the state comes from the tape)
       dy0 = None
       if need[0]:
         dy0 = _rows_out(view, ab, torch.empty((n, d), dtype=torch.float32, device=dev))
@@ -1236,7 +1147,7 @@ class _RecordedFixedGrid(torch.autograd.Function):
           a = torch.sigmoid(a)
         E = graph.e
         dw_e = torch.empty(E, dtype=torch.float32, device=dev)
-        order = gt.perm_long if ent['sweep'].swapped else graph.perm_long      # (the products lie in the order of the graph the row kernel ran on)
+        order = (graph.transposed_positions()[0] if sweep.swapped else graph).perm_long      # (the products lie in the order of the graph the row kernel ran on)
         dw_e[order] = a * ex['r_acc'][:E]
         dw = (dw_e / ctx.heads).unsqueeze(1).expand(E, ctx.heads).contiguous() if ctx.heads else dw_e
       gparams = _param_grads(_grad_vector_by_param(func, ent['grads'], d, ex), ctx.params, need[5:])
@@ -1265,9 +1176,6 @@ def _solve_fixed_recorded(func, y0, t, method, step_size):
     free = torch.cuda.mem_get_info(y0.device)[0]
   except Exception:   # noqa: BLE001
     free = _FIXED_TAPE_BUDGET_BYTES
-  if _tape_busy(func, '_tape_live_fixed'):
-    func._last_train_solve = 'differentiable host loop (the record of an earlier forward pass still awaits its backward)'
-    return _solve_fixed_host(func, y0, t, method, step_size)
   # (a tape of this method, grid and shape that already exists is not allocated again: the key of _RecordedFixedGrid.forward)
   cached = any(key[:4] == (method, tuple(dts), y0.shape[0], y0.shape[1]) for key in func.__dict__.get('_fixed_tape_state', ()))
   if not cached and need > min(_FIXED_TAPE_BUDGET_BYTES, 0.7 * free):
@@ -1319,65 +1227,30 @@ def odeint(func, y0, t, *, rtol=1e-7, atol=1e-9, method=None, options=None, use_
   method = 'dopri5' if method is None else method
   gather_dtype_requested(func)      # (a bad value raises whatever path the solve takes)
   _note_gather(func, 'fp32')        # only the native fixed-step solve below runs anything else
-  if method in ('euler', 'rk4', 'midpoint'):
-    step_size = options.get('step_size', None)
-    if step_size is None:
-      raise ValueError('fixed-grid methods need options["step_size"]')
-    if len(t) > 2:      # several output times: the same native solver with snapshot nodes, or the host loop -- and the reason
-      reason = _host_outputs_reason(func, y0, t)
-      if reason is None:
-        _note_output_solve(func, 'native fixed grid')
-        return _solve_native(func, y0, t, method, step_size, use_graph=use_graph)
-      _note_output_solve(func, 'host loop (%s)' % reason)
-    if _native_ok(func, y0, t):
-      from . import distributed as D
-      if D.shard_requested(func):     # one process per GPU, rows partitioned over the ranks (distributed.solve_sharded)
-        if method == 'midpoint':
-          raise _lib.GnpdeError('gnpde_shard: the row-partitioned solver runs euler, rk4, dopri5 and adaptive_heun; unset gnpde_shard for midpoint')
-        return D.solve_sharded(func, y0, t, method, step_size, use_graph=use_graph)
-      return _solve_native(func, y0, t, method, step_size, use_graph=use_graph)
-    if _recorded_fixed_ok(func, y0, t, method):      # training without the adjoint method: recorded solve + native reverse sweep
-      return _solve_fixed_recorded(func, y0, t, method, step_size)
+  route, reason = routes.forward(func, y0, t, method, options)
+  if len(t) > 2:
+    _note_output_solve(func, route, reason)
+  if reason is routes.TAPE_BUSY:
+    func._last_train_solve = 'differentiable host loop (%s)' % reason
+  step_size = options.get('step_size')
+  if route == 'native_fixed':
+    return _solve_native(func, y0, t, method, step_size, use_graph=use_graph)
+  if route == 'device_controller':
+    return _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=options.get('trials_per_sync'), pair=method)
+  if route == 'recorded_fixed':
+    return _solve_fixed_recorded(func, y0, t, method, step_size)
+  if route == 'recorded_dopri5':
+    return _solve_dopri5_recorded(func, y0, t, rtol, atol)
+  if route == 'host_fixed':
     return _solve_fixed_host(func, y0, t, method, step_size)
-  if method in ('dopri5', 'adaptive_heun') and hasattr(func, '_descriptor'):
-    from . import distributed as D
-    if D.shard_requested(func):
-      # rows partitioned over the ranks; the controller runs on every rank over an all-reduced error norm
-      if _native_ok(func, y0, t):
-        return D.solve_sharded(func, y0, t, method, None, rtol=rtol, atol=atol)
-      # (a replicated single-GPU solve on every rank would be a silent waste of N - 1 GPUs)
-      raise _lib.GnpdeError('gnpde_shard is set but this %s solve cannot run row-partitioned (float32 [n, d] state on a HIP device, two '
-                            'output times, no autograd) -- unset gnpde_shard for it' % method)
-  if method in ('dopri5', 'adaptive_heun') and len(t) > 2:
-    # several output times: the device controller with the emit kernel in its trial step, under the conditions of the two-time route
-    reason = _host_outputs_reason(func, y0, t)
-    if reason is None and t.dtype != torch.float32:
-      reason = 'times are not float32'
-    if reason is None and options.get('host_controller', False):
-      reason = 'host_controller'
-    if reason is None and method == 'dopri5' and options.get('eager_stages', False):
-      reason = 'eager_stages'
-    if reason is None and method == 'adaptive_heun' and options.get('norm') is not None:
-      reason = 'a norm of the caller'
-    if reason is None:
-      _note_output_solve(func, 'native device controller')
-      return _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=options.get('trials_per_sync'), pair=method)
-    _note_output_solve(func, 'host loop (%s)' % reason)
-  if method == 'dopri5':
-    if _recorded_ok(func, y0, t, options):      # training without the adjoint method: recorded solve + native reverse sweep
-      return _solve_dopri5_recorded(func, y0, t, rtol, atol)
-    if _native_ok(func, y0, t) and t.dtype == torch.float32 and not options.get('host_controller', False):
-      if options.get('eager_stages', False):      # controller on the host, one scalar read per trial step
-        return _solve_dopri5_native(func, y0, t, rtol, atol)
-      return _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=options.get('trials_per_sync'))
-    return _solve_dopri5(func, y0, t, rtol, atol, norm=options.get('norm'))
-  if method == 'adaptive_heun':
-    if (hasattr(func, '_descriptor') and _native_ok(func, y0, t) and t.dtype == torch.float32 and not options.get('host_controller', False)
-        and options.get('norm') is None):
-      # the device controller with the Heun pair's trial step (one evaluation per trial step; csrc/dopri5.hip, gnpde_dopri5_set_pair)
-      return _solve_dopri5_device(func, y0, t, rtol, atol, trials_per_sync=options.get('trials_per_sync'), pair='adaptive_heun')
-    return _solve_dopri5(func, y0, t, rtol, atol, tableau='adaptive_heun', norm=options.get('norm'))
-  raise ValueError('unsupported method %r (euler, midpoint, rk4, dopri5, adaptive_heun)' % (method,))
+  if route == 'host_loop':
+    return _solve_dopri5(func, y0, t, rtol, atol, tableau=method, norm=options.get('norm'))
+  if route == 'host_stages':
+    return _solve_dopri5_native(func, y0, t, rtol, atol)
+  from . import distributed as D      # 'sharded': one process per GPU, rows partitioned over the ranks
+  if method in routes.FIXED:
+    return D.solve_sharded(func, y0, t, method, step_size, use_graph=use_graph)
+  return D.solve_sharded(func, y0, t, method, None, rtol=rtol, atol=atol)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1453,31 +1326,8 @@ def _adjoint_fixed_grid(func, params, y, a, gparams, span, method, step_size):
   return a, gparams
 
 
-def _adjoint_native_ok(func, y, method):
-  """The fixed-grid adjoint solve runs as ONE native object (csrc/adjoint.hip) for GRAND-l, for GRAND-nl with scaled-dot, cosine_sim,
-  pearson or exp_kernel scores -- the BLEND split kernel included -- (any normaliser), alpha' = sigmoid(alpha_train) or the raw
-  alpha_train, and for the GAT function, within the shapes of _transformer_stage_native / _gat_stage_native; everything else keeps the
-  stage-by-stage loop above."""
-  if method not in ('euler', 'rk4') or not hasattr(func, '_descriptor'):
-    return False
-  if not (y.is_cuda and y.dim() == 2 and y.dtype == torch.float32 and y.shape[1] <= 256):
-    return False
-  opt = func.opt
-  if opt.get('gnpde_composite_backward') or opt.get('gnpde_host_adjoint'):
-    return False
-  kind = func.__class__.__name__
-  if kind == 'LaplacianODEFunc':
-    return True       # the weights are constants of the solve: torchdiffeq's adjoint returns gradients for y0 and func.parameters() only
-  if kind == 'ODEFuncTransformerAtt':
-    return _transformer_stage_native(func)     # (round 6: cosine_sim / pearson scores and the raw alpha of opt['no_alpha_sigmoid'] as well)
-  if kind == 'ODEFuncAtt':
-    return _gat_stage_native(func)             # (round 6)
-  return False
-
-
 def _adjoint_native(func, params, y, a, span, method, step_size):
   """(a at the earlier time, [gradient contribution per entry of `params`]) of one backward interval, by the native solver."""
-  from . import ops
   grid = time_grid(span.detach().to('cpu'), step_size)
   dts = (grid[1:] - grid[:-1]).tolist()
   n_evals = len(dts) * (4 if method == 'rk4' else 1)
@@ -1492,42 +1342,15 @@ def _adjoint_native(func, params, y, a, span, method, step_size):
     _copy_source(func, ent['x0'], view)
   graph = func._graph(y) if view is None else view.graph
   desc = func._descriptor(yb, x0_override=ent['x0'], graph=graph)
-  gt, t_from_csr = graph.transposed_positions()
-  nl = func.__class__.__name__ in ('ODEFuncTransformerAtt', 'ODEFuncAtt')
-  ex = ent['extra']
-  proj_wt = w_t = None
-  if nl:
-    proj_wt = _stage_projection_t(func, ex, y.device)
-  else:
-    if ex.get('w_t') is None or ex['w_t'].numel() != max(graph.e, 1):
-      ex['w_t'] = torch.empty(max(graph.e, 1), dtype=torch.float32, device=y.device)
-    w_t = _weights_t(func, graph, out=ex['w_t'])
-
-  def build():
-    sol = ops.AdjointSolver(desc, gt, t_from_csr if nl else None, proj_wt, w_t, method, dts, y.device)
-    ent['grads'] = torch.zeros(sol.n_grad, dtype=torch.float32, device=y.device)
-    return sol
-  sol = _solver_for(ent, (func._descriptor_signature(desc), id(gt)), build)
+  sol = _vjp_sweep(func, ent, 'solver', (func._descriptor_signature(desc),), desc, graph, method, dts, y.device)[0]
   sol.run(yb, ab, ent['grads'])
   func.nfe += n_evals
   a_out = _rows_out(view, ab, torch.empty_like(a, memory_format=torch.contiguous_format))
-  by_param = _grad_vector_by_param(func, ent['grads'], y.shape[1], ex)
+  by_param = _grad_vector_by_param(func, ent['grads'], y.shape[1], ent['extra'])
   return a_out, [by_param.get(id(p)) for p in params]
 
 
-def _adjoint_adaptive_ok(func, y, method):
-  """The ADAPTIVE adjoint methods (`adjoint_method` adaptive_heun -- the reference's default, run_GNN.py:334; best_params Pubmed -- and
-  dopri5 -- CoauthorCS, Computers) on the Laplacian function run with native stages: no autograd graph, no flat vector, two aggregation
-  launches per stage (see _adjoint_adaptive_native).  Everything else keeps the flat host loop."""
-  if method not in ('dopri5', 'adaptive_heun') or func.__class__.__name__ != 'LaplacianODEFunc' or not hasattr(func, '_descriptor'):
-    return False
-  if not (y.is_cuda and y.dim() == 2 and y.dtype == torch.float32):
-    return False
-  opt = func.opt
-  return not (opt.get('no_alpha_sigmoid') or opt.get('gnpde_composite_backward') or opt.get('gnpde_host_adjoint'))
-
-
-def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, atol):
+def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, atol, device_controller=False):
   """One backward interval of torchdiffeq's adjoint with an ADAPTIVE adjoint method, for f(u) = alpha' (A u - u) + beta x0: the augmented
   system (vjp_t, y, a, g_theta) in reversed time s = -t is
 
@@ -1537,7 +1360,8 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
   components of their own) exactly as `_solve_dopri5` does on the flat vector -- but by _solve_pair_host on the components: a
   y-component of sign -1 on the graph, an a-component of sign +1 on the transposed graph, the scalar pair (two dot products per
   stage), no autograd graph; per trial step two error-norm launches and one host read.  The initial step always runs there; the rest
-  of the interval runs on the device controller where that has the case.  Buffers and the device solver: slot _adjoint_adaptive.
+  of the interval runs on the device controller where the route rule says so (`device_controller`: routes.adjoint names the two).  Buffers
+  and the device solver: slot _adjoint_adaptive.
   Returns (a at the earlier time, new accumulated gradients of alpha_train / beta_train as a dict by parameter id)."""
   import types
   from . import ops
@@ -1596,8 +1420,7 @@ def _adjoint_adaptive_native(func, params, y, a, gparams, span, method, rtol, at
 
   sc = types.SimpleNamespace(g=g, g1=None, K=[None] * (stages + 1), stage=scal_stage, ratio=scal_ratio)
   T0, T1 = float(span[0]), float(span[-1])
-  if (ia is not None and (ib is not None or not has_src) and not func.opt.get('gnpde_host_controller_adjoint')
-      and Y.stride(0) % 4 == 0 and d <= 256):
+  if device_controller and Y.stride(0) % 4 == 0:      # (route 'adjoint_device'; the 16-byte rows are this runner's own allocation)
     # the initial step on the host, the rest of the interval with the controller on the device (csrc/adjoint_adaptive.hip: one
     # hipGraph replay per trial step of the embedded pair; the host reads a record once per batch)
     from .utils import MaxNFEException
@@ -1686,27 +1509,24 @@ class _AdjointSolve(torch.autograd.Function):
         return -_flatten(outs)
 
       options = dict(adj['options'])
-      # (a caller's own adjoint norm -- torchdiffeq's adjoint_options['norm'], e.g. 'seminorm' -- is honoured by the flat loop only: the
-      # native controller's norm is the default mixed one)
-      user_norm = options.get('norm') is not None
-      if adj['method'] in ('dopri5', 'adaptive_heun') and 'norm' not in options:
+      if adj['method'] in routes.ADAPTIVE and 'norm' not in options:
         options['norm'] = _mixed_norm(shapes)
-      fixed = adj['method'] in ('euler', 'rk4')
-      if fixed and options.get('step_size') is None:
-        raise ValueError('fixed-grid adjoint methods need adjoint_options["step_size"]')
+      # (every interval starts from a slice of `ans`: one route for all of them)
+      route = routes.adjoint(func, ans[-1], adj['method'], adj['options'], params)[0]
       for i in range(len(t) - 1, 0, -1):
         span = -t[i - 1:i + 1].flip(0)
-        if fixed and _adjoint_native_ok(func, state[1], adj['method']):
+        if route == 'adjoint_native':
           # the whole interval as one native object (one hipGraph; no PyTorch op between the stages)
           state[2], contrib = _adjoint_native(func, params, state[1], state[2], span, adj['method'], options['step_size'])
           state = state[:3] + [gp if c is None else gp + c.reshape(gp.shape) for gp, c in zip(state[3:], contrib)]
-        elif fixed:
+        elif route == 'adjoint_stagewise':
           state[2], gp = _adjoint_fixed_grid(func, params, state[1], state[2], state[3:], span, adj['method'],
                                              options['step_size'])
           state = state[:3] + list(gp)
-        elif _adjoint_adaptive_ok(func, state[1], adj['method']) and not options.get('host_flat', False) and not user_norm:
+        elif route in ('adjoint_device', 'adjoint_host_pair'):
           # adaptive adjoint method on the Laplacian function: native stages on the components (no autograd graph, no flat vector)
-          state[2], new = _adjoint_adaptive_native(func, params, state[1], state[2], state[3:], span, adj['method'], adj['rtol'], adj['atol'])
+          state[2], new = _adjoint_adaptive_native(func, params, state[1], state[2], state[3:], span, adj['method'], adj['rtol'], adj['atol'],
+                                                   device_controller=route == 'adjoint_device')
           for idx, val in new.items():
             state[3 + idx] = val
         else:

@@ -134,7 +134,7 @@ def test_check_rhs_refusals():
 
 
 def test_python_predicate_and_signature():
-  """ODEFuncAtt._has_native_rhs is the one rule _native_ok and forward consult; the descriptor signature sees the table."""
+  """ODEFuncAtt._has_native_rhs is the one rule the route rule and forward consult; the descriptor signature sees the table."""
   from helpers import Data
   n = 50
   ei = torch.stack([torch.arange(n), (torch.arange(n) + 1) % n]).long()

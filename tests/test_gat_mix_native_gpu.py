@@ -16,6 +16,7 @@ from gnpde_amd import _lib, ops
 from helpers import Data, Fixture, assert_parity, random_graph
 
 O = importlib.import_module('gnpde_amd.odeint')
+R = importlib.import_module('gnpde_amd.routes')
 pytestmark = pytest.mark.gpu
 
 OPT = dict(heads=4, attention_dim=16, attention_type='scaled_dot', attention_norm_idx=0, square_plus=False, reweight_attention=False,
@@ -415,7 +416,9 @@ def test_shapes_outside_the_rule_solve_on_the_host_loop(dev, d, A, heads):
   block = make_block(ei, x, dev, 73, attention_dim=A, heads=heads, time=2.0)
   f = block.odefunc
   t = torch.tensor([0.0, 2.0], device=dev)
-  assert not f._has_native_rhs(x) and not O._native_ok(f, x, t)
+  assert not f._has_native_rhs(x)
+  with torch.no_grad():
+    assert R.forward(f, x, t, 'rk4', {'step_size': 0.5}) == ('host_fixed', R.NO_RHS) and R.forward(f, x, t, 'dopri5', {}) == ('host_loop', R.NO_RHS)
   with pytest.raises(NotImplementedError):
     f._descriptor(x)
   ref = func_ref(f, x)
@@ -555,7 +558,7 @@ def test_training_keeps_the_differentiable_host_loop(dev):
   block = make_block(ei, xc.to(dev), dev, 97, time=2.0)
   f = block.odefunc
   t = torch.tensor([0.0, 2.0], device=dev)
-  assert not O._recorded_fixed_ok(f, xc.to(dev).requires_grad_(True), t, 'rk4') and not O._gat_stage_native(f)
+  assert R.forward(f, xc.to(dev).requires_grad_(True), t, 'rk4', {'step_size': 0.5}) == ('host_fixed', R.NO_VJP_STAGE) and not O._gat_stage_native(f)
   block.train()
   xin = xc.to(dev).clone().requires_grad_(True)
   block.set_x0(xin)

@@ -21,6 +21,7 @@ from test_split_kernel_stage_gpu import _block as _split_block
 pytestmark = pytest.mark.gpu
 
 O = importlib.import_module('gnpde_amd.odeint')
+R = importlib.import_module('gnpde_amd.routes')
 MaxNFEException = importlib.import_module('gnpde_amd.utils').MaxNFEException
 NATIVE = 'native recorded-tape dopri5'
 NAMES = fixtures('nltrain_')
@@ -366,7 +367,8 @@ def test_refusals_take_the_host_loop(dev):
   block.set_x0(x.to(dev))
   t = torch.tensor([0.0, 1.5], device=dev)
   state = x.to(dev).clone().requires_grad_(True)
-  assert O._recorded_ok(f, state, t, {}) and not O._recorded_ok(f, state, t, {'norm': O._rms})
+  assert R.forward(f, state, t, 'dopri5', {}) == ('recorded_dopri5', None)
+  assert R.forward(f, state, t, 'dopri5', {'norm': O._rms}) == ('host_loop', R.CALLER_NORM)
   f._last_train_solve = ''
   out = G.odeint(f, state, t, rtol=2e-5, atol=2e-7, method='dopri5', options={'norm': O._rms})[1]
   assert not str(f._last_train_solve).startswith('native recorded'), f._last_train_solve
@@ -380,7 +382,7 @@ def test_refusals_take_the_host_loop(dev):
   inner = block.reg_odefunc.odefunc
   xin = x.to(dev).clone().requires_grad_(True)
   block.set_x0(xin)
-  assert O._recorded_ok(inner, xin, block.t.to(dev), {})
+  assert R.forward(inner, xin, block.t.to(dev), 'dopri5', {}) == ('recorded_dopri5', None)
   inner._last_train_solve = ''
   z, regs = block(xin)
   assert len(regs) == 1 and not str(inner._last_train_solve).startswith('native recorded'), inner._last_train_solve

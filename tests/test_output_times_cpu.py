@@ -12,6 +12,7 @@ from gnpde_amd import _lib
 import output_times_cases as C
 
 O = C.O
+R = G.routes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ('gnpde_solver_set_outputs', 'gnpde_solver_set_output_order', 'gnpde_dopri5_set_outputs', 'gnpde_snapshot_rows')
 
@@ -100,8 +101,10 @@ class _Stub(object):
 def test_route_rule_and_report_on_the_host():
   f, y0 = _Stub(), torch.ones(3, 2)
   t = torch.tensor([0.0, 0.5, 1.0])
-  assert not O._native_outputs_ok(f, y0, t) and not O._native_outputs_ok(lambda tq, y: -y, y0, t)
-  assert 'HIP device' in O._host_outputs_reason(f, y0, t) and O._host_outputs_reason(lambda tq, y: -y, y0, t) == 'foreign callable'
+  for method, options, host in (('rk4', {'step_size': 0.5}, 'host_fixed'), ('dopri5', {}, 'host_loop')):
+    route, reason = R.forward(f, y0, t, method, options)
+    assert route == host and 'HIP device' in reason
+    assert R.forward(lambda tq, y: -y, y0, t, method, options) == (host, 'foreign callable')
   out = G.odeint(f, y0, t, method='rk4', options={'step_size': 0.5})
   assert out.shape == (3, 3, 2) and f._last_output_solve.startswith('host loop (')
   G.odeint(f, y0, t, method='dopri5', rtol=1e-6, atol=1e-8)
@@ -109,7 +112,7 @@ def test_route_rule_and_report_on_the_host():
   assert O._strictly_increasing(t) and not O._strictly_increasing(torch.tensor([0.0, 1.0, 1.0])) and not O._strictly_increasing(torch.tensor([0.0, 1.0, 0.5]))
   assert O.output_times(t) == (0.5, 1.0)
   f.opt = {'gnpde_host_outputs': True}
-  assert O.host_outputs_requested(f) and not O.host_outputs_requested(_Stub())
+  assert R.host_outputs_requested(f) and not R.host_outputs_requested(_Stub())
 
 
 def test_trajectory_refuses_training_with_regularisers():
